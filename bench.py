@@ -8,8 +8,12 @@ over the ranks, fp32.
            forward + hand-written backward of the 2-D U-Net + [RCCL all-reduce of the flat gradient bucket when N>1] +
            fused Adam; inputs resident in HBM; everything before the collective replayed as ONE hipGraph.
   value  = global-batch-256 training steps per second ("strong" scaling: total work fixed as N grows).
-  timing = W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + device synchronise, MAX over
-           ranks; blocks repeat until >= 1 s has been timed and the MEDIAN block is reported.
+  timing = W warm-up steps, then EXACTLY K timed steps in one block bracketed by barrier + device synchronise, MAX over
+           ranks; ms_per_step = block time / K.
+  --dump-outputs DIR  after the timed steps, rank 0 writes what the main line's last step computed (training: the mean
+                      loss, the flat parameters after Adam and the flat gradient, in named_parameters() order; c5: the
+                      samples) as DIR/<name>.npy, float32, at most 64 MB in all.  Inputs are seeded, so two runs with the
+                      same arguments can be compared array by array.
 On the same JSON line:
   sample_steps_per_s  C5: reverse-SDE Euler-Maruyama steps/s for 8192 samples of the same net (rows split over the
                       ranks, chunks of <= 4096 rows, ONE hipGraph-captured step replayed --sample-steps times per chunk);
@@ -108,7 +112,8 @@ def host_cores() -> int:
 
 def timed_blocks(step_fn, steps, warmup, dev, min_seconds=1.0, max_blocks=50):
     """W warm-up steps, then blocks of exactly `steps` steps (barrier + synchronise on both sides, MAX over ranks)
-    until >= min_seconds have been timed; returns (median block seconds, all block seconds)."""
+    until >= min_seconds have been timed; returns (median block seconds, all block seconds).  The main line passes
+    max_blocks=1: exactly `steps` timed steps."""
     import torch
     from sdeflow_light_amd import parallel
     for _ in range(warmup):
@@ -152,6 +157,38 @@ def free_gpu():
     ops.DeferredReduces.release()      # then the slab arena of the deterministic weight gradients
     gc.collect()
     torch.cuda.empty_cache()
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+NPY_HEADER_BYTES = 4096              # generous allowance for each file's .npy header
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one out_dir/<name>.npy per {name: tensor}, float32 (float64 stays float64), at most
+    DUMP_LIMIT_BYTES in all.  Arrays are fitted smallest first; one larger than what is left of the budget keeps a fixed,
+    seeded sample of its rows (leading-dimension entries) in ascending order, so every run with the same arguments writes
+    the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel() * kv[1].element_size()):
+        a = t.detach().cpu().numpy()
+        a = np.atleast_1d(a if a.dtype == np.float64 else a.astype(np.float32))
+        left -= NPY_HEADER_BYTES
+        if a.nbytes > left:
+            keep = left // (a.nbytes // a.shape[0])
+            if keep < 1:
+                raise SystemExit(f"--dump-outputs: no room left for {name} under {DUMP_LIMIT_BYTES} bytes")
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    log(f"outputs of the last timed step -> {out_dir}: {', '.join(arrays)}")
+
+
+def trainer_outputs(tr):
+    """What a training step hands its caller: the mean loss it returns and the parameters / gradients it leaves in the
+    net (flat buckets, in named_parameters() order)."""
+    return {"loss": tr.loss, "parameters": tr.flat, "gradients": tr.gbuf[: tr.n]}
 
 
 # ----------------------------------------------------------------------------------------------------- models
@@ -266,8 +303,9 @@ def cpu_baseline_unet(workload, budget_s=20.0):
 
 
 # ----------------------------------------------------------------------------------------------------- legs
-def leg_train_unet(workload, a, rank, world, dev):
-    """C3 (weak: 4096 rows per GPU) / C4 (strong: global 256 split over the ranks)."""
+def leg_train_unet(workload, a, rank, world, dev, main_line=False):
+    """C3 (weak: 4096 rows per GPU) / C4 (strong: global 256 split over the ranks).  main_line: exactly a.steps timed
+    steps, and the last step's outputs under "outputs" when a.dump_outputs is set."""
     import torch
     from sdeflow_light_amd import parallel
     from sdeflow_light_amd.train import UNetScoreTrainer
@@ -279,7 +317,7 @@ def leg_train_unet(workload, a, rank, world, dev):
     # same seed on every rank + the shard's first global row: the N-rank run draws what the 1-rank run would
     tr = UNetScoreTrainer(gen, B, d, lr=1e-4, world=world, seed=1, row_base=rank * B)
     tr.set_data(signals_1d(B, seed=1234 + rank, device=dev) if workload == "c3" else random_images(B, seed=1234 + rank, device=dev))
-    med, blocks = timed_blocks(tr.step, a.steps, a.warmup, dev)
+    med, blocks = timed_blocks(tr.step, a.steps, a.warmup, dev, max_blocks=1 if main_line else 50)
     per_step = med / a.steps
     gb = B * world
     units_per_step = world if workload == "c3" else 1          # c3 weak: B/GPU fixed; c4 strong: global 256
@@ -289,12 +327,15 @@ def leg_train_unet(workload, a, rank, world, dev):
            "final_loss": float(tr.loss), "global_batch": gb, "graph": bool(tr.use_graph),
            "whole_step": {"algorithmic_tflops_per_gpu": tf, "frac_of_f32_mfma_peak": tf / PEAK_F32_MFMA_TFLOPS,
                           "flop_per_step": flops, "note": "as-written FLOPs = 6 x forward (SURVEY.md §8d), all kernels"}}
+    if main_line and a.dump_outputs:
+        out["outputs"] = {k: v.cpu() for k, v in trainer_outputs(tr).items()}
     del tr
     return out, gen, d
 
 
-def leg_sample_unet(gen, d, a, rank, world, dev):
-    """C5: EM sampling of 8192 rows split over the ranks, ONE captured step replayed per chunk of <= 4096 rows."""
+def leg_sample_unet(gen, d, a, rank, world, dev, main_line=False):
+    """C5: EM sampling of 8192 rows split over the ranks, ONE captured step replayed per chunk of <= 4096 rows.  main_line:
+    this rank's samples under "outputs" when a.dump_outputs is set."""
     import torch
     from sdeflow_light_amd import parallel
     from sdeflow_light_amd.sde_scheme import GraphedStepSampler
@@ -317,12 +358,16 @@ def leg_sample_unet(gen, d, a, rank, world, dev):
            "chunk": chunk, "sampler_finite": bool(torch.isfinite(x).all()),
            "algorithmic_tflops_per_gpu": tf, "frac_of_f32_mfma_peak": tf / PEAK_F32_MFMA_TFLOPS,
            "workload": f"C5: EM sampling, UNet2D 64x64x3, {SAMPLE_ROWS} samples over {world} GPU(s), hipGraph-captured step"}
+    if main_line and a.dump_outputs:
+        out["outputs"] = {"samples": x}
     del gs, x
     return out
 
 
-def leg_mlp(a, rank, world, dev, steps=200, sample_steps=200):
-    """C2: MLP d=2, B=65536 per GPU (weak): graph-replayed train step + whole-loop EM sampler + k_mlp<TRAIN> roofline."""
+def leg_mlp(a, rank, world, dev, steps=200, sample_steps=200, main_line=False):
+    """C2: MLP d=2, B=65536 per GPU (weak): graph-replayed train step + whole-loop EM sampler + k_mlp<TRAIN> roofline.
+    main_line: a.warmup warm-up steps, exactly `steps` timed steps, and the last step's outputs under "outputs" when
+    a.dump_outputs is set."""
     import ctypes as C
     import torch
     from sdeflow_light_amd import parallel, ops
@@ -334,8 +379,9 @@ def leg_mlp(a, rank, world, dev, steps=200, sample_steps=200):
     parallel.broadcast_(flat, 0)
     tr = MLPScoreTrainer(gen, B_C2, lr=1e-3, world=world, use_graph=not parallel.multi(world), seed=1, row_base=rank * B_C2)
     tr.set_data(gaussian_mixture_2d(B_C2, seed=1234 + rank, device=dev))
-    med, blocks = timed_blocks(tr.step, steps, 20, dev)
+    med, blocks = timed_blocks(tr.step, steps, a.warmup if main_line else 20, dev, max_blocks=1 if main_line else 50)
     per_step = med / steps
+    outputs = {k: v.cpu() for k, v in trainer_outputs(tr).items()} if main_line and a.dump_outputs else None
     gen.base_sde.set_shard(rank * B_C2, 2)
     smp = GraphedEMSampler(gen, B_C2, sample_steps)
     x0 = gen.latent_sample(B_C2, 2)
@@ -357,6 +403,8 @@ def leg_mlp(a, rank, world, dev, steps=200, sample_steps=200):
                            "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": flop / tk / 1e12 / PEAK_F32_MFMA_TFLOPS,
                            "kernel_ms": tk * 1e3, "flop_per_launch": flop,
                            "traffic": 40.1e6, "traffic_source": "profiles/r01_pmc_traffic.json (round-1 PMC pass, not measured in this run)"}
+    if outputs is not None:
+        out["outputs"] = outputs
     del tr, smp
     return out
 
@@ -639,8 +687,14 @@ def worker(a):
            "dtype": "f32", "data": "synthetic"}
     solo = rank == 0 and world == 1
 
+    def dump(r):
+        outputs = r.pop("outputs", None)
+        if outputs is not None and rank == 0:
+            dump_outputs(a.dump_outputs, outputs)
+
     if w == "c2":
-        r = leg_mlp(a, rank, world, dev, steps=a.steps)
+        r = leg_mlp(a, rank, world, dev, steps=a.steps, main_line=True)
+        dump(r)
         out.update(metric="score-matching train steps/sec (+ reverse-SDE sample steps/sec)", value=r["train_steps_per_s"],
                    unit="train_steps/s (B=65536 per step per GPU)", ms_per_step=r["ms_per_step"], scaling="weak",
                    config={"workload": r["workload"], "global_batch": B_C2 * world, "parallelism": f"dp{world}"},
@@ -648,7 +702,8 @@ def worker(a):
                    cpu_baseline=cpu_baseline_mlp() if solo and not a.no_cpu_baseline else None)
     elif w == "c5":
         gen, d = build_unet("c5", dev)
-        r = leg_sample_unet(gen, d, a, rank, world, dev)
+        r = leg_sample_unet(gen, d, a, rank, world, dev, main_line=True)
+        dump(r)
         out.update(metric="reverse-SDE sample steps/sec", value=r["sample_steps_per_s"], unit="EM steps/s (8192 samples per step)",
                    steps=a.sample_steps, warmup=1, ms_per_step=r["ms_per_sample_step"], scaling="strong",
                    config={"workload": r["workload"], "parallelism": f"dp{world}", "rows_per_gpu": r["rows_per_gpu"]},
@@ -658,7 +713,8 @@ def worker(a):
                    cpu_baseline=None)
     else:
         log(f"{w}: training leg")
-        r, gen, d = leg_train_unet(w, a, rank, world, dev)
+        r, gen, d = leg_train_unet(w, a, rank, world, dev, main_line=True)
+        dump(r)
         name = {"c3": "C3: UNet1D L=1024, batch 4096/GPU, SGM, SSM + Adam",
                 "c4": "C4: VorticityUNet 2-D 64x64x3 (4.02 M params), GLOBAL batch 256, SGM, SSM loss + Adam"}[w]
         out.update(metric="score-matching train steps/sec (+ reverse-SDE sample steps/sec)", value=r["value"],
@@ -760,6 +816,8 @@ def main():
     ap.add_argument("--sample-steps", type=int, default=20, help="EM steps of the C5 leg (0 = skip it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the C2 / C3 extra legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the main line's last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all)")
     a = ap.parse_args()
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus > 1 and env_world == 1 and "RANK" not in os.environ:
