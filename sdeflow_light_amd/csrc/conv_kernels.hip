@@ -18,6 +18,7 @@
 // second half of the batch (n >= n_bias): convolutions are linear, only the bias
 // distinguishes the halves.
 #include "common.h"
+#include <algorithm>
 #include <type_traits>
 #include <stdlib.h>
 
@@ -1027,14 +1028,78 @@ __device__ __forceinline__ void wino_patch_load(f32x4 (&d)[4][4], const float* _
   }
 }
 
+// Output transform Y = A^T M A per (tile, co quad) and the epilogue of k_conv_tile (bias / per-sample bias / accumulate /
+// residual / channel statistics), 2x2 pixels x 4 consecutive output channels per lane and co tile; shared by every
+// Winograd kernel, so their results agree bit for bit for the same accumulators.
+template <int NCO>
+__device__ __forceinline__ void wino_epilogue(const ConvArgs& A, const f32x4 (&acc)[16][NCO], int n, int y0, int x0, int ty, int tx,
+                                              int co0, int slot, int lane) {
+  const ConvGeom g = A.g;
+  const int il = lane & 15, q = lane >> 4;
+  const bool primal = n < A.n_bias;
+  const bool vec = (A.Cout & 3) == 0;
+#pragma unroll
+  for (int c = 0; c < NCO; ++c) {
+    const int co = co0 + 16 * c + 4 * q;
+    if (co >= A.Cout) continue;
+    const bool full = vec && (co + 3 < A.Cout);
+    f32x4 add = {0.f, 0.f, 0.f, 0.f};
+    if (primal && A.bias) {
+      if (full) add = *reinterpret_cast<const f32x4*>(A.bias + co);
+      else
+#pragma unroll
+        for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] = A.bias[co + r];
+    }
+    if (A.samp_bias && n < A.n_samp) {
+      const float* sbp = A.samp_bias + (size_t)n * A.Cout + co;
+      if (full) add += *reinterpret_cast<const f32x4*>(sbp);
+      else
+#pragma unroll
+        for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] += sbp[r];
+    }
+    f32x4 t0[4], t1[4];
+#pragma unroll
+    for (int nu = 0; nu < 4; ++nu) {
+      t0[nu] = acc[nu][c] + acc[4 + nu][c] + acc[8 + nu][c];
+      t1[nu] = acc[4 + nu][c] - acc[8 + nu][c] - acc[12 + nu][c];
+    }
+    f32x4 Y[2][2];
+    Y[0][0] = t0[0] + t0[1] + t0[2]; Y[0][1] = t0[1] - t0[2] - t0[3];
+    Y[1][0] = t1[0] + t1[1] + t1[2]; Y[1][1] = t1[1] - t1[2] - t1[3];
+    f32x4 cs = {0.f, 0.f, 0.f, 0.f}, css = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const int oy = y0 + 2 * ty + dy, ox = x0 + 2 * tx + dx;
+        if (oy >= g.Ho || ox >= g.Wo) continue;
+        const size_t m = ((size_t)n * g.Ho + oy) * g.Wo + ox;
+        f32x4 v = Y[dy][dx] + add;
+        float* op = A.out + m * A.Cout + co;
+        if (full) {
+          if (A.accumulate) v += *reinterpret_cast<const f32x4*>(op);
+          if (A.residual) v += *reinterpret_cast<const f32x4*>(A.residual + (op - A.out));
+          *reinterpret_cast<f32x4*>(op) = v;
+          cs += v; css += v * v;
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (co + r < A.Cout) op[r] = (A.accumulate ? op[r] + v[r] : v[r]) + (A.residual ? A.residual[(op - A.out) + r] : 0.f);
+        }
+      }
+    // the wave's 16 Winograd tiles = 64 pixels: one statistics slot, as the direct kernel's 16x16 tiles (Cout % 4 == 0, host)
+    if (A.cstat) cstat_store(A, n, slot, co, cs, css, il);
+  }
+}
+
 // ------------------------------------------------------------------ Winograd F(2x2, 3x3) forward (sampler path)
 // The reverse-SDE sampler spends 55 % of a step in stride-1 3x3 convolutions (C5, rocprofv3), a third of that in the
 // 32-output-channel layers where the direct halo-tile kernel reaches only ~65 TFLOP/s (the halo staging is amortised over
 // half as many MFMAs).  For those convolutions the minimal-filtering form Y = A^T [ (G g G^T) o (B^T d B) ] A computes a
 // 2x2 output tile from a 4x4 input patch with 16 instead of 36 multiplications per (co, ci): 2.25x fewer MFMAs, all in
 // fp32 (the transforms are additions and halvings; the result differs from the direct form by fp32 rounding only —
-// measured in tests/test_conv_gpu.py).  No tangent-specific code (tangent rows are batch rows); r3: the training step's forward
-// and dgrad (flipped, transposed kernel image) run on it as well, the weight gradients keep their own kernels.
+// measured in tests/test_conv_gpu.py).  No tangent-specific code (tangent rows are batch rows).  The training step's forward
+// and dgrad (flipped, transposed kernel image), which carry no folded input transform, run on k_conv_wino_pipe below.
 //   * workgroup = 16x16 output pixels = 8x8 Winograd tiles x 32 output channels, the (16+2)^2 halo of a 32-channel chunk
 //     staged in LDS exactly as k_conv_tile does (same fused GroupNorm(+SiLU) input transform, two sources, folded
 //     2x upsample);
@@ -1257,62 +1322,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, i
       }
     }
 
-  // ---- output transform Y = A^T M A per (tile, co quad) and the epilogue of k_conv_tile (bias / per-sample bias /
-  //      accumulate / residual), 2x2 pixels x 4 consecutive output channels per lane and co tile
-  const bool primal = n < A.n_bias;
-  const bool vec = (A.Cout & 3) == 0;
-#pragma unroll
-  for (int c = 0; c < NCO; ++c) {
-    const int co = co0 + 16 * c + 4 * q;
-    if (co >= A.Cout) continue;
-    const bool full = vec && (co + 3 < A.Cout);
-    f32x4 add = {0.f, 0.f, 0.f, 0.f};
-    if (primal && A.bias) {
-      if (full) add = *reinterpret_cast<const f32x4*>(A.bias + co);
-      else
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] = A.bias[co + r];
-    }
-    if (A.samp_bias && n < A.n_samp) {
-      const float* sbp = A.samp_bias + (size_t)n * A.Cout + co;
-      if (full) add += *reinterpret_cast<const f32x4*>(sbp);
-      else
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] += sbp[r];
-    }
-    f32x4 t0[4], t1[4];
-#pragma unroll
-    for (int nu = 0; nu < 4; ++nu) {
-      t0[nu] = acc[nu][c] + acc[4 + nu][c] + acc[8 + nu][c];
-      t1[nu] = acc[4 + nu][c] - acc[8 + nu][c] - acc[12 + nu][c];
-    }
-    f32x4 Y[2][2];
-    Y[0][0] = t0[0] + t0[1] + t0[2]; Y[0][1] = t0[1] - t0[2] - t0[3];
-    Y[1][0] = t1[0] + t1[1] + t1[2]; Y[1][1] = t1[1] - t1[2] - t1[3];
-    f32x4 cs = {0.f, 0.f, 0.f, 0.f}, css = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 2; ++dx) {
-        const int oy = y0 + 2 * ty + dy, ox = x0 + 2 * tx + dx;
-        if (oy >= g.Ho || ox >= g.Wo) continue;
-        const size_t m = ((size_t)n * g.Ho + oy) * g.Wo + ox;
-        f32x4 v = Y[dy][dx] + add;
-        float* op = A.out + m * A.Cout + co;
-        if (full) {
-          if (A.accumulate) v += *reinterpret_cast<const f32x4*>(op);
-          if (A.residual) v += *reinterpret_cast<const f32x4*>(A.residual + (op - A.out));
-          *reinterpret_cast<f32x4*>(op) = v;
-          cs += v; css += v * v;
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (co + r < A.Cout) op[r] = (A.accumulate ? op[r] + v[r] : v[r]) + (A.residual ? A.residual[(op - A.out) + r] : 0.f);
-        }
-      }
-    // the wave's 16 Winograd tiles = 64 pixels: one statistics slot, as the direct kernel's 16x16 tiles (Cout % 4 == 0, host)
-    if (A.cstat) cstat_store(A, n, (tile - n * tiles_x * tiles_y) * 4 + w, co, cs, css, il);
-  }
+  wino_epilogue<NCO>(A, acc, n, y0, x0, ty, tx, co0, (tile - n * tiles_x * tiles_y) * 4 + w, lane);
 }
 
 // ------------------------------------------------------------------ Winograd, 32 input channels: persistent workgroups
@@ -1412,7 +1422,6 @@ __global__ void __launch_bounds__(256, 1) k_conv_wino_p32(ConvArgs A, int tiles_
   float* cur = hb0;
   float* nxt = hb1;
   const int ngrp = (C + 15) >> 4;
-  const bool vec = (A.Cout & 3) == 0;
   for (; t < n_tiles; t += gridDim.x) {
     const int tn = t + gridDim.x;
     const bool more = tn < n_tiles;
@@ -1462,61 +1471,183 @@ __global__ void __launch_bounds__(256, 1) k_conv_wino_p32(ConvArgs A, int tiles_
     // ---- output transform and epilogue (as k_conv_wino)
     int n, y0, x0;
     origin(t, n, y0, x0);
-    const bool primal = n < A.n_bias;
-#pragma unroll
-    for (int c = 0; c < NCO; ++c) {
-      const int co = 16 * c + 4 * q;
-      if (co >= A.Cout) continue;
-      const bool full = vec && (co + 3 < A.Cout);
-      f32x4 add = {0.f, 0.f, 0.f, 0.f};
-      if (primal && A.bias) {
-        if (full) add = *reinterpret_cast<const f32x4*>(A.bias + co);
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] = A.bias[co + r];
-      }
-      if (A.samp_bias && n < A.n_samp) {
-        const float* sbp = A.samp_bias + (size_t)n * A.Cout + co;
-        if (full) add += *reinterpret_cast<const f32x4*>(sbp);
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] += sbp[r];
-      }
-      f32x4 t0[4], t1[4];
-#pragma unroll
-      for (int nu = 0; nu < 4; ++nu) {
-        t0[nu] = acc[nu][c] + acc[4 + nu][c] + acc[8 + nu][c];
-        t1[nu] = acc[4 + nu][c] - acc[8 + nu][c] - acc[12 + nu][c];
-      }
-      f32x4 Y[2][2];
-      Y[0][0] = t0[0] + t0[1] + t0[2]; Y[0][1] = t0[1] - t0[2] - t0[3];
-      Y[1][0] = t1[0] + t1[1] + t1[2]; Y[1][1] = t1[1] - t1[2] - t1[3];
-      f32x4 cs = {0.f, 0.f, 0.f, 0.f}, css = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx) {
-          const int oy = y0 + 2 * ty + dy, ox = x0 + 2 * tx + dx;
-          if (oy >= g.Ho || ox >= g.Wo) continue;
-          const size_t m = ((size_t)n * g.Ho + oy) * g.Wo + ox;
-          f32x4 v = Y[dy][dx] + add;
-          float* op = A.out + m * A.Cout + co;
-          if (full) {
-            if (A.accumulate) v += *reinterpret_cast<const f32x4*>(op);
-            if (A.residual) v += *reinterpret_cast<const f32x4*>(A.residual + (op - A.out));
-            *reinterpret_cast<f32x4*>(op) = v;
-            cs += v; css += v * v;
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (co + r < A.Cout) op[r] = (A.accumulate ? op[r] + v[r] : v[r]) + (A.residual ? A.residual[(op - A.out) + r] : 0.f);
-          }
-        }
-      if (A.cstat) cstat_store(A, n, (t - n * tiles_x * tiles_y) * 4 + w, co, cs, css, il);
-    }
+    wino_epilogue<NCO>(A, acc, n, y0, x0, ty, tx, 0, (t - n * tiles_x * tiles_y) * 4 + w, lane);
     if (more) stage_store(nxt);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");               // the other buffer is complete; this one is free
     float* sw = cur; cur = nxt; nxt = sw;
+  }
+}
+
+// ------------------------------------------------------------------ Winograd F(2x2,3x3), training path: a pipelined stream of channel groups
+// Every training forward and dgrad (no folded input transform: the training step runs its own GroupNorm, a dgrad reads a
+// cotangent) takes this kernel.  The k_conv_wino forms above stage each 32-channel halo synchronously (global -> registers
+// -> LDS, the whole workgroup waiting), drain vmcnt twice per 16-channel group and compute ONE 16x16 tile per workgroup, so
+// the prologue and the epilogue of every tile are exposed (MfmaUtil 20-48 %, profiles/r03/pmc_c4_step.json).  Here:
+//   * the halo of ONE 16-channel group (18 x 18 pixels x 64 B, unpadded) travels global -> LDS by LDS-DMA like the weights:
+//     21 pieces of 1 KB, lane-linear in LDS.  Lane l of piece m fills 16-B slot s = 64 m + l with channel quad
+//     (s & 3) ^ ((P >> 1) & 3) of halo pixel P = s >> 2 — the swizzle is chosen by the per-lane SOURCE address, so the patch
+//     reads cost what the padded CT_P image did (384 LDS cycles per wave and group, counted from the ds_read_b128 lane groups);
+//     the zero border, the folded 2x upsample (iy >> 1) and the second source are per-lane source addresses too;
+//   * a workgroup walks a list of (tile, output-channel block) items — the XCD-aware order of k_conv_wino, blockIdx.x & 7
+//     picks the XCD, so the n_cob blocks of a tile stay on one XCD — and the stream of channel groups runs on across item
+//     boundaries: group k + 1's halo (the next item's group 0 at the end of an item) is requested while group k computes;
+//   * per half-group (8 positions, 64 MFMAs per wave) one raw barrier.  Issue order per group: weights of half 1, then the
+//     next group's halo; half 1 waits vmcnt(5) (every wave issues 5 or 6 halo pieces, all younger), half 0 vmcnt(0);
+//   * LDS: 2 x 16 KB weight halves + 2 x 21 KB halo stages = 74 KB: two workgroups per CU.
+// The arithmetic is that of k_conv_wino: the same transforms, channel groups in ascending order and r = 0..3 per position,
+// the same epilogue (wino_epilogue) — equal outputs, bit for bit (tests/test_wino_pipe_gpu.py).
+constexpr int WP_HPIECES = 21;                                // ceil(18 * 18 pixels * 4 quads / 64 lanes)
+constexpr int WP_HSTAGE = WP_HPIECES * 64 * 4;                // floats per halo stage
+constexpr int WP_LDS_BYTES = (2 * 4096 + 2 * WP_HSTAGE) * (int)sizeof(float);
+__device__ __attribute__((aligned(16))) float g_wino_zero[4];  // what an out-of-image (or padding) halo slot fetches
+
+__global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles_x, int tiles_y, int n_tiles, int n_cob) {
+  extern __shared__ __attribute__((aligned(16))) float cw_lds[];
+  constexpr int NCO = 2, HW = 18;
+  const int tid = threadIdx.x, lane = tid & 63, il = lane & 15, q = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const ConvGeom g = A.g;
+  float* wbuf = cw_lds;                                     // [2 halves][8 positions][2 co tiles][64 lanes][4]
+  float* hbuf = cw_lds + 2 * 4096;                          // [2 stages][WP_HPIECES x 64 slots][4]
+  const int xcd = blockIdx.x & 7, loc_stride = gridDim.x >> 3;
+  int loc = blockIdx.x >> 3;
+  int tile = (loc / n_cob) * 8 + xcd, cob = loc % n_cob;
+  if (tile >= n_tiles) return;
+  const int ngrp = A.Ktot >> 4, tpi = tiles_x * tiles_y, up = g.ups ? 1 : 0;
+  const size_t a_co_stride = (size_t)16 * A.Ktot, pos_stride = (size_t)A.CoutP * A.Ktot;
+  // this lane's Winograd tile: as k_conv_wino; its patch starts at halo pixel P0 (even), so the quad swizzle of patch row i,
+  // columns j = 0, 1 is (h0 + i) & 3 and of columns 2, 3 (h0 + i + 1) & 3
+  const int tt = 16 * w + il, ty = tt >> 3, tx = tt & 7;
+  const int P0 = 2 * ty * HW + 2 * tx, h0 = (P0 >> 1) & 3;
+
+  // half `half` of channel group grp_'s weights for output-channel block cob_: as k_conv_wino's WL form
+  auto wfill = [&](int cob_, int grp_, int half) __attribute__((always_inline)) {
+    const float* src = A.Wp + (size_t)(cob_ * (NCO * 16) + il) * A.Ktot + 16 * grp_ + 4 * q + (size_t)(8 * half) * pos_stride;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int pw = 4 * w + j;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(pw >> 1) * pos_stride + (pw & 1) * a_co_stride),
+                                       (__attribute__((address_space(3))) void*)(wbuf + half * 4096 + pw * 256), 16, 0, 0);
+    }
+  };
+  // channel group grp_'s halo of tile tile_ into stage b: wave w copies pieces w, w + 4, ... (6 for wave 0, 5 for the others)
+  // (branch-free: the source of each lane is a select between its pixel and the zero row)
+  const int Hu = g.Hi << up, Wu = g.Wi << up;
+  auto hfill = [&](int tile_, int grp_, int b) __attribute__((always_inline)) {
+    const int n = tile_ / tpi, r = tile_ - n * tpi, ty_i = r / tiles_x, y0 = ty_i * 16, x0 = (r - ty_i * tiles_x) * 16;
+    const bool s1 = 16 * grp_ >= A.C[0];                    // channel groups of the second source follow the first's (C0 % 16 == 0)
+    const int C = s1 ? A.C[1] : A.C[0];
+    const float* base = (s1 ? A.src[1] : A.src[0]) + (size_t)n * g.Hi * g.Wi * C + (16 * grp_ - (s1 ? A.C[0] : 0));
+#pragma unroll
+    for (int j = 0; j < (WP_HPIECES + 3) / 4; ++j) {
+      const int m = w + 4 * j;
+      if (m < WP_HPIECES) {
+        const int sl = 64 * m + lane, P = sl >> 2, c = (sl & 3) ^ ((P >> 1) & 3);
+        const int hy = P / HW, hx = P - hy * HW, iy = y0 + hy - 1, ix = x0 + hx - 1;
+        const bool in = P < HW * HW && (unsigned)iy < (unsigned)Hu && (unsigned)ix < (unsigned)Wu;
+        const float* p = in ? base + (((iy >> up) * g.Wi + (ix >> up)) * C + 4 * c) : g_wino_zero;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p,
+                                         (__attribute__((address_space(3))) void*)(hbuf + b * WP_HSTAGE + m * 256), 16, 0, 0);
+      }
+    }
+  };
+
+  f32x4 acc[16][NCO];
+#pragma unroll
+  for (int p = 0; p < 16; ++p)
+#pragma unroll
+    for (int c = 0; c < NCO; ++c) acc[p][c] = f32x4{0, 0, 0, 0};
+  int grp = 0, hb = 0;
+  wfill(cob, 0, 0);
+  hfill(tile, 0, 0);
+  for (;;) {
+    // the group that follows this one: the next channel group of this item, or group 0 of the workgroup's next item
+    int nloc = loc, ntile = tile, ncob = cob, ngrp_ = grp + 1;
+    if (ngrp_ == ngrp) {
+      ngrp_ = 0; nloc = loc + loc_stride;
+      ntile = (nloc / n_cob) * 8 + xcd; ncob = nloc % n_cob;
+    }
+    const bool more = ntile < n_tiles;
+    f32x4 d[4][4];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      // this half-group's weights (and at half 0 this group's halo) have landed — every wave waits for its own pieces, then
+      // all meet; the reads of the buffers refilled below are behind the same barrier
+      if (half == 1 && more) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if (half == 0) {
+        wfill(cob, grp, 1);
+        if (more) hfill(ntile, ngrp_, hb ^ 1);
+      } else if (more) {
+        wfill(ncob, ngrp_, 0);
+      }
+      if (half == 0) {
+        // ---- the lane's 4x4 patch (4 channels) and its transform V = B^T d B, in place (as k_conv_wino)
+        const float* hs = hbuf + hb * WP_HSTAGE;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float* rp = hs + 16 * (P0 + i * HW) + 4 * (q ^ ((h0 + i) & 3));
+          d[i][0] = *reinterpret_cast<const f32x4*>(rp);
+          d[i][1] = *reinterpret_cast<const f32x4*>(rp + 16);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) d[i][2 + j][r] = dpp_from_next_lane(d[i][j][r]);
+        if (tx == 7) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float* rp = hs + 16 * (P0 + i * HW + 2) + 4 * (q ^ ((h0 + i + 1) & 3));
+            d[i][2] = *reinterpret_cast<const f32x4*>(rp);
+            d[i][3] = *reinterpret_cast<const f32x4*>(rp + 16);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const f32x4 r0 = d[0][j] - d[2][j], r1 = d[1][j] + d[2][j], r2 = d[2][j] - d[1][j], r3 = d[1][j] - d[3][j];
+          d[0][j] = r0; d[1][j] = r1; d[2][j] = r2; d[3][j] = r3;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const f32x4 c0_ = d[i][0] - d[i][2], c1_ = d[i][1] + d[i][2], c2_ = d[i][2] - d[i][1], c3_ = d[i][1] - d[i][3];
+          d[i][0] = c0_; d[i][1] = c1_; d[i][2] = c2_; d[i][3] = c3_;
+        }
+      }
+      const float* wb = wbuf + half * 4096 + lane * 4;
+      f32x4 a0 = *reinterpret_cast<const f32x4*>(wb), a1 = *reinterpret_cast<const f32x4*>(wb + 256);
+#pragma unroll
+      for (int pl = 0; pl < 8; ++pl) {
+        const f32x4 x0_ = a0, x1_ = a1;
+        if (pl < 7) {
+          a0 = *reinterpret_cast<const f32x4*>(wb + (2 * pl + 2) * 256);
+          a1 = *reinterpret_cast<const f32x4*>(wb + (2 * pl + 3) * 256);
+        }
+        const int pos = 8 * half + pl;
+        const f32x4 b = d[pos >> 2][pos & 3];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          acc[pos][0] = mfma16c(x0_[r], b[r], acc[pos][0]);
+          acc[pos][1] = mfma16c(x1_[r], b[r], acc[pos][1]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (ngrp_ == 0) {
+      // ---- the item is complete.  Wait states for the VALU reads of the last MFMAs' results are written out: the epilogue is
+      //      a branch target, where hipcc has been seen to insert none
+      asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      const int n = tile / tpi, r = tile - n * tpi, ty_i = r / tiles_x;
+      wino_epilogue<NCO>(A, acc, n, ty_i * 16, (r - ty_i * tiles_x) * 16, ty, tx, cob * (NCO * 16), r * 4 + w, lane);
+      if (!more) break;
+#pragma unroll
+      for (int p = 0; p < 16; ++p)
+#pragma unroll
+        for (int c = 0; c < NCO; ++c) acc[p][c] = f32x4{0, 0, 0, 0};
+    }
+    loc = nloc; tile = ntile; cob = ncob; grp = ngrp_; hb ^= 1;
   }
 }
 
@@ -2456,6 +2587,21 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
   const int tiles_x = geom->Wo / 16, tiles_y = geom->Ho / 16;
   if (fuse && fuse->chanstats) { A.cstat = fuse->chanstats; A.cs_S = tiles_x * tiles_y * 4; }   // [N][Ho/16 * Wo/16 * 4][2][Cout]
   const int n_tiles = tiles_x * tiles_y * geom->N, gy = CoutP / 32;
+  static const int n_cu = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
+  if (!A.in_scale) {
+    // no folded input transform (every training forward and dgrad): the pipelined stream of channel groups, two
+    // workgroups per CU, each walking (tile, output-channel block) items of one XCD
+    static const int once_pipe = [] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_wino_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, WP_LDS_BYTES);
+      return 0;
+    }();
+    (void)once_pipe;
+    const int items_per_xcd = gy * ((n_tiles + 7) / 8);
+    const int wg_per_xcd = std::min(items_per_xcd, std::max(1, 2 * n_cu / 8));
+    hipLaunchKernelGGL(k_conv_wino_pipe, dim3((unsigned)(8 * wg_per_xcd)), dim3(256), WP_LDS_BYTES, S(stream), A, tiles_x, tiles_y, n_tiles, gy);
+    return msgm_check_launch();
+  }
+  // with a folded GroupNorm (+ SiLU) input transform (the sampler): the halo is transformed in registers on its way to LDS
   const size_t lds = (size_t)18 * 18 * CT_P * sizeof(float);
   dim3 grid((unsigned)(8 * gy * ((n_tiles + 7) / 8)));
   // one 32-channel chunk (Ktot = 32: the 64x64 32 -> 32 layers) has nothing to pipeline and pays the extra barriers: 96 vs
@@ -2470,7 +2616,6 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
       return 0;
     }();
     (void)once32;
-    static const int n_cu = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
     const size_t lds32 = ((size_t)2 * 16 * 2 * 256 + 2 * 18 * 18 * CT_P) * sizeof(float);
     hipLaunchKernelGGL(k_conv_wino_p32, dim3((unsigned)n_cu), dim3(256), lds32, S(stream), A, tiles_x, tiles_y, n_tiles);
     return msgm_check_launch();
