@@ -569,6 +569,29 @@ int msgm_attention_dual_backward(const float* qkv, const float* att, const float
                                  int64_t Bp, int32_t T, int32_t C, float scale, void* workspace, size_t workspace_bytes,
                                  msgm_stream_t stream);
 
+/* Multi-head forms of the three fused attention entries above (AttentionBlock with num_heads = heads, model/unet.py:220-250).
+ * C = heads * D.  The reference reshapes qkv (B, 3C, T) to (B*heads, 3D, T), so head h owns the qkv channels [3Dh, 3D(h+1)):
+ * q = the first D of them, k the next D, v the last D — NOT "split q | k | v, then split each into heads".  In the channels-last
+ * layout qkv [N][T][3C] head h's q starts at column 3Dh, k at 3Dh + D, v at 3Dh + 2D (row stride 3C).  Its output goes to the
+ * columns [Dh, D(h+1)) of att [N][T][C] (h.reshape(B, -1, T)).  scale = D^-1/2 (the two D^-1/4 of QKVAttention).
+ * stats of the dual forward are [2][Bp*heads*T] (lse | rbar per (sample, head) pair and query); the backward's workspace holds
+ * the row scalars and query-gradient slabs per pair (msgm_attention_dual_mh_workspace).  Same arithmetic per head as the
+ * single-head kernels at C = D, same fixed summation order, no float atomics: bitwise repeatable.  With heads = 1 and a
+ * shape the single-head entries support, these run the single-head entries themselves (bitwise identical).
+ * Built for D in {16, 32, 64, 128}, heads in [1, 64] and the T rules of the single-head entries at C = D (T a multiple of 64;
+ * of 32 at D = 128 on the dual path); other shapes return MSGM_E_UNSUPPORTED and the caller composes msgm_bmm +
+ * msgm_softmax_dual_* per head. */
+int msgm_attention_mh_supported(int32_t T, int32_t heads, int32_t D);
+int msgm_attention_mh_forward(const float* qkv, float* out, int64_t N, int32_t T, int32_t heads, int32_t D, float scale,
+                              msgm_stream_t stream);
+int msgm_attention_dual_mh_supported(int32_t T, int32_t heads, int32_t D);
+size_t msgm_attention_dual_mh_workspace(int64_t Bp, int32_t T, int32_t heads, int32_t D);   /* bytes, for the backward */
+int msgm_attention_dual_mh_forward(const float* qkv, float* att, float* stats, int64_t Bp, int32_t T, int32_t heads, int32_t D,
+                                   float scale, msgm_stream_t stream);
+int msgm_attention_dual_mh_backward(const float* qkv, const float* att, const float* datt, const float* stats, float* dqkv,
+                                    int64_t Bp, int32_t T, int32_t heads, int32_t D, float scale, void* workspace,
+                                    size_t workspace_bytes, msgm_stream_t stream);
+
 /* ---- reporting metric next to the hot path -------------------- */
 /* RBF kernel of compute_kernel / compute_mmd (quantitative_comparison.py:22-46):
  * k(x_i, y_j) = exp(-sum_d (x_i - y_j)^2 / d^2) for x [Nx][d], y [Ny][d].  K (may be NULL) receives the

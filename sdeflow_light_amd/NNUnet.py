@@ -72,9 +72,14 @@ class ResBlock(nn.Module):
 
 
 class AttentionBlock(nn.Module):
-    def __init__(self, channels):
+    """model/unet.py:197-231.  num_heads splits the C channels into heads of D = C / num_heads: head h owns the qkv channels
+    [3Dh, 3D(h+1)) (q | k | v of D each; qkv.reshape(B*H, 3D, T), unet.py:225) and the output channels [Dh, D(h+1))."""
+
+    def __init__(self, channels, num_heads=1):
         super().__init__()
-        self.channels = channels
+        if num_heads < 1 or channels % num_heads != 0:
+            raise MsgmError(f"AttentionBlock: {channels} channels do not split into num_heads = {num_heads} heads")
+        self.channels, self.num_heads = channels, num_heads
         self.norm = _norm(channels)
         self.qkv = nn.Conv1d(channels, channels * 3, 1)
         self.proj_out = zero_module(nn.Conv1d(channels, channels, 1))
@@ -93,16 +98,19 @@ class Upsample(nn.Module):
 
 
 class UNetModelWithLogNorm(nn.Module):
-    """Topology of UNetModel.__init__ (model/unet.py:300-446) at the options the
-    driver uses (dims=2, conv_resample, 1 head, no scale-shift norm, no classes)."""
+    """Topology of UNetModel.__init__ (model/unet.py:300-446) for dims=2, conv_resample, dropout 0, no scale-shift
+    norm, no classes; any num_heads / num_heads_upsample whose heads divide the channel counts of the attention blocks."""
 
     def __init__(self, in_channels, model_channels, out_channels, in_space, num_res_blocks, attention_resolutions,
                  dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None, use_checkpoint=False,
                  num_heads=1, num_heads_upsample=-1, use_scale_shift_norm=False, learn_potential=False, use_log_norm=False):
         super().__init__()
-        if dims != 2 or not conv_resample or num_classes is not None or num_heads != 1 or use_scale_shift_norm or \
-                learn_potential or dropout != 0:
-            raise MsgmError("HIP U-Net is built for the driver's options (dims=2, conv_resample, 1 head, dropout 0)")
+        if dims != 2 or not conv_resample or num_classes is not None or use_scale_shift_norm or learn_potential or dropout != 0:
+            raise MsgmError("HIP U-Net is built for the driver's options (dims=2, conv_resample, dropout 0, no scale-shift norm, "
+                            "no learn_potential, no classes)")
+        if num_heads_upsample == -1:                                    # model/unet.py:321-322
+            num_heads_upsample = num_heads
+        self.num_heads, self.num_heads_upsample = num_heads, num_heads_upsample
         self.use_log_norm = use_log_norm
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.channel_mult, self.num_res_blocks = tuple(channel_mult), num_res_blocks
@@ -119,21 +127,21 @@ class UNetModelWithLogNorm(nn.Module):
                 layers = [ResBlock(ch, ted, mult * model_channels)]
                 ch = mult * model_channels
                 if ds in attention_resolutions:
-                    layers.append(AttentionBlock(ch))
+                    layers.append(AttentionBlock(ch, num_heads))
                 self.input_blocks.append(nn.Sequential(*layers))
                 chans.append(ch)
             if level != len(channel_mult) - 1:
                 self.input_blocks.append(nn.Sequential(Downsample(ch)))
                 chans.append(ch)
                 ds *= 2
-        self.middle_block = nn.Sequential(ResBlock(ch, ted, ch), AttentionBlock(ch), ResBlock(ch, ted, ch))
+        self.middle_block = nn.Sequential(ResBlock(ch, ted, ch), AttentionBlock(ch, num_heads), ResBlock(ch, ted, ch))
         self.output_blocks = nn.ModuleList([])
         for level, mult in list(enumerate(channel_mult))[::-1]:
             for i in range(num_res_blocks + 1):
                 layers = [ResBlock(ch + chans.pop(), ted, model_channels * mult)]
                 ch = model_channels * mult
                 if ds in attention_resolutions:
-                    layers.append(AttentionBlock(ch))
+                    layers.append(AttentionBlock(ch, num_heads_upsample))
                 if level and i == num_res_blocks:
                     layers.append(Upsample(ch))
                     ds //= 2
@@ -178,6 +186,8 @@ class _Res:
 class _Attn:
     def __init__(self, m: AttentionBlock):
         self.m, self.c = m, m.channels
+        self.nh = m.num_heads
+        self.d = m.channels // m.num_heads             # channels per head
         self.qkv = ConvOp(m.qkv.weight, m.qkv.bias, "conv", (1,), 1, 0, [m.channels])
         self.proj = ConvOp(m.proj_out.weight, m.proj_out.bias, "conv", (1,), 1, 0, [m.channels])
         self.ops = [self.qkv, self.proj]
@@ -347,47 +357,64 @@ class VorticityUNet(nn.Module, FlatParamMixin):
 
     def _attn_fwd(self, a: _Attn, x, N, Bp, H, W, dual, tape):
         T, C = H * W, a.c
+        nh, D = a.nh, a.d                                                # heads, channels per head
         dev = x.device
-        s2 = 1.0 / math.sqrt(C)                                          # (ch^-1/4)^2           model/unet.py:245-248
-        if not dual and tape is None and ops.attention_supported(T, C):  # sampler: nothing to keep, no tangent
+        s2 = 1.0 / math.sqrt(D)                                          # (ch^-1/4)^2, ch = D   model/unet.py:245-248
+        fused = ops.attention_supported(T, C) if nh == 1 else ops.attention_mh_supported(T, nh, D)
+        if not dual and tape is None and fused:                          # sampler: nothing to keep, no tangent
             if a.qkv.can_transform_input(N, 1, T) and not os.environ.get("MSGM_NO_GN_FOLD"):
                 qkv, _, _ = a.qkv.forward([x], N, 1, T, Bp, in_affine=self._gn_fold(a.m.norm, x, Bp, T, C))   # GN folded in
             else:
                 hn, _ = self._gn(a.m.norm, x, Bp, T, C, False, False, None)
                 qkv, _, _ = a.qkv.forward([hn], N, 1, T, Bp)
-            att = ops.attention_forward(qkv, torch.empty(N * T * C, device=dev), N, T, C, s2)
+            if nh == 1:
+                att = ops.attention_forward(qkv, torch.empty(N * T * C, device=dev), N, T, C, s2)
+            else:
+                att = ops.attention_mh_forward(qkv, torch.empty(N * T * C, device=dev), N, T, nh, D, s2)
             out, _, _ = a.proj.forward([att], N, 1, T, Bp, residual=x, stats=True)    # x + proj(.) in the epilogue (unet.py:232)
             return out
         hn, st = self._gn(a.m.norm, x, Bp, T, C, dual, False, tape)
-        qkv, _, _ = a.qkv.forward([hn], N, 1, T, Bp)                     # [N][T][3C]: q | k | v channel slices
-        if dual and ops.attention_dual_supported(T, C) and not os.environ.get("MSGM_NO_ATTN_DUAL"):
+        qkv, _, _ = a.qkv.forward([hn], N, 1, T, Bp)                     # [N][T][3C]: per head q | k | v channel slices
+        fused = ops.attention_dual_supported(T, C) if nh == 1 else ops.attention_dual_mh_supported(T, nh, D)
+        if dual and fused and not os.environ.get("MSGM_NO_ATTN_DUAL"):
             # training: ONE kernel for the six products of the dual forward, nothing of size (T,T) written; the
             # backward recomputes the logits from q, k and the per-query (log-sum-exp, rbar) kept here
-            att, stats = ops.attention_dual_forward(qkv, Bp, T, C, s2)
+            if nh == 1:
+                att, stats = ops.attention_dual_forward(qkv, Bp, T, C, s2)
+            else:
+                att, stats = ops.attention_dual_mh_forward(qkv, Bp, T, nh, D, s2)
             out, _, _ = a.proj.forward([att], N, 1, T, Bp, residual=x)
             if tape is not None:
                 tape.append(("attn", a, x, H, W, hn, st, qkv, None, None, stats, att))
             return out
+        # composed form, one bmm chain per head: head h reads q | k | v at columns 3Dh, 3Dh + D, 3Dh + 2D (contraction D),
+        # keeps its (T,T) tiles at offset h*Bp*T*T of S / Wd / Pd and writes att columns [Dh, D(h+1))
         ld = 3 * C
         half = Bp * T * ld                                               # offset of the tangent rows
-        S = torch.empty(Bp * T * T, device=dev)
+        btt = Bp * T * T
+        S = torch.empty(nh * btt, device=dev)
         sq, sk, sS = (T * ld, ld, 1), (T * ld, 1, ld), (T * T, T, 1)
-        ops.bmm(qkv, 0, qkv, C, S, 0, T, T, C, Bp, sq, sk, sS, alpha=s2)
+        for h in range(nh):
+            ops.bmm(qkv, 3 * D * h, qkv, 3 * D * h + D, S, h * btt, T, T, D, Bp, sq, sk, sS, alpha=s2)
         Wd = Pd = None
         if dual:
             Wd, Pd = torch.empty_like(S), torch.empty_like(S)
-            ops.bmm(qkv, half, qkv, C, Wd, 0, T, T, C, Bp, sq, sk, sS, alpha=s2,                     # qdot k^T + q kdot^T
-                    pair2=(qkv, 0, qkv, half + C))
-        ops.softmax_dual_forward(S, T, Wd, Pd)                           # S <- P
+            for h in range(nh):
+                qo, ko = 3 * D * h, 3 * D * h + D
+                ops.bmm(qkv, half + qo, qkv, ko, Wd, h * btt, T, T, D, Bp, sq, sk, sS, alpha=s2,     # qdot k^T + q kdot^T
+                        pair2=(qkv, qo, qkv, half + ko))
+        ops.softmax_dual_forward(S, T, Wd, Pd)                           # S <- P (every head's rows)
         att = torch.empty(N * T * C, device=dev)
         sP, sv, sa = (T * T, T, 1), (T * ld, ld, 1), (T * C, C, 1)
-        if dual:
-            # adot = P vdot + Pdot v and a = P v in ONE pass over P (msgm_bmm_dual)
-            offa = Bp * T * C
-            ops.bmm(S, 0, qkv, half + 2 * C, att, offa, T, C, T, Bp, sP, sv, sa, pair2=(Pd, 0, qkv, 2 * C),
-                    third=(qkv, 2 * C, att, 0))
-        else:
-            ops.bmm(S, 0, qkv, 2 * C, att, 0, T, C, T, Bp, sP, sv, sa)                               # a = P v
+        for h in range(nh):
+            vo, ao = 3 * D * h + 2 * D, D * h
+            if dual:
+                # adot = P vdot + Pdot v and a = P v in ONE pass over P (msgm_bmm_dual)
+                offa = Bp * T * C
+                ops.bmm(S, h * btt, qkv, half + vo, att, offa + ao, T, D, T, Bp, sP, sv, sa, pair2=(Pd, h * btt, qkv, vo),
+                        third=(qkv, vo, att, ao))
+            else:
+                ops.bmm(S, h * btt, qkv, vo, att, ao, T, D, T, Bp, sP, sv, sa)                       # a = P v
         out, _, _ = a.proj.forward([att], N, 1, T, Bp, residual=x)
         if tape is not None:
             tape.append(("attn", a, x, H, W, hn, st, qkv, S, Wd, Pd, att))
@@ -687,32 +714,44 @@ class VorticityUNet(nn.Module, FlatParamMixin):
     def _attn_bwd(self, r, dout, N, Bp):
         _, a, xin, H, W, hn, st, qkv, Pm, Wd, Pd, att = r
         T, C = H * W, a.c
+        nh, D = a.nh, a.d
         dev = dout.device
-        s2 = 1.0 / math.sqrt(C)
+        s2 = 1.0 / math.sqrt(D)
         ld = 3 * C
         half, offa = Bp * T * ld, Bp * T * C
         (datt,) = a.proj.backward(dout, [att], N, 1, T, Bp)             # [N][T][C]: abar | adotbar
         if Pm is None:                                                  # fused dual attention (Pd slot = its row stats)
-            dqkv = ops.attention_dual_backward(qkv, att, datt, Pd, Bp, T, C, s2)
+            if nh == 1:
+                dqkv = ops.attention_dual_backward(qkv, att, datt, Pd, Bp, T, C, s2)
+            else:
+                dqkv = ops.attention_dual_mh_backward(qkv, att, datt, Pd, Bp, T, nh, D, s2)
             (dhn,) = a.qkv.backward(dqkv, [hn], N, 1, T, Bp)
             return self._gn_bwd(a.m.norm, xin, st, dhn, Bp, T, C, False, residual=dout)     # x + proj(.): skip cotangent fused
         dqkv = torch.empty(N * T * ld, device=dev)                     # every slice is written exactly once below
         sP, sPt = (T * T, T, 1), (T * T, 1, T)                          # P(t,s) / P^T(s,t)
         sa, sq = (T * C, C, 1), (T * ld, ld, 1)
+        btt = Bp * T * T                                                # head h's (T,T) tiles start at h*btt
+        hoff = lambda h: (3 * D * h, 3 * D * h + D, 3 * D * h + 2 * D, D * h, h * btt)      # q, k, v, att, P offsets
         # vbar = P^T abar + Pdot^T adotbar ; vdotbar = P^T adotbar
-        ops.bmm(Pm, 0, datt, 0, dqkv, 2 * C, T, C, T, Bp, sPt, sa, sq, pair2=(Pd, 0, datt, offa),
-                third=(datt, offa, dqkv, half + 2 * C))                  # both from one pass over P^T
+        for h in range(nh):
+            qo, ko, vo, ao, po = hoff(h)
+            ops.bmm(Pm, po, datt, ao, dqkv, vo, T, D, T, Bp, sPt, sa, sq, pair2=(Pd, po, datt, offa + ao),
+                    third=(datt, offa + ao, dqkv, half + vo))            # both from one pass over P^T
         # Pbar = abar v^T + adotbar vdot^T ; Pdotbar = adotbar v^T
         Pb, Pdb = torch.empty_like(Pm), torch.empty_like(Pm)
         svT = (T * ld, 1, ld)                                            # B(k=c, j=s) = v[s][c]
-        ops.bmm(datt, 0, qkv, 2 * C, Pb, 0, T, T, C, Bp, sa, svT, sP, pair2=(datt, offa, qkv, half + 2 * C))
-        ops.bmm(datt, offa, qkv, 2 * C, Pdb, 0, T, T, C, Bp, sa, svT, sP)
+        for h in range(nh):
+            qo, ko, vo, ao, po = hoff(h)
+            ops.bmm(datt, ao, qkv, vo, Pb, po, T, T, D, Bp, sa, svT, sP, pair2=(datt, offa + ao, qkv, half + vo))
+            ops.bmm(datt, offa + ao, qkv, vo, Pdb, po, T, T, D, Bp, sa, svT, sP)
         ops.softmax_dual_backward(Pm, Wd, Pb, Pdb, T)                   # Pb <- Wbar, Pdb <- Wdotbar
-        # qbar = s2 (Wbar k + Wdotbar kdot) ; qdotbar = s2 Wdotbar k
-        ops.bmm(Pdb, 0, qkv, half + C, dqkv, 0, T, C, T, Bp, sP, sq, sq, alpha=s2, pair2=(Pb, 0, qkv, C),
-                third=(qkv, C, dqkv, half))                              # Wdotbar streamed once for both
-        # kbar = s2 (Wbar^T q + Wdotbar^T qdot) ; kdotbar = s2 Wdotbar^T q
-        ops.bmm(Pdb, 0, qkv, half, dqkv, C, T, C, T, Bp, sPt, sq, sq, alpha=s2, pair2=(Pb, 0, qkv, 0),
-                third=(qkv, 0, dqkv, half + C))
+        for h in range(nh):
+            qo, ko, vo, ao, po = hoff(h)
+            # qbar = s2 (Wbar k + Wdotbar kdot) ; qdotbar = s2 Wdotbar k
+            ops.bmm(Pdb, po, qkv, half + ko, dqkv, qo, T, D, T, Bp, sP, sq, sq, alpha=s2, pair2=(Pb, po, qkv, ko),
+                    third=(qkv, ko, dqkv, half + qo))                    # Wdotbar streamed once for both
+            # kbar = s2 (Wbar^T q + Wdotbar^T qdot) ; kdotbar = s2 Wdotbar^T q
+            ops.bmm(Pdb, po, qkv, half + qo, dqkv, ko, T, D, T, Bp, sPt, sq, sq, alpha=s2, pair2=(Pb, po, qkv, qo),
+                    third=(qkv, qo, dqkv, half + ko))
         (dhn,) = a.qkv.backward(dqkv, [hn], N, 1, T, Bp)
         return self._gn_bwd(a.m.norm, xin, st, dhn, Bp, T, C, False, residual=dout)

@@ -12,22 +12,32 @@
 // of the online softmax are per-lane scalars (+ two xor-shuffles across the four key groups), the rescale of O is a
 // per-lane multiply, and exp(S - m) is directly the B operand of the second product (same k-permutation trick as
 // the MLP kernel: MFMA step r of key tile kt contracts key 16kt + 4q + r on both operands).
+//
+// Multi-head (MH, AttentionBlock with num_heads = H, model/unet.py:220-250): qkv.reshape(B*H, 3C/H, T) gives head h the
+// qkv channels [3Dh, 3D(h+1)) (q | k | v of D = C/H each), and h.reshape(B, -1, T) puts its output at channels [Dh, D(h+1)).
+// The kernel body is the single-head one at channel count D; a workgroup serves one (sample, head) pair, reads rows of
+// stride 3C from column 3Dh and writes rows of stride C from column Dh.  MH = false is the single-head build (strides
+// compile-time 3C / C, no head index).
 #include "common.h"
 
 __device__ __forceinline__ f32x4 mfma16a(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-template <int CT, int QT>   // C = 16*CT channels; QT tiles of 16 queries per wave
-__global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv, float* __restrict__ out, int T, int nqb, float scale) {
-  constexpr int C = 16 * CT, KP = C + 4, LD = 3 * C;
+template <int CT, int QT, bool MH = false>   // C = 16*CT channels (per head); QT tiles of 16 queries per wave
+__global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv, float* __restrict__ out, int T, int nqb, float scale,
+                                                  int nh) {
+  constexpr int C = 16 * CT, KP = C + 4;
   constexpr int NV = (64 * C / 4) / 256;                  // float4 per thread per matrix and key block
+  static_assert(NV >= 1 && (64 * C / 4) % 256 == 0, "key block does not divide over the workgroup's threads");
+  const int LD = MH ? 3 * C * nh : 3 * C, LA = MH ? C * nh : C;   // qkv / out row strides
   extern __shared__ __attribute__((aligned(16))) float at_lds[];
   float* Ks = at_lds;
   float* Vs = at_lds + 64 * KP;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
-  const int smp = blockIdx.x / nqb, qb = blockIdx.x - smp * nqb;   // sample, query block of 64*QT
-  const float* base = qkv + (size_t)smp * T * LD;
+  const int pr = blockIdx.x / nqb, qb = blockIdx.x - pr * nqb;     // (sample, head) pair, query block of 64*QT
+  const int smp = MH ? pr / nh : pr, hd = MH ? pr - smp * nh : 0;
+  const float* base = qkv + (size_t)smp * T * LD + 3 * C * hd;
   const int q0 = (qb * 4 + w) * 16 * QT;                  // first query of this wave
 
   f32x4 qf[QT][CT], o[QT][CT];
@@ -123,7 +133,7 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv,
     lt += __shfl_xor(lt, 16, 64);
     lt += __shfl_xor(lt, 32, 64);
     const float inv = 1.0f / lt;
-    float* orow = out + ((size_t)smp * T + q0 + 16 * qt + il) * C;
+    float* orow = out + ((size_t)smp * T + q0 + 16 * qt + il) * LA + C * hd;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) *reinterpret_cast<f32x4*>(orow + 16 * ct + 4 * q) = o[qt][ct] * inv;
   }
@@ -131,19 +141,24 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv,
 
 static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-template <int CT, int QT>
-static int launch_attn(const float* qkv, float* out, int64_t N, int T, float scale, hipStream_t st) {
+template <int CT, int QT, bool MH = false>
+static int launch_attn(const float* qkv, float* out, int64_t N, int T, float scale, hipStream_t st, int nh = 1) {
   constexpr int C = 16 * CT;
   constexpr size_t lds = (size_t)2 * 64 * (C + 4) * sizeof(float);
   static const int once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fwd<CT, QT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fwd<CT, QT, MH>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     return 0;
   }();
   (void)once;
   const int nqb = T / (64 * QT);
-  hipLaunchKernelGGL((k_attn_fwd<CT, QT>), dim3((unsigned)(N * nqb)), dim3(256), lds, st, qkv, out, T, nqb, scale);
+  hipLaunchKernelGGL((k_attn_fwd<CT, QT, MH>), dim3((unsigned)(N * nh * nqb)), dim3(256), lds, st, qkv, out, T, nqb, scale, nh);
   return msgm_check_launch();
+}
+
+template <int CT>
+static int launch_attn_mh(const float* qkv, float* out, int64_t N, int T, int nh, float scale, hipStream_t st) {
+  return T % 128 == 0 ? launch_attn<CT, 2, true>(qkv, out, N, T, scale, st, nh) : launch_attn<CT, 1, true>(qkv, out, N, T, scale, st, nh);
 }
 
 extern "C" {
@@ -162,6 +177,23 @@ int msgm_attention_forward(const float* qkv, float* out, int64_t N, int32_t T, i
   if (C == 32) return two ? launch_attn<2, 2>(qkv, out, N, T, scale, S(stream)) : launch_attn<2, 1>(qkv, out, N, T, scale, S(stream));
   if (C == 64) return two ? launch_attn<4, 2>(qkv, out, N, T, scale, S(stream)) : launch_attn<4, 1>(qkv, out, N, T, scale, S(stream));
   return two ? launch_attn<8, 2>(qkv, out, N, T, scale, S(stream)) : launch_attn<8, 1>(qkv, out, N, T, scale, S(stream));
+}
+
+int msgm_attention_mh_supported(int32_t T, int32_t heads, int32_t D) {
+  return heads >= 1 && heads <= 64 && (D == 16 || D == 32 || D == 64 || D == 128) && T >= 64 && T % 64 == 0;
+}
+
+int msgm_attention_mh_forward(const float* qkv, float* out, int64_t N, int32_t T, int32_t heads, int32_t D, float scale,
+                              msgm_stream_t stream) {
+  if (!qkv || !out || N <= 0 || T <= 0 || heads <= 0 || D <= 0) return MSGM_E_BADARG;
+  if (!msgm_attention_mh_supported(T, heads, D) || N * heads * (int64_t)(T / 64) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
+  // one head: the single-head entry (the same kernels, so the same bits)
+  if (heads == 1 && msgm_attention_supported(T, D)) return msgm_attention_forward(qkv, out, N, T, D, scale, stream);
+  // 128 queries per workgroup when T allows, except at D = 128 (the register argument of msgm_attention_forward)
+  if (D == 16) return launch_attn_mh<1>(qkv, out, N, T, heads, scale, S(stream));
+  if (D == 32) return launch_attn_mh<2>(qkv, out, N, T, heads, scale, S(stream));
+  if (D == 64) return launch_attn_mh<4>(qkv, out, N, T, heads, scale, S(stream));
+  return launch_attn<8, 1, true>(qkv, out, N, T, scale, S(stream), heads);
 }
 
 }  // extern "C"

@@ -26,6 +26,12 @@
 // matrix cores from LDS tiles that were filled with coalesced 16-byte global loads.  exp / log are the accurate expf /
 // logf, not the 2-ulp hardware approximations (3 % of the forward kernel's time): the backward multiplies P by
 // differences that cancel (Pbar - delta ...), so the probabilities are kept at fp32 accuracy.
+//
+// Multi-head (MH = true; AttentionBlock num_heads = H, model/unet.py:220-250): head h of a sample owns the qkv channels
+// [3Dh, 3D(h+1)) (q | k | v of D = C/H each) and the att channels [Dh, D(h+1)).  Every kernel is the single-head one at
+// channel count D, run over (sample, head) PAIRS pr = sample*H + h: rows of stride 3C / C from column 3Dh / Dh, the row
+// scalars (lse, rbar, c, delta) and the query-gradient slabs indexed by pair instead of sample.  MH = false is the
+// single-head build: compile-time strides, no head index, the code the single-head entries always ran.
 #include "common.h"
 
 __device__ __forceinline__ f32x4 mfma16t(float a, float b, f32x4 c) {
@@ -37,11 +43,12 @@ static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream
 // Transposed formulation (as the sampler kernel): S^T[key][query] = K Q^T, O^T[c][query] += V^T P^T, so a lane owns ONE
 // query (lane&15): running max / sums are per-lane scalars, and e^{S-m} in the C/D layout IS the B operand of the
 // second product (MFMA step r of key tile kt contracts key 16kt + 4(lane>>4) + r on both operands).
-template <int CT, int QT, int KB, int NW = 4>   // C = 16*CT channels; QT tiles of 16 queries per wave; KB keys per LDS block;
-__global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restrict__ qkv, float* __restrict__ att,   // NW waves
-                                                        float* __restrict__ lse, float* __restrict__ rbar, int T, int nqb,
-                                                        int64_t Bp, float scale) {
-  constexpr int C = 16 * CT, KP = C + 4, LD = 3 * C, KT = KB / 16, NT = 64 * NW;
+template <int CT, int QT, int KB, int NW = 4, bool MH = false>   // C = 16*CT channels (per head); QT tiles of 16 queries per
+__global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restrict__ qkv, float* __restrict__ att,   // wave; KB keys
+                                                        float* __restrict__ lse, float* __restrict__ rbar, int T, int nqb,  // per LDS
+                                                        int64_t Bp, float scale, int nh) {                                  // block; NW waves
+  constexpr int C = 16 * CT, KP = C + 4, KT = KB / 16, NT = 64 * NW;
+  const int LD = MH ? 3 * C * nh : 3 * C, LA = MH ? C * nh : C;   // qkv / att row strides
   constexpr int NV = (KB * C / 4) / NT;                   // float4 per thread per matrix and key block
   static_assert(NV >= 1 && (KB * C / 4) % NT == 0, "key block does not divide over the workgroup's threads");
   extern __shared__ __attribute__((aligned(16))) float atd_lds[];
@@ -51,15 +58,17 @@ __global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restri
   float* Vd = Vs + KB * KP;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   // XCD-aware block order: workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2); the nqb query
-  // blocks of one sample all stream that sample's K / V tiles, so they get ids 8 apart (same XCD, back to back) and
-  // the re-reads hit that L2.  Samples beyond the last multiple of 8 keep the plain order.
-  int smp, qb;
+  // blocks of one (sample, head) pair all stream that pair's K / V tiles, so they get ids 8 apart (same XCD, back to
+  // back) and the re-reads hit that L2.  Pairs beyond the last multiple of 8 keep the plain order.
+  const int64_t NP = MH ? Bp * nh : Bp;                   // (sample, head) pairs
+  int pr, qb;
   {
-    const int full = (int)(Bp / 8) * 8 * nqb, b = blockIdx.x;
-    if (b < full) { const int loc = b >> 3; smp = (loc / nqb) * 8 + (b & 7); qb = loc % nqb; }
-    else { const int r = b - full; smp = (int)(Bp / 8) * 8 + r / nqb; qb = r % nqb; }
+    const int full = (int)(NP / 8) * 8 * nqb, b = blockIdx.x;
+    if (b < full) { const int loc = b >> 3; pr = (loc / nqb) * 8 + (b & 7); qb = loc % nqb; }
+    else { const int r = b - full; pr = (int)(NP / 8) * 8 + r / nqb; qb = r % nqb; }
   }
-  const float* bp = qkv + (size_t)smp * T * LD;            // primal rows of this sample
+  const int smp = MH ? pr / nh : pr, hd = MH ? pr - smp * nh : 0;
+  const float* bp = qkv + (size_t)smp * T * LD + 3 * C * hd;   // primal rows of this sample, this head's columns
   const float* bt = bp + (size_t)Bp * T * LD;              // tangent rows
   const int q0 = (qb * NW + w) * 16 * QT;                  // first query of this wave
 
@@ -182,31 +191,41 @@ __global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restri
     rt += __shfl_xor(rt, 16, 64); rt += __shfl_xor(rt, 32, 64);
     const float inv = 1.0f / lt, rb = rt * inv;
     const size_t row = (size_t)smp * T + q0 + 16 * qt + il;
-    float* orow = att + row * C;
-    float* drow = att + ((size_t)Bp * T + row) * C;
+    float* orow = att + row * LA + C * hd;
+    float* drow = att + ((size_t)Bp * T + row) * LA + C * hd;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       const f32x4 ov = o[qt][ct] * inv;
       *reinterpret_cast<f32x4*>(orow + 16 * ct + 4 * q) = ov;
       *reinterpret_cast<f32x4*>(drow + 16 * ct + 4 * q) = od[qt][ct] * inv - ov * rb;
     }
-    if (q == 0) { lse[row] = m[qt] + logf(lt); rbar[row] = rb; }
+    if (q == 0) {
+      const size_t sr = (size_t)pr * T + q0 + 16 * qt + il;          // row scalars per (sample, head) pair
+      lse[sr] = m[qt] + logf(lt); rbar[sr] = rb;
+    }
   }
 }
 
 // =============================================================================================== backward: row scalars
 // c_i = gd_i . o_i ;  delta_i = g_i . o_i + gd_i . od_i - rbar_i c_i       (16 lanes per row, float4 each per 64 ch.)
+// rows = (sample, head) pairs x T; C = channels per head; MH: row pr*T + t reads att row (pr/nh)*T + t at column C(pr%nh)
+template <bool MH = false>
 __global__ void __launch_bounds__(256) k_attn_dual_delta(const float* __restrict__ att, const float* __restrict__ datt,
                                                           const float* __restrict__ rbar, float* __restrict__ cc,
-                                                          float* __restrict__ de, int64_t rows, int C) {
+                                                          float* __restrict__ de, int64_t rows, int C, int T, int nh) {
   const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
   const int sl = threadIdx.x & 15;
   float c = 0.f, d = 0.f;
   if (row < rows) {
-    const float* o = att + row * C;
-    const float* g = datt + row * C;
-    const float* od = att + (rows + row) * C;
-    const float* gd = datt + (rows + row) * C;
+    size_t off = (size_t)row * C;
+    if (MH) {
+      const int64_t pr = row / T, t = row - pr * T, smp = pr / nh, hd = pr - smp * nh;
+      off = ((size_t)smp * T + t) * C * nh + (size_t)C * hd;
+    }
+    const float* o = att + off;                            // the tangent half starts rows*C floats later in both layouts
+    const float* g = datt + off;
+    const float* od = att + (size_t)rows * C + off;
+    const float* gd = datt + (size_t)rows * C + off;
     for (int c4 = sl; c4 < C / 4; c4 += 16) {
       const f32x4 ov = *reinterpret_cast<const f32x4*>(o + 4 * c4), gv = *reinterpret_cast<const f32x4*>(g + 4 * c4);
       const f32x4 odv = *reinterpret_cast<const f32x4*>(od + 4 * c4), gdv = *reinterpret_cast<const f32x4*>(gd + 4 * c4);
@@ -236,17 +255,20 @@ __global__ void __launch_bounds__(256) k_attn_dual_delta(const float* __restrict
 // loop over the key blocks of a group was tried first: it needs ~37 more registers than the 246 the kernel has, spilled, and
 // ran the whole step 1 ms SLOWER at kseq = 1; it also exposed a hipcc hazard bug — no wait states between an MFMA and a global
 // store of its result when a branch sits in between — which a compile-time ACC cannot hit.)
-template <int CT, int KG, bool ACC = false>
+template <int CT, int KG, bool ACC = false, bool MH = false>
 __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restrict__ qkv, const float* __restrict__ datt,
-                                                        const float* __restrict__ stats /* [2][Bp*T]: lse | rbar */,
-                                                        const float* __restrict__ ccde /* [2][Bp*T]: c | delta */,
+                                                        const float* __restrict__ stats /* [2][NP*T]: lse | rbar */,
+                                                        const float* __restrict__ ccde /* [2][NP*T]: c | delta */,
                                                         float* __restrict__ dqkv, float* __restrict__ slab, int T, int nkg,
-                                                        int kseq, int ks, int64_t Bp, float scale) {
-  constexpr int C = 16 * CT, KP = C + 4, LD = 3 * C, KB = 16 * KG, DP = KB + 4, QB = 32, NT = 128 * KG;
-  constexpr int NK = (KB * C / 4) / NT;                   // float4 per thread per resident matrix
+                                                        int kseq, int ks, int64_t Bp, float scale, int nh) {
+  constexpr int C = 16 * CT, KP = C + 4, KB = 16 * KG, DP = KB + 4, QB = 32, NT = 128 * KG;
+  constexpr int NK = (KB * C / 4 + NT - 1) / NT;          // float4 per thread per resident matrix
+  constexpr bool KFULL = (KB * C / 4) % NT == 0;          // C = 16: only half of the threads stage a float4
   constexpr int NQ = (QB * C / 4 + NT - 1) / NT;          // float4 per thread per streamed matrix and query block
-  constexpr bool QFULL = (QB * C / 4) % NT == 0;          // C = 32: only half of the threads stage a float4
-  static_assert(NK >= 1 && (KB * C / 4) % NT == 0, "resident tiles do not divide over the workgroup");
+  constexpr bool QFULL = (QB * C / 4) % NT == 0;          // C <= 32: only a half / quarter of the threads stage a float4
+  static_assert(NK >= 1 && NQ >= 1 && (KFULL || NK == 1) && (QFULL || NQ == 1), "tiles do not divide over the workgroup");
+  const int LD = MH ? 3 * C * nh : 3 * C, LA = MH ? C * nh : C;   // qkv / att row strides
+  const int64_t NP = MH ? Bp * nh : Bp;                   // (sample, head) pairs
   extern __shared__ __attribute__((aligned(16))) float atb_lds[];
   float* Ks = atb_lds;                                    // [KB][KP] x4, resident
   float* Kd = Ks + KB * KP;
@@ -261,22 +283,24 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
                                                           // next block's phase 1 may start while a slow wave is still in phase 2
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const int qs = w & 1, kg = w >> 1;
-  int smp, kgi;                                            // XCD-aware order (see the forward kernel): the key groups
-  {                                                        // of one sample stream the same q / g rows
-    const int full = (int)(Bp / 8) * 8 * nkg, b = blockIdx.x;
-    if (b < full) { const int loc = b >> 3; smp = (loc / nkg) * 8 + (b & 7); kgi = loc % nkg; }
-    else { const int r = b - full; smp = (int)(Bp / 8) * 8 + r / nkg; kgi = r % nkg; }
+  int pr, kgi;                                             // XCD-aware order (see the forward kernel): the key groups
+  {                                                        // of one (sample, head) pair stream the same q / g rows
+    const int full = (int)(NP / 8) * 8 * nkg, b = blockIdx.x;
+    if (b < full) { const int loc = b >> 3; pr = (loc / nkg) * 8 + (b & 7); kgi = loc % nkg; }
+    else { const int r = b - full; pr = (int)(NP / 8) * 8 + r / nkg; kgi = r % nkg; }
   }
+  const int smp = MH ? pr / nh : pr, hd = MH ? pr - smp * nh : 0;
   const int kb = kgi * kseq + ks;
-  const size_t half_qkv = (size_t)Bp * T * LD, half_att = (size_t)Bp * T * C;
-  const float* bp = qkv + (size_t)smp * T * LD;
-  const float* gp = datt + (size_t)smp * T * C;
-  const size_t srow0 = (size_t)smp * T;
+  const size_t half_qkv = (size_t)Bp * T * LD, half_att = (size_t)Bp * T * LA;
+  const float* bp = qkv + (size_t)smp * T * LD + 3 * C * hd;
+  const float* gp = datt + (size_t)smp * T * LA + C * hd;
+  const size_t srow0 = (size_t)pr * T;                     // row scalars and slabs: per pair
 
   // ---- resident K, Kd, V, Vd tiles of this key block
 #pragma unroll
   for (int i = 0; i < NK; ++i) {
     const int idx = tid + NT * i, key = idx / (C / 4), c4 = idx - key * (C / 4);
+    if (!KFULL && idx >= KB * C / 4) break;
     const size_t off = (size_t)(kb * KB + key) * LD + 4 * c4;
     *reinterpret_cast<f32x4*>(Ks + key * KP + 4 * c4) = *reinterpret_cast<const f32x4*>(bp + off + C);
     *reinterpret_cast<f32x4*>(Vs + key * KP + 4 * c4) = *reinterpret_cast<const f32x4*>(bp + off + 2 * C);
@@ -298,12 +322,12 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
       const size_t row = (size_t)(qb * QB + qr);
       pq[i] = *reinterpret_cast<const f32x4*>(bp + row * LD + 4 * c4);
       pqd[i] = *reinterpret_cast<const f32x4*>(bp + half_qkv + row * LD + 4 * c4);
-      pg[i] = *reinterpret_cast<const f32x4*>(gp + row * C + 4 * c4);
-      pgd[i] = *reinterpret_cast<const f32x4*>(gp + half_att + row * C + 4 * c4);
+      pg[i] = *reinterpret_cast<const f32x4*>(gp + row * LA + 4 * c4);
+      pgd[i] = *reinterpret_cast<const f32x4*>(gp + half_att + row * LA + 4 * c4);
     }
     if (tid < 4 * QB) {
       const int which = tid >> 5, qr = tid & 31;
-      const size_t o = (size_t)(which & 1) * (size_t)Bp * T + srow0 + (size_t)qb * QB + qr;
+      const size_t o = (size_t)(which & 1) * (size_t)NP * T + srow0 + (size_t)qb * QB + qr;
       pst = which < 2 ? stats[o] : ccde[o];
     }
   };
@@ -389,8 +413,8 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
 #pragma unroll
     for (int ct = kg; ct < CT; ct += KG) {
       const size_t row = (size_t)qb * QB + 16 * qs + il;
-      float* sp = slab + (((size_t)smp * nkg + kgi) * T + row) * C + 16 * ct + 4 * q;
-      float* sdp = slab + (((size_t)(Bp + smp) * nkg + kgi) * T + row) * C + 16 * ct + 4 * q;
+      float* sp = slab + (((size_t)pr * nkg + kgi) * T + row) * C + 16 * ct + 4 * q;
+      float* sdp = slab + (((size_t)(NP + pr) * nkg + kgi) * T + row) * C + 16 * ct + 4 * q;
       f32x4 dq = {0, 0, 0, 0}, dqd = {0, 0, 0, 0}, pdq = {0, 0, 0, 0}, pdqd = {0, 0, 0, 0};
       if (ACC) {          // compile-time: what the earlier launches left for this key group — requested BEFORE the MFMAs it joins
         pdq = *reinterpret_cast<const f32x4*>(sp);
@@ -435,8 +459,8 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
   __syncthreads();
   if (qs == 0) {
     const size_t row = (size_t)smp * T + kb * KB + 16 * kg + il;     // key of this lane
-    float* kp_ = dqkv + row * LD;
-    float* kt_ = dqkv + half_qkv + row * LD;
+    float* kp_ = dqkv + row * LD + 3 * C * hd;
+    float* kt_ = dqkv + half_qkv + row * LD + 3 * C * hd;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       const f32x4* base = reinterpret_cast<const f32x4*>(scratch) + ((size_t)kg * 4 * CT + 4 * ct) * 64 + lane;
@@ -448,9 +472,11 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
   }
 }
 
-// qbar / qdbar = s2 * sum over key blocks of the slabs, in block order (deterministic); written into the q slice of dqkv
+// qbar / qdbar = s2 * sum over key blocks of the slabs, in block order (deterministic); written into the q slice of dqkv.
+// N = slab rows / T: 2 x (sample, head) pairs; MH: pair n = (half*Bp + sample)*nh + head, q slice at column 3C*head
+template <bool MH = false>
 __global__ void __launch_bounds__(256) k_attn_dq_reduce(const float* __restrict__ slab, float* __restrict__ dqkv, int64_t N,
-                                                         int T, int C, int nkb, float scale) {
+                                                         int T, int C, int nkb, float scale, int nh) {
   const int64_t total = N * T * (C / 4);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c4 = (int)(i % (C / 4));
@@ -459,47 +485,54 @@ __global__ void __launch_bounds__(256) k_attn_dq_reduce(const float* __restrict_
     const float* p = slab + ((size_t)n * nkb * T + qr) * C + 4 * c4;
     f32x4 acc = *reinterpret_cast<const f32x4*>(p);
     for (int kb = 1; kb < nkb; ++kb) acc += *reinterpret_cast<const f32x4*>(p + (size_t)kb * T * C);
-    *reinterpret_cast<f32x4*>(dqkv + (size_t)row * 3 * C + 4 * c4) = acc * scale;
+    if (MH) {
+      const int64_t nb = n / nh, hd = n - nb * nh;
+      *reinterpret_cast<f32x4*>(dqkv + ((size_t)nb * T + qr) * 3 * C * nh + 3 * C * hd + 4 * c4) = acc * scale;
+    } else {
+      *reinterpret_cast<f32x4*>(dqkv + (size_t)row * 3 * C + 4 * c4) = acc * scale;
+    }
   }
 }
 
 // =============================================================================================== launchers
-template <int CT, int QT, int KB, int NW>
-static int launch_fwd(const float* qkv, float* att, float* stats, int64_t Bp, int T, float scale, hipStream_t st) {
+template <int CT, int QT, int KB, int NW, bool MH = false>
+static int launch_fwd(const float* qkv, float* att, float* stats, int64_t Bp, int T, float scale, hipStream_t st, int nh = 1) {
   constexpr int C = 16 * CT;
   constexpr size_t lds = (size_t)4 * KB * (C + 4) * sizeof(float);
   static const int once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dual_fwd<CT, QT, KB, NW>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dual_fwd<CT, QT, KB, NW, MH>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     return 0;
   }();
   (void)once;
   const int nqb = T / (16 * NW * QT);
-  hipLaunchKernelGGL((k_attn_dual_fwd<CT, QT, KB, NW>), dim3((unsigned)(Bp * nqb)), dim3(64 * NW), lds, st, qkv, att, stats,
-                     stats + Bp * T, T, nqb, Bp, scale);
+  const int64_t NP = Bp * nh;
+  hipLaunchKernelGGL((k_attn_dual_fwd<CT, QT, KB, NW, MH>), dim3((unsigned)(NP * nqb)), dim3(64 * NW), lds, st, qkv, att, stats,
+                     stats + NP * T, T, nqb, Bp, scale, nh);
   return msgm_check_launch();
 }
 
 // keys per backward workgroup
 static inline int attn_bwd_keys(int C) { return C == 128 ? 32 : 64; }
 
-template <int CT, int KG>
+template <int CT, int KG, bool MH = false>
 static int launch_bwd(const float* qkv, const float* att, const float* datt, const float* stats, float* dqkv, int64_t Bp, int T,
-                      float scale, float* ws, hipStream_t st) {
+                      float scale, float* ws, hipStream_t st, int nh = 1) {
   constexpr int C = 16 * CT, KP = C + 4, KB = 16 * KG;
   constexpr size_t lds_main = ((size_t)4 * KB * KP + 4 * 32 * KP + 4 * 32 + 4 * 32 * (KB + 4)) * sizeof(float);
   constexpr size_t lds_epi = (size_t)KG * 4 * CT * 64 * 4 * sizeof(float);        // the cross-wave sum of the key-side gradients
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   static_assert(lds <= 160 * 1024, "backward tiles exceed the CU's LDS");
   static const int once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dual_bwd<CT, KG, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dual_bwd<CT, KG, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dual_bwd<CT, KG, false, MH>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dual_bwd<CT, KG, true, MH>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     return 0;
   }();
   (void)once;
-  const int64_t rows = Bp * T;
+  const int64_t NP = Bp * nh;                             // (sample, head) pairs: the backward's "samples"
+  const int64_t rows = NP * T;
   const int nkb = T / KB;
   // launches over the key blocks: two while each launch still has two full rounds of resident workgroups (two per CU).
   // Measured at B = 256 (rocprofv3, 7 steps): one launch 147.2 + 29.1 ms in the two backward kernels + 24.0 ms of reduce;
@@ -508,22 +541,22 @@ static int launch_bwd(const float* qkv, const float* att, const float* datt, con
   static const int kseq_x = getenv("MSGM_ATTN_KSEQ") ? atoi(getenv("MSGM_ATTN_KSEQ")) : 0;      // diagnostic override
   int kseq = 1;
   for (int k = 2; k > 1; k >>= 1)
-    if (nkb % k == 0 && Bp * (int64_t)(nkb / k) >= 1024) { kseq = k; break; }
+    if (nkb % k == 0 && NP * (int64_t)(nkb / k) >= 1024) { kseq = k; break; }
   if (kseq_x > 0 && nkb % kseq_x == 0) kseq = kseq_x;
   const int nkg = nkb / kseq;
   float* cc = ws;
   float* de = ws + rows;
   float* slab = ws + 2 * rows;
-  hipLaunchKernelGGL(k_attn_dual_delta, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, att, datt, stats + rows, cc, de,
-                     rows, C);
-  hipLaunchKernelGGL((k_attn_dual_bwd<CT, KG, false>), dim3((unsigned)(Bp * nkg)), dim3(128 * KG), lds, st, qkv, datt, stats, cc, dqkv, slab,
-                     T, nkg, kseq, 0, Bp, scale);
+  hipLaunchKernelGGL(k_attn_dual_delta<MH>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, att, datt, stats + rows, cc, de,
+                     rows, C, T, nh);
+  hipLaunchKernelGGL((k_attn_dual_bwd<CT, KG, false, MH>), dim3((unsigned)(NP * nkg)), dim3(128 * KG), lds, st, qkv, datt, stats, cc, dqkv,
+                     slab, T, nkg, kseq, 0, Bp, scale, nh);
   for (int ks = 1; ks < kseq; ++ks)
-    hipLaunchKernelGGL((k_attn_dual_bwd<CT, KG, true>), dim3((unsigned)(Bp * nkg)), dim3(128 * KG), lds, st, qkv, datt, stats, cc, dqkv, slab,
-                       T, nkg, kseq, ks, Bp, scale);
-  const int64_t work = 2 * Bp * T * (C / 4);
-  hipLaunchKernelGGL(k_attn_dq_reduce, dim3((unsigned)grid_for(work, 256, 16384)), dim3(256), 0, st, slab, dqkv, 2 * Bp, T, C,
-                     nkg, scale);
+    hipLaunchKernelGGL((k_attn_dual_bwd<CT, KG, true, MH>), dim3((unsigned)(NP * nkg)), dim3(128 * KG), lds, st, qkv, datt, stats, cc,
+                       dqkv, slab, T, nkg, kseq, ks, Bp, scale, nh);
+  const int64_t work = 2 * NP * T * (C / 4);
+  hipLaunchKernelGGL(k_attn_dq_reduce<MH>, dim3((unsigned)grid_for(work, 256, 16384)), dim3(256), 0, st, slab, dqkv, 2 * NP, T, C,
+                     nkg, scale, nh);
   return msgm_check_launch();
 }
 
@@ -566,6 +599,51 @@ int msgm_attention_dual_backward(const float* qkv, const float* att, const float
   if (C == 128) return launch_bwd<8, 2>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream));
   if (C == 32) return launch_bwd<2, 4>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream));
   return launch_bwd<4, 4>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream));
+}
+
+// ---- multi-head: D = C / heads channels per head, D in {16, 32, 64, 128}; the T rules of the single-head entries at C = D
+int msgm_attention_dual_mh_supported(int32_t T, int32_t heads, int32_t D) {
+  if (heads < 1 || heads > 64) return 0;
+  if (D == 128) return T >= 32 && T % 32 == 0;
+  return (D == 16 || D == 32 || D == 64) && T >= 64 && T % 64 == 0;
+}
+
+size_t msgm_attention_dual_mh_workspace(int64_t Bp, int32_t T, int32_t heads, int32_t D) {
+  if (!msgm_attention_dual_mh_supported(T, heads, D) || Bp <= 0) return 0;
+  if (heads == 1 && msgm_attention_dual_supported(T, D)) return msgm_attention_dual_workspace(Bp, T, D);
+  const size_t np = (size_t)Bp * heads;                    // row scalars c | delta and the slabs, per (sample, head) pair
+  return ((size_t)2 * np * T + (size_t)2 * np * (T / attn_bwd_keys(D)) * T * D) * sizeof(float);
+}
+
+int msgm_attention_dual_mh_forward(const float* qkv, float* att, float* stats, int64_t Bp, int32_t T, int32_t heads, int32_t D,
+                                   float scale, msgm_stream_t stream) {
+  if (!qkv || !att || !stats || Bp <= 0 || T <= 0 || heads <= 0 || D <= 0) return MSGM_E_BADARG;
+  if (!msgm_attention_dual_mh_supported(T, heads, D) || Bp * heads * (int64_t)(T / 32) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
+  if (heads == 1 && msgm_attention_dual_supported(T, D))   // one head: the single-head entry (same kernels, same bits)
+    return msgm_attention_dual_forward(qkv, att, stats, Bp, T, D, scale, stream);
+  const int64_t np = Bp * heads;
+  if (D == 128) {
+    if (T % 64 == 0 && np * (int64_t)(T / 64) >= 512) return launch_fwd<8, 1, 16, 4, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
+    return launch_fwd<8, 1, 16, 2, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
+  }
+  if (D == 64) return launch_fwd<4, 1, 32, 4, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
+  if (D == 32) return launch_fwd<2, 1, 64, 4, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
+  return launch_fwd<1, 1, 64, 4, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
+}
+
+int msgm_attention_dual_mh_backward(const float* qkv, const float* att, const float* datt, const float* stats, float* dqkv,
+                                    int64_t Bp, int32_t T, int32_t heads, int32_t D, float scale, void* workspace,
+                                    size_t workspace_bytes, msgm_stream_t stream) {
+  if (!qkv || !att || !datt || !stats || !dqkv || !workspace || Bp <= 0 || T <= 0 || heads <= 0 || D <= 0) return MSGM_E_BADARG;
+  if (!msgm_attention_dual_mh_supported(T, heads, D) || Bp * heads * (int64_t)(T / 32) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
+  if (workspace_bytes < msgm_attention_dual_mh_workspace(Bp, T, heads, D)) return MSGM_E_WORKSPACE;
+  if (heads == 1 && msgm_attention_dual_supported(T, D))
+    return msgm_attention_dual_backward(qkv, att, datt, stats, dqkv, Bp, T, D, scale, workspace, workspace_bytes, stream);
+  float* ws = static_cast<float*>(workspace);
+  if (D == 128) return launch_bwd<8, 2, true>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream), heads);
+  if (D == 64) return launch_bwd<4, 4, true>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream), heads);
+  if (D == 32) return launch_bwd<2, 4, true>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream), heads);
+  return launch_bwd<1, 4, true>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream), heads);
 }
 
 }  // extern "C"

@@ -947,6 +947,51 @@ def attention_dual_backward(qkv, att, datt, stats, Bp, T, C, scale):
     return dqkv
 
 
+def attention_mh_supported(T, heads, D) -> bool:
+    return bool(lib().msgm_attention_mh_supported(int(T), int(heads), int(D)))
+
+
+def attention_mh_forward(qkv, out, N, T, heads, D, scale):
+    """Fused multi-head softmax(scale q k^T) v: qkv [N][T][3C] (head h = columns [3Dh, 3D(h+1)): q | k | v of D each,
+    model/unet.py:220-250) -> out [N][T][C] (head h at columns [Dh, D(h+1))), C = heads * D, no tangent."""
+    C = heads * D
+    if qkv.numel() < N * T * 3 * C or out.numel() < N * T * C:
+        raise MsgmError("attention_mh: buffer too small")
+    check(lib().msgm_attention_mh_forward(ptr(f32(qkv)), ptr(f32(out)), N, T, heads, D, float(scale), stream()),
+          "msgm_attention_mh_forward")
+    return out
+
+
+def attention_dual_mh_supported(T, heads, D) -> bool:
+    return bool(lib().msgm_attention_dual_mh_supported(int(T), int(heads), int(D)))
+
+
+def attention_dual_mh_forward(qkv, Bp, T, heads, D, scale):
+    """Multi-head attention_dual_forward: qkv [2Bp][T][3C] -> (att [2Bp][T][C], stats [2][Bp*heads*T]), C = heads * D."""
+    C = heads * D
+    if qkv.numel() < 2 * Bp * T * 3 * C:
+        raise MsgmError("attention_dual_mh: qkv too small")
+    att = torch.empty(2 * Bp * T * C, dtype=torch.float32, device=qkv.device)
+    stats = torch.empty(2 * Bp * heads * T, dtype=torch.float32, device=qkv.device)
+    check(lib().msgm_attention_dual_mh_forward(ptr(f32(qkv)), ptr(att), ptr(stats), Bp, T, heads, D, float(scale), stream()),
+          "msgm_attention_dual_mh_forward")
+    return att, stats
+
+
+def attention_dual_mh_backward(qkv, att, datt, stats, Bp, T, heads, D, scale):
+    """Multi-head attention_dual_backward: dqkv [2Bp][T][3C]; shares the cached "attention" workspace."""
+    C = heads * D
+    if min(qkv.numel() // 3, att.numel(), datt.numel()) < 2 * Bp * T * C or stats.numel() < 2 * Bp * heads * T:
+        raise MsgmError("attention_dual_mh backward: buffer too small")
+    need = int(lib().msgm_attention_dual_mh_workspace(Bp, T, heads, D))
+    ws = scratch(qkv.device, need, "attention")
+    dqkv = torch.empty(2 * Bp * T * 3 * C, dtype=torch.float32, device=qkv.device)
+    check(lib().msgm_attention_dual_mh_backward(ptr(f32(qkv)), ptr(f32(att)), ptr(f32(datt)), ptr(f32(stats)), ptr(dqkv), Bp, T,
+                                                heads, D, float(scale), ptr(ws), ws.numel() * 4, stream()),
+          "msgm_attention_dual_mh_backward")
+    return dqkv
+
+
 def softmax_dual_backward(Pm, Wd, Pb, Pdb, T):
     rows = Pm.numel() // T
     if not (Wd.numel() == Pb.numel() == Pdb.numel() == Pm.numel()):

@@ -575,6 +575,47 @@ def g17_ssm_wellconditioned():
     save("g17_ssm_wellconditioned", **out)
 
 
+G18_FULL = ("core.input_blocks.4.1.", "core.input_blocks.7.1.", "core.middle_block.1.")   # first encoder attention per level + middle
+G18_COLS = 16      # weight gradients: every row (all heads' q / k / v rows of qkv, all output channels of proj_out), 16 input columns
+
+
+def g18_multihead():
+    """Multi-head attention (AttentionBlock num_heads = H, model/unet.py:220-250): the reference's VorticityUNet(num_heads=H)
+    on the well-conditioned parameter set (load_init_like_: proj_out re-randomised small, so the attention branch reaches the
+    output and the q / k / v gradients are not zero).  in_space 32 at H = 2 / 4 (attention at T = 256, C = 64 and T = 64,
+    C = 128: D = 32 / 16 and 64 / 32), in_space 16 at H = 2 (T = 16: the composed per-head path).  Forward at a fixed t, the
+    SSM per-sample loss with the three draws forced, the gradients of the attention parameters (norm, qkv, proj_out) of the
+    first encoder attention block of each level and of the middle block — the vectors in full, the two (rows, C, 1) weights
+    with every row and the G18_COLS input columns arange(0, C, C / G18_COLS) (stored next to them as _cols::), which are
+    spread over all heads; the whole weights would make the file 1.8 MB — and digests of all gradients."""
+    torch.manual_seed(18)
+    out = {}
+    for tag, S_, H, B in (("s32h2", 32, 2, 2), ("s32h4", 32, 4, 2), ("s16h2", 16, 2, 2)):
+        net = VorticityUNet(base_channels=32, channel_mults=(1, 2, 4), num_res_blocks=2, premodule=None, in_space=S_,
+                            attention_resolutions=(2, 4), num_heads=H, flatten_order="F")
+        load_init_like_(net)
+        rev = PluginReverseSDE(sgm(), net, Tparam())
+        d = S_ * S_
+        x, u_t, eps, u_v = torch.randn(B, d) * 3, torch.rand(B, 1), torch.randn(B, d), torch.rand(B, d)
+        res = _ssm_case(rev, x, u_t, eps, u_v, full_grads=True)
+        grads = {k[len("grad::"):]: v for k, v in res.items() if k.startswith("grad::")}
+        full = {k: v for k, v in grads.items() if k[len("a."):].startswith(G18_FULL)}
+        assert len(full) == 3 * 6 and all(float(v.norm()) > 0 for v in full.values()), sorted(full)
+        out.update({f"{tag}_x": x, f"{tag}_u_t": u_t, f"{tag}_eps": eps, f"{tag}_u_v": u_v, f"{tag}_heads": np.array(H),
+                    f"{tag}_per": res["per"], f"{tag}_loss": res["loss"]})
+        for k, v in full.items():
+            if v.dim() == 3:                                   # (rows, C, 1) conv1d weight: a fixed set of input columns
+                cols = torch.arange(0, v.shape[1], v.shape[1] // G18_COLS)
+                out[f"{tag}_cols::{k}"], v = cols, v[:, cols]
+            out[f"{tag}_grad::{k}"] = v
+        out.update({f"{tag}_gd_{k}": v for k, v in _grad_digest(grads).items()})
+        with torch.no_grad():
+            t = torch.full((B,), 0.37)
+            out[f"{tag}_fwd_t"], out[f"{tag}_fwd"] = t, net(x, t)
+        print(tag, "loss", float(res["loss"]), "per", res["per"].tolist())
+    save("g18_multihead", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
