@@ -350,21 +350,17 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
                            const float* samp_bias, int32_t n_bias, int32_t n_samp, float* out, int32_t accumulate,
                            const msgm_conv_fuse_t* fuse, msgm_stream_t stream);
 
-/* dWp[tap][co][koff + c] += sum_m gy[m][co] in[src(m,tap)][c] (float atomics across
- * position chunks; zero dWp first).  One call per concatenated source.
+/* dWp[tap][co][koff + c] += sum_m gy[m][co] in[src(m,tap)][c], without float atomics (bitwise reproducible from run to
+ * run): every workgroup column stores its partial [taps][CoutP][C] block (+ bias partials) into its own slab of the
+ * workspace and a second kernel adds the slabs in slot order into dWp.  One call per concatenated source.
  * dbias (may be NULL): dbias[co] += sum over the primal rows n < n_bias and all pixels of gy — the bias gradient
- * (torch: conv backward's grad_bias) as a by-product of the tiles the kernel stages anyway; zero it first.
+ * (torch: conv backward's grad_bias) as a by-product of the tiles the kernel stages anyway.
  * tapmask_c32 / tapmask_co32 (HOST arrays, may be NULL): per 32-channel block of the input / output channels, bit t =
  * tap t of that block is a real weight (0 = all); blocks that are structurally zero are not computed (the tile
- * kernel only — their dWp entries are then left untouched). */
-int msgm_conv_wgrad(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
-                    float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
-                    const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, msgm_stream_t stream);
-/* The same gradients WITHOUT float atomics (bitwise reproducible from run to run): every workgroup column stores its
- * partial [taps][CoutP][C] block (+ bias partials) into its own slab of the workspace and a second kernel adds the
- * slabs in slot order; `dWp` / `dbias` are accumulated into exactly as above.  Workspace bytes from
- * msgm_conv_wgrad_workspace (n_bias = 0 when dbias is NULL); ~37 MB per call at the C4 shapes, i.e. ~20 us of HBM
- * time — the trainers use this entry by default. */
+ * kernels only; their dWp entries receive zeros).  The masks serve the 3-tap 1-D convolutions; with masks, a 1x1 gradient
+ * on the pixel-streaming kernel or a 2-D 3x3 one with channel counts that are multiples of 4 returns MSGM_E_UNSUPPORTED.
+ * Workspace bytes from msgm_conv_wgrad_workspace (n_bias = 0 when dbias is NULL); ~37 MB per call at the C4 shapes, i.e.
+ * ~20 us of HBM time. */
 size_t msgm_conv_wgrad_workspace(const msgm_conv_geom_t* geom, int32_t C, int32_t Cout, int32_t CoutP, int32_t n_bias);
 int msgm_conv_wgrad_det(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                         float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
@@ -433,9 +429,8 @@ int msgm_wino_pack_weights_batched(const msgm_pack_job_t* jobs, int32_t n_jobs, 
 int msgm_act_dual_forward(int32_t act, const float* z, float* h, int64_t half, int32_t dual, msgm_stream_t stream);
 int msgm_act_dual_backward(int32_t act, const float* z, float* g, int64_t half, msgm_stream_t stream);
 
-/* S[n][c] = sum_pos x[n][pos][c]; out[n][c] = x[n][pos][c]; x[n][pos][c] += sgn*E[n][c]. */
-int msgm_colsum(const float* x, float* S, int32_t N, int32_t P, int32_t C, msgm_stream_t stream);
-/* msgm_colsum without float atomics: per-chunk partials in the workspace, added in chunk order. */
+/* S[n][c] = sum_pos x[n][pos][c] (per-chunk partials in the workspace, added in chunk order: no float atomics);
+ * out[n][c] = x[n][pos][c]; x[n][pos][c] += sgn*E[n][c]. */
 size_t msgm_colsum_workspace(int32_t N, int32_t P, int32_t C);
 int msgm_colsum_det(const float* x, float* S, int32_t N, int32_t P, int32_t C, void* workspace, size_t workspace_bytes,
                     msgm_stream_t stream);

@@ -291,7 +291,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         (ConvOp.forward(stats=True)), the statistics come from those few KB instead of a pass over the tensor."""
         cs = getattr(x, "_msgm_cs", None)
         cs1 = getattr(x1, "_msgm_cs", None) if x1 is not None else None
-        if cs is not None and (x1 is None or cs1 is not None) and self._cs_on:
+        if cs is not None and (x1 is None or cs1 is not None):
             return ops.groupnorm_affine_cs(cs[0], cs[1], C, gnm.weight.detach(), gnm.bias.detach(), Bp, P, gnm.num_groups,
                                            cs1=cs1[0] if cs1 is not None else None, S1=cs1[1] if cs1 is not None else 0, C1=C1)
         return ops.groupnorm_affine(x, C, gnm.weight.detach(), gnm.bias.detach(), Bp, P, gnm.num_groups, x1=x1, C1=C1)
@@ -317,31 +317,28 @@ class VorticityUNet(nn.Module, FlatParamMixin):
             C0, C1 = r.split
             gnm = r.m.in_layers[0]
             aff = self._gn_fold(gnm, h0, Bp, P, C0, x1=s0, C1=C1)
-            wn = getattr(self, "_wino", False)
-            h2, _, _ = r.conv1_2.forward([h0, s0], N, H, W, Bp, samp_bias=eo, emb_rows=er, in_affine=aff, in_act=1, wino=wn,
+            h2, _, _ = r.conv1_2.forward([h0, s0], N, H, W, Bp, samp_bias=eo, emb_rows=er, in_affine=aff, in_act=1, wino=True,
                                          stats=True)
             out, _, _ = r.skip_2.forward([h0, s0], N, H, W, Bp)
             if r.conv2.can_transform_input(N, H, W):
                 r.conv2.forward([h2], N, H, W, Bp, out=out, accumulate=True,
-                                in_affine=self._gn_fold(r.m.out_layers[0], h2, Bp, P, r.co), in_act=1, wino=wn, stats=True)
+                                in_affine=self._gn_fold(r.m.out_layers[0], h2, Bp, P, r.co), in_act=1, wino=True, stats=True)
             else:
                 h3, _ = self._gn(r.m.out_layers[0], h2, Bp, P, r.co, False, True, None)
-                r.conv2.forward([h3], N, H, W, Bp, out=out, accumulate=True, wino=wn, stats=True)
+                r.conv2.forward([h3], N, H, W, Bp, out=out, accumulate=True, wino=True, stats=True)
             return out
-        fold = (not dual and tape is None and not os.environ.get("MSGM_NO_GN_FOLD")
-                and r.conv1.can_transform_input(N, H, W) and r.conv2.can_transform_input(N, H, W))
+        fold = (not dual and tape is None and r.conv1.can_transform_input(N, H, W) and r.conv2.can_transform_input(N, H, W))
         if fold:
             # sampler path: GroupNorm+SiLU are applied by the consuming conv while it stages its input tile, the residual
             # is added in conv2's epilogue — the two normalised tensors and the separate add pass never exist
-            wn = getattr(self, "_wino", False)
             h2, _, _ = r.conv1.forward([x], N, H, W, Bp, samp_bias=eo, emb_rows=er,
-                                       in_affine=self._gn_fold(r.m.in_layers[0], x, Bp, P, r.ci), in_act=1, wino=wn, stats=True)
+                                       in_affine=self._gn_fold(r.m.in_layers[0], x, Bp, P, r.ci), in_act=1, wino=True, stats=True)
             aff2 = self._gn_fold(r.m.out_layers[0], h2, Bp, P, r.co)
             if r.skip is not None:
                 out, _, _ = r.skip.forward([x], N, H, W, Bp)
-                r.conv2.forward([h2], N, H, W, Bp, out=out, accumulate=True, in_affine=aff2, in_act=1, wino=wn, stats=True)
+                r.conv2.forward([h2], N, H, W, Bp, out=out, accumulate=True, in_affine=aff2, in_act=1, wino=True, stats=True)
             else:
-                out, _, _ = r.conv2.forward([h2], N, H, W, Bp, residual=x, in_affine=aff2, in_act=1, wino=wn, stats=True)
+                out, _, _ = r.conv2.forward([h2], N, H, W, Bp, residual=x, in_affine=aff2, in_act=1, wino=True, stats=True)
             return out
         h1, st1 = self._gn(r.m.in_layers[0], x, Bp, P, r.ci, dual, True, tape)
         h2, _, _ = r.conv1.forward([h1], N, H, W, Bp, samp_bias=eo, emb_rows=er)
@@ -362,7 +359,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         s2 = 1.0 / math.sqrt(D)                                          # (ch^-1/4)^2, ch = D   model/unet.py:245-248
         fused = ops.attention_supported(T, C) if nh == 1 else ops.attention_mh_supported(T, nh, D)
         if not dual and tape is None and fused:                          # sampler: nothing to keep, no tangent
-            if a.qkv.can_transform_input(N, 1, T) and not os.environ.get("MSGM_NO_GN_FOLD"):
+            if a.qkv.can_transform_input(N, 1, T):
                 qkv, _, _ = a.qkv.forward([x], N, 1, T, Bp, in_affine=self._gn_fold(a.m.norm, x, Bp, T, C))   # GN folded in
             else:
                 hn, _ = self._gn(a.m.norm, x, Bp, T, C, False, False, None)
@@ -376,7 +373,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         hn, st = self._gn(a.m.norm, x, Bp, T, C, dual, False, tape)
         qkv, _, _ = a.qkv.forward([hn], N, 1, T, Bp)                     # [N][T][3C]: per head q | k | v channel slices
         fused = ops.attention_dual_supported(T, C) if nh == 1 else ops.attention_dual_mh_supported(T, nh, D)
-        if dual and fused and not os.environ.get("MSGM_NO_ATTN_DUAL"):
+        if dual and fused:
             # training: ONE kernel for the six products of the dual forward, nothing of size (T,T) written; the
             # backward recomputes the logits from q, k and the per-query (log-sum-exp, rbar) kept here
             if nh == 1:
@@ -429,26 +426,18 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         # F(2x2,3x3) forward kernel — 2.25x fewer MFMAs, all fp32, 1.13-1.26x the direct kernel with the folded GroupNorm +
         # SiLU staging (tools/bench_wino.py), same fused options and statistics by-product; it differs from the direct form
         # by the rounding of its transforms (2-6e-7 per conv) and every sampler parity test runs through it.
-        # MSGM_NO_WINO=1 keeps the direct kernels (A/B).  (Training: see _twino below.)
-        self._wino = not dual and tape is None and not os.environ.get("MSGM_NO_WINO")
-        self._cs_on = not os.environ.get("MSGM_NO_CHANSTATS")            # diagnostic A/B: GroupNorm statistics by a pass over the tensor
         # r3: the TRAINING pass's 3x3 stride-1 convolutions — forward and dgrad, primal and tangent rows alike — take the
         # Winograd kernel too (the dgrad as a Winograd forward of the cotangent with the flipped, transposed kernels): C4 step
         # 122.5 -> 116.9 ms at B = 256, 19.9 -> 18.6 ms at the 32-row shard.  fp32 throughout; its transforms round about twice
         # as much as the direct kernel (per conv 4-8e-7 against 3-4e-7 vs float64; on the ill-conditioned det_params benchmark
         # the per-sample loss is 2.2x the fp32 oracle's own distance from float64 instead of 1.07x — tests/test_round2_gpu.py;
-        # the well-conditioned reference fixture g17 holds its absolute tolerances).  MSGM_TRAIN_WINO=0 keeps the direct kernels.
-        self._twino = tape is not None and os.environ.get("MSGM_TRAIN_WINO", "1") != "0" and not os.environ.get("MSGM_NO_WINO")
-        if self._twino:
-            x["set"].pack_wino(train=True)
-        elif self._wino:
-            x["set"].pack_wino()
-        else:
-            x["set"].clear_train_wino()
+        # the well-conditioned reference fixture g17 holds its absolute tolerances).
+        sampler = not dual and tape is None
+        x["set"].pack_wino(train=tape is not None)
         # opt-in experiment (never the default): the sampler's 3x3 convolutions with 32-multiple channel counts
         # in bf16-split arithmetic (six bf16 MFMA products per fp32 product, fp32 accumulate) instead of Winograd
-        self._b6 = self._wino and bool(os.environ.get("MSGM_SAMPLER_BF16X3"))
-        x["set"].pack_b6(self._b6)
+        b6 = sampler and bool(os.environ.get("MSGM_SAMPLER_BF16X3"))
+        x["set"].pack_b6(b6)
         core = self.core
         mc = core.model_channels
         H = W = self.in_space
@@ -477,7 +466,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
                 if kind == "conv":
                     if tape is not None:
                         tape.append(("conv", o, h, H, W))
-                    h, H, W = o.forward([h], N, H, W, Bp, stats=not dual and tape is None)
+                    h, H, W = o.forward([h], N, H, W, Bp, stats=sampler)
                     C = o.Cout
                 elif kind == "res":
                     h = self._res_fwd(o, h, N, Bp, H, W, semb, dual, tape, er)
@@ -487,7 +476,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
                 elif kind in ("down", "up"):
                     if tape is not None:
                         tape.append((kind, o, h, H, W))
-                    h, H, W = o.forward([h], N, H, W, Bp, wino=getattr(self, "_wino", False), stats=not dual and tape is None)
+                    h, H, W = o.forward([h], N, H, W, Bp, wino=sampler, stats=sampler)
             return h, C, H, W
 
         h, C = img, core.in_channels
@@ -498,19 +487,15 @@ class VorticityUNet(nn.Module, FlatParamMixin):
             if tape is not None:
                 tape.append(("save_skip",))
         h, C, H, W = run_block(x["mid"], h, C, H, W)
-        nocat = (not dual and tape is None and x["set2"] is not None and not os.environ.get("MSGM_NO_GN_FOLD"))
-        nocat_t = tape is not None and dual and x["set2t"] is not None and not os.environ.get("MSGM_TRAIN_CAT")
+        nocat = sampler and x["set2"] is not None
+        nocat_t = tape is not None and dual and x["set2t"] is not None
         if nocat:
             x["set2"].pack()
-            if self._wino:
-                x["set2"].pack_wino()
-            x["set2"].pack_b6(self._b6)
+            x["set2"].pack_wino()
+            x["set2"].pack_b6(b6)
         if nocat_t:
             x["set2t"].pack()
-            if self._twino:
-                x["set2t"].pack_wino(train=True)
-            else:
-                x["set2t"].clear_train_wino()
+            x["set2t"].pack_wino(train=True)
         for blk in x["outb"]:
             s, Cs = hs.pop()
             r0 = blk[0][1]
@@ -528,7 +513,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
             if tape is not None:
                 tape.append(("cat", C, Cs, H, W))
             h, C, H, W = run_block(blk, cat, C + Cs, H, W)
-        if not dual and tape is None and x["fin"].can_transform_input(N, H, W) and not os.environ.get("MSGM_NO_GN_FOLD"):
+        if sampler and x["fin"].can_transform_input(N, H, W):
             # sampler: the output GroupNorm + SiLU (model/unet.py:442-444) applied by the output conv while it stages its input
             out, _, _ = x["fin"].forward([h], N, H, W, Bp, in_affine=self._gn_fold(core.out[0], h, Bp, H * W, C), in_act=1)
             return out
@@ -638,7 +623,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
                 # that reaches this block's INPUT through the skip stack, when the tensor was saved for the decoder (the
                 # "save_skip" record in front of this block: it was a separate `dh += skip` pass, nine per step)
                 sk = None
-                if i - 1 >= 1 and tape[i - 1][0] == "save_skip" and pend and not os.environ.get("MSGM_NO_SKIP_FOLD"):
+                if i - 1 >= 1 and tape[i - 1][0] == "save_skip" and pend:
                     sk = pend.pop()
                     i -= 1                                          # that record is consumed here
                 dx = self._gn_bwd(rb.m.in_layers[0], xin, st1, dh1, Bp, P, rb.ci, True, residual=None if rb.skip is not None else dh,
@@ -668,7 +653,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
                 dh = None
             elif kind == "down":
                 _, o, hin, H, W = r
-                if i - 1 >= 1 and tape[i - 1][0] == "save_skip" and pend and not os.environ.get("MSGM_NO_SKIP_FOLD"):
+                if i - 1 >= 1 and tape[i - 1][0] == "save_skip" and pend:
                     sk = pend.pop()                                 # the dgrad accumulates onto the skip-stack cotangent
                     i -= 1
                     (dh,) = o.backward(dh, [hin], N, H, W, Bp, dsrc=[sk], dacc=[True])

@@ -14,8 +14,6 @@ backward.
 """
 from __future__ import annotations
 
-import os
-
 from typing import Optional
 
 import torch
@@ -78,8 +76,7 @@ class UNet1D(nn.Module, FlatParamMixin):
         E, chs = self.emb_dim, self.chs
         # Downsample / Upsample (k=4, s=2, p=1) as 3-tap stride-1 convs over position PAIRS (convnet.Stride2PairOp):
         # needs an even length at every level and channel counts that are multiples of 16
-        paired = (self.input_dim % (1 << len(chs)) == 0 and all(c % 16 == 0 for c in chs)
-                  and not os.environ.get("MSGM_NO_PAIRED_STRIDE"))
+        paired = self.input_dim % (1 << len(chs)) == 0 and all(c % 16 == 0 for c in chs)
         o = {"t0": ConvOp(self.time_mlp[0].weight, self.time_mlp[0].bias, "linear", (1,), 1, 0, [1]),
              "t2": ConvOp(self.time_mlp[2].weight, self.time_mlp[2].bias, "linear", (1,), 1, 0, [E])}
         if self.scale_embed is not None:

@@ -109,8 +109,6 @@ SIGNATURES = {
     "msgm_slot_reduce_batched": (C.c_int, [_P, _I32, _I64, _P]),
     "msgm_conv_small_cout_supported": (C.c_int, [C.POINTER(ConvGeomT), _I32, _I32, _I32]),
     "msgm_groupnorm_affine_chanstats": (C.c_int, [_P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _F, _P]),
-    "msgm_conv_wgrad": (C.c_int, [C.POINTER(ConvGeomT), _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _I32,
-                                  C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _P]),
     "msgm_conv_wgrad_workspace": (_SZ, [C.POINTER(ConvGeomT), _I32, _I32, _I32, _I32]),
     "msgm_conv_wgrad_det": (C.c_int, [C.POINTER(ConvGeomT), _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _I32,
                                       C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _P, _SZ, _P]),
@@ -120,7 +118,6 @@ SIGNATURES = {
     "msgm_unpack_weight": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _P]),
     "msgm_act_dual_forward": (C.c_int, [_I32, _P, _P, _I64, _I32, _P]),
     "msgm_act_dual_backward": (C.c_int, [_I32, _P, _P, _I64, _P]),
-    "msgm_colsum": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),
     "msgm_gather_row": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
     "msgm_add_row": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _P]),
     "msgm_groupnorm_workspace": (_SZ, [_I32, _I32]),

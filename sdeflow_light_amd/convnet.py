@@ -60,13 +60,11 @@ class ConvOpSet:
 
     def pack_wino(self, train: bool = False):
         """Winograd images G g G^T of every 3x3 stride-1 convolution of the set, ONE launch.  train = False (sampler path):
-        the forward images; the caller asks for the kernel per call (forward(wino=True)).  train = True (experiment switch
-        MSGM_TRAIN_WINO): also the images of the FLIPPED, transposed kernels (the dgrad as a Winograd forward), and every
-        capable op takes the Winograd kernel for its forward and its dgrad by itself."""
+        the forward images; the caller asks for the kernel per call (forward(wino=True)).  train = True (training pass):
+        also the images of the FLIPPED, transposed kernels (the dgrad as a Winograd forward), and every capable op takes
+        the Winograd kernel for its forward and its dgrad by itself."""
         wops = [o for o in self.ops if getattr(o, "wino_capable", lambda: False)()]
-        for o in self.ops:
-            if hasattr(o, "train_wino"):
-                o.train_wino = False
+        self.clear_train_wino()
         if not wops:
             return
         sig = (bool(train),) + tuple(o.weight.data_ptr() for o in wops)

@@ -538,11 +538,9 @@ static int launch_bwd(const float* qkv, const float* att, const float* datt, con
   // Measured at B = 256 (rocprofv3, 7 steps): one launch 147.2 + 29.1 ms in the two backward kernels + 24.0 ms of reduce;
   // two launches 154.1 + 32.4 + 10.5; four 157.5 + 34.4 + 5.3 — the ACC launches run 7 % (C = 64) to 20 % (C = 128) longer
   // than the plain ones (their slab reads are not free under the MFMAs), so two and four both end 0.5 ms per step ahead.
-  static const int kseq_x = getenv("MSGM_ATTN_KSEQ") ? atoi(getenv("MSGM_ATTN_KSEQ")) : 0;      // diagnostic override
   int kseq = 1;
   for (int k = 2; k > 1; k >>= 1)
     if (nkb % k == 0 && NP * (int64_t)(nkb / k) >= 1024) { kseq = k; break; }
-  if (kseq_x > 0 && nkb % kseq_x == 0) kseq = kseq_x;
   const int nkg = nkb / kseq;
   float* cc = ws;
   float* de = ws + rows;
@@ -583,10 +581,8 @@ int msgm_attention_dual_forward(const float* qkv, float* att, float* stats, int6
     if (T % 64 == 0 && Bp * (int64_t)(T / 64) >= 512) return launch_fwd<8, 1, 16, 4>(qkv, att, stats, Bp, T, scale, S(stream));
     return launch_fwd<8, 1, 16, 2>(qkv, att, stats, Bp, T, scale, S(stream));
   }
-  static const bool qt2 = getenv("MSGM_ATTN_DUAL_QT2") != nullptr;   // diagnostic A/B
-  const bool two = qt2 && T % 128 == 0;
   if (C == 32) return launch_fwd<2, 1, 64, 4>(qkv, att, stats, Bp, T, scale, S(stream));
-  return two ? launch_fwd<4, 2, 32, 4>(qkv, att, stats, Bp, T, scale, S(stream)) : launch_fwd<4, 1, 32, 4>(qkv, att, stats, Bp, T, scale, S(stream));
+  return launch_fwd<4, 1, 32, 4>(qkv, att, stats, Bp, T, scale, S(stream));
 }
 
 int msgm_attention_dual_backward(const float* qkv, const float* att, const float* datt, const float* stats, float* dqkv,

@@ -322,14 +322,8 @@ __global__ void __launch_bounds__(256, (PT == 4 && !DB && NCO == 4) ? CT_WIDE_MI
   // XCD-aware 1-D grid: workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2), so the n_cob
   // output-channel blocks that read the SAME input tiles are given ids 8 apart — same XCD, dispatched back to back —
   // and the re-reads of the input hit that L2 instead of HBM (matters for the 1x1 convolutions, which are HBM-bound).
-  int cob, tgrp;
-  if (n_cob > 0) {
-    const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    cob = loc % n_cob; tgrp = (loc / n_cob) * 8 + xcd;
-  } else {                       // diagnostic (MSGM_CONV_NO_XCD): tile-fastest order, channel blocks far apart
-    const int ntp = 8 * ((n_tgrp + 7) / 8);
-    cob = blockIdx.x / ntp; tgrp = blockIdx.x - cob * ntp;
-  }
+  const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
+  const int cob = loc % n_cob, tgrp = (loc / n_cob) * 8 + xcd;
   if (tgrp >= n_tgrp) return;
   const int co0 = cob * (NCO * 16);
   // A workgroup walks over tiles_per_wg consecutive spatial tiles; the pipeline unit is a (tile, channel chunk)
@@ -1685,16 +1679,15 @@ struct WgradArgs {
   const float* gy;            // [N][Ho][Wo][Cout]
   const float* src;           // one source [N][Hi][Wi][C]
   int C, koff;
-  float* dWp;                 // [taps][CoutP][Ktot], accumulated with float atomics
+  float* dWp;                 // [taps][CoutP][Ktot]: the slot reduction writes it, the kernels do not
   int Cout, CoutP, Ktot;
   int chunk;                  // output positions per workgroup
   float* dbias;               // optional: dbias[co] += sum over primal rows (n < n_bias) and pixels of gy (tile kernel)
   int n_bias;
   // structurally-zero weight blocks (tile kernel): bit t = tap t present, 0 = all; per 32-channel block of c / of co
   unsigned short tm_c[16], tm_o[16];
-  // deterministic mode (msgm_conv_wgrad_det): instead of float atomics into dWp / dbias every workgroup column
-  // blockIdx.x STORES its partial block into its own slab [taps][CoutP][C] (+ [CoutP] bias partials) and
-  // k_wgrad_slab_reduce adds the slabs in slot order.  slab == nullptr: atomics.
+  // every workgroup column blockIdx.x STORES its partial block into its own slab [taps][CoutP][C] (+ [CoutP] bias
+  // partials) and k_slot_reduce adds the slabs in slot order into dWp / dbias: no float atomics, same bits every run
   float* slab; long slab_stride;
 };
 
@@ -1756,7 +1749,7 @@ __global__ void __launch_bounds__(256) k_conv_wgrad(WgradArgs A) {
     while (ow >= g.Wo) { ow -= g.Wo; ++oh; }
     while (oh >= g.Ho) { oh -= g.Ho; ++n; }
   }
-  // cross-wave sum, then one atomic per element per workgroup
+  // cross-wave sum, then one slab store per element per workgroup
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -1774,10 +1767,7 @@ __global__ void __launch_bounds__(256) k_conv_wgrad(WgradArgs A) {
           const int idx = ((mt * KT + kt) * 4 + r) * 64 + lane;
           const float s = (red[0][idx] + red[1][idx]) + (red[2][idx] + red[3][idx]);
           const int co = co0 + 16 * mt + 4 * q + r, c = c0 + 16 * kt + il;
-          if (co < A.Cout && c < A.C) {
-            if (A.slab) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)(tap * A.CoutP + co) * A.C + c] = s;
-            else atomicAdd(A.dWp + ((size_t)(tap * A.CoutP + co) * A.Ktot + A.koff + c), s);
-          }
+          if (co < A.Cout && c < A.C) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)(tap * A.CoutP + co) * A.C + c] = s;
         }
   }
 }
@@ -1788,8 +1778,8 @@ __global__ void __launch_bounds__(256) k_conv_wgrad(WgradArgs A) {
 // spatial tiles of TH x TW = 128 output pixels: per tile it stages gy [pixel][co] and the input halo tile
 // [halo pixel][c] ONCE (coalesced 16-B global loads, stored transposed as [channel][pixel] so that the reduction
 // index — the pixel — is contiguous for the MFMA fragments), then every tap reads its shifted window from LDS.
-// Each wave reduces its own 32 pixels; the four partial sums meet in LDS at the end and are added to dWp with one
-// float atomic per element per workgroup.
+// Each wave reduces its own 32 pixels; the four partial sums meet in LDS at the end and go to the workgroup's slab with
+// one store per element.
 #define WT_GP 132
 // gy^T rows are [channel][pixel ^ WT_SWZ(channel)]: the transposed store of a staged float4 (lane = 4 channels of one pixel, 8
 // lanes per pixel) put 32 lanes on 8 banks (pitch 132 = 4 mod 32: channel quads c4 and c4 + 2 collide, 4-way) — measured
@@ -1966,10 +1956,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
     bsum += __shfl_xor(bsum, 2, 64);
     bsum += __shfl_xor(bsum, 4, 64);
     const int co = co0 + (tid >> 3);
-    if ((tid & 7) == 0 && co < A.Cout) {
-      if (A.slab) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)TAPS * A.CoutP * A.C + co] = bsum;
-      else atomicAdd(A.dbias + co, bsum);
-    }
+    if ((tid & 7) == 0 && co < A.Cout) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)TAPS * A.CoutP * A.C + co] = bsum;
   }
   // cross-wave reduction through LDS (reuse the staging area): up to four taps per round — every wave parks its partial
   // tiles of the round's taps, one barrier, then wave w adds the four partials of tap (round base + w) in wave order and
@@ -1997,8 +1984,8 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
     __syncthreads();
     {
       const int tt = w, t = t0 + tt;                       // wave-uniform
-      // a skipped (structurally zero) block still stores its zeros into a slab (the slab reduction reads every slot)
-      if (tt < TR && t < TAPS && (((tmask >> t) & 1u) || A.slab)) {
+      // a skipped (structurally zero) block still stores its zeros into the slab (the slab reduction reads every slot)
+      if (tt < TR && t < TAPS) {
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -2008,10 +1995,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
               const int idx = tt * 4096 + ((m * 2 + kt) * 4 + r) * 64 + lane;
               const float sum = (red[idx] + red[1024 + idx]) + (red[2048 + idx] + red[3072 + idx]);
               const int co = co0 + 16 * m + 4 * q + r, c = c0 + 16 * kt + il;
-              if (co < A.Cout && c < A.C) {
-                if (A.slab) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)(t * A.CoutP + co) * A.C + c] = sum;
-                else atomicAdd(A.dWp + ((size_t)(t * A.CoutP + co) * A.Ktot + A.koff + c), sum);
-              }
+              if (co < A.Cout && c < A.C) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)(t * A.CoutP + co) * A.C + c] = sum;
             }
       }
     }
@@ -2145,10 +2129,7 @@ __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x
     bsum += __shfl_xor(bsum, 2, 64);
     bsum += __shfl_xor(bsum, 4, 64);
     const int co = co0 + (tid >> 3);
-    if ((tid & 7) == 0 && co < A.Cout) {
-      if (A.slab) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)TAPS * A.CoutP * A.C + co] = bsum;
-      else atomicAdd(A.dbias + co, bsum);
-    }
+    if ((tid & 7) == 0 && co < A.Cout) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)TAPS * A.CoutP * A.C + co] = bsum;
   }
   const int c = c0 + 16 * kt + il;
 #pragma unroll
@@ -2156,10 +2137,7 @@ __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int co = co0 + 16 * m + 4 * q + r;
-      if (co < A.Cout && c < A.C) {
-        if (A.slab) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)(t * A.CoutP + co) * A.C + c] = acc[t][r];
-        else atomicAdd(A.dWp + ((size_t)(t * A.CoutP + co) * A.Ktot + A.koff + c), acc[t][r]);
-      }
+      if (co < A.Cout && c < A.C) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)(t * A.CoutP + co) * A.C + c] = acc[t][r];
     }
 }
 
@@ -2175,7 +2153,7 @@ __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x
 // four waves split the OUTPUT block (wave tile MT x NT: MT + NT LDS reads per MT NT MFMAs), two LDS buffers, one barrier
 // per tile, the next tile's global loads in flight under this tile's MFMAs.  Every gy / x byte is read once per output-
 // channel block (one block for Cout <= 192); the workgroup's partial dW goes to its slab (slot = blockIdx.x, reduced in
-// slot order like every other wgrad) or to dWp with float atomics, the bias gradient (column sums of the primal pixels'
+// slot order like every other wgrad), the bias gradient (column sums of the primal pixels'
 // gy rows) comes from the staged tile.
 // Pixels per staged tile for a row of W floats: the largest multiple of 16 with PX W <= 8192 floats (2 x 33 KB of LDS, two
 // workgroups per CU) whose float4 count is a multiple of 256, so that every thread stages exactly PX W / 1024 items.
@@ -2290,30 +2268,17 @@ __global__ void __launch_bounds__(256, 2) k_wgrad1x1(WgradArgs A, long Mtot, lon
       t += __shfl_xor(t, 16, 64);
       t += __shfl_xor(t, 32, 64);
       const int co = co_blk + 16 * (wm * MT + m) + il;
-      if (q == 0) {
-        if (A.slab) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)A.CoutP * A.C + co] = t;
-        else atomicAdd(A.dbias + co, t);
-      }
+      if (q == 0) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)A.CoutP * A.C + co] = t;
     }
   }
-  if (A.slab) {
-    float* sl = A.slab + (size_t)blockIdx.x * A.slab_stride;
+  float* sl = A.slab + (size_t)blockIdx.x * A.slab_stride;
 #pragma unroll
-    for (int m = 0; m < MT; ++m)
+  for (int m = 0; m < MT; ++m)
 #pragma unroll
-      for (int n = 0; n < NT; ++n)
+    for (int n = 0; n < NT; ++n)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          sl[(size_t)(co_blk + 16 * (wm * MT + m) + 4 * q + r) * A.C + 16 * (wn * NT + n) + il] = acc[m][n][r];
-  } else {
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int n = 0; n < NT; ++n)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          atomicAdd(A.dWp + ((size_t)(co_blk + 16 * (wm * MT + m) + 4 * q + r) * A.Ktot + A.koff + 16 * (wn * NT + n) + il), acc[m][n][r]);
-  }
+      for (int r = 0; r < 4; ++r)
+        sl[(size_t)(co_blk + 16 * (wm * MT + m) + 4 * q + r) * A.C + 16 * (wn * NT + n) + il] = acc[m][n][r];
 }
 
 // ------------------------------------------------------------------ weight (un)packing
@@ -2399,9 +2364,6 @@ __global__ void k_act_dual_bwd(const float* __restrict__ z, float* __restrict__ 
   }
 }
 
-// S[n][c] (+)= sum over positions of x[n][pos][c]  (bias / embedding gradients).  Grid (n, position
-// chunk): threads along channels, LDS across pixel lanes, one float atomic per (n, c) per block into a
-// zeroed S (a per-sample workgroup would leave the chip idle at small batch).
 // 32 elements x 8 slot slices per workgroup: every slice adds its slots in order, the slices are added in order.
 // out[map(e)] (+)= sum_slot part[slot * stride + e] — the deterministic replacement of float atomics (no run-to-run
 // difference in the weight / bias gradients).  map: wgrad image element e = (tap*CoutP + co)*C + c ->
@@ -2466,7 +2428,10 @@ __global__ void __launch_bounds__(256) k_slot_reduce_batched(const msgm_reduce_j
                     J.rowsP, J.rows, (long)J.n_elem2, J.out2);
 }
 
-__global__ void __launch_bounds__(256) k_colsum(const float* __restrict__ x, float* __restrict__ S, int P, int C, int chunk, int acc) {
+// Sums over positions of x[n][pos][c]  (bias / embedding gradients).  Grid (n, position chunk): threads along channels,
+// LDS across pixel lanes (a per-sample workgroup would leave the chip idle at small batch).  One chunk: S[n][c] = the
+// sum; several: S = [chunk][n][C] partials, added in chunk order by k_slot_reduce.
+__global__ void __launch_bounds__(256) k_colsum(const float* __restrict__ x, float* __restrict__ S, int P, int C, int chunk) {
   __shared__ float red[256];
   const int n = blockIdx.x;
   const float* xn = x + (size_t)n * P * C;
@@ -2483,9 +2448,7 @@ __global__ void __launch_bounds__(256) k_colsum(const float* __restrict__ x, flo
     if (pr == 0) {
       float t = 0.f;
       for (int r = 0; r < rows; ++r) t += red[r * lanes_c + c];
-      if (acc == 2) S[((size_t)blockIdx.y * gridDim.x + n) * C + cb + c] = t;     // slot mode: S = [chunk][n][C] partials
-      else if (gridDim.y == 1 && !acc) S[(size_t)n * C + cb + c] = t;
-      else atomicAdd(S + (size_t)n * C + cb + c, t);
+      S[((size_t)blockIdx.y * gridDim.x + n) * C + cb + c] = t;
     }
     __syncthreads();
   }
@@ -2535,8 +2498,7 @@ static bool conv_tile_eligible(const msgm_conv_geom_t* geom, int32_t C0, const f
                     (geom->KH & 1) && (geom->KW & 1) && geom->padH == (geom->KH - 1) / 2 && geom->padW == (geom->KW - 1) / 2 &&
                     geom->KH <= 3 && geom->KW <= 3;
   return same && fast && CoutP % 32 == 0 && (int64_t)geom->Ho * geom->Wo >= 64 &&
-         (geom->Ho > 1 ? geom->KH == geom->KW : geom->KH == 1) &&          // square kernels in 2-D, KH = 1 in 1-D
-         !getenv("MSGM_NO_CONV_TILE");
+         (geom->Ho > 1 ? geom->KH == geom->KW : geom->KH == 1);            // square kernels in 2-D, KH = 1 in 1-D
 }
 
 int msgm_conv_input_transform_supported(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t CoutP) {
@@ -2606,10 +2568,8 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
   dim3 grid((unsigned)(8 * gy * ((n_tiles + 7) / 8)));
   // one 32-channel chunk (Ktot = 32: the 64x64 32 -> 32 layers) has nothing to pipeline and pays the extra barriers: 96 vs
   // 104 TFLOP/s as written; from 64 input channels on the LDS weights win, +2 .. +18 % (AFF=1 tools/bench_wino.py)
-  static const bool reg_weights = getenv("MSGM_WINO_REGW") != nullptr;    // A/B: the register weight ring everywhere
-  static const bool no_p32 = getenv("MSGM_WINO_NO_P32") != nullptr;       // A/B: the 32-channel layers without the persistent form
-  static const int p32_min = getenv("MSGM_WINO_P32_MIN") ? atoi(getenv("MSGM_WINO_P32_MIN")) : 1024;      // >= 4 tiles per workgroup (B = 32: 18.6 -> 18.5 ms)
-  if (!reg_weights && !no_p32 && !src1 && Ktot == 32 && CoutP == 32 && n_tiles >= p32_min) {
+  constexpr int p32_min = 1024;                            // >= 4 tiles per workgroup (B = 32: 18.6 -> 18.5 ms)
+  if (!src1 && Ktot == 32 && CoutP == 32 && n_tiles >= p32_min) {
     // one persistent workgroup per CU (>= 8 tiles each): weights resident in LDS, halo double-buffered
     static const int once32 = [] {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_wino_p32), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -2620,7 +2580,7 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
     hipLaunchKernelGGL(k_conv_wino_p32, dim3((unsigned)n_cu), dim3(256), lds32, S(stream), A, tiles_x, tiles_y, n_tiles);
     return msgm_check_launch();
   }
-  if (reg_weights || Ktot < 64) {
+  if (Ktot < 64) {
     hipLaunchKernelGGL((k_conv_wino<2, false>), grid, dim3(256), lds, S(stream), A, tiles_x, tiles_y, n_tiles, gy, n_tiles);
     return msgm_check_launch();
   }
@@ -2718,8 +2678,7 @@ struct ConvRoute {
 };
 // first / last convolution of the U-Net: 3x3 "same", one source, <= 4 channels on one side and 32 on the other
 static bool conv_small_shape(const msgm_conv_geom_t* geom, bool has1, bool masks) {
-  static const bool off = getenv("MSGM_NO_CONV_SMALL") != nullptr;         // diagnostic A/B
-  return !off && geom->KH == 3 && geom->KW == 3 && geom->strideH == 1 && geom->strideW == 1 &&
+  return geom->KH == 3 && geom->KW == 3 && geom->strideH == 1 && geom->strideW == 1 &&
          geom->padH == 1 && geom->padW == 1 && !geom->ups && geom->Hi == geom->Ho && geom->Wi == geom->Wo && geom->Ho > 1 &&
          !has1 && !masks;
 }
@@ -2733,9 +2692,8 @@ static ConvRoute conv_route(const msgm_conv_geom_t* geom, int32_t C0, bool has1,
   }
   const bool fast = (C0 % 16 == 0) && (!has1 || C1 % 16 == 0);
   const int Ktot = ((C0 + 15) / 16) * 16 + (has1 ? ((C1 + 15) / 16) * 16 : 0);
-  static const bool no1 = getenv("MSGM_NO_CONV1X1") != nullptr;            // diagnostic A/B
   const int kg = Ktot / 16;
-  if (!no1 && geom->KH == 1 && geom->KW == 1 && geom->strideH == 1 && geom->strideW == 1 && geom->padH == 0 && geom->padW == 0 &&
+  if (geom->KH == 1 && geom->KW == 1 && geom->strideH == 1 && geom->strideW == 1 && geom->padH == 0 && geom->padW == 0 &&
       !geom->ups && geom->Hi == geom->Ho && geom->Wi == geom->Wo && fast && !masks && (Mtot >= 4096 || any_size) &&
       (kg == 2 || kg == 4 || kg == 6 || kg == 8 || kg == 12 || kg == 16) && Cout % 16 == 0 && !both_extra) {
     // resident activations: PT * KG float4 per lane (<= 64 registers).  Fewer pixels per wave (more waves per SIMD) measured
@@ -2752,10 +2710,9 @@ static ConvRoute conv_route(const msgm_conv_geom_t* geom, int32_t C0, bool has1,
     r.two_d = geom->Ho > 1;
     r.nco = (CoutP % 64 == 0) ? 4 : 2;
     // 3-tap / 3x3 kernels: 256-pixel tiles (4 MFMA column tiles per wave, one LDS buffer) when the image has them —
-    // measured +10..27 % in 2-D and +3..8 % in 1-D over the 128-pixel double-buffered form (tools/exp_wide.py);
+    // measured +10..27 % in 2-D and +3..8 % in 1-D over the 128-pixel double-buffered form;
     // 1x1 kernels (no tap reuse, HBM-bound) stay on the 128-pixel form, which measured equal or better
-    const bool no_wide = getenv("MSGM_NO_CONV_WIDE") != nullptr;            // diagnostic A/B
-    bool wide = geom->KW == 3 && !no_wide && (r.two_d ? (geom->Ho >= 16 && geom->Wo >= 16) : geom->Wo >= 256);
+    bool wide = geom->KW == 3 && (r.two_d ? (geom->Ho >= 16 && geom->Wo >= 16) : geom->Wo >= 256);
     if (wide) {
       // small launches (the 32-row per-GPU shard of C4): below two 256-pixel workgroups per CU the chip is not
       // filled — 128-pixel tiles double the workgroup count (B = 32 step 26.3 -> 25.5 ms; no change at B >= 128)
@@ -2768,9 +2725,8 @@ static ConvRoute conv_route(const msgm_conv_geom_t* geom, int32_t C0, bool has1,
     r.tiles_x = (geom->Wo + r.TW - 1) / r.TW; r.tiles_y = (geom->Ho + r.TH - 1) / r.TH;
     // still fewer than two workgroups per CU (the 16x16 layers of the 32-row shard: 128 tiles x 2 channel blocks): 32
     // instead of 64 output channels per workgroup doubles the count; the input tile is then staged twice, from L2
-    static const bool no_split = getenv("MSGM_NO_CONV_COSPLIT") != nullptr;  // diagnostic A/B
     // (not with tap masks: tapmask_out is indexed by the 64-channel block when CoutP % 64 == 0)
-    if (!wide && r.nco == 4 && !no_split && !masks && (int64_t)geom->N * r.tiles_x * r.tiles_y * (CoutP / 64) < 512) r.nco = 2;
+    if (!wide && r.nco == 4 && !masks && (int64_t)geom->N * r.tiles_x * r.tiles_y * (CoutP / 64) < 512) r.nco = 2;
     return r;
   }
   r.pt = (CoutP >= 64 && CoutP % 64 == 0) ? 2 : 4;         // NT of the k_conv_gemm<MT, NT> instantiation launched below
@@ -2827,8 +2783,7 @@ int msgm_conv_forward_fused(const msgm_conv_geom_t* geom, const float* src0, int
   // training step at the 32-row shard).
   msgm_conv_geom_t lin = *geom;
   const bool as_pixels = geom->Hi == 1 && geom->Wi == 1 && geom->Ho == 1 && geom->Wo == 1 && geom->KH == 1 && geom->KW == 1 &&
-                         geom->N >= 32 && !samp_bias && (!bias || n_bias >= geom->N) && !(fuse && (fuse->in_scale || fuse->chanstats)) &&
-                         !getenv("MSGM_NO_LINEAR_AS_PIXELS");
+                         geom->N >= 32 && !samp_bias && (!bias || n_bias >= geom->N) && !(fuse && (fuse->in_scale || fuse->chanstats));
   if (as_pixels) {
     lin.Wi = lin.Wo = geom->N; lin.N = 1; lin.mode = 0;
     const ConvRoute rl = conv_route(&lin, C0, src1 != nullptr, C1, Cout, CoutP, masks, both_extra, true);
@@ -2908,8 +2863,7 @@ int msgm_conv_forward_fused(const msgm_conv_geom_t* geom, const float* src0, int
     // several consecutive tiles per workgroup (the next tile's halo loads overlap this tile's MFMAs) — but only
     // while >= 8 rounds of resident workgroups (3 per CU) remain: below that the tail of the last round costs more
     // than the hidden prologues gain (measured, tools/bench_conv.py)
-    const int max_per = getenv("MSGM_CONV_TILES") ? atoi(getenv("MSGM_CONV_TILES")) : 4;
-    const int rounds = getenv("MSGM_CONV_ROUNDS") ? atoi(getenv("MSGM_CONV_ROUNDS")) : 8;
+    constexpr int max_per = 4, rounds = 8;
     int per = (int)(((int64_t)n_tiles * gy) / (768 * rounds));
     if (per > max_per) per = max_per;
     if (per < 1) per = 1;
@@ -2917,7 +2871,7 @@ int msgm_conv_forward_fused(const msgm_conv_geom_t* geom, const float* src0, int
     dim3 grid((unsigned)(8 * gy * ((n_tgrp + 7) / 8)));
     const int flip = geom->mode;
 #define CT_LAUNCH(TH_, TW_, NCO_, KS_, PT_, DB_) \
-  hipLaunchKernelGGL((k_conv_tile<TH_, TW_, NCO_, KS_, PT_, DB_>), grid, dim3(256), lds, S(stream), A, flip, tiles_x, tiles_y, per, n_tiles, getenv("MSGM_CONV_NO_XCD") ? -gy : gy, n_tgrp)
+  hipLaunchKernelGGL((k_conv_tile<TH_, TW_, NCO_, KS_, PT_, DB_>), grid, dim3(256), lds, S(stream), A, flip, tiles_x, tiles_y, per, n_tiles, gy, n_tgrp)
     const bool k3 = geom->KW == 3;
     if (two_d) {
       if (wide) { if (nco == 4) CT_LAUNCH(16, 16, 4, 3, 4, false); else CT_LAUNCH(16, 16, 2, 3, 4, false); }
@@ -2968,8 +2922,7 @@ static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n
   const bool same = geom->mode == 0 && geom->strideH == 1 && geom->strideW == 1 && (geom->Hi << ups_sh) == geom->Ho &&
                     (geom->Wi << ups_sh) == geom->Wo && (geom->KH & 1) && (geom->KW & 1) && geom->padH == (geom->KH - 1) / 2 &&
                     geom->padW == (geom->KW - 1) / 2 && geom->KH <= 3 && geom->KW <= 3;
-  if (taps == 1 && same && !geom->ups && geom->padH == 0 && geom->padW == 0 && ((int64_t)n_bias * geom->Ho * geom->Wo) % 16 == 0 &&
-      !getenv("MSGM_NO_WGRAD1X1")) {
+  if (taps == 1 && same && !geom->ups && geom->padH == 0 && geom->padW == 0 && ((int64_t)n_bias * geom->Ho * geom->Wo) % 16 == 0) {
     wgrad1x1_shape(C, Cout, &p.mt, &p.nt, &p.wm);
     if (p.mt) {
       p.one = true;
@@ -2988,19 +2941,19 @@ static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n
     }
   }
   const bool aligned = C % 4 == 0 && Cout % 4 == 0;      // otherwise only the 2-D 3x3 form has the element-wise staging (RAG)
-  p.tile = same && (aligned || (taps == 9 && geom->Ho > 1 && !getenv("MSGM_NO_WGRAD_RAG"))) && (int64_t)geom->Ho * geom->Wo >= 64 &&
-           (taps == 1 || taps == 3 || (taps == 9 && geom->Ho > 1)) && (geom->Ho > 1 || geom->KH == 1) && !getenv("MSGM_NO_WGRAD_TILE");
+  p.tile = same && (aligned || (taps == 9 && geom->Ho > 1)) && (int64_t)geom->Ho * geom->Wo >= 64 &&
+           (taps == 1 || taps == 3 || (taps == 9 && geom->Ho > 1)) && (geom->Ho > 1 || geom->KH == 1);
   if (p.tile) {
     const bool two_d = geom->Ho > 1;
     const int TH = two_d ? 8 : 1, TW = two_d ? 16 : 128;
     p.tiles_x = (geom->Wo + TW - 1) / TW; p.tiles_y = (geom->Ho + TH - 1) / TH;
     p.n_tiles = p.tiles_x * p.tiles_y * geom->N;
     p.yblocks = ((Cout + 31) / 32) * ((C + 31) / 32);
-    static const int wg_target = getenv("MSGM_WGRAD_WGS") ? (atoi(getenv("MSGM_WGRAD_WGS")) > 0 ? atoi(getenv("MSGM_WGRAD_WGS")) : 1) : 768;    // = 3 resident workgroups per CU (k_wgrad_tile9 and the 1- / 3-tap forms); r3 measured 768 / 1024 / 1536 / 3072: 124.0 / 126.4 / 124.7 / 124.9 ms per C4 step (r2, two workgroups per CU: 1024 was best)
+    constexpr int wg_target = 768;                         // = 3 resident workgroups per CU (k_wgrad_tile9 and the 1- / 3-tap forms); r3 measured 768 / 1024 / 1536 / 3072: 124.0 / 126.4 / 124.7 / 124.9 ms per C4 step (r2, two workgroups per CU: 1024 was best)
     int wgs = wg_target / p.yblocks;                       // ~4 workgroups per CU overall
     if (wgs < 1) wgs = 1;
     int per = (p.n_tiles + wgs - 1) / wgs;
-    static const int min_per = getenv("MSGM_WGRAD_PER") ? (atoi(getenv("MSGM_WGRAD_PER")) > 0 ? atoi(getenv("MSGM_WGRAD_PER")) : 1) : 8;   // >= 8 tiles per workgroup amortise the cross-wave sum + atomics
+    constexpr int min_per = 8;                             // >= 8 tiles per workgroup amortise the cross-wave sum + slab stores
     if (per < min_per) per = p.n_tiles < min_per ? p.n_tiles : min_per;
     if (per < 1) per = 1;
     p.per = per;
@@ -3030,7 +2983,7 @@ static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n
 
 static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                       float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
-                      const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, float* ws, size_t ws_bytes, bool det,
+                      const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, float* ws, size_t ws_bytes,
                       msgm_stream_t stream, msgm_reduce_job_t* jobs_out = nullptr, int32_t* n_jobs_out = nullptr);
 
 size_t msgm_conv_wgrad_workspace(const msgm_conv_geom_t* geom, int32_t C, int32_t Cout, int32_t CoutP, int32_t n_bias) {
@@ -3041,20 +2994,13 @@ size_t msgm_conv_wgrad_workspace(const msgm_conv_geom_t* geom, int32_t C, int32_
   return (slots * stride + (size_t)p.bias_slots * Cout) * sizeof(float);
 }
 
-int msgm_conv_wgrad(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
-                    float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
-                    const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, msgm_stream_t stream) {
-  return wgrad_impl(geom, gy, src, C, koff, dWp, Cout, CoutP, Ktot, dbias, n_bias, tapmask_c32, tapmask_co32, nullptr, 0, false,
-                    stream);
-}
-
 int msgm_conv_wgrad_det(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                         float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
                         const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, void* workspace, size_t workspace_bytes,
                         msgm_stream_t stream) {
   if (!workspace) return MSGM_E_BADARG;
   return wgrad_impl(geom, gy, src, C, koff, dWp, Cout, CoutP, Ktot, dbias, n_bias, tapmask_c32, tapmask_co32,
-                    static_cast<float*>(workspace), workspace_bytes, true, stream);
+                    static_cast<float*>(workspace), workspace_bytes, stream);
 }
 
 int msgm_conv_wgrad_slabs(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
@@ -3064,7 +3010,7 @@ int msgm_conv_wgrad_slabs(const msgm_conv_geom_t* geom, const float* gy, const f
   if (!workspace || !jobs_out || !n_jobs_out) return MSGM_E_BADARG;
   *n_jobs_out = 0;
   return wgrad_impl(geom, gy, src, C, koff, dWp, Cout, CoutP, Ktot, dbias, n_bias, tapmask_c32, tapmask_co32,
-                    static_cast<float*>(workspace), workspace_bytes, true, stream, jobs_out, n_jobs_out);
+                    static_cast<float*>(workspace), workspace_bytes, stream, jobs_out, n_jobs_out);
 }
 
 int msgm_slot_reduce_batched(const msgm_reduce_job_t* jobs_dev, int32_t n_jobs, int64_t total_blocks, msgm_stream_t stream) {
@@ -3075,22 +3021,21 @@ int msgm_slot_reduce_batched(const msgm_reduce_job_t* jobs_dev, int32_t n_jobs, 
 
 static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                       float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
-                      const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, float* ws, size_t ws_bytes, bool det,
+                      const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, float* ws, size_t ws_bytes,
                       msgm_stream_t stream, msgm_reduce_job_t* jobs_out, int32_t* n_jobs_out) {
   int rc = check_geom(geom);
   if (rc) return rc;
   if (!gy || !src || !dWp || C <= 0 || Cout <= 0 || koff < 0 || koff + C > Ktot || (dbias && n_bias <= 0)) return MSGM_E_BADARG;
-  if (det && ws_bytes < msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, dbias ? n_bias : 0)) return MSGM_E_WORKSPACE;
-  WgradArgs A{to_geom(geom), gy, src, C, koff, dWp, Cout, CoutP, Ktot, 0, dbias, n_bias, {0}, {0}, nullptr, 0};
-  const WgradPlan pl = wgrad_plan(geom, C, Cout, dbias ? n_bias : 0);
+  if (ws_bytes < msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, dbias ? n_bias : 0)) return MSGM_E_WORKSPACE;
   const long img = (long)geom->KH * geom->KW * CoutP * C;
-  if (det) { A.slab = ws; A.slab_stride = img + CoutP; }
+  WgradArgs A{to_geom(geom), gy, src, C, koff, dWp, Cout, CoutP, Ktot, 0, dbias, n_bias, {0}, {0}, ws, img + CoutP};
+  const WgradPlan pl = wgrad_plan(geom, C, Cout, dbias ? n_bias : 0);
   for (int i = 0; i < 16; ++i) {
     A.tm_c[i] = (tapmask_c32 && i < (C + 31) / 32) ? tapmask_c32[i] : 0;
     A.tm_o[i] = (tapmask_co32 && i < (Cout + 31) / 32) ? tapmask_co32[i] : 0;
   }
   const int taps = geom->KH * geom->KW;
-  auto reduce_slabs = [&](int nslots, bool with_bias) {     // deterministic mode: slabs -> dWp (+ dbias), slot order
+  auto reduce_slabs = [&](int nslots, bool with_bias) {     // slabs -> dWp (+ dbias), slot order
     if (jobs_out) {                                          // deferred: the caller batches the reductions of a whole pass
       msgm_reduce_job_t& J = jobs_out[(*n_jobs_out)++];
       J = msgm_reduce_job_t{ws, dWp, with_bias ? dbias : nullptr, (int64_t)A.slab_stride, (int64_t)img, with_bias ? (int64_t)Cout : 0, 0,
@@ -3135,7 +3080,7 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
       default: return MSGM_E_UNSUPPORTED;
     }
 #undef W1_LAUNCH
-    if (det) reduce_slabs(pl.wgs, dbias != nullptr);
+    reduce_slabs(pl.wgs, dbias != nullptr);
     return msgm_check_launch();
   }
   if (pl.tile) {
@@ -3162,9 +3107,8 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
     const bool rag = (C & 3) || (Cout & 3);
     if (two_d) {
       if (taps == 9) {
-        static const bool old9 = getenv("MSGM_WGRAD_OLD9") != nullptr;      // A/B: the pixel-split kernel
         if (rag) WT_LAUNCH2(8, 16, 9, true);
-        else if (old9 || tapmask_c32 || tapmask_co32) WT_LAUNCH(8, 16, 9);
+        else if (tapmask_c32 || tapmask_co32) return MSGM_E_UNSUPPORTED;   // k_wgrad_tile9 has no tap masks (they come from 3-tap 1-D convs)
         else {
           const size_t lds9 = (size_t)(32 * WT_GP + 32 * IP) * sizeof(float);
           hipLaunchKernelGGL(k_wgrad_tile9, grid, dim3(256), lds9, S(stream), A, tiles_x, tiles_y, per, n_tiles);
@@ -3175,28 +3119,24 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
     else { if (taps == 3) WT_LAUNCH(1, 128, 3); else WT_LAUNCH(1, 128, 1); }
 #undef WT_LAUNCH
 #undef WT_LAUNCH2
-    if (det) reduce_slabs(wgs, dbias != nullptr);
+    reduce_slabs(wgs, dbias != nullptr);
     return msgm_check_launch();
   }
   const int64_t nchunks = pl.nchunks;
   A.chunk = (int)pl.chunk;
   dim3 grid((unsigned)nchunks, (unsigned)pl.yblocks, (unsigned)taps);
   hipLaunchKernelGGL((k_conv_wgrad<2, 4>), grid, dim3(256), 0, S(stream), A);
-  if (det) reduce_slabs((int)nchunks, false);
-  if (dbias) {                                             // no by-product in this kernel: a separate accumulating column sum
+  reduce_slabs((int)nchunks, false);
+  if (dbias) {                                             // no by-product in this kernel: a separate column sum
     const int64_t Pb = (int64_t)n_bias * geom->Ho * geom->Wo;
-    if (det) {
-      float* part = ws + (size_t)nchunks * A.slab_stride;   // [bias_slots][Cout] partials, then slot-ordered sum
-      hipLaunchKernelGGL(k_colsum, dim3(1, (unsigned)pl.bias_slots), dim3(256), 0, S(stream), gy, part, (int)Pb, Cout, (int)pl.bias_chunk, 2);
-      if (jobs_out) {
-        msgm_reduce_job_t& J = jobs_out[(*n_jobs_out)++];
-        J = msgm_reduce_job_t{part, dbias, nullptr, (int64_t)Cout, (int64_t)Cout, 0, 0, (int32_t)pl.bias_slots, 1, 0, 0, 0, 0, 1, 0};
-      } else
+    float* part = ws + (size_t)nchunks * A.slab_stride;     // [bias_slots][Cout] partials, then slot-ordered sum
+    hipLaunchKernelGGL(k_colsum, dim3(1, (unsigned)pl.bias_slots), dim3(256), 0, S(stream), gy, part, (int)Pb, Cout, (int)pl.bias_chunk);
+    if (jobs_out) {
+      msgm_reduce_job_t& J = jobs_out[(*n_jobs_out)++];
+      J = msgm_reduce_job_t{part, dbias, nullptr, (int64_t)Cout, (int64_t)Cout, 0, 0, (int32_t)pl.bias_slots, 1, 0, 0, 0, 0, 1, 0};
+    } else
       hipLaunchKernelGGL(k_slot_reduce, dim3((unsigned)((Cout + 31) / 32)), dim3(256), 0, S(stream), (const float*)part,
                          (int)pl.bias_slots, (long)Cout, (long)Cout, dbias, 1, 0, 0, 1, 0, 0, 0L, (float*)nullptr);
-    } else {
-      hipLaunchKernelGGL(k_colsum, dim3(1, (unsigned)pl.bias_slots), dim3(256), 0, S(stream), gy, dbias, (int)Pb, Cout, (int)pl.bias_chunk, 1);
-    }
   }
   return msgm_check_launch();
 }
@@ -3256,18 +3196,6 @@ int msgm_act_dual_backward(int32_t act, const float* z, float* g, int64_t half, 
   return msgm_check_launch();
 }
 
-int msgm_colsum(const float* x, float* Sout, int32_t N, int32_t P, int32_t C, msgm_stream_t stream) {
-  if (!x || !Sout || N <= 0 || P <= 0 || C <= 0) return MSGM_E_BADARG;
-  int nch = (1024 + N - 1) / N;
-  int chunk = (P + nch - 1) / nch;
-  if (chunk < 64) chunk = 64;
-  if (chunk > P) chunk = P;
-  nch = (P + chunk - 1) / chunk;
-  if (nch > 1 && msgm_zero_async(Sout, (size_t)N * C * sizeof(float), S(stream)) != MSGM_OK) return MSGM_E_LAUNCH;
-  hipLaunchKernelGGL(k_colsum, dim3(N, nch), dim3(256), 0, S(stream), x, Sout, P, C, chunk, 0);
-  return msgm_check_launch();
-}
-
 size_t msgm_colsum_workspace(int32_t N, int32_t P, int32_t C) {
   if (N <= 0 || P <= 0 || C <= 0) return 0;
   int nch = (1024 + N - 1) / N;
@@ -3278,7 +3206,7 @@ size_t msgm_colsum_workspace(int32_t N, int32_t P, int32_t C) {
   return nch > 1 ? (size_t)nch * N * C * sizeof(float) : 0;
 }
 
-// the same sums without float atomics: per-chunk partials [chunk][N][C] in the workspace, added in chunk order
+// S[n][c] = sum over positions of x[n][pos][c]: per-chunk partials [chunk][N][C] in the workspace, added in chunk order
 int msgm_colsum_det(const float* x, float* Sout, int32_t N, int32_t P, int32_t C, void* workspace, size_t workspace_bytes,
                     msgm_stream_t stream) {
   if (!x || !Sout || N <= 0 || P <= 0 || C <= 0) return MSGM_E_BADARG;
@@ -3288,12 +3216,12 @@ int msgm_colsum_det(const float* x, float* Sout, int32_t N, int32_t P, int32_t C
   if (chunk > P) chunk = P;
   nch = (P + chunk - 1) / chunk;
   if (nch == 1) {
-    hipLaunchKernelGGL(k_colsum, dim3(N, 1), dim3(256), 0, S(stream), x, Sout, P, C, chunk, 0);
+    hipLaunchKernelGGL(k_colsum, dim3(N, 1), dim3(256), 0, S(stream), x, Sout, P, C, chunk);
     return msgm_check_launch();
   }
   if (!workspace || workspace_bytes < msgm_colsum_workspace(N, P, C)) return MSGM_E_WORKSPACE;
   float* part = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(k_colsum, dim3(N, nch), dim3(256), 0, S(stream), x, part, P, C, chunk, 2);
+  hipLaunchKernelGGL(k_colsum, dim3(N, nch), dim3(256), 0, S(stream), x, part, P, C, chunk);
   const long n_elem = (long)N * C;
   hipLaunchKernelGGL(k_slot_reduce, dim3((unsigned)((n_elem + 31) / 32)), dim3(256), 0, S(stream), (const float*)part, nch, n_elem,
                      n_elem, Sout, 1, 0, 0, 0, 0, 0, 0L, (float*)nullptr);

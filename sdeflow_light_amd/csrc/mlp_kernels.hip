@@ -937,7 +937,7 @@ static void set_lds_attr() {
 }
 
 // workgroups that fit one CU with this carve (inference modes: 2, or 3 with the tiny carve)
-static bool mlp_tiny(const MlpArgs& A) { return A.in_dim <= 4 && A.P.d <= 4 && !getenv("MSGM_NO_TINY_CARVE"); }
+static bool mlp_tiny(const MlpArgs& A) { return A.in_dim <= 4 && A.P.d <= 4; }
 
 template <int MODE>
 static int launch_mlp(const MlpArgs& A, int grid, hipStream_t st) {

@@ -1115,7 +1115,7 @@ static int gn_chunks(int Bp, int P, int* chunk, int* sub) {
   const int nsub = (P + c - 1) / c;
   // ~512 workgroups in all: every workgroup ends with a fixed tail (LDS group sums of up to 5 moments + the parameter
   // partials), so fewer, fatter workgroups win — measured 1024 -> 512: B = 32 step 23.5 -> 23.1 ms, B = 256 129.7 -> 128.8 ms
-  static const int target = getenv("MSGM_GN_WGS") ? atoi(getenv("MSGM_GN_WGS")) : 512;
+  constexpr int target = 512;
   int want = (target + Bp - 1) / Bp;            // workgroups per sample
   if (want < 1) want = 1;
   int m = nsub / want;
@@ -1357,11 +1357,10 @@ int msgm_bmm_dual(const float* A, const float* B, const float* A2, const float* 
   // LDS-staged kernel: every operand has a unit stride (along k or along its row index), 16-byte aligned bases and
   // strides, K a multiple of 32, M and N multiples of 4
   {
-    static const bool no_lds = getenv("MSGM_BMM_NO_LDS") != nullptr;   // diagnostic A/B
     auto mode = [&](long sRow, long sK, long sB) { return (sK == 1 && sRow % 4 == 0 && sB % 4 == 0) ? (int)BL_KV
                                                         : (sRow == 1 && sK % 4 == 0 && sB % 4 == 0) ? (int)BL_RV : -1; };
     const int am = mode(P.sAi, P.sAk, P.sAb), bm = mode(P.sBj, P.sBk, P.sBb);
-    if (!no_lds && am >= 0 && bm >= 0 && P.K % 32 == 0 && P.M % 4 == 0 && P.N % 4 == 0 && al16(P.A) && al16(P.A2) && al16(P.B) &&
+    if (am >= 0 && bm >= 0 && P.K % 32 == 0 && P.M % 4 == 0 && P.N % 4 == 0 && al16(P.A) && al16(P.A2) && al16(P.B) &&
         al16(P.B2) && al16(P.A3)) {
       dim3 grid((unsigned)(((P.M + 63) / 64) * ((P.N + 63) / 64)), (unsigned)batch);
 #define BL_GO(AM, BM)                                                                                              \

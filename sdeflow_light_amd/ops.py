@@ -10,8 +10,6 @@ import ctypes as C_
 import math
 from typing import Optional
 
-import os
-
 import torch
 
 from . import _lib as L
@@ -434,11 +432,7 @@ def conv_wgrad(geom: L.ConvGeomT, gy: torch.Tensor, src: torch.Tensor, C: int, k
     mo = (C_.c_uint16 * len(tapmask_co32))(*tapmask_co32) if tapmask_co32 else None
     if (mc is not None and len(mc) < (C + 31) // 32) or (mo is not None and len(mo) < (Cout + 31) // 32):
         raise MsgmError("wgrad: tap masks need one entry per 32-channel block")
-    if os.environ.get("MSGM_ATOMIC_WGRAD"):            # diagnostic A/B: float atomics across the position chunks
-        check(lib().msgm_conv_wgrad(geom, ptr(f32(gy)), ptr(f32(src)), C, koff, ptr(f32(dWp)), Cout, CoutP, Ktot,
-                                    ptr(dbias), int(n_bias), mc, mo, stream()), "msgm_conv_wgrad")
-        return
-    # default: deterministic — per-workgroup slabs added in slot order (no float atomics; same bits every run)
+    # per-workgroup slabs added in slot order (no float atomics; same bits every run)
     need = int(lib().msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, int(n_bias) if dbias is not None else 0))
     d = DeferredReduces.active
     if d is not None and d.device == gy.device:
@@ -686,9 +680,6 @@ def colsum(x: torch.Tensor, N: int, P: int, C: int, out: Optional[torch.Tensor] 
     if x.numel() < N * P * C:
         raise MsgmError("colsum: tensor too small")
     out = torch.empty(N, C, dtype=torch.float32, device=x.device) if out is None else out
-    if os.environ.get("MSGM_ATOMIC_WGRAD"):
-        check(lib().msgm_colsum(ptr(f32(x)), ptr(out), N, P, C, stream()), "msgm_colsum")
-        return out
     need = int(lib().msgm_colsum_workspace(N, P, C))
     ws = scratch(x.device, need, "colsum") if need else None
     check(lib().msgm_colsum_det(ptr(f32(x)), ptr(out), N, P, C, ptr(ws), need, stream()), "msgm_colsum_det")

@@ -15,8 +15,6 @@ Extra keyword ``noise=`` (steps,B,n) injects the standard-normal draws
 """
 from __future__ import annotations
 
-import os
-
 from typing import Optional
 
 import torch
@@ -259,10 +257,10 @@ class GraphedEMSampler:
         self._keep = (P, st)
         # B > 32: the whole loop is ONE launch (msgm_mlp_em_loop — rows never interact, so a workgroup carries its rows
         # through all steps); otherwise N single-step kernel nodes.  Same Philox numbers either way.
-        self.one_launch = B > 32 and not os.environ.get("MSGM_EM_PER_STEP")
+        one_launch = B > 32
 
         def body():
-            if self.one_launch:
+            if one_launch:
                 ops.mlp_em_loop(P, self.x, st, self.ts_dev, delta, lmbd, self.rng, 0)
             else:
                 for i in range(num_steps):
@@ -358,10 +356,8 @@ class GraphedStepSampler:
                 ops.lincomb(x, xn, 1.0)
             ops.counter_inc(self.step)
 
+        # the captured graph holds raw pointers only: the stage buffers (other, dW, k1, ...) live as long as this closure
         self._body = body
-        self.graph = None
-        if os.environ.get("MSGM_NO_GRAPH_SAMPLER"):          # diagnostic: the same step enqueued eagerly every time
-            return
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -379,9 +375,6 @@ class GraphedStepSampler:
             ops.lincomb(self.norm0, ops.row_norm(self.x), 1.0)
         self.step.zero_()
         for _ in range(self.N):
-            if self.graph is None:
-                self._body()
-            else:
-                self.graph.replay()
+            self.graph.replay()
         self.rng.advance(self.N)
         return self.x

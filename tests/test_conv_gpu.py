@@ -415,7 +415,7 @@ def test_groupnorm_affine_chanstats_two_sources():
 @pytest.mark.parametrize("N,nb,Cin,H,W_", [(5, 3, 3, 32, 32), (4, 4, 1, 20, 24), (3, 2, 3, 64, 64)])
 def test_unet_input_conv_small_cin(N, nb, Cin, H, W_):
     """model/unet.py:353-359, conv3x3(image channels -> 32) on k_conv3x3_cin_small vs F.conv2d (bias on the first nb rows
-    only: the tangent rows of the dual batch carry none); with MSGM_NO_CONV_SMALL the MFMA implicit GEMM served it."""
+    only: the tangent rows of the dual batch carry none); before that kernel the MFMA implicit GEMM served it."""
     torch.manual_seed(N + Cin + H)
     x = torch.randn(N, Cin, H, W_)
     w, b = torch.randn(32, Cin, 3, 3) * 0.3, torch.randn(32)
@@ -475,7 +475,7 @@ def test_pixel_stationary_1x1_kernel(N, C0, C1, Cout, T, aff, extra):
     """k_conv1x1 (1x1 convolutions with >= 4096 pixels: qkv / proj_out / skip convs, model/unet.py:216-232,158) with its
     fused options — folded GroupNorm(+SiLU) on the input, second source, residual / accumulate in the epilogue, per-sample
     bias on the primal rows — against plain PyTorch fp32, and against the halo-tile kernel that served these shapes
-    before (MSGM_NO_CONV1X1 is read once per process, so that comparison lives in tools/bench_1x1.py)."""
+    before (that comparison lives in tools/bench_1x1.py)."""
     from sdeflow_light_amd import ops
     torch.manual_seed(N + C0 + Cout)
     C = C0 + C1
@@ -519,18 +519,16 @@ def test_pixel_stationary_1x1_kernel(N, C0, C1, Cout, T, aff, extra):
 
 
 # every (MT, NT, WM) instance of the pixel-streaming 1x1 wgrad (k_wgrad1x1), 1-D and 2-D pixel grids, pixel counts that are
-# not a multiple of the staged tile, primal rows < N (the bias gradient stops at n_bias), both the slot-ordered
-# (deterministic, default) and the float-atomic form, accumulation into a non-zero packed image at a K offset
+# not a multiple of the staged tile, primal rows < N (the bias gradient stops at n_bias), the slot reduction per call and
+# deferred to the end of a pass (DeferredReduces), accumulation into a non-zero packed image at a K offset
 @pytest.mark.parametrize("N,nb,C,Cout,H,W_", [(3, 2, 32, 32, 8, 8), (2, 1, 64, 32, 16, 16), (2, 2, 128, 32, 8, 8),
                                               (3, 2, 32, 64, 1, 80), (2, 1, 32, 128, 8, 8), (2, 1, 32, 192, 4, 4),
                                               (5, 3, 64, 64, 1, 48), (2, 1, 64, 128, 8, 8), (3, 2, 64, 192, 1, 272),
                                               (2, 1, 128, 64, 8, 8), (3, 2, 128, 128, 16, 16), (2, 1, 128, 384, 1, 256),
                                               (2, 1, 256, 64, 8, 8), (2, 2, 256, 128, 8, 8)])
-@pytest.mark.parametrize("atomic", [False, True])
-def test_wgrad_1x1_pixel_streaming(N, nb, C, Cout, H, W_, atomic, monkeypatch):
+@pytest.mark.parametrize("deferred", [False, True])
+def test_wgrad_1x1_pixel_streaming(N, nb, C, Cout, H, W_, deferred):
     from sdeflow_light_amd import ops
-    if atomic:
-        monkeypatch.setenv("MSGM_ATOMIC_WGRAD", "1")
     torch.manual_seed(C + Cout + H)
     P = H * W_
     gy = torch.randn(N * P, Cout)
@@ -540,7 +538,14 @@ def test_wgrad_1x1_pixel_streaming(N, nb, C, Cout, H, W_, atomic, monkeypatch):
     dWp0 = torch.randn(Cout * Ktot)
     db0 = torch.randn(Cout)
     dWp, db = dWp0.clone().to(DEV), db0.clone().to(DEV)
-    ops.conv_wgrad(geom, gy.to(DEV), x.to(DEV), C, koff, dWp, Cout, Cout, Ktot, dbias=db, n_bias=nb)
+
+    def wgrad(dW, dbias):
+        if not deferred:
+            ops.conv_wgrad(geom, gy.to(DEV), x.to(DEV), C, koff, dW, Cout, Cout, Ktot, dbias=dbias, n_bias=nb)
+            return
+        with ops.DeferredReduces.on(DEV):                  # the backward pass's form: slot reductions batched at exit
+            ops.conv_wgrad(geom, gy.to(DEV), x.to(DEV), C, koff, dW, Cout, Cout, Ktot, dbias=dbias, n_bias=nb)
+    wgrad(dWp, db)
     want = dWp0.view(Cout, Ktot).double().clone()
     want[:, koff:koff + C] += gy.double().t() @ x.double()
     assert rel_l2(dWp.view(Cout, Ktot).cpu().double(), want) <= 1e-6
@@ -549,10 +554,10 @@ def test_wgrad_1x1_pixel_streaming(N, nb, C, Cout, H, W_, atomic, monkeypatch):
     assert torch.equal(got[:, :koff], dWp0.view(Cout, Ktot)[:, :koff]) and torch.equal(got[:, koff + C:], dWp0.view(Cout, Ktot)[:, koff + C:])
     wb = db0.double() + gy[: nb * P].double().sum(0)
     assert rel_l2(db.cpu().double(), wb) <= 1e-6
-    if not atomic:                                            # slot order: the same bits every time
-        dWp2, db2 = dWp0.clone().to(DEV), db0.clone().to(DEV)
-        ops.conv_wgrad(geom, gy.to(DEV), x.to(DEV), C, koff, dWp2, Cout, Cout, Ktot, dbias=db2, n_bias=nb)
-        assert torch.equal(dWp2, dWp) and torch.equal(db2, db)
+    # slot order: the same bits every time
+    dWp2, db2 = dWp0.clone().to(DEV), db0.clone().to(DEV)
+    wgrad(dWp2, db2)
+    assert torch.equal(dWp2, dWp) and torch.equal(db2, db)
 
 
 # opt-in experiment: the sampler's 3x3 convolution in bf16-SPLIT arithmetic (three bf16 pieces per fp32 operand,
@@ -607,7 +612,7 @@ def test_bf16_split_conv_is_fp32_grade(N, H, Ci, Co, two, ups, aff):
                                               (2, 16, 64, 0, 64, True), (2, 32, 64, 32, 32, False),
                                               (128, 64, 32, 0, 32, False)])        # the persistent 32-channel form, forward and dgrad
 def test_winograd_training_forward_and_dgrad(N, H, C0, C1, Co, ups):
-    """MSGM_TRAIN_WINO (ConvOpSet.pack_wino(train=True)): forward AND dgrad of a 3x3 stride-1 convolution on the Winograd
+    """The training pass's Winograd route (ConvOpSet.pack_wino(train=True)): forward AND dgrad of a 3x3 stride-1 convolution on the Winograd
     kernel — the dgrad as a Winograd forward of gy with the flipped, transposed kernels — against the direct kernels of the same
     op and against PyTorch fp32; the weight gradient path is untouched."""
     from sdeflow_light_amd.convnet import ConvOp, ConvOpSet

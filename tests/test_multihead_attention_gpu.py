@@ -214,8 +214,10 @@ def test_training_fused_equals_composed_two_heads(monkeypatch):
     monkeypatch.setattr(ops, "attention_dual_mh_backward", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
     pf, gf = run()
     assert calls, "the fused multi-head dual attention was not taken"
-    monkeypatch.setenv("MSGM_NO_ATTN_DUAL", "1")
+    n_fused = len(calls)
+    monkeypatch.setattr(ops, "attention_dual_mh_supported", lambda T, H, D: False)
     pc, gc = run()
+    assert len(calls) == n_fused, "the composed per-head attention was not taken"
     within(rel_l2(pf.cpu(), pc.cpu()), 1e-5, "training H=2: per-sample loss, fused vs composed")
     within(rel_l2(gf.cpu(), gc.cpu()), 1e-4, "training H=2: all gradients, fused vs composed")
 

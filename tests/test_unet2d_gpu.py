@@ -469,7 +469,9 @@ def test_unet_gradients_are_bitwise_reproducible(kind):
 
 def test_unet2d_sampler_forward_gn_fold_equals_unfused(monkeypatch):
     """The no-tangent forward folds GroupNorm(+SiLU) into the consuming conv and the residual into its epilogue;
-    with MSGM_NO_GN_FOLD the separate GroupNorm kernels run.  Same net, same input: 2e-4 (whole network)."""
+    when no conv can transform its input the separate GroupNorm kernels run.  Same net, same input: 2e-4 (whole network)."""
+    from sdeflow_light_amd import ops
+    from sdeflow_light_amd.convnet import ConvOp
     from sdeflow_light_amd.NNUnet import VorticityUNet
     from oracle.det_params import load_det_
     torch.manual_seed(4)
@@ -477,9 +479,15 @@ def test_unet2d_sampler_forward_gn_fold_equals_unfused(monkeypatch):
                         flatten_order="F", premodule="NormalizeLogRadius").to(DEV)
     load_det_(net.core)
     x, t = torch.randn(5, 256, device=DEV), torch.rand(5, device=DEV)
+    folds = []                                              # every folded GroupNorm asks for one of these two affine maps
+    real_cs, real_full = ops.groupnorm_affine_cs, ops.groupnorm_affine
+    monkeypatch.setattr(ops, "groupnorm_affine_cs", lambda *a, **k: (folds.append(1), real_cs(*a, **k))[1])
+    monkeypatch.setattr(ops, "groupnorm_affine", lambda *a, **k: (folds.append(1), real_full(*a, **k))[1])
     fused = net(x, t).clone()
-    monkeypatch.setenv("MSGM_NO_GN_FOLD", "1")
+    n_fold = len(folds)
+    monkeypatch.setattr(ConvOp, "can_transform_input", lambda self, N, Hi, Wi: False)
     plain = net(x, t)
+    assert n_fold > 0 and len(folds) == n_fold, "the unfused GroupNorm path was not taken"
     from conftest import within
     within(rel_l2(fused.cpu(), plain.cpu()), 1.5e-4, "sampler forward, GroupNorm folded into the conv vs separate")
 
@@ -577,14 +585,19 @@ def test_training_decoder_without_cat_equals_cat_path(monkeypatch):
     gen = make_gen("sgm", _vunet(32, "F"))
     B, d = 3, 1024
     x, u, eps, uv = torch.randn(B, d, device=DEV), torch.rand(B, device=DEV), torch.randn(B, d, device=DEV), torch.rand(B, d, device=DEV)
+    two_src = []                                            # the two-source GroupNorm runs only on the no-cat path
+    real = ops.groupnorm_dual_forward2
+    monkeypatch.setattr(ops, "groupnorm_dual_forward2", lambda *a, **k: (two_src.append(1), real(*a, **k))[1])
     res = {}
     for cat in (False, True):
         if cat:
-            monkeypatch.setenv("MSGM_TRAIN_CAT", "1")
+            n_two = len(two_src)
+            monkeypatch.setitem(gen.a._build(), "set2t", None)       # no two-source twins: the decoder concatenates
         gen.zero_grad()
         per = gen.ssm(x, u=u, eps=eps, u_v=uv)
         per.mean().backward()
         res[cat] = (per.detach().clone(), {k: p.grad.detach().clone() for k, p in gen.a.named_parameters()})
+    assert n_two > 0 and len(two_src) == n_two, "the concatenating decoder path was not taken"
     from conftest import within
     within(rel_l2(res[False][0].cpu(), res[True][0].cpu()), 1e-6, "no-cat vs cat training path: per-sample loss")
     worst = max(rel_l2(res[False][1][k].cpu(), g.cpu()) for k, g in res[True][1].items() if float(g.norm()) > 1e-3 * max(float(v.norm()) for v in res[True][1].values()))
@@ -625,10 +638,11 @@ def test_bmm_lds_staged_equals_register_direct(T, C, monkeypatch):
     assert max(e1, e2, e3) <= 2e-6
 
 
-def test_sampler_forward_groupnorm_statistics_from_conv_epilogues(monkeypatch):
+def test_sampler_groupnorm_statistics_from_conv_epilogues_equal_statistics_pass(monkeypatch):
     """Sampler path: the GroupNorm statistics come from the per-channel sums the producing convolutions leave behind
-    (no pass over the tensor).  Same score as with the statistics pass (MSGM_NO_CHANSTATS) up to fp32 summation order, and
-    the stand-alone statistics kernel no longer runs for the layers whose producer has the by-product."""
+    (no pass over the tensor).  Same score as with the statistics pass (no conv asked for the by-product) up to fp32
+    summation order, and the stand-alone statistics kernel no longer runs for the layers whose producer has the by-product."""
+    from sdeflow_light_amd.convnet import ConvOp
     net = _vunet(32, "F")
     torch.manual_seed(2)
     B = 40                                                  # 16x16 tiles at 32x32, 8x16 tiles below
@@ -640,13 +654,15 @@ def test_sampler_forward_groupnorm_statistics_from_conv_epilogues(monkeypatch):
     monkeypatch.setattr(ops, "groupnorm_affine", lambda *a, **k: (calls.__setitem__("full", calls["full"] + 1), real_full(*a, **k))[1])
     a = net(x, s)
     n_cs, n_full = calls["cs"], calls["full"]
-    monkeypatch.setenv("MSGM_NO_CHANSTATS", "1")
+    real_fwd = ConvOp.forward                               # the convolutions leave no statistics behind
+    monkeypatch.setattr(ConvOp, "forward", lambda self, *a, **k: real_fwd(self, *a, **{**k, "stats": False}))
     b = net(x, s)
     e = rel_l2(a.cpu(), b.cpu())
     print(f"sampler forward, GroupNorm statistics from conv epilogues ({n_cs} layers; {n_full} by a pass over the tensor) "
           f"vs all by passes: rel-L2 {e:.2e}")
     assert n_cs >= 40 and n_full <= 2
-    assert calls["full"] - n_full == n_cs + n_full          # the switch sends every layer through the statistics pass
+    assert calls["cs"] == n_cs                              # the statistics by-product was not used ...
+    assert calls["full"] - n_full == n_cs + n_full          # ... and every layer went through the statistics pass
     # the statistics themselves agree to ~1e-8 (tests/test_conv_gpu.py::test_conv_channel_statistics_byproduct); the
     # untrained deterministic-parameter U-Net amplifies ANY fp32 reordering by ~100x over its 45 normalisations — the same
     # 1-2e-5 separates the HIP forward from the fp32 oracle.  Measured 1.5e-5.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU box: time individual conv / wgrad / bmm shapes of the C4 U-Net (dual batch 512) — TFLOP/s per kernel."""
-import os, sys, time
+import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,21 +28,11 @@ for (H, Ci, Co) in ((64, 32, 32), (64, 96, 32), (32, 64, 64), (32, 192, 64), (16
     out = torch.empty(N * H * H * Co, device=dev)
     geom = ops.conv_geom(N, H, H, H, H, 3, 3, 1, 1)
     fl = 2 * 9 * Ci * Co * N * H * H
-    res = []
-    for env in ("1", None):
-        if env:
-            os.environ["MSGM_NO_CONV_TILE"] = env
-        else:
-            os.environ.pop("MSGM_NO_CONV_TILE", None)
-        t = timeit(lambda: ops.conv_forward(geom, x, Ci, Wp, Co, out, n_bias=N // 2))
-        res.append(fl / t / 1e12)
+    t = timeit(lambda: ops.conv_forward(geom, x, Ci, Wp, Co, out, n_bias=N // 2))
     gy = torch.randn(N * H * H * Co, device=dev)
     dWp = torch.zeros(9 * ops.pad16(Co) * ops.pad16(Ci), device=dev)
-    os.environ["MSGM_NO_WGRAD_TILE"] = "1"
     tw = timeit(lambda: ops.conv_wgrad(geom, gy, x, Ci, 0, dWp, Co, ops.pad16(Co), ops.pad16(Ci)))
-    os.environ.pop("MSGM_NO_WGRAD_TILE")
-    tw2 = timeit(lambda: ops.conv_wgrad(geom, gy, x, Ci, 0, dWp, Co, ops.pad16(Co), ops.pad16(Ci)))
-    print(f"  {H}x{H} {Ci:3d}->{Co:3d}: gemm {res[0]:5.1f} TF/s | tile {res[1]:5.1f} TF/s | wgrad {fl / tw / 1e12:5.1f} -> tile {fl / tw2 / 1e12:5.1f} TF/s")
+    print(f"  {H}x{H} {Ci:3d}->{Co:3d}: forward {fl / t / 1e12:5.1f} TF/s | wgrad {fl / tw / 1e12:5.1f} TF/s")
 print("conv1d (k3 s1), dual batch 8192:")
 for (L, Ci, Co) in ((1024, 32, 32), (1024, 64, 32), (512, 64, 64), (512, 128, 64), (256, 128, 128), (256, 256, 128)):
     Nn = 8192
@@ -51,20 +41,11 @@ for (L, Ci, Co) in ((1024, 32, 32), (1024, 64, 32), (512, 64, 64), (512, 128, 64
     out = torch.empty(Nn * L * Co, device=dev)
     geom = ops.conv_geom(Nn, 1, L, 1, L, 1, 3, 1, 1)
     fl = 2 * 3 * Ci * Co * Nn * L
-    res = []
-    for env in ("1", None):
-        if env:
-            os.environ["MSGM_NO_CONV_TILE"] = env
-        else:
-            os.environ.pop("MSGM_NO_CONV_TILE", None)
-        res.append(fl / timeit(lambda: ops.conv_forward(geom, x, Ci, Wp, Co, out, n_bias=Nn // 2), 5) / 1e12)
+    t = timeit(lambda: ops.conv_forward(geom, x, Ci, Wp, Co, out, n_bias=Nn // 2), 5)
     gy = torch.randn(Nn * L * Co, device=dev)
     dWp = torch.zeros(3 * ops.pad16(Co) * ops.pad16(Ci), device=dev)
-    os.environ["MSGM_NO_WGRAD_TILE"] = "1"
     tw = timeit(lambda: ops.conv_wgrad(geom, gy, x, Ci, 0, dWp, Co, ops.pad16(Co), ops.pad16(Ci)), 5)
-    os.environ.pop("MSGM_NO_WGRAD_TILE")
-    tw2 = timeit(lambda: ops.conv_wgrad(geom, gy, x, Ci, 0, dWp, Co, ops.pad16(Co), ops.pad16(Ci)), 5)
-    print(f"  L={L} {Ci:3d}->{Co:3d}: gemm {res[0]:5.1f} | tile {res[1]:5.1f} | wgrad {fl / tw / 1e12:5.1f} -> tile {fl / tw2 / 1e12:5.1f} TF/s")
+    print(f"  L={L} {Ci:3d}->{Co:3d}: forward {fl / t / 1e12:5.1f} | wgrad {fl / tw / 1e12:5.1f} TF/s")
 print("attention products (per block, batch = N/2):")
 for (T, C) in ((1024, 64), (256, 128)):
     Bp = N // 2

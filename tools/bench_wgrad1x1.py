@@ -1,6 +1,6 @@
-"""1x1 weight-gradient kernels on the C4 shapes (GPU box): the pixel-streaming kernel (k_wgrad1x1, default) against the
-32 x 32-block tile kernel it replaces (MSGM_NO_WGRAD1X1=1 in a second process).  Usage: python tools/bench_wgrad1x1.py [B]"""
-import os, sys, time
+"""1x1 weight-gradient kernels on the C4 shapes (GPU box): the pixel-streaming kernel (k_wgrad1x1).
+Usage: python tools/bench_wgrad1x1.py [B]"""
+import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sdeflow_light_amd import ops
