@@ -489,6 +489,41 @@ int msgm_groupnorm_dual_backward_slots(const float* x0, int32_t C0, const float*
  * that reached this tensor through the U-Net's skip stack (model/unet.py:514: the encoder activations feed the decoder as
  * well), which was a separate `dh += skip` pass over the tensor for each of the nine encoder blocks. */
 
+/* ---- Dropout of a ResBlock's out_layers (model/unet.py:152-158: GroupNorm, SiLU, Dropout(p), zero-init conv3x3; torch
+ * Dropout semantics in train mode) fused into the GroupNorm+SiLU kernels — no mask tensor, no extra pass.  The mask rule:
+ *   - ResBlock l = its position among all ResBlocks, input_blocks -> middle_block -> output_blocks;
+ *     stream = RNG_STREAM_DROPOUT + l, RNG_STREAM_DROPOUT = 64;
+ *   - element e = ((row_base + b) P + p) C + c for primal row b < Bp, pixel p < P, channel c < C (channels-last, GLOBAL
+ *     row: row_base = rng[2], so a shard draws what the one-GPU run draws for its rows; elem_base is not used);
+ *   - word e & 3 of the Philox4x32-10 block of quad e >> 2 at (seed, offset) = (rng[0], rng[1]), with msgm_philox's
+ *     counter / key folding: counter (quad lo, quad hi, stream, offset lo), key (seed lo, seed hi ^ offset hi);
+ *   - kept iff (word >> 8) >= thr, thr = ceil(p 2^24) (host, double); kept values x scale = fp32(1 / (1 - p)) (host,
+ *     double), dropped values are 0.  The tangent rows b + Bp use row b's mask.  0 <= p < 1; C % 4 == 0.
+ * A network pass that draws masks reads the stream's current offset and then advances it by 1 (msgm_rng_advance, a kernel
+ * node: every replay of a captured graph draws fresh masks). */
+typedef struct {
+  const uint64_t* rng;   /* device Philox state {seed, offset, row_base, elem_base}                 */
+  uint32_t stream;       /* RNG_STREAM_DROPOUT + l                                                  */
+  uint32_t thr;          /* keep iff (word >> 8) >= thr;  thr <= 2^24                               */
+  float scale;           /* 1 / (1 - p)                                                             */
+} msgm_dropout_t;
+/* msgm_groupnorm_dual_forward with the post-SiLU primal and tangent multiplied by keep * scale (replaces the
+ * GroupNorm -> SiLU -> Dropout(p) of out_layers, model/unet.py:152-155).  One source. */
+int msgm_groupnorm_dual_forward_dropout(const float* x, const float* gamma, const float* beta, float* out, float* stats,
+                                        int32_t Bp, int32_t P, int32_t C, int32_t G, int32_t dual, int32_t silu, float eps,
+                                        void* workspace, size_t workspace_bytes, const msgm_dropout_t* drop,
+                                        msgm_stream_t stream);
+/* msgm_groupnorm_dual_backward_slots (one source) of that map: both incoming cotangents are multiplied by keep * scale as they
+ * are loaded, in the moment reduction and in the apply pass. */
+int msgm_groupnorm_dual_backward_slots_dropout(const float* x, const float* gamma, const float* beta, const float* stats,
+                                               const float* gout, float* gx, float* dgamma, float* dbeta, int32_t Bp, int32_t P,
+                                               int32_t C, int32_t G, int32_t silu, float eps, const float* residual,
+                                               const float* residual2, void* workspace, size_t workspace_bytes, float* pslots,
+                                               size_t pslots_bytes, msgm_reduce_job_t* jobs_out, int32_t* n_jobs_out,
+                                               const msgm_dropout_t* drop, msgm_stream_t stream);
+/* keep_out[Bp][P][C] = the 0/1 keep mask the two entries above apply (tests and diagnostics). */
+int msgm_dropout_mask(const msgm_dropout_t* drop, int32_t Bp, int32_t P, int32_t C, float* keep_out, msgm_stream_t stream);
+
 /* GroupNorm statistics only, returned as the per-(sample, channel) affine map y = scale x + shift
  * (scale = gamma/sigma, shift = beta - mean scale; [Bp][C0+C1] each) for a consumer that applies it while reading
  * x (msgm_conv_forward_fused) — the normalised tensor is never written.  x1 (may be NULL) is a second tensor whose

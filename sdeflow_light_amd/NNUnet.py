@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import MsgmError
+from ._lib import MsgmError, PhiloxState
 from .NN import FlatParamMixin
 from .convnet import ConvOp, ConvOpSet
 
@@ -59,14 +59,16 @@ def _norm(c):            # normalization(): GroupNorm32(min(c,32), c)      model
 
 
 class ResBlock(nn.Module):
-    """Parameter holder with the reference's child names (model/unet.py:139-168)."""
+    """Parameter holder with the reference's child names (model/unet.py:139-168).  out_layers[2] is the reference's
+    Dropout(p) (no parameters; train() / eval() switch it as in torch); the HIP path applies it inside the GroupNorm+SiLU
+    kernels of out_layers[0]."""
 
-    def __init__(self, channels, emb_channels, out_channels):
+    def __init__(self, channels, emb_channels, out_channels, dropout=0.0):
         super().__init__()
         self.channels, self.out_channels = channels, out_channels
         self.in_layers = nn.Sequential(_norm(channels), nn.Identity(), nn.Conv2d(channels, out_channels, 3, padding=1))
         self.emb_layers = nn.Sequential(nn.Identity(), nn.Linear(emb_channels, out_channels))
-        self.out_layers = nn.Sequential(_norm(out_channels), nn.Identity(), nn.Identity(),
+        self.out_layers = nn.Sequential(_norm(out_channels), nn.Identity(), nn.Dropout(p=dropout),
                                         zero_module(nn.Conv2d(out_channels, out_channels, 3, padding=1)))
         self.skip_connection = nn.Identity() if out_channels == channels else nn.Conv2d(channels, out_channels, 1)
 
@@ -98,16 +100,21 @@ class Upsample(nn.Module):
 
 
 class UNetModelWithLogNorm(nn.Module):
-    """Topology of UNetModel.__init__ (model/unet.py:300-446) for dims=2, conv_resample, dropout 0, no scale-shift
-    norm, no classes; any num_heads / num_heads_upsample whose heads divide the channel counts of the attention blocks."""
+    """Topology of UNetModel.__init__ (model/unet.py:300-446) for dims=2, conv_resample, no scale-shift norm, no classes;
+    any num_heads / num_heads_upsample whose heads divide the channel counts of the attention blocks; any dropout in [0, 1)
+    (every ResBlock's out_layers, model/unet.py:152-158)."""
 
     def __init__(self, in_channels, model_channels, out_channels, in_space, num_res_blocks, attention_resolutions,
                  dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None, use_checkpoint=False,
                  num_heads=1, num_heads_upsample=-1, use_scale_shift_norm=False, learn_potential=False, use_log_norm=False):
         super().__init__()
-        if dims != 2 or not conv_resample or num_classes is not None or use_scale_shift_norm or learn_potential or dropout != 0:
-            raise MsgmError("HIP U-Net is built for the driver's options (dims=2, conv_resample, dropout 0, no scale-shift norm, "
+        if dims != 2 or not conv_resample or num_classes is not None or use_scale_shift_norm or learn_potential:
+            raise MsgmError("HIP U-Net is built for the driver's options (dims=2, conv_resample, no scale-shift norm, "
                             "no learn_potential, no classes)")
+        dropout = float(dropout)
+        if not 0.0 <= dropout < 1.0:
+            raise MsgmError(f"dropout {dropout} outside [0, 1)")
+        self.dropout = dropout
         if num_heads_upsample == -1:                                    # model/unet.py:321-322
             num_heads_upsample = num_heads
         self.num_heads, self.num_heads_upsample = num_heads, num_heads_upsample
@@ -124,7 +131,7 @@ class UNetModelWithLogNorm(nn.Module):
         chans, ds = [ch], 1
         for level, mult in enumerate(channel_mult):
             for _ in range(num_res_blocks):
-                layers = [ResBlock(ch, ted, mult * model_channels)]
+                layers = [ResBlock(ch, ted, mult * model_channels, dropout)]
                 ch = mult * model_channels
                 if ds in attention_resolutions:
                     layers.append(AttentionBlock(ch, num_heads))
@@ -134,11 +141,12 @@ class UNetModelWithLogNorm(nn.Module):
                 self.input_blocks.append(nn.Sequential(Downsample(ch)))
                 chans.append(ch)
                 ds *= 2
-        self.middle_block = nn.Sequential(ResBlock(ch, ted, ch), AttentionBlock(ch, num_heads), ResBlock(ch, ted, ch))
+        self.middle_block = nn.Sequential(ResBlock(ch, ted, ch, dropout), AttentionBlock(ch, num_heads),
+                                          ResBlock(ch, ted, ch, dropout))
         self.output_blocks = nn.ModuleList([])
         for level, mult in list(enumerate(channel_mult))[::-1]:
             for i in range(num_res_blocks + 1):
-                layers = [ResBlock(ch + chans.pop(), ted, model_channels * mult)]
+                layers = [ResBlock(ch + chans.pop(), ted, model_channels * mult, dropout)]
                 ch = model_channels * mult
                 if ds in attention_resolutions:
                     layers.append(AttentionBlock(ch, num_heads_upsample))
@@ -214,6 +222,29 @@ class VorticityUNet(nn.Module, FlatParamMixin):
                                          use_log_norm=(premodule == "NormalizeLogRadius"))
         self._x = None
         self._flat = None
+        self._drop = None                # Philox state of the pass being run when its dropout is active (else None)
+        self.dropout_rng: Optional[PhiloxState] = None     # the net's own mask stream (train-mode forward); replaceable
+
+    def dropout_active(self) -> bool:
+        """Dropout draws masks iff the net is in training mode and p > 0 (torch Dropout semantics)."""
+        return self.training and self.core.dropout > 0
+
+    def dropout_stream(self, device) -> PhiloxState:
+        """The stream a train-mode ``forward`` draws its masks from: created on first use (like SDE.philox), replaceable by
+        assigning ``dropout_rng``.  A pass advances it by 1."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.dropout_rng is None or self.dropout_rng.state.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise MsgmError("the U-Net's dropout stream is created for the first time inside a graph capture; "
+                                "run one eager step first")
+            self.dropout_rng = PhiloxState(int(torch.initial_seed()) ^ 0xD409, device)
+        return self.dropout_rng
+
+    def _drop_desc(self, r):
+        """msgm_dropout_t of ResBlock r in the current pass (None when dropout is inactive)."""
+        return None if self._drop is None else ops.dropout_desc(self._drop, r.bank_i, self.core.dropout)
 
     # ------------------------------------------------------------------ build
     def _build(self):
@@ -279,10 +310,11 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         return x
 
     # ------------------------------------------------------------------ forward pieces
-    def _gn(self, gnm: nn.GroupNorm, h, Bp, P, C, dual, silu, tape):
+    def _gn(self, gnm: nn.GroupNorm, h, Bp, P, C, dual, silu, tape, dropout=None):
         G = gnm.num_groups
         stats = torch.empty(Bp * G * 4, device=h.device) if tape is not None else None
-        out = ops.groupnorm_dual_forward(h, gnm.weight.detach(), gnm.bias.detach(), Bp, P, C, G, dual, silu, stats=stats)
+        out = ops.groupnorm_dual_forward(h, gnm.weight.detach(), gnm.bias.detach(), Bp, P, C, G, dual, silu, stats=stats,
+                                         dropout=dropout)
         return out, stats
 
     def _gn_fold(self, gnm: nn.GroupNorm, x, Bp, P, C, x1=None, C1=0):
@@ -307,10 +339,11 @@ class VorticityUNet(nn.Module, FlatParamMixin):
             h1 = ops.groupnorm_dual_forward2(h0, C0, s0, C1, gnm.weight.detach(), gnm.bias.detach(), Bp, P, gnm.num_groups, dual, True,
                                              stats=st1)
             h2, _, _ = r.conv1.forward([h1], N, H, W, Bp, samp_bias=eo, emb_rows=er)
-            h3, st2 = self._gn(r.m.out_layers[0], h2, Bp, P, r.co, dual, True, tape)
+            dd = self._drop_desc(r)
+            h3, st2 = self._gn(r.m.out_layers[0], h2, Bp, P, r.co, dual, True, tape, dropout=dd)
             out, _, _ = r.skip_2t.forward([h0, s0], N, H, W, Bp)
             r.conv2.forward([h3], N, H, W, Bp, out=out, accumulate=True)
-            tape.append(("res2", r, h0, s0, H, W, h1, st1, h2, st2, h3))
+            tape.append(("res2", r, h0, s0, H, W, h1, st1, h2, st2, h3, dd))
             return out
         if isinstance(x, tuple):                                 # (h, skip): decoder block without the concatenation
             h0, s0 = x
@@ -320,7 +353,12 @@ class VorticityUNet(nn.Module, FlatParamMixin):
             h2, _, _ = r.conv1_2.forward([h0, s0], N, H, W, Bp, samp_bias=eo, emb_rows=er, in_affine=aff, in_act=1, wino=True,
                                          stats=True)
             out, _, _ = r.skip_2.forward([h0, s0], N, H, W, Bp)
-            if r.conv2.can_transform_input(N, H, W):
+            dd = self._drop_desc(r)
+            if dd is not None:
+                # train-mode dropout: out_layers' GroupNorm+SiLU+mask is materialised, conv2 reads it unfused
+                h3, _ = self._gn(r.m.out_layers[0], h2, Bp, P, r.co, False, True, None, dropout=dd)
+                r.conv2.forward([h3], N, H, W, Bp, out=out, accumulate=True, wino=True, stats=True)
+            elif r.conv2.can_transform_input(N, H, W):
                 r.conv2.forward([h2], N, H, W, Bp, out=out, accumulate=True,
                                 in_affine=self._gn_fold(r.m.out_layers[0], h2, Bp, P, r.co), in_act=1, wino=True, stats=True)
             else:
@@ -333,6 +371,16 @@ class VorticityUNet(nn.Module, FlatParamMixin):
             # is added in conv2's epilogue — the two normalised tensors and the separate add pass never exist
             h2, _, _ = r.conv1.forward([x], N, H, W, Bp, samp_bias=eo, emb_rows=er,
                                        in_affine=self._gn_fold(r.m.in_layers[0], x, Bp, P, r.ci), in_act=1, wino=True, stats=True)
+            dd = self._drop_desc(r)
+            if dd is not None:
+                # train-mode dropout: out_layers' GroupNorm+SiLU+mask is materialised, conv2 reads it unfused
+                h3, _ = self._gn(r.m.out_layers[0], h2, Bp, P, r.co, False, True, None, dropout=dd)
+                if r.skip is not None:
+                    out, _, _ = r.skip.forward([x], N, H, W, Bp)
+                    r.conv2.forward([h3], N, H, W, Bp, out=out, accumulate=True, wino=True, stats=True)
+                else:
+                    out, _, _ = r.conv2.forward([h3], N, H, W, Bp, residual=x, wino=True, stats=True)
+                return out
             aff2 = self._gn_fold(r.m.out_layers[0], h2, Bp, P, r.co)
             if r.skip is not None:
                 out, _, _ = r.skip.forward([x], N, H, W, Bp)
@@ -342,14 +390,15 @@ class VorticityUNet(nn.Module, FlatParamMixin):
             return out
         h1, st1 = self._gn(r.m.in_layers[0], x, Bp, P, r.ci, dual, True, tape)
         h2, _, _ = r.conv1.forward([h1], N, H, W, Bp, samp_bias=eo, emb_rows=er)
-        h3, st2 = self._gn(r.m.out_layers[0], h2, Bp, P, r.co, dual, True, tape)
+        dd = self._drop_desc(r)
+        h3, st2 = self._gn(r.m.out_layers[0], h2, Bp, P, r.co, dual, True, tape, dropout=dd)
         if r.skip is not None:
             out, _, _ = r.skip.forward([x], N, H, W, Bp)
             r.conv2.forward([h3], N, H, W, Bp, out=out, accumulate=True)
         else:
             out, _, _ = r.conv2.forward([h3], N, H, W, Bp, residual=x)          # h + x in the epilogue (unet.py:187)
         if tape is not None:
-            tape.append(("res", r, x, H, W, h1, st1, h2, st2, h3))
+            tape.append(("res", r, x, H, W, h1, st1, h2, st2, h3, dd))
         return out
 
     def _attn_fwd(self, a: _Attn, x, N, Bp, H, W, dual, tape):
@@ -546,15 +595,25 @@ class VorticityUNet(nn.Module, FlatParamMixin):
             d = flat.shape[1]
             flat, logr = ops.normalize_dual(flat, B, d, False, float(d) ** 0.5)      # NNUnet.py:203-205
         img = ops.flat_to_image(flat, B, Cc, S_, S_, forder, sc_in)
-        out = self._run(img, t, B, B, False, None, logr=logr)
+        # train mode with dropout (how the reference driver samples): masks from the net's own stream, which then moves on
+        self._drop = self.dropout_stream(img.device) if self.dropout_active() else None
+        try:
+            out = self._run(img, t, B, B, False, None, logr=logr)
+        finally:
+            drop, self._drop = self._drop, None
+        if drop is not None:
+            drop.advance(1)
         y = ops.image_to_flat(out, B, Cc, S_, S_, forder, sc_out)
         return y if need_flat else y.view(B, Cc, S_, S_)
 
     # ------------------------------------------------------------------ training
     @torch.no_grad()
-    def ssm_grad(self, y, t, v, u, cst, inv_batch):
+    def ssm_grad(self, y, t, v, u, cst, inv_batch, rng: Optional[PhiloxState] = None):
         """Per-sample SSM loss (B,) in the general form loss_b = adot.u + cst + |a|^2/2 (u, cst from
-        ``msgm_ssm_terms``: any SDE family); gradients of sum_b loss_b*inv_batch into .grad."""
+        ``msgm_ssm_terms``: any SDE family); gradients of sum_b loss_b*inv_batch into .grad.
+        With dropout active the masks are drawn from ``rng`` (the caller's training stream, shard base included; the net's
+        own stream when None) at its current offset — the forward and the backward use the same masks, primal and tangent
+        share them — and the stream is advanced by 1 afterwards."""
         B, d = y.shape
         N = 2 * B
         S_, Cc = self.in_space, self.channels
@@ -577,12 +636,19 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         img = ops.flat_to_image(stacked, N, Cc, S_, S_, forder, 1.0 / scale_image)
         tape = []
         tt = t.reshape(-1).contiguous().float()
-        out = self._run(img, tt, N, B, True, tape, logr=logr)
+        drop = (rng if rng is not None else self.dropout_stream(y.device)) if self.dropout_active() else None
+        self._drop = drop
+        try:
+            out = self._run(img, tt, N, B, True, tape, logr=logr)
+        finally:
+            self._drop = None
         a_flat = ops.image_to_flat(out, N, Cc, S_, S_, forder, float(scale_image))      # [2B][d]: a | adot
         per, g = ops.ssm_loss(a_flat.view(-1), u, cst, inv_batch)
         gimg = ops.flat_to_image(g.view(N, d), N, Cc, S_, S_, forder, float(scale_image))   # adjoint of (x5, unflatten)
         with ops.DeferredReduces.on(y.device):           # the ~140 slot reductions of the weight / bias gradients: one launch
             self._backward(tape, gimg, N, B)
+        if drop is not None:
+            drop.advance(1)                              # after the backward: it regenerates the forward's masks
         x["set"].unpack_grads()
         if x["set2t"] is not None and any(rec[0] == "res2" for rec in tape):
             x["set2t"].unpack_grads()            # after "set": the twins' images replace the (unused, zero) single-source ones
@@ -591,9 +657,9 @@ class VorticityUNet(nn.Module, FlatParamMixin):
     def _groupnorms(self):
         return [m for m in self.modules() if isinstance(m, nn.GroupNorm)]
 
-    def _gn_bwd(self, gnm, xin, stats, g, Bp, P, C, silu, residual=None, residual2=None):
+    def _gn_bwd(self, gnm, xin, stats, g, Bp, P, C, silu, residual=None, residual2=None, dropout=None):
         return ops.groupnorm_dual_backward(xin, gnm.weight.detach(), gnm.bias.detach(), stats, g, gnm.weight.grad, gnm.bias.grad,
-                                           Bp, P, C, gnm.num_groups, silu, residual=residual, residual2=residual2)
+                                           Bp, P, C, gnm.num_groups, silu, residual=residual, residual2=residual2, dropout=dropout)
 
     def _backward(self, tape, g, N, Bp):
         x = self._x
@@ -613,10 +679,10 @@ class VorticityUNet(nn.Module, FlatParamMixin):
                 (dhf,) = x["fin"].backward(dh, [hf], N, H, W, Bp)
                 dh = self._gn_bwd(self.core.out[0], h, stf, dhf, Bp, H * W, C, True)
             elif kind == "res":
-                _, rb, xin, H, W, h1, st1, h2, st2, h3 = r
+                _, rb, xin, H, W, h1, st1, h2, st2, h3, dd = r
                 P = H * W
                 (dh3,) = rb.conv2.backward(dh, [h3], N, H, W, Bp)
-                dh2 = self._gn_bwd(rb.m.out_layers[0], h2, st2, dh3, Bp, P, rb.co, True)
+                dh2 = self._gn_bwd(rb.m.out_layers[0], h2, st2, dh3, Bp, P, rb.co, True, dropout=dd)
                 (dh1,) = rb.conv1.backward(dh2, [h1], N, H, W, Bp, dsamp_bias=deo_all[rb.bank_i], emb_rows=er,
                                            bias_grad_elsewhere=True)
                 # identity skip: the `h + x` cotangent is added in the GroupNorm apply pass (no separate axpy); so is the cotangent
@@ -632,11 +698,11 @@ class VorticityUNet(nn.Module, FlatParamMixin):
                     rb.skip.backward(dh, [xin], N, H, W, Bp, dsrc=[dx], dacc=[True])
                 dh = dx
             elif kind == "res2":                                   # decoder ResBlock on (h, skip) without the concatenation
-                _, rb, h0, s0, H, W, h1, st1, h2, st2, h3 = r
+                _, rb, h0, s0, H, W, h1, st1, h2, st2, h3, dd = r
                 P = H * W
                 C0, C1 = rb.split
                 (dh3,) = rb.conv2.backward(dh, [h3], N, H, W, Bp)
-                dh2 = self._gn_bwd(rb.m.out_layers[0], h2, st2, dh3, Bp, P, rb.co, True)
+                dh2 = self._gn_bwd(rb.m.out_layers[0], h2, st2, dh3, Bp, P, rb.co, True, dropout=dd)
                 (dh1,) = rb.conv1.backward(dh2, [h1], N, H, W, Bp, dsamp_bias=deo_all[rb.bank_i], emb_rows=er,
                                            bias_grad_elsewhere=True)
                 gnm = rb.m.in_layers[0]

@@ -181,9 +181,10 @@ class UNet1D(nn.Module, FlatParamMixin):
     # ------------------------------------------------------------------ training
     @torch.no_grad()
     def ssm_grad(self, y: torch.Tensor, t: torch.Tensor, v: torch.Tensor, u: torch.Tensor, cst: torch.Tensor,
-                 inv_batch: float):
+                 inv_batch: float, rng=None):
         """Per-sample SSM loss (B,) in the general form loss_b = adot.u + cst + |a|^2/2 (u, cst from
-        ``msgm_ssm_terms``: any SDE family); d(sum_b loss_b * inv_batch)/d(params) is written into ``.grad``."""
+        ``msgm_ssm_terms``: any SDE family); d(sum_b loss_b * inv_batch)/d(params) is written into ``.grad``.
+        ``rng`` (the caller's training stream) is accepted like the 2-D U-Net's; this net draws nothing from it."""
         B, L = y.shape
         N = 2 * B
         flat, gflat = self.flat_parameters()

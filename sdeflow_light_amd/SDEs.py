@@ -535,7 +535,8 @@ class PluginReverseSDE(nn.Module):
                 if p_.grad is None:
                     keep[off:off + p_.numel()].zero_()
                 off += p_.numel()
-            per = net.ssm_grad(y, t.reshape(-1), v, uu, cst, 1.0 / B)
+            # a 2-D U-Net with active dropout draws its masks from the SDE's stream (shard base, checkpoint, graph replay)
+            per = net.ssm_grad(y, t.reshape(-1), v, uu, cst, 1.0 / B, rng=rng)
             flat, gflat = net.flat_parameters()
             gtmp = gflat.clone()
             gflat.copy_(keep)

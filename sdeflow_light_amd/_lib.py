@@ -19,6 +19,7 @@ MSGM_OK = 0
 SDE_SGM, SDE_MSGM_SPARSE, SDE_MSGM_DENSE = 0, 1, 2
 PROC_REVERSE, PROC_FORWARD = 0, 1
 RNG_STREAM_T, RNG_STREAM_EPS, RNG_STREAM_V, RNG_STREAM_DW, RNG_STREAM_ROWS, RNG_STREAM_USER = 0, 1, 2, 3, 4, 16
+RNG_STREAM_DROPOUT = 64          # + the ResBlock's index: the U-Net's dropout masks (include/msgm_hip.h, msgm_dropout_t)
 
 
 class MsgmError(RuntimeError):
@@ -55,6 +56,11 @@ class EmbJobT(C.Structure):
     """msgm_emb_job_t (include/msgm_hip.h)."""
     _fields_ = [("W", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("dout", C.c_void_p), ("dW", C.c_void_p),
                 ("db", C.c_void_p), ("db2", C.c_void_p), ("co", C.c_int32), ("block_begin", C.c_int32)]
+
+
+class DropoutT(C.Structure):
+    """msgm_dropout_t (include/msgm_hip.h)."""
+    _fields_ = [("rng", C.c_void_p), ("stream", C.c_uint32), ("thr", C.c_uint32), ("scale", C.c_float)]
 
 
 class ConvGeomT(C.Structure):
@@ -126,6 +132,12 @@ SIGNATURES = {
     "msgm_groupnorm_dual_forward2": (C.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _SZ, _P]),
     "msgm_groupnorm_dual_backward2": (C.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F,
                                                 _P, _SZ, _P]),
+    "msgm_groupnorm_dual_forward_dropout": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _SZ,
+                                                      C.POINTER(DropoutT), _P]),
+    "msgm_groupnorm_dual_backward_slots_dropout": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P,
+                                                             _P, _SZ, _P, _SZ, C.POINTER(ReduceJobT), C.POINTER(C.c_int32),
+                                                             C.POINTER(DropoutT), _P]),
+    "msgm_dropout_mask": (C.c_int, [C.POINTER(DropoutT), _I32, _I32, _I32, _P, _P]),
     "msgm_groupnorm_param_slots_bytes": (_SZ, [_I32, _I32, _I32]),
     "msgm_groupnorm_dual_backward_slots": (C.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F,
                                                      _P, _P, _P, _SZ, _P, _SZ, C.POINTER(ReduceJobT), C.POINTER(C.c_int32), _P]),

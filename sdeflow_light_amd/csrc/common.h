@@ -53,7 +53,10 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 // index space of a data-parallel run (row_base = first global row of the shard, elem_base = row_base * n, a multiple of
 // 4), so a sharded run draws exactly the numbers the single-GPU run draws for the same rows.  Streams indexed by ROW
 // (the per-sample time draw and RNG_STREAM_ROWS) use row_base, every other stream is indexed by element.
-enum { RNG_STREAM_T = 0, RNG_STREAM_EPS = 1, RNG_STREAM_V = 2, RNG_STREAM_DW = 3, RNG_STREAM_ROWS = 4, RNG_STREAM_USER = 16 };
+// RNG_STREAM_USER + 1 draws the latent's second normal block (SDEs.py).  RNG_STREAM_DROPOUT + l: the dropout masks of the
+// U-Net's ResBlock l, indexed by the global (row, pixel, channel) element (include/msgm_hip.h, msgm_dropout_t).
+enum { RNG_STREAM_T = 0, RNG_STREAM_EPS = 1, RNG_STREAM_V = 2, RNG_STREAM_DW = 3, RNG_STREAM_ROWS = 4, RNG_STREAM_USER = 16,
+       RNG_STREAM_DROPOUT = 64 };
 __device__ __forceinline__ uint64_t msgm_rng_base(const uint64_t* rng, uint32_t stream) {
   return (stream == RNG_STREAM_T || stream == RNG_STREAM_ROWS) ? rng[2] : rng[3];
 }

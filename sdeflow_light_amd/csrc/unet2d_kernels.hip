@@ -55,7 +55,27 @@ struct GnArgs {
   float* pslots;// backward: dgamma | dbeta partials, [2][Bp * GN_SLOTS][C]
   const float* resid;   // backward apply: added to gx (skip-branch cotangent), may alias gx
   const float* resid2;  // a second addend (the cotangent that reached this tensor through the U-Net's skip stack)
+  // dropout after the SiLU (model/unet.py:152-158), read by the DROP builds only: msgm_dropout_t's Philox state, stream,
+  // keep threshold and scale
+  const uint64_t* drng; uint32_t dstream, dthr; float dscale;
 };
+
+// ------------------------------------------------------------------ dropout mask (include/msgm_hip.h, msgm_dropout_t)
+// The mask is never stored: every kernel that touches an element regenerates its keep bit from the Philox block of its
+// channel quad.  The state words are read once per thread; the key / counter folding is msgm_philox's.
+struct DropKey { uint64_t row0; uint32_t k0, k1, off, stream, thr; float s; };
+__device__ __forceinline__ DropKey drop_key(const uint64_t* rng, uint32_t stream, uint32_t thr, float s) {
+  const uint64_t seed = rng[0], off = rng[1];
+  return DropKey{rng[2], (uint32_t)seed, (uint32_t)(seed >> 32) ^ (uint32_t)(off >> 32), (uint32_t)off, stream, thr, s};
+}
+// keep * scale of channels c .. c+3 (c % 4 == 0) of primal row b, pixel p: element e = ((row0 + b) P + p) C + c of the
+// GLOBAL channels-last index, words 0..3 of Philox block e / 4; kept iff (word >> 8) >= thr
+__device__ __forceinline__ f32x4 drop_mul4(const DropKey& k, int b, int P, int C, int p, int c) {
+  const uint64_t q = (((k.row0 + (uint64_t)b) * (uint64_t)P + (uint64_t)p) * (uint64_t)C + (uint64_t)c) >> 2;
+  const Philox4 r = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), k.stream, k.off, k.k0, k.k1);
+  return f32x4{(r.x >> 8) >= k.thr ? k.s : 0.f, (r.y >> 8) >= k.thr ? k.s : 0.f, (r.z >> 8) >= k.thr ? k.s : 0.f,
+               (r.w >> 8) >= k.thr ? k.s : 0.f};
+}
 
 // Reduction tail of the reduce kernels: every thread holds V double partials per moment (channels V*cv .. V*cv+V-1 of pixel
 // lane pl; per-thread fp32 sums over one sub-chunk are widened and from there on everything is added in double).  ALL moments
@@ -198,8 +218,10 @@ __device__ __forceinline__ GnSrc gn_src(const GnArgs& A, int c) {
   return GnSrc{(second ? A.x1 : A.x) + (second ? c - C0 : c), (long)A.Bp * A.P * pitch, pitch};
 }
 
-template <bool VEC>
+// DROP (VEC only): the post-SiLU primal and tangent are multiplied by keep * scale of the dropout mask.
+template <bool VEC, bool DROP = false>
 __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
+  static_assert(VEC || !DROP, "dropout masks are drawn per channel quad");
   constexpr int V = VEC ? 4 : 1;
   __shared__ f32x4 sst[64];
   const int C = A.C, P = A.P, G = A.G, cpg = C / G;
@@ -231,6 +253,8 @@ __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
   }
   const int p0 = blockIdx.x * A.chunk, p1 = min(p0 + A.chunk, P);
   const GnSrc sx = gn_src(A, V * cv);
+  DropKey dk;
+  if constexpr (DROP) dk = drop_key(A.drng, A.dstream, A.dthr, A.dscale);
   for (int p = p0 + pl; p < p1; p += PL) {
     const long e = ((long)b * P + p) * C + V * cv;
     const long ex = ((long)b * P + p) * sx.pitch;
@@ -259,6 +283,11 @@ __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
         y[k] = z0; yd[k] = z1 * yd[k];
       }
     }
+    if constexpr (DROP) {
+      const f32x4 m = drop_mul4(dk, b, P, C, p, V * cv);
+#pragma unroll
+      for (int k = 0; k < V; ++k) { y[k] *= m[k]; yd[k] *= m[k]; }
+    }
     if (VEC) {
       f32x4 o, od;
 #pragma unroll
@@ -277,8 +306,11 @@ __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
 //   xdotbar = inv (W - mean W - xhat p),                      p = mean(xhat W)
 //   xbar    = inv (X - mean X - xhat mean(xhat X)) - inv (c xhat + a xdotbar + p what),  c = mean(W what)
 // (derived by hand, checked against autograd in tests/test_unet2d_gpu.py).
-template <bool VEC>
+// DROP (VEC only): both incoming cotangents are multiplied by keep * scale as they are loaded (the moments see the masked
+// cotangent), in this kernel and in k_gn_bwd_apply.
+template <bool VEC, bool DROP = false>
 __global__ void __launch_bounds__(256) k_gn_bwd_reduce(GnArgs A) {
+  static_assert(VEC || !DROP, "dropout masks are drawn per channel quad");
   constexpr int V = VEC ? 4 : 1;
   __shared__ double redd[5 * 1024];      // the five moments and (below) both parameter partials: ONE barrier in the tail
   __shared__ float red[2 * 1024];
@@ -302,6 +334,8 @@ __global__ void __launch_bounds__(256) k_gn_bwd_reduce(GnArgs A) {
   float dga[V], dbe[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) { dX[k] = dXx[k] = dW[k] = dWx[k] = dWw[k] = 0.0; dga[k] = dbe[k] = 0.f; }
+  DropKey dk;
+  if constexpr (DROP) dk = drop_key(A.drng, A.dstream, A.dthr, A.dscale);
   if (live)
    for (int ps = p0; ps < p1; ps += max(A.sub, 1)) {
     const int pe = min(ps + max(A.sub, 1), p1);
@@ -319,6 +353,11 @@ __global__ void __launch_bounds__(256) k_gn_bwd_reduce(GnArgs A) {
         for (int k = 0; k < V; ++k) { x[k] = v0[k]; xd[k] = v1[k]; zb[k] = v2[k]; zdb[k] = v3[k]; }
       } else {
         x[0] = sx.base[ex]; xd[0] = sx.base[ex + sx.half]; zb[0] = A.gout[e]; zdb[0] = A.gout[e + tot];
+      }
+      if constexpr (DROP) {
+        const f32x4 m = drop_mul4(dk, b, P, C, p, V * cv);
+#pragma unroll
+        for (int k = 0; k < V; ++k) { zb[k] *= m[k]; zdb[k] *= m[k]; }
       }
 #pragma unroll
       for (int k = 0; k < V; ++k) {
@@ -396,8 +435,9 @@ __global__ void __launch_bounds__(1024) k_gn_param_reduce(const float* __restric
   }
 }
 
-template <bool VEC>
+template <bool VEC, bool DROP = false>
 __global__ void __launch_bounds__(256) k_gn_bwd_apply(GnArgs A) {
+  static_assert(VEC || !DROP, "dropout masks are drawn per channel quad");
   constexpr int V = VEC ? 4 : 1;
   const int C = A.C, P = A.P, G = A.G, cpg = C / G;
   const int CV = C / V, PL = 256 / CV;
@@ -432,6 +472,8 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(GnArgs A) {
   float* gbase = A.x1 ? ((V * cv >= A.C0) ? A.gx1 + (V * cv - A.C0) : A.gx + V * cv) : A.gx + V * cv;
   const float* rbase = A.resid ? A.resid + V * cv : nullptr;            // single-source only (host checks)
   const float* rbase2 = A.resid2 ? A.resid2 + V * cv : nullptr;
+  DropKey dk;
+  if constexpr (DROP) dk = drop_key(A.drng, A.dstream, A.dthr, A.dscale);
   for (int p = p0 + pl; p < p1; p += PL) {
     const long e = ((long)b * P + p) * C + V * cv;
     const long ex = ((long)b * P + p) * sx.pitch;
@@ -443,6 +485,11 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(GnArgs A) {
       for (int k = 0; k < V; ++k) { x[k] = v0[k]; xd[k] = v1[k]; zb[k] = v2[k]; zdb[k] = v3[k]; }
     } else {
       x[0] = sx.base[ex]; xd[0] = sx.base[ex + sx.half]; zb[0] = A.gout[e]; zdb[0] = A.gout[e + tot];
+    }
+    if constexpr (DROP) {
+      const f32x4 m = drop_mul4(dk, b, P, C, p, V * cv);
+#pragma unroll
+      for (int k = 0; k < V; ++k) { zb[k] *= m[k]; zdb[k] *= m[k]; }
     }
 #pragma unroll
     for (int k = 0; k < V; ++k) {
@@ -1146,14 +1193,26 @@ size_t msgm_groupnorm_workspace(int32_t Bp, int32_t G) {
   return gn_acc_bytes(Bp, G) + gn_accf_bytes(Bp, G) + gn_stats_bytes(Bp, G) + (size_t)2 * Bp * GN_SLOTS * 256 * sizeof(float);
 }
 
+// dropout descriptor -> the DROP kernels' arguments (single-source input, C % 4 == 0: one Philox block per channel quad)
+static int gn_set_dropout(GnArgs& A, const msgm_dropout_t* drop) {
+  if (!drop->rng || drop->thr > (1u << 24) || !(drop->scale >= 1.0f)) return MSGM_E_BADARG;
+  if (A.x1 || A.C % 4) return MSGM_E_UNSUPPORTED;
+  A.drng = drop->rng; A.dstream = drop->stream; A.dthr = drop->thr; A.dscale = drop->scale;
+  return MSGM_OK;
+}
+
 static int gn_forward_impl(const float* x, int32_t C0, const float* x1, int32_t C, const float* gamma, const float* beta, float* out,
                            float* stats, int32_t Bp, int32_t P, int32_t G, int32_t dual, int32_t silu, float eps, void* workspace,
-                           size_t workspace_bytes, msgm_stream_t stream) {
+                           size_t workspace_bytes, msgm_stream_t stream, const msgm_dropout_t* drop = nullptr) {
   if (!x || !gamma || !beta || !out || !workspace || Bp <= 0 || P <= 0 || C <= 0 || G <= 0) return MSGM_E_BADARG;
   if (C % G || C > 256 || G > 64 || (x1 && (C0 % 4 || (C - C0) % 4 || C0 <= 0 || C0 >= C))) return MSGM_E_UNSUPPORTED;
   if (workspace_bytes < msgm_groupnorm_workspace(Bp, G)) return MSGM_E_WORKSPACE;
   GnArgs A{x, gamma, beta, out, reinterpret_cast<double*>(workspace), stats, P, C, G, Bp, dual, silu, 0, eps,
            nullptr, nullptr, nullptr, nullptr, x1, C0};
+  if (drop) {
+    const int rc = gn_set_dropout(A, drop);
+    if (rc != MSGM_OK) return rc;
+  }
   const int nch = gn_chunks(Bp, P, &A.chunk, &A.sub);
   if (nch > GN_SLOTS) return MSGM_E_UNSUPPORTED;
   A.nch = nch;
@@ -1161,7 +1220,8 @@ static int gn_forward_impl(const float* x, int32_t C0, const float* x1, int32_t 
   if (C % 4 == 0) hipLaunchKernelGGL(k_gn_fwd_reduce<true>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
   else hipLaunchKernelGGL(k_gn_fwd_reduce<false>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
   const int nap = gn_chunks_apply(Bp, P, &A.chunk);
-  if (C % 4 == 0) hipLaunchKernelGGL(k_gn_fwd_apply<true>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
+  if (drop) hipLaunchKernelGGL((k_gn_fwd_apply<true, true>), dim3(nap, Bp), dim3(256), 0, S(stream), A);
+  else if (C % 4 == 0) hipLaunchKernelGGL(k_gn_fwd_apply<true>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
   else hipLaunchKernelGGL(k_gn_fwd_apply<false>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
   return msgm_check_launch();
 }
@@ -1177,6 +1237,37 @@ int msgm_groupnorm_dual_forward2(const float* x0, int32_t C0, const float* x1, i
                                  void* workspace, size_t workspace_bytes, msgm_stream_t stream) {
   if (!x1 || C1 <= 0) return MSGM_E_BADARG;
   return gn_forward_impl(x0, C0, x1, C0 + C1, gamma, beta, out, stats, Bp, P, G, dual, silu, eps, workspace, workspace_bytes, stream);
+}
+
+int msgm_groupnorm_dual_forward_dropout(const float* x, const float* gamma, const float* beta, float* out, float* stats, int32_t Bp,
+                                        int32_t P, int32_t C, int32_t G, int32_t dual, int32_t silu, float eps, void* workspace,
+                                        size_t workspace_bytes, const msgm_dropout_t* drop, msgm_stream_t stream) {
+  if (!drop) return MSGM_E_BADARG;
+  return gn_forward_impl(x, C, nullptr, C, gamma, beta, out, stats, Bp, P, G, dual, silu, eps, workspace, workspace_bytes, stream,
+                         drop);
+}
+
+// the 0/1 keep mask of msgm_dropout_t, [Bp][P][C]: one thread per channel quad, the quads of the tensor in order
+__global__ void __launch_bounds__(256) k_dropout_mask(const uint64_t* __restrict__ rng, uint32_t stream, uint32_t thr, int Bp, int P,
+                                                      int C, float* __restrict__ keep) {
+  const DropKey dk = drop_key(rng, stream, thr, 1.0f);
+  const int CQ = C / 4;
+  const size_t nq = (size_t)Bp * P * CQ;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nq; i += (size_t)gridDim.x * 256) {
+    const int cq = (int)(i % CQ);
+    const size_t bp = i / CQ;
+    const int p = (int)(bp % P), b = (int)(bp / P);
+    *reinterpret_cast<f32x4*>(keep + 4 * i) = drop_mul4(dk, b, P, C, p, 4 * cq);
+  }
+}
+
+int msgm_dropout_mask(const msgm_dropout_t* drop, int32_t Bp, int32_t P, int32_t C, float* keep_out, msgm_stream_t stream) {
+  if (!drop || !drop->rng || !keep_out || Bp <= 0 || P <= 0 || C <= 0 || drop->thr > (1u << 24)) return MSGM_E_BADARG;
+  if (C % 4) return MSGM_E_UNSUPPORTED;
+  const int64_t nq = (int64_t)Bp * P * (C / 4);
+  hipLaunchKernelGGL(k_dropout_mask, dim3(grid_for(nq, 256, 4096)), dim3(256), 0, S(stream), drop->rng, drop->stream, drop->thr,
+                     (int)Bp, (int)P, (int)C, keep_out);
+  return msgm_check_launch();
 }
 
 int msgm_groupnorm_affine(const float* x0, int32_t C0, const float* x1, int32_t C1, const float* gamma, const float* beta,
@@ -1248,7 +1339,8 @@ static int gn_backward_impl(const float* x, int32_t C0, const float* x1, int32_t
                             const float* stats, const float* gout, float* gx, float* gx1, float* dgamma, float* dbeta, int32_t Bp,
                             int32_t P, int32_t G, int32_t silu, float eps, const float* residual, void* workspace,
                             size_t workspace_bytes, msgm_stream_t stream, float* pslots_ext = nullptr, size_t pslots_bytes = 0,
-                            msgm_reduce_job_t* jobs_out = nullptr, int32_t* n_jobs_out = nullptr, const float* residual2 = nullptr) {
+                            msgm_reduce_job_t* jobs_out = nullptr, int32_t* n_jobs_out = nullptr, const float* residual2 = nullptr,
+                            const msgm_dropout_t* drop = nullptr) {
   if (!x || !gamma || !beta || !stats || !gout || !gx || !dgamma || !dbeta || !workspace || Bp <= 0 || P <= 0 || C <= 0 || G <= 0)
     return MSGM_E_BADARG;
   if (C % G || C > 256 || G > 64) return MSGM_E_UNSUPPORTED;
@@ -1256,6 +1348,10 @@ static int gn_backward_impl(const float* x, int32_t C0, const float* x1, int32_t
   if (workspace_bytes < msgm_groupnorm_workspace(Bp, G)) return MSGM_E_WORKSPACE;
   GnArgs A{x, gamma, beta, nullptr, reinterpret_cast<double*>(workspace), const_cast<float*>(stats), P, C, G, Bp, 1, silu, 0,
            eps, gout, gx, dgamma, dbeta, x1, C0, gx1};
+  if (drop) {
+    const int rc = gn_set_dropout(A, drop);
+    if (rc != MSGM_OK) return rc;
+  }
   const int nch = gn_chunks(Bp, P, &A.chunk, &A.sub);
   if (nch > GN_SLOTS) return MSGM_E_UNSUPPORTED;
   A.nch = nch;
@@ -1269,7 +1365,8 @@ static int gn_backward_impl(const float* x, int32_t C0, const float* x1, int32_t
   }
   A.resid = residual;
   A.resid2 = residual2;
-  if (C % 4 == 0) hipLaunchKernelGGL(k_gn_bwd_reduce<true>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
+  if (drop) hipLaunchKernelGGL((k_gn_bwd_reduce<true, true>), dim3(Bp, nch), dim3(256), 0, S(stream), A);
+  else if (C % 4 == 0) hipLaunchKernelGGL(k_gn_bwd_reduce<true>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
   else hipLaunchKernelGGL(k_gn_bwd_reduce<false>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
   if (pslots_ext) {
     for (int w = 0; w < 2; ++w)
@@ -1282,7 +1379,8 @@ static int gn_backward_impl(const float* x, int32_t C0, const float* x1, int32_t
                        nbc);
   }
   const int nap = gn_chunks_apply(Bp, P, &A.chunk);
-  if (C % 4 == 0) hipLaunchKernelGGL(k_gn_bwd_apply<true>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
+  if (drop) hipLaunchKernelGGL((k_gn_bwd_apply<true, true>), dim3(nap, Bp), dim3(256), 0, S(stream), A);
+  else if (C % 4 == 0) hipLaunchKernelGGL(k_gn_bwd_apply<true>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
   else hipLaunchKernelGGL(k_gn_bwd_apply<false>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
   return msgm_check_launch();
 }
@@ -1304,6 +1402,18 @@ int msgm_groupnorm_dual_backward_slots(const float* x0, int32_t C0, const float*
   *n_jobs_out = 0;
   return gn_backward_impl(x0, C0, x1, C0 + C1, gamma, beta, stats, gout, gx0, gx1, dgamma, dbeta, Bp, P, G, silu, eps, residual,
                           workspace, workspace_bytes, stream, pslots, pslots_bytes, jobs_out, n_jobs_out, residual2);
+}
+
+int msgm_groupnorm_dual_backward_slots_dropout(const float* x, const float* gamma, const float* beta, const float* stats,
+                                               const float* gout, float* gx, float* dgamma, float* dbeta, int32_t Bp, int32_t P,
+                                               int32_t C, int32_t G, int32_t silu, float eps, const float* residual,
+                                               const float* residual2, void* workspace, size_t workspace_bytes, float* pslots,
+                                               size_t pslots_bytes, msgm_reduce_job_t* jobs_out, int32_t* n_jobs_out,
+                                               const msgm_dropout_t* drop, msgm_stream_t stream) {
+  if (!pslots || !jobs_out || !n_jobs_out || !drop) return MSGM_E_BADARG;
+  *n_jobs_out = 0;
+  return gn_backward_impl(x, C, nullptr, C, gamma, beta, stats, gout, gx, nullptr, dgamma, dbeta, Bp, P, G, silu, eps, residual,
+                          workspace, workspace_bytes, stream, pslots, pslots_bytes, jobs_out, n_jobs_out, residual2, drop);
 }
 
 int msgm_groupnorm_dual_backward(const float* x, const float* gamma, const float* beta, const float* stats, const float* gout,

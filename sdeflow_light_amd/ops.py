@@ -713,7 +713,33 @@ def _gn_ws(Bp: int, G: int, device) -> torch.Tensor:
     return _GN_WS[key]
 
 
-def groupnorm_dual_forward(x, gamma, beta, Bp, P, C, G, dual, silu, stats=None, out=None, eps=1e-5):
+def dropout_threshold(p: float):
+    """(thr, scale) of the mask rule (include/msgm_hip.h, msgm_dropout_t): keep iff (word >> 8) >= thr = ceil(p 2^24), kept
+    values times scale = 1 / (1 - p), both computed in double (scale is rounded to fp32 where it is stored)."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise MsgmError(f"dropout probability {p} outside [0, 1)")
+    return int(math.ceil(p * 16777216.0)), 1.0 / (1.0 - p)
+
+
+def dropout_desc(rng: PhiloxState, layer: int, p: float) -> L.DropoutT:
+    """msgm_dropout_t of ResBlock ``layer`` (its position among all ResBlocks): stream RNG_STREAM_DROPOUT + layer of ``rng``
+    at its current device offset."""
+    thr, scale = dropout_threshold(p)
+    if layer < 0:
+        raise MsgmError("dropout layer index must be >= 0")
+    return L.DropoutT(rng.ptr(), L.RNG_STREAM_DROPOUT + int(layer), thr, scale)
+
+
+def dropout_mask(desc: L.DropoutT, Bp: int, P: int, C: int, device) -> torch.Tensor:
+    """The 0/1 keep mask [Bp][P][C] that the dropout GroupNorm entries apply (tests, diagnostics)."""
+    keep = torch.empty(Bp * P * C, dtype=torch.float32, device=device)
+    check(lib().msgm_dropout_mask(C_.byref(desc), int(Bp), int(P), int(C), ptr(keep), stream()), "msgm_dropout_mask")
+    return keep
+
+
+def groupnorm_dual_forward(x, gamma, beta, Bp, P, C, G, dual, silu, stats=None, out=None, eps=1e-5, dropout=None):
+    """``dropout`` (an L.DropoutT, or None): the post-SiLU primal and tangent are multiplied by the mask's keep * scale."""
     N = 2 * Bp if dual else Bp
     if x.numel() != N * P * C or gamma.numel() != C or beta.numel() != C:
         raise MsgmError("groupnorm: size mismatch")
@@ -721,6 +747,11 @@ def groupnorm_dual_forward(x, gamma, beta, Bp, P, C, G, dual, silu, stats=None, 
         raise MsgmError("groupnorm: stats must be [Bp][G][4]")
     out = torch.empty_like(x) if out is None else out
     ws = _gn_ws(Bp, G, x.device)
+    if dropout is not None:
+        check(lib().msgm_groupnorm_dual_forward_dropout(ptr(f32(x)), ptr(f32(gamma)), ptr(f32(beta)), ptr(out), ptr(stats), Bp, P, C,
+                                                        G, int(bool(dual)), int(bool(silu)), float(eps), ptr(ws), ws.numel() * 8,
+                                                        C_.byref(dropout), stream()), "msgm_groupnorm_dual_forward_dropout")
+        return out
     check(lib().msgm_groupnorm_dual_forward(ptr(f32(x)), ptr(f32(gamma)), ptr(f32(beta)), ptr(out), ptr(stats), Bp, P, C, G,
                                             int(bool(dual)), int(bool(silu)), float(eps), ptr(ws), ws.numel() * 8, stream()),
           "msgm_groupnorm_dual_forward")
@@ -744,11 +775,27 @@ def _gn_backward_slots(x0, C0, x1, C1, gamma, beta, stats, gout, gx0, gx1, dgamm
     d.add(jobs, nj.value, (dgamma, dbeta))
 
 
+def _gn_backward_dropout(x, gamma, beta, stats, gout, gx, dgamma, dbeta, Bp, P, C, G, silu, eps, residual, residual2, drop, d):
+    """The slots backward of the dropout map (its parameter reductions join the DeferredReduces pass ``d``)."""
+    need = int(lib().msgm_groupnorm_param_slots_bytes(Bp, P, C))
+    ps, nbytes = d.take(need)
+    ws = _gn_ws(Bp, G, x.device)
+    jobs, nj = (L.ReduceJobT * 2)(), C_.c_int32(0)
+    check(lib().msgm_groupnorm_dual_backward_slots_dropout(ptr(f32(x)), ptr(f32(gamma)), ptr(f32(beta)), ptr(f32(stats)),
+                                                           ptr(f32(gout)), ptr(gx), ptr(dgamma), ptr(dbeta), Bp, P, C, G,
+                                                           int(bool(silu)), float(eps), ptr(residual), ptr(residual2), ptr(ws),
+                                                           ws.numel() * 8, ps, nbytes, jobs, C_.byref(nj), C_.byref(drop), stream()),
+          "msgm_groupnorm_dual_backward_slots_dropout")
+    d.add(jobs, nj.value, (dgamma, dbeta))
+
+
 def groupnorm_dual_backward(x, gamma, beta, stats, gout, dgamma, dbeta, Bp, P, C, G, silu, gx=None, eps=1e-5, residual=None,
-                            residual2=None):
+                            residual2=None, dropout=None):
     """``residual`` (same shape as x) is added to the returned cotangent in the apply pass (skip branch, no extra axpy);
     ``residual2``: a second addend (the skip-stack cotangent) — in the same pass inside a DeferredReduces backward, by one
-    lincomb otherwise."""
+    lincomb otherwise.  ``dropout`` (an L.DropoutT): the backward of groupnorm_dual_forward(dropout=) with the same
+    descriptor (same Philox offset); it always runs in the slots form, in a DeferredReduces pass of its own when none is
+    active."""
     if x.numel() != 2 * Bp * P * C or gout.numel() != x.numel() or stats.numel() != Bp * G * 4:
         raise MsgmError("groupnorm backward: size mismatch")
     if dgamma.numel() != C or dbeta.numel() != C:
@@ -757,6 +804,15 @@ def groupnorm_dual_backward(x, gamma, beta, stats, gout, dgamma, dbeta, Bp, P, C
     if (residual is not None and residual.numel() != x.numel()) or (residual2 is not None and residual2.numel() != x.numel()):
         raise MsgmError("groupnorm backward: residual size")
     d = DeferredReduces.active
+    if dropout is not None:
+        if d is not None and d.device == x.device:
+            _gn_backward_dropout(x, gamma, beta, stats, gout, gx, dgamma, dbeta, Bp, P, C, G, silu, eps, residual, residual2,
+                                 dropout, d)
+        else:
+            with DeferredReduces.on(x.device) as d1:
+                _gn_backward_dropout(x, gamma, beta, stats, gout, gx, dgamma, dbeta, Bp, P, C, G, silu, eps, residual, residual2,
+                                     dropout, d1)
+        return gx
     if d is not None and d.device == x.device:
         _gn_backward_slots(x, C, None, 0, gamma, beta, stats, gout, gx, None, dgamma, dbeta, Bp, P, G, silu, eps, residual, d,
                            residual2=residual2)

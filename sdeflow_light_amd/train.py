@@ -263,7 +263,7 @@ class UNetScoreTrainer(_TrainerState):
                                         self.d, self.st, self.rng.ptr(), self.step_dev.data_ptr(), s), "msgm_ssm_prep")
             y, t, vp = self.y, self.t, self.vp
             u, cst = ops.ssm_terms(y, vp, t, self.st)
-        per = self.net.ssm_grad(y, t, vp, u, cst, self.inv_batch)
+        per = self.net.ssm_grad(y, t, vp, u, cst, self.inv_batch, rng=self.rng)     # 2-D U-Net dropout masks: the trainer's stream
         flat, gflat = self.net.flat_parameters()
         if flat.data_ptr() != self.flat.data_ptr() or gflat.data_ptr() != self.gbuf.data_ptr():
             raise MsgmError("the flat parameter bucket moved; rebuild the trainer")

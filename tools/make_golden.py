@@ -616,6 +616,102 @@ def g18_multihead():
     save("g18_multihead", **out)
 
 
+G19_FULL = ("core.input_blocks.1.0.", "core.input_blocks.4.0.", "core.input_blocks.7.0.", "core.output_blocks.0.0.")
+G19_PARTS = ("out_layers.0.", "out_layers.3.", "in_layers.2.")
+G19_SUB = 16       # (Co, Ci, 3, 3) weight gradients: G19_SUB output rows x G19_SUB input columns, evenly spaced
+
+
+def _force_dropout(net, seed, offset, row_base, p):
+    """Replace the forward of every reference Dropout (ResBlock out_layers[2], model/unet.py:152-158) by a multiply with the
+    mask the rule gives for that ResBlock's index l (its position among all ResBlocks in named_modules() order) at
+    (seed, offset, row_base) — tests/philox_np.py, the restatement the tests use.  Returns the indices in order."""
+    import philox_np as PX
+    from model.unet import ResBlock as RefResBlock
+    blocks = [m for m in net.modules() if isinstance(m, RefResBlock)]
+    for l, blk in enumerate(blocks):
+        drop = blk.out_layers[2]
+        assert isinstance(drop, torch.nn.Dropout) and drop.p == p
+
+        def fwd(h, l=l):
+            B, C, H, W = h.shape
+            return h * torch.from_numpy(PX.dropout_multiplier(seed, offset, row_base, l, p, B, H, W, C)).to(h.dtype)
+        drop.forward = fwd
+    return len(blocks)
+
+
+def _g19_store(out, tag, grads, detail):
+    if detail:
+        full = {k: v for k, v in grads.items() if k[len("a."):].startswith(G19_FULL) and
+                k[len("a."):].split(".", 4)[-1].startswith(G19_PARTS)}
+        assert len(full) == 4 * 6 and all(float(v.norm()) > 0 for v in full.values()), sorted(full)
+        for k, v in full.items():
+            if v.dim() == 4:
+                rows = torch.arange(0, v.shape[0], max(1, v.shape[0] // G19_SUB))
+                cols = torch.arange(0, v.shape[1], max(1, v.shape[1] // G19_SUB))
+                out[f"{tag}_rows::{k}"], out[f"{tag}_cols::{k}"] = rows, cols
+                v = v[rows][:, cols]
+            out[f"{tag}_grad::{k}"] = v
+    out.update({f"{tag}_gd_{k}": v for k, v in _grad_digest(grads).items()})
+
+
+def g19_dropout():
+    """Dropout(p) in every ResBlock's out_layers (model/unet.py:152-158): the reference's VorticityUNet(dropout=p) in TRAIN
+    mode on the well-conditioned fill, each Dropout forced to the mask rule (include/msgm_hip.h, msgm_dropout_t) at a
+    recorded (seed, offset) and at row_base 0 and 4.  Cases: in_space 32, p = 0.1, SGM (ssm with the three draws forced);
+    in_space 16, p = 0.3, NormalizeLogRadius, the MSGM sparse SDE (ssm_loss(t, x, y) with the probe forced, as g14).  Stored:
+    the per-sample loss, the gradients of out_layers.{0,3} and in_layers.2 of the first ResBlock of each level and of the
+    first decoder block (skip conv) — vectors in full, conv weights at G19_SUB rows x G19_SUB columns (_rows:: / _cols::) —
+    at row_base 0, digests of all gradients at both row_bases, and one train-mode forward at a fixed t (row_base 0)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    torch.manual_seed(19)
+    out = {}
+    seed, off_ssm, off_fwd = 0x5DE5_1234_9ABC, 3, 8
+    for tag, S_, p, pre, kind in (("s32", 32, 0.1, None, "sgm"), ("s16m", 16, 0.3, "NormalizeLogRadius", "sparse")):
+        B, d = 2, S_ * S_
+        net = VorticityUNet(base_channels=32, channel_mults=(1, 2, 4), num_res_blocks=2, dropout=p, premodule=pre, in_space=S_,
+                            attention_resolutions=(2, 4), flatten_order="F")
+        load_init_like_(net)
+        net.train()
+        if kind == "sgm":
+            rev = PluginReverseSDE(sgm(), net, Tparam())
+            x, u_t, eps, u_v = torch.randn(B, d) * 3, torch.rand(B, 1), torch.randn(B, d), torch.rand(B, d)
+            out.update({f"{tag}_x": x, f"{tag}_u_t": u_t, f"{tag}_eps": eps, f"{tag}_u_v": u_v})
+        else:
+            base = msgm(torch.randn(64, d) * 1.5, dense=False, nsf=4)
+            rev = PluginReverseSDE(base, net, Tparam())
+            t_, y, u_v = torch.rand(B, 1).clamp_min(1e-3), torch.randn(B, d) * 1.3, torch.rand(B, d)
+            out.update({f"{tag}_t": t_, f"{tag}_y": y, f"{tag}_u_v": u_v})
+            out.update({f"{tag}_base::" + k: v for k, v in sd_np(rev.state_dict()).items() if not k.startswith("a.")})
+        for rb in (0, 4):
+            nl = _force_dropout(net, seed, off_ssm, rb, p)
+            if kind == "sgm":
+                res = _ssm_case(rev, x, u_t, eps, u_v, full_grads=True)
+                per = res["per"]
+                grads = {k[len("grad::"):]: v for k, v in res.items() if k.startswith("grad::")}
+            else:
+                o = torch.rand
+                torch.rand = lambda *a, **k: u_v.clone()
+                try:
+                    rev.zero_grad()
+                    per = rev.ssm_loss(t_, y, y.clone().requires_grad_(True))
+                    per.mean().backward()
+                finally:
+                    torch.rand = o
+                per = per.detach()
+                grads = {k: q.grad.detach().clone() for k, q in rev.named_parameters() if q.grad is not None}
+            out[f"{tag}_rb{rb}_per"] = per
+            _g19_store(out, f"{tag}_rb{rb}", grads, detail=rb == 0)
+            print(tag, "row_base", rb, "per", per.tolist(), "ResBlocks", nl)
+        out.update({f"{tag}_p": np.array(p), f"{tag}_seed": np.array(seed, dtype=np.int64),
+                    f"{tag}_offset": np.array(off_ssm, dtype=np.int64), f"{tag}_fwd_offset": np.array(off_fwd, dtype=np.int64)})
+        _force_dropout(net, seed, off_fwd, 0, p)
+        with torch.no_grad():
+            xf = torch.randn(B, d) * 3
+            t = torch.full((B,), 0.37)
+            out[f"{tag}_fwd_x"], out[f"{tag}_fwd_t"], out[f"{tag}_fwd"] = xf, t, net(xf, t)
+    save("g19_dropout", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
