@@ -14,7 +14,9 @@ over the ranks, fp32.
                       loss, the flat parameters after Adam and the flat gradient, in named_parameters() order; c5: the
                       samples) as DIR/<name>.npy, float32, at most 64 MB in all.  Inputs are seeded, so two runs with the
                       same arguments can be compared array by array.
-On the same JSON line:
+A plain run does only that: set-up, warm-up, the timed steps, the dump and the JSON line (its `roofline`, where it has
+one, is the whole-step rate of the timed steps).  Everything below takes runs of its own and is measured with --full only.
+On the same JSON line with --full:
   sample_steps_per_s  C5: reverse-SDE Euler-Maruyama steps/s for 8192 samples of the same net (rows split over the
                       ranks, chunks of <= 4096 rows, ONE hipGraph-captured step replayed --sample-steps times per chunk);
   roofline            the kernel family with the LARGEST MEASURED SHARE of the C4 step: one eager step of the same kernels
@@ -24,7 +26,8 @@ On the same JSON line:
   cpu_baseline        the CPU oracle on this host's cores at batch 8 incl. Adam, scaled to 256 (rank 0, N=1 only);
   extra               C2 (MLP, B=65536), C3 (UNet1D L=1024, B=4096) and MSGM (multiplicative SDE: UNet1D d=1024 and the C4
                       net at d=12288, sparse tensor, nsf=16) short legs (N=1 only).
---workload c2|c3 selects those configs as the main line instead (c5 = sampling only).
+--workload c2|c3 selects those configs as the main line instead (c5 = sampling only); with --full, c2 adds its sampler
+and k_mlp roofline legs and c2 / c3 the CPU baseline.
 
 `--gpus N` with N > 1 and no torchrun environment: this process touches no GPU and starts N ranks itself
 (`python -m torch.distributed.run ... bench.py --gpus N ...`), relaying their output; under the driver's own
@@ -364,10 +367,10 @@ def leg_sample_unet(gen, d, a, rank, world, dev, main_line=False):
     return out
 
 
-def leg_mlp(a, rank, world, dev, steps=200, sample_steps=200, main_line=False):
+def leg_mlp(a, rank, world, dev, steps=200, sample_steps=200, main_line=False, full=True):
     """C2: MLP d=2, B=65536 per GPU (weak): graph-replayed train step + whole-loop EM sampler + k_mlp<TRAIN> roofline.
     main_line: a.warmup warm-up steps, exactly `steps` timed steps, and the last step's outputs under "outputs" when
-    a.dump_outputs is set."""
+    a.dump_outputs is set.  full=False: the training steps only (no sampler, no roofline)."""
     import ctypes as C
     import torch
     from sdeflow_light_amd import parallel, ops
@@ -382,15 +385,20 @@ def leg_mlp(a, rank, world, dev, steps=200, sample_steps=200, main_line=False):
     med, blocks = timed_blocks(tr.step, steps, a.warmup if main_line else 20, dev, max_blocks=1 if main_line else 50)
     per_step = med / steps
     outputs = {k: v.cpu() for k, v in trainer_outputs(tr).items()} if main_line and a.dump_outputs else None
+    out = {"workload": "C2: 2-D Gaussian mixture, MLP (d=2, hidden 128), SGM, batch 65536/GPU, SSM + Adam",
+           "train_steps_per_s": world / per_step, "ms_per_step": per_step * 1e3, "final_loss": float(tr.loss.item())}
+    if outputs is not None:
+        out["outputs"] = outputs
+    if not full:
+        del tr
+        return out
     gen.base_sde.set_shard(rank * B_C2, 2)
     smp = GraphedEMSampler(gen, B_C2, sample_steps)
     x0 = gen.latent_sample(B_C2, 2)
     smp.run(x0)
     meds, _ = timed_blocks(lambda: smp.run(x0), 3, 0, dev, min_seconds=0.2)
-    out = {"workload": "C2: 2-D Gaussian mixture, MLP (d=2, hidden 128), SGM, batch 65536/GPU, SSM + Adam",
-           "train_steps_per_s": world / per_step, "ms_per_step": per_step * 1e3, "final_loss": float(tr.loss.item()),
-           "sample_steps_per_s": world * 3 * sample_steps / meds,
-           "sample_config": f"EM, {sample_steps} steps, 65536 rows/GPU, whole loop = one launch replayed as a hipGraph"}
+    out.update(sample_steps_per_s=world * 3 * sample_steps / meds,
+               sample_config=f"EM, {sample_steps} steps, 65536 rows/GPU, whole loop = one launch replayed as a hipGraph")
     if rank == 0:
         lib = ops.lib()
         nsl = C.c_int32(0)
@@ -403,8 +411,6 @@ def leg_mlp(a, rank, world, dev, steps=200, sample_steps=200, main_line=False):
                            "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": flop / tk / 1e12 / PEAK_F32_MFMA_TFLOPS,
                            "kernel_ms": tk * 1e3, "flop_per_launch": flop,
                            "traffic": 40.1e6, "traffic_source": "profiles/r01_pmc_traffic.json (round-1 PMC pass, not measured in this run)"}
-    if outputs is not None:
-        out["outputs"] = outputs
     del tr, smp
     return out
 
@@ -693,13 +699,13 @@ def worker(a):
             dump_outputs(a.dump_outputs, outputs)
 
     if w == "c2":
-        r = leg_mlp(a, rank, world, dev, steps=a.steps, main_line=True)
+        r = leg_mlp(a, rank, world, dev, steps=a.steps, main_line=True, full=a.full)
         dump(r)
         out.update(metric="score-matching train steps/sec (+ reverse-SDE sample steps/sec)", value=r["train_steps_per_s"],
                    unit="train_steps/s (B=65536 per step per GPU)", ms_per_step=r["ms_per_step"], scaling="weak",
                    config={"workload": r["workload"], "global_batch": B_C2 * world, "parallelism": f"dp{world}"},
-                   sample_steps_per_s=r["sample_steps_per_s"], final_loss=r["final_loss"], roofline=r.get("roofline"),
-                   cpu_baseline=cpu_baseline_mlp() if solo and not a.no_cpu_baseline else None)
+                   sample_steps_per_s=r.get("sample_steps_per_s"), final_loss=r["final_loss"], roofline=r.get("roofline"),
+                   cpu_baseline=cpu_baseline_mlp() if a.full and solo and not a.no_cpu_baseline else None)
     elif w == "c5":
         gen, d = build_unet("c5", dev)
         r = leg_sample_unet(gen, d, a, rank, world, dev, main_line=True)
@@ -722,8 +728,13 @@ def worker(a):
                    ms_per_step=r["ms_per_step"], scaling="weak" if w == "c3" else "strong",
                    config={"workload": name, "global_batch": r["global_batch"], "parallelism": f"dp{world}", "graph": r["graph"]},
                    final_loss=r["final_loss"], timed_blocks_s=r["blocks_s"], whole_step=r["whole_step"])
+        ws = r["whole_step"]
+        out["roofline"] = {"kernel": "whole step (all kernels)" if solo else "whole step (all kernels), per GPU", "bound": "mfma",
+                           "achieved": ws["algorithmic_tflops_per_gpu"], "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                           "frac": ws["frac_of_f32_mfma_peak"], "traffic": None}
+        out["cpu_baseline"] = None
         free_gpu()
-        if w == "c4" and a.sample_steps > 0:
+        if a.full and w == "c4" and a.sample_steps > 0:
             log("c5: sampling leg")
             s = leg_sample_unet(gen, d, a, rank, world, dev)
             out.update(sample_steps_per_s=s["sample_steps_per_s"], sample=s)
@@ -743,7 +754,7 @@ def worker(a):
                 out["sample_bf16_split_experiment"] = s6
         del gen
         free_gpu()
-        if solo:
+        if a.full and solo:
             if w == "c4":
                 log("c4: per-launch profile of one eager step")
                 fams, total = leg_step_profile(dev, GLOBAL_BATCH[w])
@@ -768,10 +779,6 @@ def worker(a):
                 free_gpu()
                 log("HBM-bound kernels")
                 out["roofline_hbm"] = hbm_rooflines(dev)
-            else:
-                ws = r["whole_step"]
-                out["roofline"] = {"kernel": "whole step (all kernels)", "bound": "mfma", "achieved": ws["algorithmic_tflops_per_gpu"],
-                                   "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ws["frac_of_f32_mfma_peak"], "traffic": None}
             free_gpu()
             if w == "c4" and not a.no_extra:
                 extra = {}
@@ -792,11 +799,6 @@ def worker(a):
             log("cpu baseline (oracle on the host cores)")
             out["cpu_baseline"] = None if a.no_cpu_baseline else cpu_baseline_unet(w)
             log("done")
-        else:
-            ws = r["whole_step"]
-            out["roofline"] = {"kernel": "whole step (all kernels), per GPU", "bound": "mfma", "achieved": ws["algorithmic_tflops_per_gpu"],
-                               "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ws["frac_of_f32_mfma_peak"], "traffic": None}
-            out["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(out), flush=True)
     parallel.barrier()
@@ -805,20 +807,30 @@ def worker(a):
         dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=["c2", "c3", "c4", "c5"], default="c4",
-                    help="c4 (default, the driver's line): 2-D U-Net 64x64x3 global batch 256 (+ C5 sampling leg, kernel "
-                         "rooflines, C2/C3 extras, CPU baseline); c2 / c3 / c5: the other BASELINE.json configs as the main line")
+                    help="c4 (default, the driver's line): 2-D U-Net 64x64x3 global batch 256 (with --full: + C5 sampling "
+                         "leg, kernel rooflines, C2/C3 extras, CPU baseline); c2 / c3 / c5: the other BASELINE.json configs "
+                         "as the main line")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--sample-steps", type=int, default=20, help="EM steps of the C5 leg (0 = skip it)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C2 / C3 extra legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the main line (sampling legs, per-kernel rooflines, extras, CPU "
+                         "baseline); a plain run sets up, warms up, times the steps, dumps and prints the line only")
+    ap.add_argument("--sample-steps", type=int, default=20,
+                    help="EM steps of the C5 leg (c4 with --full; 0 = skip it) or of the c5 main line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the bf16-split sampling experiment and the C2 / C3 / MSGM extra legs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the main line's last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all)")
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    a = parse_args()
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus > 1 and env_world == 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(a))              # before ANY GPU call in this process

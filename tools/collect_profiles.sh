@@ -7,7 +7,7 @@ out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 echo "[prof] bench under --stats" >> $out/log.txt
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_under_rocprof.json 2>> $out/log.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_under_rocprof.json 2>> $out/log.txt
 export TRAIN_ONLY=1
 for B in 32 256; do
   echo "[prof] train-only stats B=$B" >> $out/log.txt
