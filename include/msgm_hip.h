@@ -359,13 +359,16 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
  * tap t of that block is a real weight (0 = all); blocks that are structurally zero are not computed (the tile
  * kernels only; their dWp entries receive zeros).  The masks serve the 3-tap 1-D convolutions; with masks, a 1x1 gradient
  * on the pixel-streaming kernel or a 2-D 3x3 one with channel counts that are multiples of 4 returns MSGM_E_UNSUPPORTED.
- * Workspace bytes from msgm_conv_wgrad_workspace (n_bias = 0 when dbias is NULL); ~37 MB per call at the C4 shapes, i.e.
- * ~20 us of HBM time. */
-size_t msgm_conv_wgrad_workspace(const msgm_conv_geom_t* geom, int32_t C, int32_t Cout, int32_t CoutP, int32_t n_bias);
+ * Workspace bytes from msgm_conv_wgrad_workspace (n_bias = 0 when dbias is NULL, same wino as the call); ~37 MB per call
+ * at the C4 shapes, i.e. ~20 us of HBM time.
+ * wino = 1: a 2-D 3x3 stride-1 "same" gradient with channel counts that are multiples of 4 runs Winograd F(3x3, 2x2)
+ * (k_wgrad_wino, 2.25x fewer MFMAs than the direct k_wgrad_tile9, same slabs and reduction); any other shape, or tap
+ * masks, return MSGM_E_UNSUPPORTED without launching anything, and the caller repeats the call with wino = 0. */
+size_t msgm_conv_wgrad_workspace(const msgm_conv_geom_t* geom, int32_t C, int32_t Cout, int32_t CoutP, int32_t n_bias, int32_t wino);
 int msgm_conv_wgrad_det(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                         float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
                         const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, void* workspace, size_t workspace_bytes,
-                        msgm_stream_t stream);
+                        int32_t wino, msgm_stream_t stream);
 
 /* Deferred form of msgm_conv_wgrad_det: launches the producing kernel(s) only and describes the slot reduction(s) it would
  * have launched in jobs_out[0 .. *n_jobs_out) (host memory, room for 2) — the workspace must stay untouched until the
@@ -382,7 +385,7 @@ typedef struct {
 int msgm_conv_wgrad_slabs(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                           float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
                           const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, void* workspace, size_t workspace_bytes,
-                          msgm_reduce_job_t* jobs_out, int32_t* n_jobs_out, msgm_stream_t stream);
+                          msgm_reduce_job_t* jobs_out, int32_t* n_jobs_out, int32_t wino, msgm_stream_t stream);
 int msgm_slot_reduce_batched(const msgm_reduce_job_t* jobs_dev, int32_t n_jobs, int64_t total_blocks, msgm_stream_t stream);
 
 /* Wp[t][r][kp_off + c] = W[r*sr + (col_off + c)*sc + t*st] for r < rows, c < ncols

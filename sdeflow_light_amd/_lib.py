@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmsgm_hip.so")
 
 MSGM_OK = 0
+MSGM_E_UNSUPPORTED = -2
 SDE_SGM, SDE_MSGM_SPARSE, SDE_MSGM_DENSE = 0, 1, 2
 PROC_REVERSE, PROC_FORWARD = 0, 1
 RNG_STREAM_T, RNG_STREAM_EPS, RNG_STREAM_V, RNG_STREAM_DW, RNG_STREAM_ROWS, RNG_STREAM_USER = 0, 1, 2, 3, 4, 16
@@ -111,13 +112,13 @@ SIGNATURES = {
     "msgm_groupnorm_affine": (C.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _F, _P, C.c_size_t, _P]),
     "msgm_conv_chanstats_slots": (C.c_int32, [C.POINTER(ConvGeomT), _I32, _I32, _I32, _I32]),
     "msgm_conv_wgrad_slabs": (C.c_int, [C.POINTER(ConvGeomT), _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _SZ,
-                                        C.POINTER(ReduceJobT), C.POINTER(C.c_int32), _P]),
+                                        C.POINTER(ReduceJobT), C.POINTER(C.c_int32), _I32, _P]),
     "msgm_slot_reduce_batched": (C.c_int, [_P, _I32, _I64, _P]),
     "msgm_conv_small_cout_supported": (C.c_int, [C.POINTER(ConvGeomT), _I32, _I32, _I32]),
     "msgm_groupnorm_affine_chanstats": (C.c_int, [_P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _F, _P]),
-    "msgm_conv_wgrad_workspace": (_SZ, [C.POINTER(ConvGeomT), _I32, _I32, _I32, _I32]),
+    "msgm_conv_wgrad_workspace": (_SZ, [C.POINTER(ConvGeomT), _I32, _I32, _I32, _I32, _I32]),
     "msgm_conv_wgrad_det": (C.c_int, [C.POINTER(ConvGeomT), _P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _I32,
-                                      C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _P, _SZ, _P]),
+                                      C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _P, _SZ, _I32, _P]),
     "msgm_colsum_workspace": (_SZ, [_I32, _I32, _I32]),
     "msgm_colsum_det": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _SZ, _P]),
     "msgm_pack_weight": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I64, _I64, _I64, _I32, _I32, _I32, _P]),

@@ -340,9 +340,11 @@ class ConvOp:
         self._bias_zeroed = False
         if fuse_bias and not bias_grad_zeroed:
             self.bias.grad.zero_()
+        # Winograd weight gradient (k_wgrad_wino) where the forward / dgrad of this conv take Winograd too
+        wg = bool(self.train_wino and ops.conv_wino_supported(geom, self.srcC[0], self.srcC[1] if len(self.srcC) > 1 else 0, self.CoutP))
         for s, C in enumerate(self.srcC):
             ops.conv_wgrad(geom, gy, srcs[s], C, self.koff[s], self.dWp, self.Cout, self.CoutP, self.Ktot,
-                           dbias=self.bias.grad.view(-1) if (fuse_bias and s == 0) else None, n_bias=n_bias)
+                           dbias=self.bias.grad.view(-1) if (fuse_bias and s == 0) else None, n_bias=n_bias, wino=wg)
         S = None
         er = n_bias if emb_rows is None else emb_rows
         if fuse_bias:
@@ -399,7 +401,8 @@ class ConvOp:
         if self.bias is not None and not bias_grad_zeroed:
             self.bias.grad.zero_()
         ops.conv_wgrad(geom, gy, src, C, 0, self.dWp, self.Cout, self.CoutP, self.Ktot,
-                       dbias=self.bias.grad.view(-1) if self.bias is not None else None, n_bias=n_bias)
+                       dbias=self.bias.grad.view(-1) if self.bias is not None else None, n_bias=n_bias,
+                       wino=bool(self.train_wino and ops.conv_wino_supported(geom, C, 0, self.CoutP)))
         gd = ops.conv_geom(N, Ho, Wo, 2 * Hi, 2 * Wi, self.KH, self.KW, self.stride, self.pad, 1 - self.mode, 0)
         gup = torch.empty(N * 4 * Hi * Wi * C, device=dev)
         g0 = ops.conv_geom(N, Ho, Wo, 2 * Hi, 2 * Wi, self.KH, self.KW, 1, 1, 0, 0) if (self.train_wino and self.WdW[0] is not None) else None

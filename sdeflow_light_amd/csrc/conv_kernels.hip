@@ -2141,6 +2141,215 @@ __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x
     }
 }
 
+// ------------------------------------------------------------------ wgrad of 3x3 "same" convolutions, Winograd F(3x3, 2x2)
+// The weight gradient of a 3x3 conv is itself a correlation: dW[kh][kw] = sum_pixels gy[oh][ow] x[oh+kh-1][ow+kw-1], i.e. per
+// 2x2 block of gy at (2i, 2j) with its 4x4 input patch d (rows 2i-1 .., cols 2j-1 ..) a 3x3 output of a 2x2 "filter" g:
+//   dW = A^T [ sum_blocks (G g G^T) .* (B^T d B) ] A,   A^T = [[1,1,1,0],[0,1,-1,0],[0,1,1,1]],  G = [[1,0],[1/2,1/2],[1/2,-1/2],[0,1]],
+//   B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,-1,0,1]]            (exact in fp32: every factor is 0, +-1 or +-1/2)
+// so the sum over blocks is 16 independent (co x c) products — one MFMA accumulator per position xi — where the direct form
+// (k_wgrad_tile9) has 9 taps x 4 pixels = 36: 2.25x fewer MFMAs.  Same staging, tiles and slab / bias outputs as
+// k_wgrad_tile9: a workgroup owns a 32 co x 32 c block, walks 8 x 16-pixel tiles (32 Winograd blocks, the 10 x 18 halo), and
+// wave (m, kt) owns the 16 x 16 output tile (m, kt) at all 16 positions (64 accumulator registers); k-step s takes four
+// blocks, one per lane group q (the MFMA's reduction index): block row s >> 1, column 4 (s & 1) + q.  Lane (il, q) transforms
+// the gy block of channel 16 m + il (A operand) and the input patch of channel 16 kt + il (B operand) itself — ~50 VALU per
+// 16 MFMAs, hidden under the other waves' MFMAs — and the 16 sums of one (co, c) element end in ONE lane, so A^T M A runs
+// in registers.  Input rows pitch WW_IP = 188 = -4 (mod 64): the b64 patch reads of a half-wave (16 channels x 2 blocks
+// 2 floats apart) fall on 32 distinct bank pairs.  ~200 VGPRs (at the 168 of three workgroups per CU the compiler spills
+// 44-176 bytes), so two workgroups per CU (WW_LB) and a double-buffered LDS staging area (2 x 40 KB, one barrier per tile):
+// C4 3x3 wgrad family 17.7 -> 13.2 ms per step (tools/bench_wgrad3x3.py; single buffer 13.4, three workgroups 14.3).
+#define WW_IP 188
+#ifndef WW_LB
+#define WW_LB 2
+#endif
+#ifndef WW_DBUF
+#define WW_DBUF 1
+#endif
+__global__ void __launch_bounds__(256, WW_LB) k_wgrad_wino(WgradArgs A, int tiles_x, int tiles_y, int tiles_per_wg, int n_tiles) {
+  extern __shared__ __attribute__((aligned(16))) float wt_lds[];
+  constexpr int TH = 8, TW = 16, HW = TW + 2, halo = (TH + 2) * HW, IP = WW_IP;
+  static_assert(IP >= halo && IP % 2 == 0, "input row pitch");
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
+  const int m = w >> 1, kt = w & 1;                         // this wave's 16 x 16 output tile of every position
+  const ConvGeom g = A.g;
+  constexpr int BUF = 32 * WT_GP + 32 * IP;                 // one staging buffer: gy^T [32][WT_GP] | input^T [32][IP]
+  const int cblocks = (A.C + 31) / 32;
+  const int coblk = blockIdx.y / cblocks, cblk = blockIdx.y - coblk * cblocks;
+  const int co0 = coblk * 32, c0 = cblk * 32;
+  const int t_beg = blockIdx.x * tiles_per_wg, t_end = min(t_beg + tiles_per_wg, n_tiles);
+  if (t_beg >= t_end) return;
+  f32x4 acc[16];
+#pragma unroll
+  for (int x = 0; x < 16; ++x) acc[x] = f32x4{0, 0, 0, 0};
+  constexpr int MAXIN = (halo * 8 + 255) / 256;
+  f32x4 sg[4], si[MAXIN];
+  const int up = g.ups ? 1 : 0;
+  constexpr int n_in = halo * 8;
+  auto stage_load = [&](int tile) {
+    int bx = tile;
+    const int tx_i = bx % tiles_x; bx /= tiles_x;
+    const int ty_i = bx % tiles_y;
+    const int n = bx / tiles_y;
+    const int y0 = ty_i * TH, x0 = tx_i * TW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int idx = tid + 256 * k;
+      const int p = idx >> 3, c4 = idx & 7;
+      const int py = p / TW, px = p - py * TW;
+      const int oy = y0 + py, ox = x0 + px, co = co0 + 4 * c4;
+      f32x4 v = {0, 0, 0, 0};
+      if (oy < g.Ho && ox < g.Wo && co < A.Cout)
+        v = *reinterpret_cast<const f32x4*>(A.gy + (((size_t)n * g.Ho + oy) * g.Wo + ox) * A.Cout + co);
+      sg[k] = v;
+    }
+#pragma unroll
+    for (int k = 0; k < MAXIN; ++k) {
+      const int idx = tid + 256 * k;
+      f32x4 v = {0, 0, 0, 0};
+      if (idx < n_in) {
+        const int hp = idx >> 3, c4 = idx & 7;
+        const int hy = hp / HW, hx = hp - hy * HW;
+        const int iy = y0 + hy - g.padH, ix = x0 + hx - g.padW, c = c0 + 4 * c4;
+        if (iy >= 0 && iy < (g.Hi << up) && ix >= 0 && ix < (g.Wi << up) && c < A.C)
+          v = *reinterpret_cast<const f32x4*>(A.src + (((size_t)n * g.Hi + (iy >> up)) * g.Wi + (ix >> up)) * A.C + c);
+      }
+      si[k] = v;
+    }
+  };
+  auto stage_store = [&](int b) {
+    float* gT = wt_lds + b * BUF;
+    float* iT = gT + 32 * WT_GP;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int idx = tid + 256 * k;
+      const int p = idx >> 3, c4 = idx & 7;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) gT[(4 * c4 + r) * WT_GP + (p ^ WT_SWZ(4 * c4))] = sg[k][r];
+    }
+#pragma unroll
+    for (int k = 0; k < MAXIN; ++k) {
+      const int idx = tid + 256 * k;
+      if (idx < n_in) {
+        const int hp = idx >> 3, c4 = idx & 7;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) iT[(4 * c4 + r) * IP + hp] = si[k][r];
+      }
+    }
+  };
+  const bool do_bias = A.dbias != nullptr && cblk == 0;
+  const int tiles_per_sample = tiles_x * tiles_y;
+  float bsum = 0.f;                                        // thread (co = tid>>3, 16-pixel part = tid&7)
+  stage_load(t_beg);
+  stage_store(0);
+  __syncthreads();
+  const int gsw = WT_SWZ(16 * m + il);
+  int cur = 0;
+  for (int tile = t_beg; tile < t_end; ++tile) {
+    const bool more = tile + 1 < t_end;
+    if (more) stage_load(tile + 1);
+    const float* gT = wt_lds + cur * BUF;
+    const float* ga = gT + (16 * m + il) * WT_GP;          // + (pixel ^ swizzle of this lane's channel)
+    const float* ib = gT + 32 * WT_GP + (16 * kt + il) * IP;
+    if (do_bias && tile / tiles_per_sample < A.n_bias) {   // as k_wgrad_tile9: same bits
+      const float* gr = gT + (tid >> 3) * WT_GP + 16 * (tid & 7);
+      f32x4 t4 = *reinterpret_cast<const f32x4*>(gr);
+      t4 += *reinterpret_cast<const f32x4*>(gr + 4);
+      t4 += *reinterpret_cast<const f32x4*>(gr + 8);
+      t4 += *reinterpret_cast<const f32x4*>(gr + 12);
+      bsum += (t4[0] + t4[1]) + (t4[2] + t4[3]);
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int bi = s >> 1, bj = 4 * (s & 1) + q;          // this lane's 2 x 2 block of the 8 x 16 tile
+      // U = G g G^T of the gy block (pixel pairs stay contiguous under the swizzle: it XORs bits 2..4 of the pixel)
+      const int p0 = 2 * bi * TW + 2 * bj;
+      const f32x2 g0 = *reinterpret_cast<const f32x2*>(ga + (p0 ^ gsw));
+      const f32x2 g1 = *reinterpret_cast<const f32x2*>(ga + ((p0 + TW) ^ gsw));
+      float gr[4][2];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        gr[0][b] = g0[b];
+        gr[1][b] = 0.5f * (g0[b] + g1[b]);
+        gr[2][b] = 0.5f * (g0[b] - g1[b]);
+        gr[3][b] = g1[b];
+      }
+      float U[16];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        U[4 * i + 0] = gr[i][0];
+        U[4 * i + 1] = 0.5f * (gr[i][0] + gr[i][1]);
+        U[4 * i + 2] = 0.5f * (gr[i][0] - gr[i][1]);
+        U[4 * i + 3] = gr[i][1];
+      }
+      // V = B^T d B of the 4 x 4 input patch (halo rows 2 bi .. 2 bi + 3, columns 2 bj .. 2 bj + 3)
+      float d[4][4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const float* rp = ib + (2 * bi + a) * HW + 2 * bj;
+        const f32x2 lo = *reinterpret_cast<const f32x2*>(rp), hi = *reinterpret_cast<const f32x2*>(rp + 2);
+        d[a][0] = lo[0]; d[a][1] = lo[1]; d[a][2] = hi[0]; d[a][3] = hi[1];
+      }
+      float t[4][4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        t[0][b] = d[0][b] - d[2][b];
+        t[1][b] = d[1][b] + d[2][b];
+        t[2][b] = d[2][b] - d[1][b];
+        t[3][b] = d[3][b] - d[1][b];
+      }
+      float V[16];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        V[4 * i + 0] = t[i][0] - t[i][2];
+        V[4 * i + 1] = t[i][1] + t[i][2];
+        V[4 * i + 2] = t[i][2] - t[i][1];
+        V[4 * i + 3] = t[i][3] - t[i][1];
+      }
+#pragma unroll
+      for (int x = 0; x < 16; ++x) acc[x] = mfma16c(U[x], V[x], acc[x]);
+    }
+    if (WW_DBUF) {                                          // two buffers: the next tile goes into the other one, one barrier
+      if (more) stage_store(cur ^ 1);
+      __syncthreads();
+      cur ^= 1;
+    } else {
+      __syncthreads();                                      // every wave is done reading the buffer
+      if (more) { stage_store(0); __syncthreads(); }
+    }
+  }
+  if (do_bias) {
+    bsum += __shfl_xor(bsum, 1, 64);
+    bsum += __shfl_xor(bsum, 2, 64);
+    bsum += __shfl_xor(bsum, 4, 64);
+    const int co = co0 + (tid >> 3);
+    if ((tid & 7) == 0 && co < A.Cout) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)9 * A.CoutP * A.C + co] = bsum;
+  }
+  // dW = A^T M A per (co, c) element, all in this lane's registers
+  const int c = c0 + 16 * kt + il;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float R[3][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float s12 = acc[4 + j][r] + acc[8 + j][r];
+      R[0][j] = acc[j][r] + s12;
+      R[1][j] = acc[4 + j][r] - acc[8 + j][r];
+      R[2][j] = s12 + acc[12 + j][r];
+    }
+    const int co = co0 + 16 * m + 4 * q + r;
+    if (co < A.Cout && c < A.C) {
+      float* sp = A.slab + (size_t)blockIdx.x * A.slab_stride + (size_t)co * A.C + c;
+      const size_t tap = (size_t)A.CoutP * A.C;
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh) {
+        const float s12 = R[kh][1] + R[kh][2];
+        sp[(3 * kh + 0) * tap] = R[kh][0] + s12;
+        sp[(3 * kh + 1) * tap] = R[kh][1] - R[kh][2];
+        sp[(3 * kh + 2) * tap] = s12 + R[kh][3];
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ wgrad of 1x1 convolutions: pixel-streaming kernel
 // dW[co][c] = sum_p gy[p][co] x[p][c] with the pixel as the reduction index: 2 Cout C / (4 (Cout + C)) = 8..48 FLOPs per
 // byte, i.e. HBM-bound below ~128 x 128 channels and MFMA-bound above.  k_wgrad_tile<., ., 1> splits dW into 32 x 32
@@ -2903,7 +3112,7 @@ int msgm_conv_forward_fused(const msgm_conv_geom_t* geom, const float* src0, int
 
 // launch geometry shared by the launcher and the workspace query
 struct WgradPlan { bool tile; int wgs, per, tiles_x, tiles_y, n_tiles, yblocks; int64_t nchunks, chunk; int64_t bias_slots, bias_chunk;
-                   bool one; int mt, nt, wm, px; int64_t n_tiles1; };
+                   bool one; int mt, nt, wm, px; int64_t n_tiles1; bool wino; };
 // The pixel-streaming 1x1 wgrad (k_wgrad1x1): instance (MT, NT, WM) for (Cout, C), or mt = 0
 static void wgrad1x1_shape(int C, int Cout, int* mt, int* nt, int* wm) {
   *mt = 0; *nt = 0; *wm = 4;
@@ -2914,7 +3123,9 @@ static void wgrad1x1_shape(int C, int Cout, int* mt, int* nt, int* wm) {
   if (C == 256) { *mt = 1; return; }
   *mt = Cout % 192 == 0 ? 3 : (Cout % 128 == 0 ? 2 : 1);
 }
-static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n_bias) {
+// wino: the caller asks for k_wgrad_wino; the plan takes it when the shape is one k_wgrad_tile9 would serve (2-D 3x3 "same",
+// stride 1, channel counts that are multiples of 4) and says so in p.wino
+static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n_bias, bool wino) {
   WgradPlan p{};
   const int64_t Mtot = (int64_t)geom->N * geom->Ho * geom->Wo;
   const int taps = geom->KH * geom->KW;
@@ -2949,7 +3160,9 @@ static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n
     p.tiles_x = (geom->Wo + TW - 1) / TW; p.tiles_y = (geom->Ho + TH - 1) / TH;
     p.n_tiles = p.tiles_x * p.tiles_y * geom->N;
     p.yblocks = ((Cout + 31) / 32) * ((C + 31) / 32);
-    constexpr int wg_target = 768;                         // = 3 resident workgroups per CU (k_wgrad_tile9 and the 1- / 3-tap forms); r3 measured 768 / 1024 / 1536 / 3072: 124.0 / 126.4 / 124.7 / 124.9 ms per C4 step (r2, two workgroups per CU: 1024 was best)
+    p.wino = wino && two_d && taps == 9 && aligned;
+    // k_wgrad_wino: WW_LB resident workgroups per CU (registers), so one full round of them on the 256 CUs; the others:
+    const int wg_target = p.wino ? 256 * WW_LB : 768;                         // = 3 resident workgroups per CU (k_wgrad_tile9 and the 1- / 3-tap forms); r3 measured 768 / 1024 / 1536 / 3072: 124.0 / 126.4 / 124.7 / 124.9 ms per C4 step (r2, two workgroups per CU: 1024 was best)
     int wgs = wg_target / p.yblocks;                       // ~4 workgroups per CU overall
     if (wgs < 1) wgs = 1;
     int per = (p.n_tiles + wgs - 1) / wgs;
@@ -2984,11 +3197,11 @@ static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n
 static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                       float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
                       const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, float* ws, size_t ws_bytes,
-                      msgm_stream_t stream, msgm_reduce_job_t* jobs_out = nullptr, int32_t* n_jobs_out = nullptr);
+                      int32_t wino, msgm_stream_t stream, msgm_reduce_job_t* jobs_out = nullptr, int32_t* n_jobs_out = nullptr);
 
-size_t msgm_conv_wgrad_workspace(const msgm_conv_geom_t* geom, int32_t C, int32_t Cout, int32_t CoutP, int32_t n_bias) {
+size_t msgm_conv_wgrad_workspace(const msgm_conv_geom_t* geom, int32_t C, int32_t Cout, int32_t CoutP, int32_t n_bias, int32_t wino) {
   if (check_geom(geom) || C <= 0 || Cout <= 0 || CoutP < Cout) return 0;
-  const WgradPlan p = wgrad_plan(geom, C, Cout, n_bias);
+  const WgradPlan p = wgrad_plan(geom, C, Cout, n_bias, wino != 0);
   const size_t stride = (size_t)geom->KH * geom->KW * CoutP * C + CoutP;
   const size_t slots = (p.tile || p.one) ? (size_t)p.wgs : (size_t)p.nchunks;
   return (slots * stride + (size_t)p.bias_slots * Cout) * sizeof(float);
@@ -2997,20 +3210,20 @@ size_t msgm_conv_wgrad_workspace(const msgm_conv_geom_t* geom, int32_t C, int32_
 int msgm_conv_wgrad_det(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                         float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
                         const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, void* workspace, size_t workspace_bytes,
-                        msgm_stream_t stream) {
+                        int32_t wino, msgm_stream_t stream) {
   if (!workspace) return MSGM_E_BADARG;
   return wgrad_impl(geom, gy, src, C, koff, dWp, Cout, CoutP, Ktot, dbias, n_bias, tapmask_c32, tapmask_co32,
-                    static_cast<float*>(workspace), workspace_bytes, stream);
+                    static_cast<float*>(workspace), workspace_bytes, wino, stream);
 }
 
 int msgm_conv_wgrad_slabs(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                           float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
                           const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, void* workspace, size_t workspace_bytes,
-                          msgm_reduce_job_t* jobs_out, int32_t* n_jobs_out, msgm_stream_t stream) {
+                          msgm_reduce_job_t* jobs_out, int32_t* n_jobs_out, int32_t wino, msgm_stream_t stream) {
   if (!workspace || !jobs_out || !n_jobs_out) return MSGM_E_BADARG;
   *n_jobs_out = 0;
   return wgrad_impl(geom, gy, src, C, koff, dWp, Cout, CoutP, Ktot, dbias, n_bias, tapmask_c32, tapmask_co32,
-                    static_cast<float*>(workspace), workspace_bytes, stream, jobs_out, n_jobs_out);
+                    static_cast<float*>(workspace), workspace_bytes, wino, stream, jobs_out, n_jobs_out);
 }
 
 int msgm_slot_reduce_batched(const msgm_reduce_job_t* jobs_dev, int32_t n_jobs, int64_t total_blocks, msgm_stream_t stream) {
@@ -3022,19 +3235,20 @@ int msgm_slot_reduce_batched(const msgm_reduce_job_t* jobs_dev, int32_t n_jobs, 
 static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                       float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,
                       const uint16_t* tapmask_c32, const uint16_t* tapmask_co32, float* ws, size_t ws_bytes,
-                      msgm_stream_t stream, msgm_reduce_job_t* jobs_out, int32_t* n_jobs_out) {
+                      int32_t wino, msgm_stream_t stream, msgm_reduce_job_t* jobs_out, int32_t* n_jobs_out) {
   int rc = check_geom(geom);
   if (rc) return rc;
   if (!gy || !src || !dWp || C <= 0 || Cout <= 0 || koff < 0 || koff + C > Ktot || (dbias && n_bias <= 0)) return MSGM_E_BADARG;
-  if (ws_bytes < msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, dbias ? n_bias : 0)) return MSGM_E_WORKSPACE;
+  if (ws_bytes < msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, dbias ? n_bias : 0, wino)) return MSGM_E_WORKSPACE;
   const long img = (long)geom->KH * geom->KW * CoutP * C;
   WgradArgs A{to_geom(geom), gy, src, C, koff, dWp, Cout, CoutP, Ktot, 0, dbias, n_bias, {0}, {0}, ws, img + CoutP};
-  const WgradPlan pl = wgrad_plan(geom, C, Cout, dbias ? n_bias : 0);
+  const WgradPlan pl = wgrad_plan(geom, C, Cout, dbias ? n_bias : 0, wino != 0);
   for (int i = 0; i < 16; ++i) {
     A.tm_c[i] = (tapmask_c32 && i < (C + 31) / 32) ? tapmask_c32[i] : 0;
     A.tm_o[i] = (tapmask_co32 && i < (Cout + 31) / 32) ? tapmask_co32[i] : 0;
   }
   const int taps = geom->KH * geom->KW;
+  if (wino && (!pl.wino || tapmask_c32 || tapmask_co32)) return MSGM_E_UNSUPPORTED;   // the caller falls back to wino = 0
   auto reduce_slabs = [&](int nslots, bool with_bias) {     // slabs -> dWp (+ dbias), slot order
     if (jobs_out) {                                          // deferred: the caller batches the reductions of a whole pass
       msgm_reduce_job_t& J = jobs_out[(*n_jobs_out)++];
@@ -3109,7 +3323,15 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
       if (taps == 9) {
         if (rag) WT_LAUNCH2(8, 16, 9, true);
         else if (tapmask_c32 || tapmask_co32) return MSGM_E_UNSUPPORTED;   // k_wgrad_tile9 has no tap masks (they come from 3-tap 1-D convs)
-        else {
+        else if (pl.wino) {
+          const size_t ldsw = (size_t)(WW_DBUF ? 2 : 1) * (32 * WT_GP + 32 * WW_IP) * sizeof(float);
+          static const int once = [] {                      // more than 64 KB of dynamic LDS is opted into per kernel
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_wino), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            return 0;
+          }();
+          (void)once;
+          hipLaunchKernelGGL(k_wgrad_wino, grid, dim3(256), ldsw, S(stream), A, tiles_x, tiles_y, per, n_tiles);
+        } else {
           const size_t lds9 = (size_t)(32 * WT_GP + 32 * IP) * sizeof(float);
           hipLaunchKernelGGL(k_wgrad_tile9, grid, dim3(256), lds9, S(stream), A, tiles_x, tiles_y, per, n_tiles);
         }

@@ -418,8 +418,10 @@ def conv_wino_supported(geom: L.ConvGeomT, C0: int, C1: int, CoutP: int) -> bool
 
 def conv_wgrad(geom: L.ConvGeomT, gy: torch.Tensor, src: torch.Tensor, C: int, koff: int, dWp: torch.Tensor, Cout: int,
                CoutP: int, Ktot: int, dbias: Optional[torch.Tensor] = None, n_bias: int = 0, tapmask_c32=None,
-               tapmask_co32=None):
-    """dbias (Cout floats, ACCUMULATED into): bias gradient over the primal rows n < n_bias, as a by-product."""
+               tapmask_co32=None, wino: bool = False):
+    """dbias (Cout floats, ACCUMULATED into): bias gradient over the primal rows n < n_bias, as a by-product.
+    wino: a 2-D 3x3 stride-1 "same" gradient runs Winograd F(3x3, 2x2) (k_wgrad_wino); shapes the native side refuses
+    (MSGM_E_UNSUPPORTED) take the direct kernel, as they do with wino=False."""
     taps = geom.KH * geom.KW
     if dbias is not None and (dbias.numel() != Cout or n_bias <= 0 or n_bias > geom.N):
         raise MsgmError("wgrad: bad bias-gradient arguments")
@@ -433,21 +435,29 @@ def conv_wgrad(geom: L.ConvGeomT, gy: torch.Tensor, src: torch.Tensor, C: int, k
     if (mc is not None and len(mc) < (C + 31) // 32) or (mo is not None and len(mo) < (Cout + 31) // 32):
         raise MsgmError("wgrad: tap masks need one entry per 32-channel block")
     # per-workgroup slabs added in slot order (no float atomics; same bits every run)
-    need = int(lib().msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, int(n_bias) if dbias is not None else 0))
+    nb = int(n_bias) if dbias is not None else 0
+    need = max(int(lib().msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, nb, w)) for w in ((1, 0) if wino else (0,)))
     d = DeferredReduces.active
     if d is not None and d.device == gy.device:
         # inside a backward pass that batches its slot reductions: slabs go to the pass's arena, the reduction is described
         # to the pass and runs with all the others in one launch (DeferredReduces.flush)
         ws, nbytes = d.take(need)
         jobs, nj = (L.ReduceJobT * 2)(), C_.c_int32(0)
-        check(lib().msgm_conv_wgrad_slabs(geom, ptr(f32(gy)), ptr(f32(src)), C, koff, ptr(f32(dWp)), Cout, CoutP, Ktot,
-                                          ptr(dbias), int(n_bias), mc, mo, ws, nbytes, jobs, C_.byref(nj), stream()),
-              "msgm_conv_wgrad_slabs")
+        args = (geom, ptr(f32(gy)), ptr(f32(src)), C, koff, ptr(f32(dWp)), Cout, CoutP, Ktot, ptr(dbias), int(n_bias), mc, mo,
+                ws, nbytes, jobs, C_.byref(nj))
+        rc = lib().msgm_conv_wgrad_slabs(*args, 1, stream()) if wino else L.MSGM_E_UNSUPPORTED
+        if rc == L.MSGM_E_UNSUPPORTED:
+            rc = lib().msgm_conv_wgrad_slabs(*args, 0, stream())
+        check(rc, "msgm_conv_wgrad_slabs")
         d.add(jobs, nj.value, (dWp, dbias))
         return
     ws = scratch(gy.device, need, "wgrad")
-    check(lib().msgm_conv_wgrad_det(geom, ptr(f32(gy)), ptr(f32(src)), C, koff, ptr(f32(dWp)), Cout, CoutP, Ktot,
-                                    ptr(dbias), int(n_bias), mc, mo, ptr(ws), ws.numel() * 4, stream()), "msgm_conv_wgrad_det")
+    args = (geom, ptr(f32(gy)), ptr(f32(src)), C, koff, ptr(f32(dWp)), Cout, CoutP, Ktot, ptr(dbias), int(n_bias), mc, mo,
+            ptr(ws), ws.numel() * 4)
+    rc = lib().msgm_conv_wgrad_det(*args, 1, stream()) if wino else L.MSGM_E_UNSUPPORTED
+    if rc == L.MSGM_E_UNSUPPORTED:
+        rc = lib().msgm_conv_wgrad_det(*args, 0, stream())
+    check(rc, "msgm_conv_wgrad_det")
 
 
 class DeferredReduces:
