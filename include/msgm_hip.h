@@ -302,8 +302,9 @@ int msgm_conv_forward(const msgm_conv_geom_t* geom, const float* src0, int32_t C
  *    187,232) — saves one read-modify-write pass over the output;
  *  - in_scale / in_shift [N][C0+C1] (+ in_act = 1: SiLU): the convolution reads act(a x + b) instead of x, i.e.
  *    GroupNorm(+SiLU) (model/unet.py:140-143,152-155,214) is applied while the input tile is staged and the
- *    normalised tensor is never written.  Only the halo-tile kernel (stride-1 "same" shapes) can do this:
- *    msgm_conv_input_transform_supported() tells; otherwise the call returns MSGM_E_UNSUPPORTED.
+ *    normalised tensor is never written.  Only the halo-tile kernel (stride-1 "same" shapes) and the vector-ALU kernel
+ *    of the U-Net's output convolution (3x3 "same", 32 input channels, <= 4 output channels; model/unet.py:442-446) can
+ *    do this: msgm_conv_input_transform_supported() tells; otherwise the call returns MSGM_E_UNSUPPORTED.
  * fuse may be NULL (= msgm_conv_forward). */
 typedef struct {
   const float* residual;
@@ -324,12 +325,8 @@ typedef struct {
    * (scale, shift) a consuming convolution applies — the separate statistics pass over the tensor disappears. */
   float* chanstats;
 } msgm_conv_fuse_t;
-int msgm_conv_input_transform_supported(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t CoutP);
+int msgm_conv_input_transform_supported(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t Cout, int32_t CoutP);
 int32_t msgm_conv_chanstats_slots(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t Cout, int32_t CoutP);
-/* 1 if this forward convolution is the U-Net's output convolution shape (3x3 "same", 32 input channels, <= 4 output
- * channels; model/unet.py:442-446) that the vector-ALU kernel serves — it also accepts the in_scale / in_shift input
- * transform, although msgm_conv_input_transform_supported() (which does not see Cout) says no for CoutP = 16. */
-int msgm_conv_small_cout_supported(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t Cout);
 int msgm_conv_forward_fused(const msgm_conv_geom_t* geom, const float* src0, int32_t C0, const float* src1, int32_t C1,
                             const float* Wp, int32_t Cout, int32_t CoutP, int32_t Ktot, const float* bias,
                             const float* samp_bias, int32_t n_bias, int32_t n_samp, float* out, int32_t accumulate,
@@ -361,9 +358,10 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
  * on the pixel-streaming kernel or a 2-D 3x3 one with channel counts that are multiples of 4 returns MSGM_E_UNSUPPORTED.
  * Workspace bytes from msgm_conv_wgrad_workspace (n_bias = 0 when dbias is NULL, same wino as the call); ~37 MB per call
  * at the C4 shapes, i.e. ~20 us of HBM time.
- * wino = 1: a 2-D 3x3 stride-1 "same" gradient with channel counts that are multiples of 4 runs Winograd F(3x3, 2x2)
- * (k_wgrad_wino, 2.25x fewer MFMAs than the direct k_wgrad_tile9, same slabs and reduction); any other shape, or tap
- * masks, return MSGM_E_UNSUPPORTED without launching anything, and the caller repeats the call with wino = 0. */
+ * wino = 1 (a preference): a 2-D 3x3 stride-1 "same" gradient with channel counts that are multiples of 4 runs Winograd
+ * F(3x3, 2x2) (k_wgrad_wino, 2.25x fewer MFMAs than the direct k_wgrad_tile9, same slabs and reduction); any other shape
+ * runs exactly what wino = 0 runs, with the same workspace.  Tap masks on such a gradient return MSGM_E_UNSUPPORTED, as
+ * with wino = 0. */
 size_t msgm_conv_wgrad_workspace(const msgm_conv_geom_t* geom, int32_t C, int32_t Cout, int32_t CoutP, int32_t n_bias, int32_t wino);
 int msgm_conv_wgrad_det(const msgm_conv_geom_t* geom, const float* gy, const float* src, int32_t C, int32_t koff,
                         float* dWp, int32_t Cout, int32_t CoutP, int32_t Ktot, float* dbias, int32_t n_bias,

@@ -264,11 +264,38 @@ class ConvOp:
         Ho, Wo = self.out_hw(Hi, Wi)
         return ops.conv_geom(N, Hi, Wi, Ho, Wo, self.KH, self.KW, self.stride, self.pad, self.mode, int(self.ups)), Ho, Wo
 
+    def _C1(self) -> int:
+        return self.srcC[1] if len(self.srcC) > 1 else 0
+
+    def _forward_image(self, geom, wino: bool, b6: bool):
+        """(weight image, wino, b6) of the kernel that serves this forward: the bf16-split image when asked for (b6, or
+        wino with ConvOpSet.pack_b6) and the geometry allows it, else the Winograd image when asked for (wino, or
+        train_wino) and allowed, else the direct image."""
+        if (b6 or (wino and self.use_b6)) and self.Wb is not None and ops.conv_b6_supported(geom, self.srcC[0], self._C1(), self.CoutP):
+            return self.Wb, False, True
+        if (wino or self.train_wino) and self.WpW is not None and ops.conv_wino_supported(geom, self.srcC[0], self._C1(), self.CoutP):
+            return self.WpW, True, False
+        return self.Wp, False, False
+
+    def _wino_wgrad(self, geom) -> bool:
+        """Winograd weight gradient (k_wgrad_wino) where the forward / dgrad of this conv take Winograd too."""
+        return bool(self.train_wino and ops.conv_wino_supported(geom, self.srcC[0], self._C1(), self.CoutP))
+
+    def _dgrad(self, gy, s: int, N: int, Ho: int, Wo: int, Hi: int, Wi: int, out: torch.Tensor, accumulate: bool):
+        """d(src_s) on the Hi x Wi grid (the 2x grid of a folded upsample): the Winograd forward of the flipped, transposed
+        kernels where train_wino and the geometry allow it, else the direct kernel's transposed gather."""
+        C = self.srcC[s]
+        if self.train_wino and self.WdW[s] is not None:
+            g0 = ops.conv_geom(N, Ho, Wo, Hi, Wi, self.KH, self.KW, 1, 1, 0, 0)
+            if ops.conv_wino_supported(g0, self.Cout, 0, pad16(C)):
+                return ops.conv_forward(g0, gy, self.Cout, self.WdW[s], C, out, accumulate=accumulate, CoutP=pad16(C), wino=True)
+        gd = ops.conv_geom(N, Ho, Wo, Hi, Wi, self.KH, self.KW, self.stride, self.pad, 1 - self.mode, 0)
+        return ops.conv_forward(gd, gy, self.Cout, self.Wd[s], C, out, accumulate=accumulate, CoutP=pad16(C))
+
     def can_transform_input(self, N: int, Hi: int, Wi: int) -> bool:
         """True when forward() can apply a per-(sample, channel) affine (+SiLU) to its input on the fly."""
         geom, _, _ = self._geom(N, Hi, Wi)
-        return ops.conv_input_transform_supported(geom, self.srcC[0], self.srcC[1] if len(self.srcC) > 1 else 0, self.CoutP,
-                                                  Cout=self.Cout)
+        return ops.conv_input_transform_supported(geom, self.srcC[0], self._C1(), self.Cout, self.CoutP)
 
     # -------------------------------------------------------------- forward
     def forward(self, srcs: List[torch.Tensor], N: int, Hi: int, Wi: int, n_bias: int, emb: Optional[torch.Tensor] = None,
@@ -281,10 +308,7 @@ class ConvOp:
         stats: if the kernel serving this convolution can, leave the per-channel sums of the output on the returned
         tensor as ``out._msgm_cs = (chanstats, slots)`` for the GroupNorm that reads it next."""
         geom, Ho, Wo = self._geom(N, Hi, Wi)
-        b6 = bool((b6 or (wino and self.use_b6)) and self.Wb is not None and
-                  ops.conv_b6_supported(geom, self.srcC[0], self.srcC[1] if len(srcs) > 1 else 0, self.CoutP))
-        wino = bool(not b6 and (wino or self.train_wino) and self.WpW is not None and
-                    ops.conv_wino_supported(geom, self.srcC[0], self.srcC[1] if len(srcs) > 1 else 0, self.CoutP))
+        W, wino, b6 = self._forward_image(geom, wino, b6)
         dev = srcs[0].device
         if out is None:
             out = torch.empty(N * Ho * Wo * self.Cout, device=dev)
@@ -303,11 +327,10 @@ class ConvOp:
         cs, S = None, 0
         out._msgm_cs = None                      # whatever was there described the values about to be overwritten
         if stats and not self.embC:
-            S = ((Ho // 16) * (Wo // 16) * 4 if (wino or b6) and self.Cout % 4 == 0 else 0 if (wino or b6) else
-                 ops.conv_chanstats_slots(geom, self.srcC[0], self.srcC[1] if len(srcs) > 1 else 0, self.Cout, self.CoutP))
+            S = ops.conv_chanstats_slots(geom, self.srcC[0], self._C1(), self.Cout, self.CoutP, wino=wino or b6)
             if S > 0:
                 cs = torch.empty(N * S * 2 * self.Cout, device=dev)
-        ops.conv_forward(geom, srcs[0], self.srcC[0], self.Wb if b6 else (self.WpW if wino else self.Wp), self.Cout, out,
+        ops.conv_forward(geom, srcs[0], self.srcC[0], W, self.Cout, out,
                          src1=srcs[1] if len(srcs) > 1 else None, C1=self.srcC[1] if len(srcs) > 1 else 0,
                          bias=self.bias.detach() if self.bias is not None else None, samp_bias=sb, n_bias=n_bias,
                          accumulate=accumulate, CoutP=self.CoutP, n_samp=er, residual=residual,
@@ -340,8 +363,7 @@ class ConvOp:
         self._bias_zeroed = False
         if fuse_bias and not bias_grad_zeroed:
             self.bias.grad.zero_()
-        # Winograd weight gradient (k_wgrad_wino) where the forward / dgrad of this conv take Winograd too
-        wg = bool(self.train_wino and ops.conv_wino_supported(geom, self.srcC[0], self.srcC[1] if len(self.srcC) > 1 else 0, self.CoutP))
+        wg = self._wino_wgrad(geom)
         for s, C in enumerate(self.srcC):
             ops.conv_wgrad(geom, gy, srcs[s], C, self.koff[s], self.dWp, self.Cout, self.CoutP, self.Ktot,
                            dbias=self.bias.grad.view(-1) if (fuse_bias and s == 0) else None, n_bias=n_bias, wino=wg)
@@ -370,7 +392,6 @@ class ConvOp:
                 ops.conv_wgrad(gE, G[t], emb, E, 0, self.dWpE[t * perE:(t + 1) * perE], self.Cout, self.Cout, pad16(E))
         outs = []
         need = [True] * len(self.srcC) if need is None else need
-        gd = ops.conv_geom(N, Ho, Wo, Hi, Wi, self.KH, self.KW, self.stride, self.pad, 1 - self.mode, 0)
         for s, C in enumerate(self.srcC):
             if not need[s]:
                 outs.append(None)
@@ -378,14 +399,7 @@ class ConvOp:
             if self.ups:
                 raise MsgmError("dgrad through a folded upsample is handled by the caller (sum of 2x2 blocks)")
             d = dsrc[s] if (dsrc is not None and dsrc[s] is not None) else torch.empty(N * Hi * Wi * C, device=dev)
-            g0 = ops.conv_geom(N, Ho, Wo, Hi, Wi, self.KH, self.KW, 1, 1, 0, 0) if (self.train_wino and self.WdW[s] is not None) else None
-            if g0 is not None and ops.conv_wino_supported(g0, self.Cout, 0, pad16(C)):
-                ops.conv_forward(g0, gy, self.Cout, self.WdW[s], C, d, accumulate=bool(dacc[s]) if dacc is not None else False,
-                                 CoutP=pad16(C), wino=True)
-            else:
-                ops.conv_forward(gd, gy, self.Cout, self.Wd[s], C, d, accumulate=bool(dacc[s]) if dacc is not None else False,
-                                 CoutP=pad16(C))
-            outs.append(d)
+            outs.append(self._dgrad(gy, s, N, Ho, Wo, Hi, Wi, d, bool(dacc[s]) if dacc is not None else False))
         return outs
 
     def backward_ups(self, gy: torch.Tensor, src: torch.Tensor, N: int, Hi: int, Wi: int, n_bias: int,
@@ -402,14 +416,9 @@ class ConvOp:
             self.bias.grad.zero_()
         ops.conv_wgrad(geom, gy, src, C, 0, self.dWp, self.Cout, self.CoutP, self.Ktot,
                        dbias=self.bias.grad.view(-1) if self.bias is not None else None, n_bias=n_bias,
-                       wino=bool(self.train_wino and ops.conv_wino_supported(geom, C, 0, self.CoutP)))
-        gd = ops.conv_geom(N, Ho, Wo, 2 * Hi, 2 * Wi, self.KH, self.KW, self.stride, self.pad, 1 - self.mode, 0)
+                       wino=self._wino_wgrad(geom))
         gup = torch.empty(N * 4 * Hi * Wi * C, device=dev)
-        g0 = ops.conv_geom(N, Ho, Wo, 2 * Hi, 2 * Wi, self.KH, self.KW, 1, 1, 0, 0) if (self.train_wino and self.WdW[0] is not None) else None
-        if g0 is not None and ops.conv_wino_supported(g0, self.Cout, 0, pad16(C)):
-            ops.conv_forward(g0, gy, self.Cout, self.WdW[0], C, gup, CoutP=pad16(C), wino=True)     # the dgrad on the 2x grid: a plain same-size conv
-        else:
-            ops.conv_forward(gd, gy, self.Cout, self.Wd[0], C, gup, CoutP=pad16(C))
+        self._dgrad(gy, 0, N, Ho, Wo, 2 * Hi, 2 * Wi, gup, False)          # the dgrad on the 2x grid: a plain same-size conv
         return ops.sum2x2(gup, N, Hi, Wi, C)
 
 

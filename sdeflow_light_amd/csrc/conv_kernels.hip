@@ -2696,36 +2696,66 @@ static ConvGeom to_geom(const msgm_conv_geom_t* g) {
   return ConvGeom{g->N, g->Hi, g->Wi, g->Ho, g->Wo, g->KH, g->KW, g->strideH, g->padH, g->strideW, g->padW, g->mode, g->ups};
 }
 
+// stride 1, output = input (x2 with the folded upsample), odd kernel <= 3 with centred padding: the "same" shapes
+static bool conv_same(const msgm_conv_geom_t* g) {
+  const int ups_sh = g->ups ? 1 : 0;
+  return g->strideH == 1 && g->strideW == 1 && (g->Hi << ups_sh) == g->Ho && (g->Wi << ups_sh) == g->Wo &&
+         (g->KH & 1) && (g->KW & 1) && g->KH <= 3 && g->KW <= 3 && g->padH == (g->KH - 1) / 2 && g->padW == (g->KW - 1) / 2;
+}
+
 extern "C" {
 
-// is this (geometry, channels) served by the halo-tile kernel?  (the only one that can transform its input)
-static bool conv_tile_eligible(const msgm_conv_geom_t* geom, int32_t C0, const float* src1, int32_t C1, int32_t CoutP) {
-  const bool fast = (C0 % 16 == 0) && (!src1 || C1 % 16 == 0);
-  const int ups_sh = geom->ups ? 1 : 0;
-  const bool same = geom->strideH == 1 && geom->strideW == 1 && (!geom->ups || geom->mode == 0) &&
-                    (geom->Hi << ups_sh) == geom->Ho && (geom->Wi << ups_sh) == geom->Wo &&
-                    (geom->KH & 1) && (geom->KW & 1) && geom->padH == (geom->KH - 1) / 2 && geom->padW == (geom->KW - 1) / 2 &&
-                    geom->KH <= 3 && geom->KW <= 3;
-  return same && fast && CoutP % 32 == 0 && (int64_t)geom->Ho * geom->Wo >= 64 &&
+// is this (geometry, channels) served by the halo-tile kernel?
+static bool conv_tile_eligible(const msgm_conv_geom_t* geom, int32_t C0, bool has1, int32_t C1, int32_t CoutP) {
+  const bool fast = (C0 % 16 == 0) && (!has1 || C1 % 16 == 0);
+  return conv_same(geom) && (!geom->ups || geom->mode == 0) && fast && CoutP % 32 == 0 && (int64_t)geom->Ho * geom->Wo >= 64 &&
          (geom->Ho > 1 ? geom->KH == geom->KW : geom->KH == 1);            // square kernels in 2-D, KH = 1 in 1-D
 }
 
-int msgm_conv_input_transform_supported(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t CoutP) {
-  if (check_geom(geom)) return 0;
-  static const float dummy = 0.f;
-  return conv_tile_eligible(geom, C0, C1 > 0 ? &dummy : nullptr, C1, CoutP) ? 1 : 0;
-}
-
-static bool conv_wino_eligible(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t CoutP) {
-  const int ups_sh = geom->ups ? 1 : 0;
-  return geom->mode == 0 && geom->KH == 3 && geom->KW == 3 && geom->strideH == 1 && geom->strideW == 1 && geom->padH == 1 &&
-         geom->padW == 1 && (geom->Hi << ups_sh) == geom->Ho && (geom->Wi << ups_sh) == geom->Wo && geom->Ho % 16 == 0 &&
-         geom->Wo % 16 == 0 && C0 % 16 == 0 && C1 % 16 == 0 && CoutP % 32 == 0;
+// the Winograd (cmul = 16) and bf16-split (cmul = 32) 3x3 forward kernels: 16x16 output tiles
+static bool conv_wino_eligible(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t CoutP, int cmul) {
+  return geom->mode == 0 && geom->KH == 3 && geom->KW == 3 && conv_same(geom) && geom->Ho % 16 == 0 && geom->Wo % 16 == 0 &&
+         C0 % cmul == 0 && C1 % cmul == 0 && CoutP % 32 == 0;
 }
 
 int msgm_conv_wino_supported(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t CoutP) {
   if (check_geom(geom)) return 0;
-  return conv_wino_eligible(geom, C0, C1, CoutP) ? 1 : 0;
+  return conv_wino_eligible(geom, C0, C1, CoutP, 16) ? 1 : 0;
+}
+
+// Validates what every forward entry point takes and fills ConvArgs.  padded_k: each source's channels are padded to 16 in
+// the K axis of the weight image (the fp32 images); the bf16-split image is unpadded.
+static int conv_args(ConvArgs* A, const msgm_conv_geom_t* geom, const float* src0, int32_t C0, const float* src1, int32_t C1,
+                     const void* W, int32_t Cout, int32_t CoutP, int32_t Ktot, const float* bias, const float* samp_bias,
+                     int32_t n_bias, int32_t n_samp, float* out, int32_t accumulate, const msgm_conv_fuse_t* fuse,
+                     bool padded_k) {
+  int rc = check_geom(geom);
+  if (rc) return rc;
+  if (fuse && ((fuse->in_scale == nullptr) != (fuse->in_shift == nullptr) || (fuse->in_act != 0 && fuse->in_act != 1)))
+    return MSGM_E_BADARG;
+  if (!src0 || !W || !out || C0 <= 0 || Cout <= 0 || (src1 && C1 <= 0)) return MSGM_E_BADARG;
+  const int k0 = padded_k ? ((C0 + 15) / 16) * 16 : C0, k1 = !src1 ? 0 : padded_k ? ((C1 + 15) / 16) * 16 : C1;
+  if (Ktot != k0 + k1 || CoutP % 16 || CoutP < Cout) return MSGM_E_BADARG;
+  *A = ConvArgs{};
+  A->g = to_geom(geom);
+  A->src[0] = src0; A->C[0] = C0; A->koff[0] = 0;
+  A->src[1] = src1; A->C[1] = src1 ? C1 : 0; A->koff[1] = k0;
+  A->nsrc = src1 ? 2 : 1;
+  A->Wp = static_cast<const float*>(W); A->Cout = Cout; A->CoutP = CoutP; A->Ktot = Ktot;
+  A->bias = bias; A->samp_bias = samp_bias; A->n_bias = n_bias; A->n_samp = n_samp; A->out = out; A->accumulate = accumulate;
+  if (fuse) {
+    A->residual = fuse->residual; A->in_scale = fuse->in_scale; A->in_shift = fuse->in_shift; A->in_act = fuse->in_act;
+    for (int i = 0; i < 16; ++i) A->tapmask_in[i] = fuse->tapmask_in[i];
+    for (int i = 0; i < 8; ++i) A->tapmask_out[i] = fuse->tapmask_out[i];
+    A->cstat = fuse->chanstats;                              // cs_S: the launcher's tiling decides
+  }
+  return MSGM_OK;
+}
+static bool conv_has_masks(const ConvArgs& A) {
+  unsigned m = 0;
+  for (int i = 0; i < 16; ++i) m |= A.tapmask_in[i];
+  for (int i = 0; i < 8; ++i) m |= A.tapmask_out[i];
+  return m != 0;
 }
 
 int msgm_wino_pack_weights_batched(const msgm_pack_job_t* jobs, int32_t n_jobs, msgm_stream_t stream) {
@@ -2734,29 +2764,23 @@ int msgm_wino_pack_weights_batched(const msgm_pack_job_t* jobs, int32_t n_jobs, 
   return msgm_check_launch();
 }
 
+// chanstats of the 16x16-tile 3x3 kernels (Winograd, bf16-split): one slot per (tile, wave), [N][(Ho/16) (Wo/16) 4][2][Cout]
+static bool tile16_chanstats(ConvArgs& A) {
+  if (!A.cstat) return true;
+  A.cs_S = (A.g.Wo / 16) * (A.g.Ho / 16) * 4;
+  return A.Cout % 4 == 0;
+}
+
 int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int32_t C0, const float* src1, int32_t C1,
                            const float* WpW, int32_t Cout, int32_t CoutP, int32_t Ktot, const float* bias,
                            const float* samp_bias, int32_t n_bias, int32_t n_samp, float* out, int32_t accumulate,
                            const msgm_conv_fuse_t* fuse, msgm_stream_t stream) {
-  int rc = check_geom(geom);
+  ConvArgs A;
+  int rc = conv_args(&A, geom, src0, C0, src1, C1, WpW, Cout, CoutP, Ktot, bias, samp_bias, n_bias, n_samp, out, accumulate,
+                     fuse, true);
   if (rc) return rc;
-  if (fuse && ((fuse->in_scale == nullptr) != (fuse->in_shift == nullptr) || (fuse->in_act != 0 && fuse->in_act != 1)))
-    return MSGM_E_BADARG;
-  if (!src0 || !WpW || !out || C0 <= 0 || Cout <= 0 || (src1 && C1 <= 0)) return MSGM_E_BADARG;
-  if (!conv_wino_eligible(geom, C0, src1 ? C1 : 0, CoutP)) return MSGM_E_UNSUPPORTED;
-  const int k0 = ((C0 + 15) / 16) * 16, k1 = src1 ? ((C1 + 15) / 16) * 16 : 0;
-  if (Ktot != k0 + k1 || CoutP < Cout) return MSGM_E_BADARG;
-  ConvArgs A{};
-  A.g = to_geom(geom);
-  A.src[0] = src0; A.C[0] = C0; A.koff[0] = 0;
-  A.src[1] = src1; A.C[1] = src1 ? C1 : 0; A.koff[1] = k0;
-  A.nsrc = src1 ? 2 : 1;
-  A.Wp = WpW; A.Cout = Cout; A.CoutP = CoutP; A.Ktot = Ktot;
-  A.bias = bias; A.samp_bias = samp_bias; A.n_bias = n_bias; A.n_samp = n_samp; A.out = out; A.accumulate = accumulate;
-  if (fuse && fuse->chanstats && (Cout & 3)) return MSGM_E_UNSUPPORTED;
-  if (fuse) { A.residual = fuse->residual; A.in_scale = fuse->in_scale; A.in_shift = fuse->in_shift; A.in_act = fuse->in_act; }
+  if (!conv_wino_eligible(geom, C0, A.C[1], CoutP, 16) || !tile16_chanstats(A)) return MSGM_E_UNSUPPORTED;
   const int tiles_x = geom->Wo / 16, tiles_y = geom->Ho / 16;
-  if (fuse && fuse->chanstats) { A.cstat = fuse->chanstats; A.cs_S = tiles_x * tiles_y * 4; }   // [N][Ho/16 * Wo/16 * 4][2][Cout]
   const int n_tiles = tiles_x * tiles_y * geom->N, gy = CoutP / 32;
   static const int n_cu = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
   if (!A.in_scale) {
@@ -2814,16 +2838,9 @@ __global__ void __launch_bounds__(256) k_b6_split(const float* __restrict__ Wp, 
   }
 }
 
-static bool conv_b6_eligible(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t CoutP) {
-  const int ups_sh = geom->ups ? 1 : 0;
-  return geom->mode == 0 && geom->KH == 3 && geom->KW == 3 && geom->strideH == 1 && geom->strideW == 1 && geom->padH == 1 &&
-         geom->padW == 1 && (geom->Hi << ups_sh) == geom->Ho && (geom->Wi << ups_sh) == geom->Wo && geom->Ho % 16 == 0 && geom->Wo % 16 == 0 &&
-         C0 % 32 == 0 && C1 % 32 == 0 && CoutP % 32 == 0;
-}
-
 int msgm_conv_b6_supported(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t CoutP) {
   if (check_geom(geom)) return 0;
-  return conv_b6_eligible(geom, C0, C1, CoutP) ? 1 : 0;
+  return conv_wino_eligible(geom, C0, C1, CoutP, 32) ? 1 : 0;
 }
 
 int msgm_b6_split_weights(const float* Wp, void* Wb, int64_t n_elem, msgm_stream_t stream) {
@@ -2836,30 +2853,13 @@ int msgm_conv_forward_b6(const msgm_conv_geom_t* geom, const float* src0, int32_
                          const void* Wb, int32_t Cout, int32_t CoutP, int32_t Ktot, const float* bias,
                          const float* samp_bias, int32_t n_bias, int32_t n_samp, float* out, int32_t accumulate,
                          const msgm_conv_fuse_t* fuse, msgm_stream_t stream) {
-  int rc = check_geom(geom);
+  ConvArgs A;
+  int rc = conv_args(&A, geom, src0, C0, src1, C1, Wb, Cout, CoutP, Ktot, bias, samp_bias, n_bias, n_samp, out, accumulate,
+                     fuse, false);
   if (rc) return rc;
-  if (fuse && ((fuse->in_scale == nullptr) != (fuse->in_shift == nullptr) || (fuse->in_act != 0 && fuse->in_act != 1)))
-    return MSGM_E_BADARG;
-  if (!src0 || !Wb || !out || C0 <= 0 || Cout <= 0 || (src1 && C1 <= 0)) return MSGM_E_BADARG;
-  if (!conv_b6_eligible(geom, C0, src1 ? C1 : 0, CoutP)) return MSGM_E_UNSUPPORTED;
-  if (Ktot != C0 + (src1 ? C1 : 0) || CoutP < Cout) return MSGM_E_BADARG;
-  if (fuse)
-    for (int i = 0; i < 16; ++i)
-      if (fuse->tapmask_in[i] || (i < 8 && fuse->tapmask_out[i])) return MSGM_E_UNSUPPORTED;
-  ConvArgs A{};
-  A.g = to_geom(geom);
-  A.src[0] = src0; A.C[0] = C0; A.koff[0] = 0;
-  A.src[1] = src1; A.C[1] = src1 ? C1 : 0; A.koff[1] = C0;
-  A.nsrc = src1 ? 2 : 1;
-  A.Wp = static_cast<const float*>(Wb); A.Cout = Cout; A.CoutP = CoutP; A.Ktot = Ktot;
-  A.bias = bias; A.samp_bias = samp_bias; A.n_bias = n_bias; A.n_samp = n_samp; A.out = out; A.accumulate = accumulate;
-  if (fuse) { A.residual = fuse->residual; A.in_scale = fuse->in_scale; A.in_shift = fuse->in_shift; A.in_act = fuse->in_act; }
+  if (!conv_wino_eligible(geom, C0, A.C[1], CoutP, 32) || conv_has_masks(A) || !tile16_chanstats(A)) return MSGM_E_UNSUPPORTED;
   const int nco = (CoutP % 64 == 0) ? 4 : 2;
   const int tiles_x = (geom->Wo + 15) / 16, tiles_y = (geom->Ho + 15) / 16;
-  if (fuse && fuse->chanstats) {                            // the direct wide kernel's layout: one slot per (16x16 tile, wave)
-    if (Cout & 3) return MSGM_E_UNSUPPORTED;
-    A.cstat = fuse->chanstats; A.cs_S = tiles_x * tiles_y * 4;
-  }
   const int n_tiles = tiles_x * tiles_y * geom->N, gy = CoutP / (16 * nco);
   int per = (int)(((int64_t)n_tiles * gy) / (512 * 8));     // two resident workgroups per CU (67 KB of LDS each)
   if (per > 4) per = 4;
@@ -2887,9 +2887,7 @@ struct ConvRoute {
 };
 // first / last convolution of the U-Net: 3x3 "same", one source, <= 4 channels on one side and 32 on the other
 static bool conv_small_shape(const msgm_conv_geom_t* geom, bool has1, bool masks) {
-  return geom->KH == 3 && geom->KW == 3 && geom->strideH == 1 && geom->strideW == 1 &&
-         geom->padH == 1 && geom->padW == 1 && !geom->ups && geom->Hi == geom->Ho && geom->Wi == geom->Wo && geom->Ho > 1 &&
-         !has1 && !masks;
+  return conv_same(geom) && geom->KH == 3 && geom->KW == 3 && !geom->ups && geom->Ho > 1 && !has1 && !masks;
 }
 static ConvRoute conv_route(const msgm_conv_geom_t* geom, int32_t C0, bool has1, int32_t C1, int32_t Cout, int32_t CoutP,
                             bool masks, bool both_extra = false /* accumulate AND residual */, bool any_size = false) {
@@ -2902,8 +2900,7 @@ static ConvRoute conv_route(const msgm_conv_geom_t* geom, int32_t C0, bool has1,
   const bool fast = (C0 % 16 == 0) && (!has1 || C1 % 16 == 0);
   const int Ktot = ((C0 + 15) / 16) * 16 + (has1 ? ((C1 + 15) / 16) * 16 : 0);
   const int kg = Ktot / 16;
-  if (geom->KH == 1 && geom->KW == 1 && geom->strideH == 1 && geom->strideW == 1 && geom->padH == 0 && geom->padW == 0 &&
-      !geom->ups && geom->Hi == geom->Ho && geom->Wi == geom->Wo && fast && !masks && (Mtot >= 4096 || any_size) &&
+  if (conv_same(geom) && geom->KH == 1 && geom->KW == 1 && !geom->ups && fast && !masks && (Mtot >= 4096 || any_size) &&
       (kg == 2 || kg == 4 || kg == 6 || kg == 8 || kg == 12 || kg == 16) && Cout % 16 == 0 && !both_extra) {
     // resident activations: PT * KG float4 per lane (<= 64 registers).  Fewer pixels per wave (more waves per SIMD) measured
     // equal at 64 input channels and 1.4x slower at 128 (tools/bench_1x1.py)
@@ -2913,8 +2910,7 @@ static ConvRoute conv_route(const msgm_conv_geom_t* geom, int32_t C0, bool has1,
     const int pt = kg <= 4 ? 4 : (kg <= 8 ? 2 : (kg == 12 && (geom->Ho * geom->Wo) % 32 == 0 ? 2 : 1));
     if ((geom->Ho * geom->Wo) % (16 * pt) == 0) { r.kind = 1; r.kg = kg; r.pt = pt; return r; }
   }
-  static const float dummy = 0.f;
-  if (conv_tile_eligible(geom, C0, has1 ? &dummy : nullptr, C1, CoutP)) {
+  if (conv_tile_eligible(geom, C0, has1, C1, CoutP)) {
     r.kind = 2;
     r.two_d = geom->Ho > 1;
     r.nco = (CoutP % 64 == 0) ? 4 : 2;
@@ -2956,9 +2952,14 @@ int32_t msgm_conv_chanstats_slots(const msgm_conv_geom_t* geom, int32_t C0, int3
   return conv_route_slots(conv_route(geom, C0, C1 > 0, C1, Cout, CoutP, false), geom, Cout);
 }
 
-int msgm_conv_small_cout_supported(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t Cout) {
-  if (check_geom(geom) || C1 != 0) return 0;
-  return conv_route(geom, C0, false, 0, Cout, 16, false).kind == 4 ? 1 : 0;
+// the launcher folds an input transform (in_scale / in_shift) into the halo-tile kernel and the U-Net's output convolution
+static bool conv_in_transform_ok(const ConvRoute& r, const msgm_conv_geom_t* geom, int32_t C0, bool has1, int32_t C1, int32_t CoutP) {
+  return r.kind == 4 || conv_tile_eligible(geom, C0, has1, C1, CoutP);
+}
+
+int msgm_conv_input_transform_supported(const msgm_conv_geom_t* geom, int32_t C0, int32_t C1, int32_t Cout, int32_t CoutP) {
+  if (check_geom(geom)) return 0;
+  return conv_in_transform_ok(conv_route(geom, C0, C1 > 0, C1, Cout, CoutP, false), geom, C0, C1 > 0, C1, CoutP) ? 1 : 0;
 }
 
 int msgm_conv_forward(const msgm_conv_geom_t* geom, const float* src0, int32_t C0, const float* src1, int32_t C1,
@@ -2973,52 +2974,32 @@ int msgm_conv_forward_fused(const msgm_conv_geom_t* geom, const float* src0, int
                             const float* Wp, int32_t Cout, int32_t CoutP, int32_t Ktot, const float* bias,
                             const float* samp_bias, int32_t n_bias, int32_t n_samp, float* out, int32_t accumulate,
                             const msgm_conv_fuse_t* fuse, msgm_stream_t stream) {
-  int rc = check_geom(geom);
+  ConvArgs A;
+  int rc = conv_args(&A, geom, src0, C0, src1, C1, Wp, Cout, CoutP, Ktot, bias, samp_bias, n_bias, n_samp, out, accumulate,
+                     fuse, true);
   if (rc) return rc;
-  if (fuse && ((fuse->in_scale == nullptr) != (fuse->in_shift == nullptr) || (fuse->in_act != 0 && fuse->in_act != 1)))
-    return MSGM_E_BADARG;
-  if (!src0 || !Wp || !out || C0 <= 0 || Cout <= 0 || (src1 && C1 <= 0)) return MSGM_E_BADARG;
-  const int k0 = ((C0 + 15) / 16) * 16, k1 = src1 ? ((C1 + 15) / 16) * 16 : 0;
-  if (Ktot != k0 + k1 || CoutP % 16 || CoutP < Cout) return MSGM_E_BADARG;
-  bool masks = false;
-  if (fuse) {
-    for (int i = 0; i < 16; ++i) masks = masks || fuse->tapmask_in[i];
-    for (int i = 0; i < 8; ++i) masks = masks || fuse->tapmask_out[i];
-  }
-  const bool both_extra = accumulate && fuse && fuse->residual;
+  const bool masks = conv_has_masks(A);
+  const bool both_extra = accumulate && A.residual;
   // A Linear layer (H = W = 1: the embedding / time MLPs, model/unet.py:334-340,128-134) whose rows all take the same bias
   // path is the 1x1 convolution of ONE sample with N pixels: that shape takes the pixel-stationary kernel (a few
   // microseconds at N = 32..1024 rows) instead of the implicit GEMM's chain of L2 round trips (18-37 us, 49 launches per
   // training step at the 32-row shard).
   msgm_conv_geom_t lin = *geom;
   const bool as_pixels = geom->Hi == 1 && geom->Wi == 1 && geom->Ho == 1 && geom->Wo == 1 && geom->KH == 1 && geom->KW == 1 &&
-                         geom->N >= 32 && !samp_bias && (!bias || n_bias >= geom->N) && !(fuse && (fuse->in_scale || fuse->chanstats));
+                         geom->N >= 32 && !samp_bias && (!bias || n_bias >= geom->N) && !A.in_scale && !A.cstat;
   if (as_pixels) {
     lin.Wi = lin.Wo = geom->N; lin.N = 1; lin.mode = 0;
     const ConvRoute rl = conv_route(&lin, C0, src1 != nullptr, C1, Cout, CoutP, masks, both_extra, true);
-    if (rl.kind == 1) { geom = &lin; n_bias = bias ? 1 : 0; n_samp = 0; }
+    if (rl.kind == 1) { geom = &lin; A.g = to_geom(geom); A.n_bias = bias ? 1 : 0; A.n_samp = 0; }
   }
   const ConvRoute rt = conv_route(geom, C0, src1 != nullptr, C1, Cout, CoutP, masks, both_extra, geom == &lin);
-  if (fuse && fuse->in_scale && rt.kind != 4 && !conv_tile_eligible(geom, C0, src1, C1, CoutP)) return MSGM_E_UNSUPPORTED;
-  ConvArgs A{};
-  A.g = to_geom(geom);
-  A.src[0] = src0; A.C[0] = C0; A.koff[0] = 0;
-  A.src[1] = src1; A.C[1] = src1 ? C1 : 0; A.koff[1] = k0;
-  A.nsrc = src1 ? 2 : 1;
-  A.Wp = Wp; A.Cout = Cout; A.CoutP = CoutP; A.Ktot = Ktot;
-  A.bias = bias; A.samp_bias = samp_bias; A.n_bias = n_bias; A.n_samp = n_samp; A.out = out; A.accumulate = accumulate;
-  if (fuse) {
-    A.residual = fuse->residual; A.in_scale = fuse->in_scale; A.in_shift = fuse->in_shift; A.in_act = fuse->in_act;
-    for (int i = 0; i < 16; ++i) A.tapmask_in[i] = fuse->tapmask_in[i];
-    for (int i = 0; i < 8; ++i) A.tapmask_out[i] = fuse->tapmask_out[i];
-  }
+  if (A.in_scale && !conv_in_transform_ok(rt, geom, C0, src1 != nullptr, C1, CoutP)) return MSGM_E_UNSUPPORTED;
   const int64_t Mtot = (int64_t)geom->N * geom->Ho * geom->Wo;
   const bool fast = (C0 % 16 == 0) && (!src1 || C1 % 16 == 0);
-  if (fuse && fuse->chanstats) {
+  if (A.cstat) {
     A.cs_S = masks ? 0 : conv_route_slots(rt, geom, Cout);
     // the caller sized the buffer from msgm_conv_chanstats_slots(), which sees neither masks nor accumulate + residual
     if (A.cs_S == 0 || A.cs_S != msgm_conv_chanstats_slots(geom, C0, src1 ? C1 : 0, Cout, CoutP)) return MSGM_E_UNSUPPORTED;
-    A.cstat = fuse->chanstats;
   }
   // the U-Net's first / last 3x3 convolution: vector ALU, weights in scalar registers
   if (rt.kind == 3) {
@@ -3045,7 +3026,7 @@ int msgm_conv_forward_fused(const msgm_conv_geom_t* geom, const float* src0, int
     int split = wgs >= 768 ? 1 : (int)((768 + wgs - 1) / wgs);          // aim at >= 3 workgroups per CU
     if (split > ntile) split = ntile;
     const int ct_per = (ntile + split - 1) / split, gy = (ntile + ct_per - 1) / ct_per;
-    const bool extra = accumulate || (fuse && fuse->residual);
+    const bool extra = accumulate || A.residual;
 #define C1_LAUNCH(PT_, KG_)                                                                                          \
   do {                                                                                                               \
     if (extra) hipLaunchKernelGGL((k_conv1x1<PT_, KG_, 1>), dim3((unsigned)wgs, (unsigned)gy), dim3(256), 0, S(stream), A, P, (long)Mtot, ct_per); \
@@ -3123,16 +3104,13 @@ static void wgrad1x1_shape(int C, int Cout, int* mt, int* nt, int* wm) {
   if (C == 256) { *mt = 1; return; }
   *mt = Cout % 192 == 0 ? 3 : (Cout % 128 == 0 ? 2 : 1);
 }
-// wino: the caller asks for k_wgrad_wino; the plan takes it when the shape is one k_wgrad_tile9 would serve (2-D 3x3 "same",
-// stride 1, channel counts that are multiples of 4) and says so in p.wino
+// wino: the caller prefers k_wgrad_wino; the plan takes it when the shape is one k_wgrad_tile9 would serve (2-D 3x3 "same",
+// stride 1, channel counts that are multiples of 4) and says so in p.wino; otherwise it is the plan of wino = 0
 static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n_bias, bool wino) {
   WgradPlan p{};
   const int64_t Mtot = (int64_t)geom->N * geom->Ho * geom->Wo;
   const int taps = geom->KH * geom->KW;
-  const int ups_sh = geom->ups ? 1 : 0;
-  const bool same = geom->mode == 0 && geom->strideH == 1 && geom->strideW == 1 && (geom->Hi << ups_sh) == geom->Ho &&
-                    (geom->Wi << ups_sh) == geom->Wo && (geom->KH & 1) && (geom->KW & 1) && geom->padH == (geom->KH - 1) / 2 &&
-                    geom->padW == (geom->KW - 1) / 2 && geom->KH <= 3 && geom->KW <= 3;
+  const bool same = geom->mode == 0 && conv_same(geom);
   if (taps == 1 && same && !geom->ups && geom->padH == 0 && geom->padW == 0 && ((int64_t)n_bias * geom->Ho * geom->Wo) % 16 == 0) {
     wgrad1x1_shape(C, Cout, &p.mt, &p.nt, &p.wm);
     if (p.mt) {
@@ -3248,7 +3226,6 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
     A.tm_o[i] = (tapmask_co32 && i < (Cout + 31) / 32) ? tapmask_co32[i] : 0;
   }
   const int taps = geom->KH * geom->KW;
-  if (wino && (!pl.wino || tapmask_c32 || tapmask_co32)) return MSGM_E_UNSUPPORTED;   // the caller falls back to wino = 0
   auto reduce_slabs = [&](int nslots, bool with_bias) {     // slabs -> dWp (+ dbias), slot order
     if (jobs_out) {                                          // deferred: the caller batches the reductions of a whole pass
       msgm_reduce_job_t& J = jobs_out[(*n_jobs_out)++];

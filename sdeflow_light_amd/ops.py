@@ -330,10 +330,11 @@ def conv_forward(geom: L.ConvGeomT, src0: torch.Tensor, C0: int, Wp: torch.Tenso
         if (in_scale is None) != (in_shift is None) or (in_scale is not None and
                                                         (in_scale.numel() != geom.N * ctot or in_shift.numel() != geom.N * ctot)):
             raise MsgmError("in_scale / in_shift must both be [N][C0+C1]")
+        if (wino or b6) and (tapmask_in or tapmask_out):
+            raise MsgmError("the Winograd and bf16-split kernels have no tap masks")
         fuse = L.ConvFuseT(ptr(residual), ptr(in_scale), ptr(in_shift), int(in_act), 0)
         if chanstats is not None:
-            S = ((geom.Ho // 16) * (geom.Wo // 16) * 4 if (wino or b6) else
-                 conv_chanstats_slots(geom, C0, C1 if src1 is not None else 0, Cout, CoutP))
+            S = conv_chanstats_slots(geom, C0, C1 if src1 is not None else 0, Cout, CoutP, wino=wino or b6)
             if S <= 0 or chanstats.numel() < geom.N * S * 2 * Cout or chanstats.dtype != torch.float32:
                 raise MsgmError("chanstats: this convolution has no statistics by-product, or the buffer is too small")
             fuse.chanstats = ptr(chanstats)
@@ -341,28 +342,18 @@ def conv_forward(geom: L.ConvGeomT, src0: torch.Tensor, C0: int, Wp: torch.Tenso
             fuse.tapmask_in[i] = int(m)
         for i, m in enumerate((tapmask_out or [])[:8]):
             fuse.tapmask_out[i] = int(m)
-    if b6:
-        if tapmask_in or tapmask_out:
-            raise MsgmError("the bf16-split kernel has no tap masks")
-        check(lib().msgm_conv_forward_b6(geom, ptr(f32(src0)), C0, ptr(src1), C1, ptr(Wp), Cout, CoutP, Ktot, ptr(bias),
-                                         ptr(samp_bias), int(n_bias), int(n_samp), ptr(f32(out)), int(bool(accumulate)),
-                                         fuse, stream()), "msgm_conv_forward_b6")
-        return out
-    if wino:
-        if tapmask_in or tapmask_out:
-            raise MsgmError("the Winograd kernel has no tap masks")
-        check(lib().msgm_conv_forward_wino(geom, ptr(f32(src0)), C0, ptr(src1), C1, ptr(f32(Wp)), Cout, CoutP, Ktot, ptr(bias),
-                                           ptr(samp_bias), int(n_bias), int(n_samp), ptr(f32(out)), int(bool(accumulate)),
-                                           fuse, stream()), "msgm_conv_forward_wino")
-        return out
-    check(lib().msgm_conv_forward_fused(geom, ptr(f32(src0)), C0, ptr(src1), C1, ptr(f32(Wp)), Cout, CoutP, Ktot, ptr(bias),
-                                        ptr(samp_bias), int(n_bias), int(n_samp), ptr(f32(out)), int(bool(accumulate)),
-                                        fuse, stream()), "msgm_conv_forward")
+    name = "msgm_conv_forward_b6" if b6 else "msgm_conv_forward_wino" if wino else "msgm_conv_forward_fused"
+    check(getattr(lib(), name)(geom, ptr(f32(src0)), C0, ptr(src1), C1, ptr(Wp if b6 else f32(Wp)), Cout, CoutP, Ktot,
+                               ptr(bias), ptr(samp_bias), int(n_bias), int(n_samp), ptr(f32(out)), int(bool(accumulate)), fuse,
+                               stream()), name)
     return out
 
 
-def conv_chanstats_slots(geom: L.ConvGeomT, C0: int, C1: int, Cout: int, CoutP: int) -> int:
-    """Slots per sample of the per-channel statistics by-product of this forward convolution (0 = it has none)."""
+def conv_chanstats_slots(geom: L.ConvGeomT, C0: int, C1: int, Cout: int, CoutP: int, wino: bool = False) -> int:
+    """Slots per sample of the per-channel statistics by-product of this forward convolution (0 = it has none).
+    wino: of the Winograd / bf16-split 3x3 kernels, one slot per (16x16 tile, wave)."""
+    if wino:
+        return (geom.Ho // 16) * (geom.Wo // 16) * 4 if Cout % 4 == 0 else 0
     return int(lib().msgm_conv_chanstats_slots(geom, int(C0), int(C1), int(Cout), int(CoutP)))
 
 
@@ -380,10 +371,8 @@ def groupnorm_affine_cs(cs0, S0, C0, gamma, beta, Bp, P, G, cs1=None, S1=0, C1=0
     return scale, shift
 
 
-def conv_input_transform_supported(geom: L.ConvGeomT, C0: int, C1: int, CoutP: int, Cout: Optional[int] = None) -> bool:
-    if Cout is not None and lib().msgm_conv_small_cout_supported(geom, int(C0), int(C1), int(Cout)):
-        return True
-    return bool(lib().msgm_conv_input_transform_supported(geom, int(C0), int(C1), int(CoutP)))
+def conv_input_transform_supported(geom: L.ConvGeomT, C0: int, C1: int, Cout: int, CoutP: int) -> bool:
+    return bool(lib().msgm_conv_input_transform_supported(geom, int(C0), int(C1), int(Cout), int(CoutP)))
 
 
 def groupnorm_affine(x0, C0, gamma, beta, Bp, P, G, x1=None, C1=0, eps=1e-5):
@@ -420,8 +409,8 @@ def conv_wgrad(geom: L.ConvGeomT, gy: torch.Tensor, src: torch.Tensor, C: int, k
                CoutP: int, Ktot: int, dbias: Optional[torch.Tensor] = None, n_bias: int = 0, tapmask_c32=None,
                tapmask_co32=None, wino: bool = False):
     """dbias (Cout floats, ACCUMULATED into): bias gradient over the primal rows n < n_bias, as a by-product.
-    wino: a 2-D 3x3 stride-1 "same" gradient runs Winograd F(3x3, 2x2) (k_wgrad_wino); shapes the native side refuses
-    (MSGM_E_UNSUPPORTED) take the direct kernel, as they do with wino=False."""
+    wino: prefer Winograd F(3x3, 2x2) (k_wgrad_wino) for a 2-D 3x3 stride-1 "same" gradient; any other shape runs the
+    direct kernel, as it does with wino=False."""
     taps = geom.KH * geom.KW
     if dbias is not None and (dbias.numel() != Cout or n_bias <= 0 or n_bias > geom.N):
         raise MsgmError("wgrad: bad bias-gradient arguments")
@@ -429,35 +418,27 @@ def conv_wgrad(geom: L.ConvGeomT, gy: torch.Tensor, src: torch.Tensor, C: int, k
         raise MsgmError("wgrad operands do not match the geometry")
     if dWp.numel() < taps * CoutP * Ktot:
         raise MsgmError("packed gradient too small")
-    import ctypes as C_
     mc = (C_.c_uint16 * len(tapmask_c32))(*tapmask_c32) if tapmask_c32 else None
     mo = (C_.c_uint16 * len(tapmask_co32))(*tapmask_co32) if tapmask_co32 else None
     if (mc is not None and len(mc) < (C + 31) // 32) or (mo is not None and len(mo) < (Cout + 31) // 32):
         raise MsgmError("wgrad: tap masks need one entry per 32-channel block")
     # per-workgroup slabs added in slot order (no float atomics; same bits every run)
-    nb = int(n_bias) if dbias is not None else 0
-    need = max(int(lib().msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, nb, w)) for w in ((1, 0) if wino else (0,)))
+    wino = int(bool(wino))
+    need = int(lib().msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, int(n_bias) if dbias is not None else 0, wino))
     d = DeferredReduces.active
     if d is not None and d.device == gy.device:
         # inside a backward pass that batches its slot reductions: slabs go to the pass's arena, the reduction is described
         # to the pass and runs with all the others in one launch (DeferredReduces.flush)
         ws, nbytes = d.take(need)
         jobs, nj = (L.ReduceJobT * 2)(), C_.c_int32(0)
-        args = (geom, ptr(f32(gy)), ptr(f32(src)), C, koff, ptr(f32(dWp)), Cout, CoutP, Ktot, ptr(dbias), int(n_bias), mc, mo,
-                ws, nbytes, jobs, C_.byref(nj))
-        rc = lib().msgm_conv_wgrad_slabs(*args, 1, stream()) if wino else L.MSGM_E_UNSUPPORTED
-        if rc == L.MSGM_E_UNSUPPORTED:
-            rc = lib().msgm_conv_wgrad_slabs(*args, 0, stream())
-        check(rc, "msgm_conv_wgrad_slabs")
+        check(lib().msgm_conv_wgrad_slabs(geom, ptr(f32(gy)), ptr(f32(src)), C, koff, ptr(f32(dWp)), Cout, CoutP, Ktot,
+                                          ptr(dbias), int(n_bias), mc, mo, ws, nbytes, jobs, C_.byref(nj), wino, stream()),
+              "msgm_conv_wgrad_slabs")
         d.add(jobs, nj.value, (dWp, dbias))
         return
     ws = scratch(gy.device, need, "wgrad")
-    args = (geom, ptr(f32(gy)), ptr(f32(src)), C, koff, ptr(f32(dWp)), Cout, CoutP, Ktot, ptr(dbias), int(n_bias), mc, mo,
-            ptr(ws), ws.numel() * 4)
-    rc = lib().msgm_conv_wgrad_det(*args, 1, stream()) if wino else L.MSGM_E_UNSUPPORTED
-    if rc == L.MSGM_E_UNSUPPORTED:
-        rc = lib().msgm_conv_wgrad_det(*args, 0, stream())
-    check(rc, "msgm_conv_wgrad_det")
+    check(lib().msgm_conv_wgrad_det(geom, ptr(f32(gy)), ptr(f32(src)), C, koff, ptr(f32(dWp)), Cout, CoutP, Ktot, ptr(dbias),
+                                    int(n_bias), mc, mo, ptr(ws), ws.numel() * 4, wino, stream()), "msgm_conv_wgrad_det")
 
 
 class DeferredReduces:

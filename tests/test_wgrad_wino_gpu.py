@@ -5,7 +5,8 @@ GPU: ops.conv_wgrad(..., wino=True) against the float64 reference of tests/layer
 conv_wgrad family (tests/test_layer_census_gpu.py): channel counts 32 / 64 / 128, a second source at a K offset (the
 decoder's concatenation), the folded 2x upsample, sample counts and image sizes whose tiles do not divide the workgroup
 plan, the bias gradient over the primal rows only, per-call and deferred (DeferredReduces) slot reductions; two runs give
-the same bits; a ConvOp whose geometry ops.conv_wino_supported refuses goes back to the direct kernel."""
+the same bits; a ConvOp whose geometry ops.conv_wino_supported refuses goes back to the direct kernel; wino = 1 is a
+preference: on shapes the plan declines the raw ABI runs what wino = 0 runs."""
 import numpy as np
 import pytest
 import torch
@@ -193,3 +194,53 @@ def test_conv_op_routes_wgrad(monkeypatch, supported):
             orig(geom, gys, xs[s], C, o.koff[s], want, o.Cout, o.CoutP, o.Ktot, wino=supported)
         torch.cuda.synchronize()
         assert torch.equal(o.dWp, want)
+
+
+# shapes the Winograd plan declines: the U-Net's 3-channel input conv (2-D 3x3), a 1-D 3-tap, a 1x1
+# (N, n_bias, Hi, Wi, KH, KW, pad, C, Cout)
+DECLINED = [
+    (4, 2, 32, 32, 3, 3, 1, 3, 32),
+    (4, 2, 1, 256, 1, 3, 1, 64, 64),
+    (4, 2, 16, 16, 1, 1, 0, 64, 128),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("deferred", [False, True])
+@pytest.mark.parametrize("N,nb,Hi,Wi,KH,KW,pad,C,Cout", DECLINED)
+def test_wgrad_wino_preference_on_declined_shapes(N, nb, Hi, Wi, KH, KW, pad, C, Cout, deferred):
+    """msgm_conv_wgrad_det / _slabs with wino = 1 on a shape the plan declines: status 0, the workspace of wino = 0, and
+    the weight and bias gradients of wino = 0, bit for bit."""
+    import ctypes as C_
+    from sdeflow_light_amd import ops, _lib as L
+    torch.manual_seed(N * 1000 + Wi + C + Cout)
+    geom = ops.conv_geom(N, Hi, Wi, Hi, Wi, KH, KW, 1, pad)
+    CoutP, Ktot = ops.pad16(Cout), ops.pad16(C)
+    gy = torch.randn(N * Hi * Wi * Cout, device=DEV)
+    x = torch.randn(N * Hi * Wi * C, device=DEV)
+    base = torch.randn(KH * KW * CoutP * Ktot, device=DEV)
+    db0 = torch.randn(Cout, device=DEV)
+    lib = L.lib()
+    need = [int(lib.msgm_conv_wgrad_workspace(geom, C, Cout, CoutP, nb, w)) for w in (0, 1)]
+    assert need[0] == need[1] > 0
+
+    def run(wino):
+        dWp, db = base.clone(), db0.clone()
+        args = (geom, L.ptr(gy), L.ptr(x), C, 0, L.ptr(dWp), Cout, CoutP, Ktot, L.ptr(db), nb, None, None)
+        if deferred:
+            d = ops.DeferredReduces(DEV)
+            ws, nbytes = d.take(need[wino])
+            jobs, nj = (L.ReduceJobT * 2)(), C_.c_int32(0)
+            assert lib.msgm_conv_wgrad_slabs(*args, ws, nbytes, jobs, C_.byref(nj), wino, L.stream()) == 0
+            d.add(jobs, nj.value, None)
+            d.flush()
+        else:
+            ws = torch.empty(need[wino] // 4, device=DEV)
+            assert lib.msgm_conv_wgrad_det(*args, L.ptr(ws), ws.numel() * 4, wino, L.stream()) == 0
+        torch.cuda.synchronize()
+        return dWp, db
+
+    w0, b0 = run(0)
+    w1, b1 = run(1)
+    assert not torch.equal(w0, base) and not torch.equal(b0, db0)
+    assert torch.equal(w1, w0) and torch.equal(b1, b0)
