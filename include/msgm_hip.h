@@ -207,7 +207,7 @@ int msgm_counter_inc(int64_t* ctr, msgm_stream_t stream);
 /* Parameters are the reference state_dict tensors, PyTorch layout:
  *   W1 (128, in), b1 (128), W2 (128,128), b2, W3 (128,128), b3, W4 (d,128), b4 (d)
  * with in = d + 1 (premodule None) or d + 2 (NormalizeLogRadius: [x^, log r, t]).
- * Supported: hidden 128, d <= 30. */
+ * Supported: hidden 128, 1 <= d <= 128 (d > 30 runs the extra-wide kernel class). */
 typedef struct {
   const float* W1; const float* b1;
   const float* W2; const float* b2;

@@ -90,8 +90,8 @@ class MLP(nn.Module, FlatParamMixin):
         if act is not None and not isinstance(act, Swish):
             raise MsgmError("fused MLP kernel implements Swish only")
         assert premodule is None or premodule in ["NormalizeLogRadius"]
-        if input_dim > 30:
-            raise MsgmError("fused MLP kernel supports input_dim <= 30")
+        if not 1 <= input_dim <= 128:
+            raise MsgmError(f"fused MLP kernel supports 1 <= input_dim <= 128 (the hidden width), got {input_dim}")
         self.input_dim, self.index_dim, self.hidden_dim = input_dim, index_dim, hidden_dim
         self.output_dim = input_dim
         self.premodule = premodule

@@ -140,6 +140,7 @@ __device__ __forceinline__ float swish0(float z) { return z * __builtin_amdgcn_r
 // address arithmetic out of the vector registers: with flat loads hipcc hoists a 64-bit address per (matrix, k-group)
 // out of the persistent tile loop — 32+ VGPRs — and spills.
 typedef __amdgpu_buffer_rsrc_t wrsrc_t;
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ wrsrc_t make_wrsrc(const float* W) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, HID * HID * 4, 0x00020000);
 }
@@ -862,6 +863,567 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
   }
 }
 
+// ============================================================ the extra-wide class (31 <= d <= 128)
+// Once d can reach 128, layers 1 and 4 have the shape of layers 2 and 3 (128 x <= 132 and <= 128 x 128) and are run
+// the same way: their weight fragments are streamed from L2 by buffer loads (nothing but activations and biases sits
+// in LDS), and every wave owns output features of layer 4 too — row tiles w and w + 4, so d = 32 already spreads over
+// two waves — instead of the narrow classes' K-split + LDS partial sum.  The loss phase reads a and adot from an LDS
+// image of layer 4's output; the layer-4 dgrad is the transposed-A path with K = d padded to 16.  K of layer 1
+// (in_dim) and of the layer-4 backward (d) is a run-time count of k-groups / k-tiles, so the work follows d.
+// Registers: dW2 and dW3 are resident accumulators as in k_mlp; dW4 and dW1 (with them resident too the kernel
+// spills) accumulate in the workgroup's own gradient slab: the wave's slice is read into registers a block at a time,
+// extended by the tile's product and written back.  Only this lane ever touches those slab words, so no atomics, and
+// the summation order is fixed.
+#define XP 148   // pitch of an h0 row: in_dim <= 130 -> 9 k-groups of 16 (144) + 4
+
+template <int MODE>
+struct MlpLdsXW {
+  static constexpr bool TRAIN = MODE == 2;
+  static constexpr int SPT = TRAIN ? 16 : 32;      // samples per tile
+  // raw input buffer: y | v (pitch d), t, cst; u is read straight from global memory by the loss phase
+  static constexpr int RY = 0;
+  static constexpr int RV = RY + SPT * HID;
+  static constexpr int RT = RV + (TRAIN ? SPT * HID : 0);
+  static constexpr int RC = RT + 32;
+  static constexpr int RAWN = RC + 16;
+  static constexpr int X = 0;
+  static constexpr int Y = X + 32 * ACT_P;
+  static constexpr int Z = Y + 32 * ACT_P;                     // train: h3, then zbar2 (inference: h3 goes to X|Y)
+  static constexpr int U = Z + (TRAIN ? 32 * ACT_P : 0);       // train: layer-4 output image, then zbar3, then zbar1
+  static constexpr int ABAR = U + (TRAIN ? 32 * ACT_P : 0);    // train: cotangent of layer 4's output [sample][o]
+  static constexpr int H0 = ABAR + (TRAIN ? 32 * ACT_P : 0);   // double-buffered (built one tile ahead)
+  static constexpr int B1 = H0 + 2 * 32 * XP;
+  static constexpr int B2 = B1 + HID;
+  static constexpr int B3 = B2 + HID;
+  static constexpr int B4 = B3 + HID;
+  static constexpr int RED = B4 + HID;
+  static constexpr int RAW = RED + 64;
+  static constexpr int FLOATS = RAW + 2 * RAWN;
+  static constexpr int BYTES = FLOATS * 4;
+  static_assert(BYTES <= 160 * 1024, "the extra-wide carve must fit the 160 KiB of LDS of a CU");
+};
+
+// Wait states written out after the last MFMAs of a loop with run-time trip count: their results are read by VALU
+// code or stores behind a branch target, where hipcc has been seen to insert none.
+__device__ __forceinline__ void mfma_drain() {
+  asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// acc[it][ck] += sum_{g < ng} A(it, g) . buf[ck*16+il][16g + 4q + r] for the row tiles it < nit (both wave-uniform):
+// the A fragments come from `afrag` (buffer loads, two k-groups ahead), the B operand from LDS one k-group ahead.
+template <int IT, int GMAX, typename AF>
+__device__ __forceinline__ void gemm_xw(AF afrag, const float* buf, int pitch, int il, int q, f32x4 (&acc)[IT][2],
+                                        int ng, int nit) {
+  f32x4 ring[3][IT];
+  const float* bp0 = buf + il * pitch + 4 * q;
+  const float* bp1 = buf + (16 + il) * pitch + 4 * q;
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int it = 0; it < IT; ++it) ring[j][it] = (j < ng && it < nit) ? afrag(it, j) : f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 bn0 = *reinterpret_cast<const f32x4*>(bp0), bn1 = *reinterpret_cast<const f32x4*>(bp1);
+#pragma unroll
+  for (int g = 0; g < GMAX; ++g) {
+    if (g >= ng) continue;
+    const f32x4 b0 = bn0, b1 = bn1;
+    if (g + 2 < ng) {
+#pragma unroll
+      for (int it = 0; it < IT; ++it)
+        if (it < nit) ring[(g + 2) % 3][it] = afrag(it, g + 2);
+    }
+    if (g + 1 < ng) {
+      bn0 = *reinterpret_cast<const f32x4*>(bp0 + 16 * (g + 1));
+      bn1 = *reinterpret_cast<const f32x4*>(bp1 + 16 * (g + 1));
+    }
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+      if (it >= nit) continue;
+      const f32x4 a = ring[g % 3][it];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[it][0] = mfma16(a[r], b0[r], acc[it][0]);
+        acc[it][1] = mfma16(a[r], b1[r], acc[it][1]);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  mfma_drain();
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
+  constexpr int NW = 4, NT = 256, IT = 2, FW = 32;
+  constexpr bool TRN = MODE == MODE_TRAIN;
+  constexpr int SPT = TRN ? 16 : 32;
+  constexpr int KT1 = 9;              // k-tiles of dW1 (in_dim <= 130)
+  using LO = MlpLdsXW<MODE>;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x;
+  const int w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
+  const int d = A.P.d, in_dim = A.in_dim;
+  const int fb = FW * w;
+  // Lane-dependent offsets of the streamed operands are derived from lane_v, which the tile loop re-defines opaquely
+  // every iteration: otherwise hipcc hoists every (matrix, k-group, row) offset and mask out of the persistent loop as
+  // a loop invariant — over a hundred registers — and spills.
+  int lane_v = lane;
+  const int ng1 = (in_dim + 15) >> 4;                          // k-groups of layer 1 = k-tiles of dW1
+  const int nk4 = (d + 15) >> 4;                               // 16-output tiles of layer 4
+  const int nit4 = (d > 16 * w ? 1 : 0) + (d > 16 * (w + NW) ? 1 : 0);   // this wave's layer-4 row tiles (w, w + 4)
+  float* X = lds + LO::X; float* Y = lds + LO::Y; float* Z = lds + LO::Z; float* U = lds + LO::U;
+  float* ABAR = lds + LO::ABAR; float* H0 = lds + LO::H0;
+  float* B1s = lds + LO::B1; float* B2s = lds + LO::B2; float* B3s = lds + LO::B3; float* B4s = lds + LO::B4;
+  float* RED = lds + LO::RED; float* RAW0 = lds + LO::RAW;
+
+  f32x4 dW2[IT][8], dW3[IT][8], db1[IT], db2[IT], db3[IT];
+  float db4[8];                       // thread (sample c, output lane ol) of the loss phase: outputs 16 ot + ol
+  float loss_acc = 0.f;
+  if (TRN) {
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { dW2[it][k] = f32x4{0, 0, 0, 0}; dW3[it][k] = f32x4{0, 0, 0, 0}; }
+      db1[it] = f32x4{0, 0, 0, 0}; db2[it] = f32x4{0, 0, 0, 0}; db3[it] = f32x4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) db4[k] = 0.f;
+  }
+
+  // ---- input pipeline, as in k_mlp: fetched one tile ahead into registers, parked in LDS a phase later
+  constexpr int NR = SPT * HID / NT;
+  float pf_y[NR], pf_v[NR], pf_t = 0.f, pf_c = 0.f;
+  const int64_t etot = A.B * d;
+  auto raw_issue = [&](int64_t tl, int step = 0) {
+    const int64_t e0 = tl * SPT * d;
+    const int cnt = SPT * d;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const int e = (w << 6) + lane_v + NT * k;
+      const bool ok = e < cnt && e0 + e < etot;
+      if (MODE == MODE_EM) pf_y[k] = ok ? __hip_atomic_load(A.y + e0 + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+      else pf_y[k] = ok ? A.y[e0 + e] : 0.f;
+      if (TRN) pf_v[k] = ok ? A.v[e0 + e] : 0.f;
+    }
+    if (tid < SPT) {
+      const int64_t smp = tl * SPT + tid;
+      pf_t = smp < A.B ? (A.t ? A.t[smp] : ((MODE == MODE_EM && A.ts) ? A.ts[step] : A.t_scalar)) : 0.f;
+      if (TRN) pf_c = (smp < A.B && A.u && A.cst) ? A.cst[smp] : 0.f;
+    }
+  };
+  auto raw_commit = [&](float* R) {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const int e = (w << 6) + lane_v + NT * k;
+      R[LO::RY + e] = pf_y[k];
+      if (TRN) R[LO::RV + e] = pf_v[k];
+    }
+    if (tid < SPT) { R[LO::RT + tid] = pf_t; if (TRN) R[LO::RC + tid] = pf_c; }
+  };
+  // h0 (and its tangent) of tile tl, by ALL threads: GS = NT / SPT threads per sample row, the norm of
+  // NormalizeLogRadius meets by shuffle within the group.  Same formulas as k_mlp's build_h0 (NN.py:56-70,113-119).
+  constexpr int GS = NT / SPT;
+  auto build_h0 = [&](float* H0b, const float* R, int64_t tl) {
+    const int tv = (w << 6) + lane_v;
+    const int l = tv / GS, sub = tv % GS;
+    const int64_t smp = tl * SPT + l;
+    const bool live = smp < A.B;
+    float* hp = H0b + l * XP;
+    float* ht = H0b + (16 + l) * XP;
+    float tt = 0.f;
+    if (live) {
+      tt = R[LO::RT + l];
+      if (MODE == MODE_EM) tt = A.T - tt;
+    }
+    const float* yr = R + LO::RY + l * d;
+    const float* vr = R + LO::RV + l * d;
+    if (A.P.premodule == 0) {
+      for (int i = sub; i < d; i += GS) {
+        hp[i] = yr[i];
+        if (TRN) ht[i] = vr[i];
+      }
+      if (sub == 0) { hp[d] = tt; if (TRN) ht[d] = 0.f; }
+    } else {
+      float ss = 0.f, yv = 0.f;
+      for (int i = sub; i < d; i += GS) {
+        const float yi = live ? yr[i] : 1.0f;
+        ss += yi * yi;
+        if (TRN) yv += yi * vr[i];
+      }
+#pragma unroll
+      for (int m = GS / 2; m > 0; m >>= 1) { ss += __shfl_xor(ss, m, 64); if (TRN) yv += __shfl_xor(yv, m, 64); }
+      const float nr = sqrtf(ss);
+      const float r = nr + 1e-6f;
+      const float rdot = yv / nr;
+      for (int i = sub; i < d; i += GS) {
+        const float yi = live ? yr[i] : 1.0f;
+        hp[i] = yi / r;
+        if (TRN) ht[i] = vr[i] / r - yi * rdot / (r * r);
+      }
+      if (sub == 0) {
+        hp[d] = logf(r);
+        hp[d + 1] = tt;
+        if (TRN) { ht[d] = rdot / r; ht[d + 1] = 0.f; }
+      }
+    }
+  };
+
+  // ---- weight fragments.  W1 has pitch in_dim, W4 has d rows.  A lane whose element lies outside the matrix (a column
+  // >= in_dim, a row >= d) gets a voffset past the buffer: it fetches nothing and reads an exact zero.  (The range
+  // check does not cover the scalar offset, so the out-of-range lanes are moved in the voffset.)
+  const wrsrc_t R1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.P.W1), 0, HID * in_dim * 4, 0x00020000);
+  const wrsrc_t R2 = make_wrsrc(A.P.W2), R3 = make_wrsrc(A.P.W3);
+  const wrsrc_t R4 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.P.W4), 0, d * HID * 4, 0x00020000);
+  constexpr int OFF_NONE = 0x7ffffff0;   // past every buffer here
+  auto af1 = [&](int it, int g) {         // A[r] = W1[fb+16it+il][16g+4q+r]
+    const int il_ = lane_v & 15, q_ = lane_v >> 4;
+    const int voff1 = ((fb + il_) * in_dim + 4 * q_) * 4;
+    f32x4 v;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int o = 16 * g + 4 * q_ + r < in_dim ? voff1 + 4 * r : OFF_NONE;
+      v[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(R1, o, (16 * it * in_dim + 16 * g) * 4, 0));
+    }
+    return v;
+  };
+  auto af4 = [&](int it, int g) {         // A[r] = W4[16(w+4it)+il][16g+4q+r]: this wave's output rows
+    const int il_ = lane_v & 15, q_ = lane_v >> 4;
+    const int o = 16 * (w + NW * it) + il_ < d ? ((16 * w + il_) * HID + 4 * q_) * 4 : OFF_NONE;
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R4, o, (64 * it * HID + 16 * g) * 4, 0));
+  };
+  auto af4t = [&](int it, int g) {        // A = W4^T: A[r] = W4[16g+4q+r][fb+16it+il]
+    const int il_ = lane_v & 15, q_ = lane_v >> 4;
+    const int voff4t = (4 * q_ * HID + fb + il_) * 4;
+    f32x4 v;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int o = 16 * g + 4 * q_ + r < d ? voff4t + r * HID * 4 : OFF_NONE;
+      v[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(R4, o, (16 * g * HID + 16 * it) * 4, 0));
+    }
+    return v;
+  };
+
+  // ---- prologue
+  raw_issue(blockIdx.x);
+  WPre pre;
+  prefetch_w<false>(R2, fb, il, q, pre);
+  if (tid < HID) {
+    B1s[tid] = A.P.b1[tid]; B2s[tid] = A.P.b2[tid]; B3s[tid] = A.P.b3[tid];
+    B4s[tid] = tid < d ? A.P.b4[tid] : 0.f;
+  }
+  for (int i = tid; i < 2 * 32 * XP; i += NT) H0[i] = 0.f;
+  raw_commit(RAW0);
+  __syncthreads();
+  build_h0(H0, RAW0, blockIdx.x);
+  __syncthreads();
+
+  f32x4 z1[IT][2];
+  auto layer1 = [&](const float* H0b, float* dst) {
+    f32x4 h1[IT][2];
+#pragma unroll
+    for (int it = 0; it < IT; ++it) { z1[it][0] = f32x4{0, 0, 0, 0}; z1[it][1] = f32x4{0, 0, 0, 0}; }
+    gemm_xw<IT, KT1>(af1, H0b, XP, il, q, z1, ng1, IT);
+    bias_swish<TRN, IT>(z1, h1, B1s, fb, q, 0);
+    store_act<IT>(dst, fb, il, q, h1);
+  };
+  layer1(H0, X);
+  __syncthreads();
+
+  const int64_t n_tiles = (A.B + SPT - 1) / SPT;
+  const float ca = 1.0f - 0.5f * A.lmbd;
+  int cur = 0;
+  float* slab = TRN ? A.slabs + (int64_t)blockIdx.x * slab_stride(A.n_params) : nullptr;
+  const int64_t oW4 = (int64_t)HID * in_dim + HID + 2 * ((int64_t)HID * HID + HID);
+  // the slab's dW1 / dW4 words by buffer loads / stores (one per-lane offset per row; a masked-off word gets an offset
+  // past the slab, where a load reads 0 and a store is dropped)
+  const wrsrc_t RS = __builtin_amdgcn_make_buffer_rsrc(slab, 0, TRN ? (int)(slab_stride(A.n_params) * 4) : 0, 0x00020000);
+  // dW1[fb + 4q][il] (+ r rows, + (it, kt) scalar) and dW4[o = il][fb + 4q] (+ (it, kt) scalar)
+  auto vo1 = [&] { return (((fb + 4 * (lane_v >> 4)) * in_dim + (lane_v & 15)) * 4); };
+  auto vo4 = [&] { return (int)((oW4 + (int64_t)(lane_v & 15) * HID + fb + 4 * (lane_v >> 4)) * 4); };
+  const int n_steps = (MODE == MODE_EM && A.n_steps > 1) ? A.n_steps : 1;
+  int step = 0;
+  for (int64_t tile = blockIdx.x; tile < n_tiles;) {
+    asm volatile("" : "+v"(lane_v));
+    const int64_t s_base = tile * SPT;
+    int64_t ntile = tile + gridDim.x;
+    int nstep = step;
+    if (ntile >= n_tiles) { ++nstep; ntile = nstep < n_steps ? (int64_t)blockIdx.x : n_tiles; }
+    const float* H0c = H0 + cur * 32 * XP;
+    float* H0n = H0 + (cur ^ 1) * 32 * XP;
+    const float* Rc = RAW0 + cur * LO::RAWN;
+    float* Rn = RAW0 + (cur ^ 1) * LO::RAWN;
+    float* Xc = cur ? Y : X;
+    float* Yc = cur ? X : Y;
+    f32x4 z2[IT][2], z3[IT][2], z4[IT][2], h[IT][2];
+    cur ^= 1;
+
+    // ---- layer 2
+#pragma unroll
+    for (int it = 0; it < IT; ++it) { z2[it][0] = f32x4{0, 0, 0, 0}; z2[it][1] = f32x4{0, 0, 0, 0}; }
+    if (!TRN) raw_issue(ntile, nstep);
+    gemm128<false, (TRN ? 1 : 2), IT>(R2, pre, Xc, fb, il, q, z2, B2s, h);
+    prefetch_w<false>(R3, fb, il, q, pre);
+    bias_swish<TRN, IT>(z2, h, B2s, fb, q, GemmTail<IT>::FIRST);
+    store_act<IT>(Yc, fb, il, q, h);
+    if (!TRN) raw_commit(Rn);
+    lds_barrier();
+
+    // ---- layer 3; h3 -> Z (train) / Xc (inference: h1 is dead)
+#pragma unroll
+    for (int it = 0; it < IT; ++it) { z3[it][0] = f32x4{0, 0, 0, 0}; z3[it][1] = f32x4{0, 0, 0, 0}; }
+    if (!TRN) build_h0(H0n, Rn, ntile);
+    else raw_issue(ntile);
+    gemm128<false, (TRN ? 1 : 2), IT>(R3, pre, Yc, fb, il, q, z3, B3s, h);
+    if (TRN) prefetch_w<true>(R3, fb, il, q, pre);
+    else prefetch_w<false>(R2, fb, il, q, pre);
+    bias_swish<TRN, IT>(z3, h, B3s, fb, q, GemmTail<IT>::FIRST);
+    float* H3 = TRN ? Z : Xc;
+    store_act<IT>(H3, fb, il, q, h);
+    if (TRN) raw_commit(Rn);
+    lds_barrier();
+
+    // ---- layer 4: this wave's output row tiles 16(w + 4it), K = 128
+#pragma unroll
+    for (int it = 0; it < IT; ++it) { z4[it][0] = f32x4{0, 0, 0, 0}; z4[it][1] = f32x4{0, 0, 0, 0}; }
+    gemm_xw<IT, 8>(af4, H3, ACT_P, il, q, z4, 8, nit4);
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+      if (it >= nit4) continue;
+      const int o0 = 16 * (w + NW * it);
+      const f32x4 bb = *reinterpret_cast<const f32x4*>(B4s + o0 + 4 * q);
+      z4[it][0] += bb;
+      if (!TRN) z4[it][1] += bb;
+    }
+
+    if (!TRN) {
+      // outputs straight from the accumulators: lane (sample 16ck + il), register r -> output o0 + 4q + r
+#pragma unroll
+      for (int it = 0; it < IT; ++it) {
+        if (it >= nit4) continue;
+        const int o0 = 16 * (w + NW * it);
+#pragma unroll
+        for (int ck = 0; ck < 2; ++ck)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int c = 16 * ck + il, o = o0 + 4 * q + r;
+            const int64_t smp = s_base + c;
+            if (o < d && smp < A.B) {
+              const float a = z4[it][ck][r];
+              const int64_t e = smp * d + o;
+              if (MODE == MODE_FWD) {
+                A.out[e] = a;
+              } else {
+                const float s = A.T - Rc[LO::RT + c];
+                const float beta = sde_beta(A.b0, A.b1, s);
+                const float sb = sqrtf(beta);
+                const float x = Rc[LO::RY + c * d + o];
+                const float zz = A.z ? A.z[e] : philox_normal1(A.rng, A.rng_step + (uint64_t)step, RNG_STREAM_DW, (uint64_t)e);
+                const float mu = ca * (sb * a) - (-0.5f * beta * x);
+                A.out[e] = x + (mu * A.delta + (sqrtf(1.0f - A.lmbd) * sb) * (A.sqrt_delta * zz));
+              }
+            }
+          }
+      }
+      layer1(H0n, Yc);                                   // next item's h1 (h2 is dead)
+      if (n_steps > 1) __syncthreads();                  // + vmcnt(0): this tile's new x must leave the CU before it is re-read
+      else lds_barrier();
+      tile = ntile; step = nstep;
+      continue;
+    }
+
+    if (TRN) {
+      // layer-4 output image [sample][o] for the loss phase
+#pragma unroll
+      for (int it = 0; it < IT; ++it) {
+        if (it >= nit4) continue;
+        const int o0 = 16 * (w + NW * it);
+#pragma unroll
+        for (int ck = 0; ck < 2; ++ck) *reinterpret_cast<f32x4*>(U + (ck * 16 + il) * ACT_P + o0 + 4 * q) = z4[it][ck];
+      }
+      lds_barrier();
+
+      // ---- loss: thread (c = sample, ol) takes outputs 16 ot + ol; the sample's terms meet by shuffle
+      {
+        const int tv = (w << 6) + lane_v;
+        const int c = tv >> 4, ol = tv & 15;
+        const int64_t smp = s_base + c;
+        const bool live = smp < A.B;
+        const float wgt = live ? A.inv_batch : 0.f;
+        float beta = 0.f, sb = 0.f;
+        if (!A.u) { beta = sde_beta(A.b0, A.b1, Rc[LO::RT + c]); sb = sqrtf(beta); }
+        float uo[8];
+#pragma unroll
+        for (int ot = 0; ot < 8; ++ot) {
+          const int o = 16 * ot + ol;
+          uo[ot] = (A.u && live && o < d) ? A.u[smp * d + o] : 0.f;
+        }
+        float lj = 0.f;
+#pragma unroll
+        for (int ot = 0; ot < 8; ++ot) {
+          if (ot >= nk4) continue;
+          const int o = 16 * ot + ol;
+          const bool oo = o < d;
+          const float a = oo ? U[c * ACT_P + o] : 0.f, ad = oo ? U[(16 + c) * ACT_P + o] : 0.f;
+          float adb;
+          if (A.u) {
+            lj += ad * uo[ot] + 0.5f * a * a;
+            adb = uo[ot] * wgt;
+          } else {
+            const float vo = oo ? Rc[LO::RV + c * d + o] : 0.f;
+            lj += vo * (sb * ad + 0.5f * beta * vo) + 0.5f * a * a;
+            adb = sb * vo * wgt;
+          }
+          const float ab = a * wgt;
+          ABAR[c * ACT_P + o] = ab;
+          ABAR[(16 + c) * ACT_P + o] = adb;
+          db4[ot] += ab;
+        }
+#pragma unroll
+        for (int m = 8; m > 0; m >>= 1) lj += __shfl_xor(lj, m, 64);
+        if (ol == 0 && live) {
+          if (A.u && A.cst) lj += Rc[LO::RC + c];
+          loss_acc += lj;
+          if (A.loss_per) A.loss_per[smp] = lj;
+        }
+      }
+      build_h0(H0n, Rn, ntile);                          // next tile's layer-1 operand
+      lds_barrier();
+
+      // ---- layer-4 backward: dgrad (W4^T, K = d), dW4 into the slab, Swish' on layer 3
+      const bool first = tile == (int64_t)blockIdx.x;
+      f32x4 g[IT][2];
+#pragma unroll
+      for (int it = 0; it < IT; ++it) { g[it][0] = f32x4{0, 0, 0, 0}; g[it][1] = f32x4{0, 0, 0, 0}; }
+      gemm_xw<IT, 8>(af4t, ABAR, ACT_P, il, q, g, nk4, IT);
+      // dW4^T[feat][o] += h3 . abar through the slab, in blocks of two 16-output tiles: lane (o = 16kt + il, q),
+      // register r -> feature fb + 16it + 4q + r
+#pragma unroll
+      for (int kb = 0; kb < 8; kb += 2) {
+        if (kb >= nk4) continue;
+        f32x4 dW4[IT][2];
+#pragma unroll
+        for (int it = 0; it < IT; ++it)
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt) {
+            const int v = (!first && 16 * (kb + kt) + (lane_v & 15) < d) ? vo4() : OFF_NONE;
+            dW4[it][kt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(RS, v, (16 * (kb + kt) * HID + 16 * it) * 4, 0));
+          }
+        wgrad<2, IT>(Z, ABAR + 16 * kb, ACT_P, fb, il, q, dW4);
+        mfma_drain();
+#pragma unroll
+        for (int it = 0; it < IT; ++it)
+#pragma unroll
+          for (int kt = 0; kt < 2; ++kt) {
+            const int v = 16 * (kb + kt) + (lane_v & 15) < d ? vo4() : OFF_NONE;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, dW4[it][kt]), RS, v, (16 * (kb + kt) * HID + 16 * it) * 4, 0);
+          }
+      }
+      swish_bwd_inplace<IT>(z3, g);                      // Swish' of layer 3
+#pragma unroll
+      for (int it = 0; it < IT; ++it) db3[it] += g[it][0];
+      store_act<IT>(U, fb, il, q, g);
+      lds_barrier();
+
+      // ---- dgrad layer 3 (W3^T), dW3, Swish' on layer 2
+#pragma unroll
+      for (int it = 0; it < IT; ++it) { g[it][0] = f32x4{0, 0, 0, 0}; g[it][1] = f32x4{0, 0, 0, 0}; }
+      gemm128<true, 0, IT>(R3, pre, U, fb, il, q, g, nullptr, h);
+      prefetch_w<true>(R2, fb, il, q, pre);
+      wgrad_swish<8, IT>(U, Yc, ACT_P, fb, il, q, dW3, z2, g);
+#pragma unroll
+      for (int it = 0; it < IT; ++it) db2[it] += g[it][0];
+      store_act<IT>(Z, fb, il, q, g);
+      lds_barrier();
+
+      // ---- dgrad layer 2 (W2^T), dW2, Swish' on layer 1; dW1 (K = in_dim) into the slab; next tile's layer 1
+#pragma unroll
+      for (int it = 0; it < IT; ++it) { g[it][0] = f32x4{0, 0, 0, 0}; g[it][1] = f32x4{0, 0, 0, 0}; }
+      gemm128<true, 0, IT>(R2, pre, Z, fb, il, q, g, nullptr, h);
+      prefetch_w<false>(R2, fb, il, q, pre);
+      wgrad_swish<8, IT>(Z, Xc, ACT_P, fb, il, q, dW2, z1, g);
+#pragma unroll
+      for (int it = 0; it < IT; ++it) db1[it] += g[it][0];
+      store_act<IT>(U, fb, il, q, g);
+      // dW1 (this wave's own zbar1 columns: no barrier in between) through the slab, in blocks of one row tile x three
+      // k-tiles (48 columns of h0; the columns past in_dim are zeros and are not stored):
+      // lane (k = 16kt + il, q), register r -> row fb + 16it + 4q + r
+#pragma unroll
+      for (int it = 0; it < IT; ++it)
+#pragma unroll
+        for (int kb = 0; kb < KT1; kb += 3) {
+          if (kb >= ng1) continue;
+          f32x4 dW1[1][3];
+#pragma unroll
+          for (int kt = 0; kt < 3; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int v = (!first && 16 * (kb + kt) + (lane_v & 15) < in_dim) ? vo1() + r * in_dim * 4 : OFF_NONE;
+              dW1[0][kt][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(RS, v, (16 * it * in_dim + 16 * (kb + kt)) * 4, 0));
+            }
+          wgrad<3, 1>(U, H0c + 16 * kb, XP, fb + 16 * it, il, q, dW1);
+          mfma_drain();
+#pragma unroll
+          for (int kt = 0; kt < 3; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int v = 16 * (kb + kt) + (lane_v & 15) < in_dim ? vo1() + r * in_dim * 4 : OFF_NONE;
+              float x = dW1[0][kt][r];
+              asm volatile("" : "+v"(x));   // without it hipcc (ROCm 7.2) stores register 0 of the fragment for all four r
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, x), RS, v, (16 * it * in_dim + 16 * (kb + kt)) * 4, 0);
+            }
+        }
+      layer1(H0n, Yc);
+      lds_barrier();
+    }
+    tile = ntile; step = nstep;
+  }
+
+  // ---- epilogue (train): the rest of this workgroup's gradient slab (dW1 and dW4 are already there)
+  if (TRN) {
+    const int64_t ob1 = (int64_t)HID * in_dim, oW2 = ob1 + HID, ob2 = oW2 + HID * HID,
+                  oW3 = ob2 + HID, ob3 = oW3 + HID * HID, ob4 = oW4 + (int64_t)d * HID;
+#pragma unroll
+    for (int it = 0; it < IT; ++it)
+#pragma unroll
+      for (int kt = 0; kt < 8; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = fb + 16 * it + 4 * q + r, col = 16 * kt + il;
+          slab[oW2 + row * HID + col] = dW2[it][kt][r];
+          slab[oW3 + row * HID + col] = dW3[it][kt][r];
+        }
+#pragma unroll
+    for (int it = 0; it < IT; ++it)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float s1 = db1[it][r], s2 = db2[it][r], s3 = db3[it][r];
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); s3 += __shfl_xor(s3, o, 64); }
+        if (il == 0) {
+          const int feat = fb + 16 * it + 4 * q + r;
+          slab[ob1 + feat] = s1; slab[ob2 + feat] = s2; slab[ob3 + feat] = s3;
+        }
+      }
+    __syncthreads();
+    {
+      const int c = tid >> 4, ol = tid & 15;
+#pragma unroll
+      for (int ot = 0; ot < 8; ++ot) X[c * HID + 16 * ot + ol] = db4[ot];   // X is free: 16 x 128 per-sample-lane sums
+    }
+    if ((tid & 15) == 0) RED[tid >> 4] = loss_acc;
+    __syncthreads();
+    if (tid < d) {
+      float s = 0.f;
+      for (int j = 0; j < 16; ++j) s += X[j * HID + tid];
+      slab[ob4 + tid] = s;
+    }
+    if (tid == 0) {
+      float s = 0.f;
+      for (int j = 0; j < 16; ++j) s += RED[j];
+      slab[A.n_params] = s;
+    }
+  }
+}
+
 // grads[p] = sum_wg slab[wg][p]; element n_params = loss sum (x inv_batch -> mean).
 // 64 parameters (16 quads) x 16 slab groups per block, 16-B loads, fixed summation order (see the kernel).
 // ADAM: one thread per parameter then applies the fused Adam update
@@ -936,11 +1498,23 @@ static void set_lds_attr() {
   (void)once;
 }
 
-// workgroups that fit one CU with this carve (inference modes: 2, or 3 with the tiny carve)
+// workgroups that fit one CU with this carve (inference modes: 2, or 3 with the tiny carve, 1 with the extra-wide one)
 static bool mlp_tiny(const MlpArgs& A) { return A.in_dim <= 4 && A.P.d <= 4; }
+static bool mlp_xwide(const MlpArgs& A) { return A.P.d > 30 || A.in_dim > 32; }
+static int64_t mlp_wg_per_cu(const MlpArgs& A) { return mlp_xwide(A) ? 1 : (mlp_tiny(A) ? 3 : 2); }
 
 template <int MODE>
 static int launch_mlp(const MlpArgs& A, int grid, hipStream_t st) {
+  if (mlp_xwide(A)) {
+    static const int once = [] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mlp_xw<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                MlpLdsXW<MODE>::BYTES);
+      return 0;
+    }();
+    (void)once;
+    hipLaunchKernelGGL((k_mlp_xw<MODE>), dim3(grid), dim3(256), MlpLdsXW<MODE>::BYTES, st, A);
+    return msgm_check_launch();
+  }
   const bool wide = A.in_dim > 16 || A.P.d > 16;
   constexpr int nw_w = MlpCfg<MODE, true>::NW, nw_n = MlpCfg<MODE, false>::NW;
   constexpr size_t lds_wide = MlpLds<MODE, true, nw_w>::BYTES, lds_narrow = MlpLds<MODE, false, nw_n>::BYTES;
@@ -957,7 +1531,7 @@ static int launch_mlp(const MlpArgs& A, int grid, hipStream_t st) {
 
 static int fill_common(MlpArgs& A, const msgm_mlp_params_t* P, int64_t B) {
   if (!P || !P->W1 || !P->b1 || !P->W2 || !P->b2 || !P->W3 || !P->b3 || !P->W4 || !P->b4 || B <= 0) return MSGM_E_BADARG;
-  if (P->d < 1 || P->d > 30 || (P->premodule != 0 && P->premodule != 1)) return MSGM_E_UNSUPPORTED;
+  if (P->d < 1 || P->d > HID || (P->premodule != 0 && P->premodule != 1)) return MSGM_E_UNSUPPORTED;
   A.P = *P; A.B = B;
   A.in_dim = P->d + 1 + (P->premodule ? 1 : 0);
   A.in4 = (A.in_dim + 3) / 4; A.d4 = (P->d + 3) / 4;
@@ -983,7 +1557,7 @@ int msgm_mlp_forward(const msgm_mlp_params_t* P, const float* y, const float* t,
   if (!y || !t || !a) return MSGM_E_BADARG;
   A.y = y; A.t = t; A.out = a;
   const int64_t tiles = (B + 31) / 32;
-  const int64_t cap = (mlp_tiny(A) ? 3 : 2) * MLP_MAX_GRID;   // forward modes: two (tiny carve: three) workgroups per CU
+  const int64_t cap = mlp_wg_per_cu(A) * MLP_MAX_GRID;   // forward modes: two (tiny carve: three, extra-wide: one) workgroups per CU
   return launch_mlp<MODE_FWD>(A, (int)(tiles < cap ? tiles : cap), S(stream));
 }
 
@@ -999,7 +1573,7 @@ int msgm_mlp_em_step(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm
   A.delta = delta; A.sqrt_delta = (float)sqrt((double)delta); A.lmbd = lmbd;
   A.z = z; A.rng = rng; A.rng_step = rng_step;
   const int64_t tiles = (B + 31) / 32;
-  const int64_t cap = (mlp_tiny(A) ? 3 : 2) * MLP_MAX_GRID;
+  const int64_t cap = mlp_wg_per_cu(A) * MLP_MAX_GRID;
   return launch_mlp<MODE_EM>(A, (int)(tiles < cap ? tiles : cap), S(stream));
 }
 
@@ -1017,7 +1591,7 @@ int msgm_mlp_em_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm
   A.delta = delta; A.sqrt_delta = (float)sqrt((double)delta); A.lmbd = lmbd;
   A.z = nullptr; A.rng = rng; A.rng_step = rng_step0;
   A.n_steps = n_steps; A.ts = ts;
-  const int64_t cap = (mlp_tiny(A) ? 3 : 2) * MLP_MAX_GRID;
+  const int64_t cap = mlp_wg_per_cu(A) * MLP_MAX_GRID;
   const int64_t grid = tiles / 2 < cap ? tiles / 2 : cap;
   return launch_mlp<MODE_EM>(A, (int)grid, S(stream));
 }

@@ -712,6 +712,81 @@ def g19_dropout():
     save("g19_dropout", **out)
 
 
+def g20_mlp_wide():
+    """The MLP at 31 <= d <= 128 (the extra-wide kernel class).  Weights are rebuilt from oracle.det_params
+    (load_init_like_ on the reference module) and not stored; only their names and shapes are, so the port's
+    state_dict layout can be checked without a GPU."""
+    torch.manual_seed(20)
+    out = {}
+
+    def net_of(d, pre):
+        net = MLP(d, premodule=pre)
+        load_init_like_(net)
+        return net
+
+    for tag, d, pre in (("f31", 31, None), ("f32", 32, None), ("f64n", 64, "NormalizeLogRadius"), ("f128", 128, None)):
+        net = net_of(d, pre)
+        x, t = torch.randn(40, d) * 1.5, torch.rand(40)
+        with torch.no_grad():
+            y = net(x, t)
+        out.update({f"{tag}_x": x, f"{tag}_t": t, f"{tag}_out": y})
+        out[f"{tag}_names"] = np.array(list(net.state_dict()))
+        out[f"{tag}_shapes"] = np.array([list(v.shape) + [0] * (2 - v.dim()) for v in net.state_dict().values()])
+    # ssm(x): full gradients at d = 32, the digest at d = 128 with premodule
+    for tag, d, pre, B, full in (("s32", 32, None, 48, True), ("s128n", 128, "NormalizeLogRadius", 40, False)):
+        rev = PluginReverseSDE(sgm(), net_of(d, pre), Tparam())
+        x, u_t, eps, u_v = torch.randn(B, d) * 1.5, torch.rand(B, 1), torch.randn(B, d), torch.rand(B, d)
+        res = _ssm_case(rev, x, u_t, eps, u_v, full_grads=full)
+        out.update({f"{tag}_x": x, f"{tag}_u_t": u_t, f"{tag}_eps": eps, f"{tag}_u_v": u_v})
+        out.update({f"{tag}_{k}": v for k, v in res.items()})
+    # ssm_loss(t, x, y) of the multiplicative SDE: dense tensor at d = 32, sparse at d = 128
+    for tag, d, dense, B in (("m32d", 32, True, 32), ("m128s", 128, False, 24)):
+        xi = torch.randn(64, d) * 1.5
+        base = msgm(xi, dense=dense, nsf=4)
+        rev = PluginReverseSDE(base, net_of(d, None), Tparam())
+        t_ = torch.rand(B, 1).clamp_min(1e-3)
+        y = torch.randn(B, d) * 1.3
+        u_v = torch.rand(B, d)
+        o = torch.rand
+        torch.rand = lambda *a, **k: u_v.clone()
+        try:
+            rev.zero_grad()
+            per = rev.ssm_loss(t_, y, y.clone().requires_grad_(True))
+            per.mean().backward()
+        finally:
+            torch.rand = o
+        grads = {k: p.grad.detach().clone() for k, p in rev.named_parameters() if p.grad is not None}
+        out.update({f"{tag}_t": t_, f"{tag}_y": y, f"{tag}_u_v": u_v, f"{tag}_per": per.detach(),
+                    f"{tag}_x_init": xi})
+        out.update({f"{tag}_gd_" + k: v for k, v in _grad_digest(grads).items()})
+        if dense:
+            out[f"{tag}_G"] = base.G
+    # three SSM + Adam steps at d = 32 (as g11)
+    B, d = 64, 32
+    rev = PluginReverseSDE(sgm(), net_of(d, None), Tparam())
+    opt = torch.optim.Adam(rev.parameters(), lr=1e-3)
+    xs, uts, epss, uvs, losses = [], [], [], [], []
+    for i in range(3):
+        x, u_t, eps, u_v = torch.randn(B, d) * 1.5, torch.rand(B, 1), torch.randn(B, d), torch.rand(B, d)
+        seq = iter([u_t, eps, u_v])
+        o = (torch.rand, torch.randn_like)
+        torch.rand = lambda *a, **k: next(seq).clone()
+        torch.randn_like = lambda *a, **k: next(seq).clone()
+        try:
+            opt.zero_grad()
+            loss = rev.ssm(x).mean()
+            loss.backward()
+            opt.step()
+        finally:
+            torch.rand, torch.randn_like = o
+        xs.append(x); uts.append(u_t); epss.append(eps); uvs.append(u_v); losses.append(loss.detach())
+    out.update(tr_x=torch.stack(xs), tr_u_t=torch.stack(uts), tr_eps=torch.stack(epss), tr_u_v=torch.stack(uvs),
+               tr_loss=torch.stack(losses))
+    out.update({"tr_final_gd_" + k: v for k, v in _grad_digest({k: v for k, v in rev.state_dict().items()
+                                                              if k not in ("T", "base_sde.T")}).items()})
+    save("g20_mlp_wide", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
