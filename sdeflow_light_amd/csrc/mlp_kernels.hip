@@ -41,11 +41,7 @@ __device__ unsigned long long g_stamps[16];
 // the weight fragments and the next tile's inputs that are deliberately left in flight across phase boundaries;
 // LDS traffic completes in order, so lgkmcnt(0) + s_barrier is all an LDS producer/consumer pair needs.  hipcc's
 // own waitcnt insertion still guards the first use of every in-flight load.
-#ifndef MLP_FULL_BARRIER
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#else
-__device__ __forceinline__ void lds_barrier() { __syncthreads(); }
-#endif
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -162,24 +158,7 @@ __device__ __forceinline__ f32x4 load_afrag(wrsrc_t W, int fb, int il, int q, in
 // (a k-group = 16 MFMAs = 512 cycles of matrix pipe per wave), so only
 // (PF+1) x 8 registers hold weights at any time; `pre` carries groups
 // 0..PF-1 of the NEXT gemm across the phase boundary.
-#ifndef PF
-#define PF 2
-#endif
-#ifndef MLP_HINTS
-#define MLP_HINTS 0
-#endif
-#ifndef MLP_SB
-#define MLP_SB 1
-#endif
-#ifndef MLP_OVL_FWD
-#define MLP_OVL_FWD 1
-#endif
-#ifndef MLP_OVL_BWD
-#define MLP_OVL_BWD 1
-#endif
-#ifndef MLP_STAGGER
-#define MLP_STAGGER 1
-#endif
+constexpr int PF = 2;
 struct WPre { f32x4 a[PF]; };     // fragments j = 0..PF-1 of the next gemm (j = it*8 + g: row tile 0 first)
 
 template <bool TR>
@@ -198,7 +177,7 @@ template <bool TR, int HOOK, int IT>
 __device__ __forceinline__ void gemm128(wrsrc_t W, const WPre& pre, const float* buf, int fb, int il,
                                         int q, f32x4 (&acc)[IT][2], const float* bias_lds, f32x4 (&h)[IT][2]) {
   constexpr int NJ = 8 * IT;
-  constexpr bool OVL = MLP_OVL_FWD && HOOK && IT == 2;   // a second row tile to hide the first one's Swish under
+  constexpr bool OVL = HOOK && IT == 2;   // a second row tile to hide the first one's Swish under
   f32x4 ring[PF + 1];
 #pragma unroll
   for (int j = 0; j < PF; ++j) ring[j] = pre.a[j];
@@ -235,15 +214,11 @@ __device__ __forceinline__ void gemm128(wrsrc_t W, const WPre& pre, const float*
       acc[it][0] = mfma16(a[r], b0[r], acc[it][0]);
       acc[it][1] = mfma16(a[r], b1[r], acc[it][1]);
     }
-    if (MLP_HINTS && OVL && j >= 8 && j < 12) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x002, 6, 0); }
-    }
-    if (MLP_SB) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 // row tiles whose bias + Swish the caller still has to apply after gemm128<.., HOOK != 0, IT>
-template <int IT> struct GemmTail { static constexpr int FIRST = (MLP_OVL_FWD && IT == 2) ? 1 : 0; };
+template <int IT> struct GemmTail { static constexpr int FIRST = IT == 2; };
 
 // bias + (dual) Swish of row tiles [first, IT): train -> h = (s(z), s'(z) zdot); inference -> both halves primal
 template <bool TRAIN, int IT>
@@ -335,7 +310,7 @@ __device__ __forceinline__ void wgrad_core(const float* zb, const float* hb, int
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) nb[kt] = hb[n * hb_pitch + 16 * kt + il];
     }
-    if (SWISH && MLP_OVL_BWD && st < 4 * IT) {
+    if (SWISH && st < 4 * IT) {
       const int it = st >> 2, r = st & 3;
       float s0, s1, s2;
       swish012(z[it][0][r], s0, s1, s2);
@@ -347,22 +322,7 @@ __device__ __forceinline__ void wgrad_core(const float* zb, const float* hb, int
     for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
       for (int it = 0; it < IT; ++it) dW[it][kt] = mfma16(a[it], b[kt], dW[it][kt]);
-    if (MLP_HINTS && SWISH) {
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x002, 3, 0); }
-    }
-    if (MLP_SB) __builtin_amdgcn_sched_barrier(0);
-  }
-  if (SWISH && !MLP_OVL_BWD) {
-#pragma unroll
-    for (int st = 0; st < 4 * IT; ++st) {
-      const int it = st >> 2, r = st & 3;
-      float s0, s1, s2;
-      swish012(z[it][0][r], s0, s1, s2);
-      const float gt = g[it][1][r];
-      g[it][0][r] = g[it][0][r] * s1 + gt * (s2 * z[it][1][r]);
-      g[it][1][r] = gt * s1;
-    }
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 // dual Swish backward in registers, in place: (gP,gT) cotangents of (hP,hT) -> cotangents of (zP,zT)
@@ -390,6 +350,241 @@ __device__ __forceinline__ void wgrad_swish(const float* zbuf, const float* hb, 
   wgrad_core<KT, IT, true>(zbuf, hb, hb_pitch, fb, il, q, dW, z, g);
 }
 
+// ============================================================ phases that the two fused kernels share
+// Each takes the thread's indices (il, q, tid, ...) from its caller: k_mlp_xw derives its own from an opaque lane value.
+template <int IT, int K>
+__device__ __forceinline__ void zero_tiles(f32x4 (&a)[IT][K]) {
+#pragma unroll
+  for (int it = 0; it < IT; ++it)
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[it][k] = f32x4{0, 0, 0, 0};
+}
+template <int IT>
+__device__ __forceinline__ void zero_tiles(f32x4 (&a)[IT]) {
+#pragma unroll
+  for (int it = 0; it < IT; ++it) a[it] = f32x4{0, 0, 0, 0};
+}
+
+// Offsets of the parameters in the flat parameter vector, which is also the layout of a gradient slab:
+// W1 b1 W2 b2 W3 b3 W4 b4, every weight row-major [out][in].
+struct MlpLayout {
+  int64_t oW1, ob1, oW2, ob2, oW3, ob3, oW4, ob4, n_params;
+  __host__ __device__ MlpLayout(int d, int in_dim) {
+    oW1 = 0; ob1 = oW1 + (int64_t)HID * in_dim;
+    oW2 = ob1 + HID; ob2 = oW2 + HID * HID;
+    oW3 = ob2 + HID; ob3 = oW3 + HID * HID;
+    oW4 = ob3 + HID; ob4 = oW4 + (int64_t)d * HID;
+    n_params = ob4 + d;
+  }
+};
+
+// ---- input pipeline: the tile's y / v / u / t / cst chunks (contiguous in global memory) are fetched into
+// registers ONE TILE AHEAD (raw_issue), parked in LDS a phase later (raw_commit) and turned into the layer-1
+// operand h0 at the end of the previous tile (build_h0) — no global-load latency sits on the tile's critical path.
+// A thread holds NR elements of each chunk (element ev + NT k of the tile, ev = its index in the workgroup), and
+// thread tid < SPT the t / cst of sample tid.  STAGE_U: the u chunk travels the same way (else its reader fetches it).
+template <int NR> struct RawRegs { float y[NR], v[NR], u[NR], t = 0.f, c = 0.f; };
+
+template <int MODE, class LO, int NT, bool STAGE_U, int NR>
+__device__ __forceinline__ void raw_issue(const MlpArgs& A, RawRegs<NR>& pf, int ev, int tid, int64_t tl, int step) {
+  constexpr int SPT = LO::SPT;
+  const int d = A.P.d;
+  const int64_t etot = A.B * d;
+  const int64_t e0 = tl * SPT * d;                 // tl past the last tile => e0 >= etot => zeros
+  const int cnt = SPT * d;
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    const int e = ev + NT * k;
+    const bool ok = e < cnt && e0 + e < etot;
+    // EM loop: x was rewritten by THIS workgroup a sweep ago — device-scope load so no stale L1 line is served
+    if (MODE == MODE_EM) pf.y[k] = ok ? __hip_atomic_load(A.y + e0 + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+    else pf.y[k] = ok ? A.y[e0 + e] : 0.f;
+    if (MODE == MODE_TRAIN) {
+      pf.v[k] = ok ? A.v[e0 + e] : 0.f;
+      if (STAGE_U) pf.u[k] = (ok && A.u) ? A.u[e0 + e] : 0.f;
+    }
+  }
+  if (tid < SPT) {
+    const int64_t smp = tl * SPT + tid;
+    pf.t = smp < A.B ? (A.t ? A.t[smp] : ((MODE == MODE_EM && A.ts) ? A.ts[step] : A.t_scalar)) : 0.f;
+    if (MODE == MODE_TRAIN) pf.c = (smp < A.B && A.u && A.cst) ? A.cst[smp] : 0.f;
+  }
+}
+template <int MODE, class LO, int NT, bool STAGE_U, int NR>
+__device__ __forceinline__ void raw_commit(const RawRegs<NR>& pf, float* R, int ev, int tid) {
+  constexpr int SPT = LO::SPT, CHUNK = SPT * LO::DMAX;
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    const int e = ev + NT * k;
+    if (NR * NT == CHUNK || e < CHUNK) {           // (the last round may be a partial one)
+      R[LO::RY + e] = pf.y[k];
+      if (MODE == MODE_TRAIN) R[LO::RV + e] = pf.v[k];
+      if constexpr (MODE == MODE_TRAIN && STAGE_U) R[LO::RU + e] = pf.u[k];
+    }
+  }
+  if (tid < SPT) { R[LO::RT + tid] = pf.t; if (MODE == MODE_TRAIN) R[LO::RC + tid] = pf.c; }
+}
+// h0 (and its tangent) of tile tl from its raw buffer, GS threads per sample row: thread (l, sub) takes the elements
+// sub, sub + GS, .. of row l, and the norm of NormalizeLogRadius meets by shuffle within the group.
+// premodule none: h0 = [y, t], h0dot = [v, 0]                     NN.py:113-119
+// NormalizeLogRadius: h0 = [y/r, log r, t], r = |y| + 1e-6          NN.py:56-70
+template <int MODE, class LO, int GS, int PITCH>
+__device__ __forceinline__ void build_h0(const MlpArgs& A, float* H0b, const float* R, int64_t tl, int l, int sub) {
+  constexpr bool TRN = MODE == MODE_TRAIN;
+  const int d = A.P.d;
+  const int64_t smp = tl * LO::SPT + l;
+  const bool live = smp < A.B;
+  float* hp = H0b + l * PITCH;
+  float* ht = H0b + (16 + l) * PITCH;   // tangent row (train only)
+  float tt = 0.f;
+  if (live) {
+    tt = R[LO::RT + l];
+    if (MODE == MODE_EM) tt = A.T - tt;                                 // s = T - t  SDEs.py:556-557
+  }
+  const float* yr = R + LO::RY + l * d;
+  const float* vr = R + LO::RV + l * d;
+  if (A.P.premodule == 0) {
+    for (int i = sub; i < d; i += GS) {
+      hp[i] = yr[i];
+      if (TRN) ht[i] = vr[i];
+    }
+    if (sub == 0) { hp[d] = tt; if (TRN) ht[d] = 0.f; }
+  } else {
+    float ss = 0.f, yv = 0.f;
+    for (int i = sub; i < d; i += GS) {
+      const float yi = live ? yr[i] : 1.0f;
+      ss += yi * yi;
+      if (TRN) yv += yi * vr[i];
+    }
+#pragma unroll
+    for (int m = GS / 2; m > 0; m >>= 1) { ss += __shfl_xor(ss, m, 64); if (TRN) yv += __shfl_xor(yv, m, 64); }
+    const float nr = sqrtf(ss);
+    const float r = nr + 1e-6f;
+    const float rdot = yv / nr;                                          // d|y| along v
+    for (int i = sub; i < d; i += GS) {
+      const float yi = live ? yr[i] : 1.0f;
+      hp[i] = yi / r;
+      if (TRN) ht[i] = vr[i] / r - yi * rdot / (r * r);
+    }
+    if (sub == 0) {
+      hp[d] = logf(r);
+      hp[d + 1] = tt;
+      if (TRN) { ht[d] = rdot / r; ht[d + 1] = 0.f; }
+    }
+  }
+}
+
+// One hidden layer (2 or 3) of the forward pass: z = W . in (`pre` holds W's first fragments and leaves with those of
+// Wnext, the next gemm's weights, transposed if NEXT_TR), h = Swish(z + bias) (train: and its tangent).
+template <bool TRN, bool NEXT_TR, int IT>
+__device__ __forceinline__ void fwd_hidden(wrsrc_t W, wrsrc_t Wnext, WPre& pre, const float* in, const float* bias_lds,
+                                           int fb, int il, int q, f32x4 (&z)[IT][2], f32x4 (&h)[IT][2]) {
+  zero_tiles(z);
+  gemm128<false, (TRN ? 1 : 2), IT>(W, pre, in, fb, il, q, z, bias_lds, h);
+  prefetch_w<NEXT_TR>(Wnext, fb, il, q, pre);         // head of the next gemm's weights
+  bias_swish<TRN, IT>(z, h, bias_lds, fb, q, GemmTail<IT>::FIRST);
+}
+
+// One hidden layer (3 or 2) of the backward pass.  zb holds the layer's zbar (cotangent of its pre-activation, dual),
+// hb its input activations, z the pre-activations of the layer below:
+//   g = W^T . zbar (dgrad), dW += zbar . hb^T, g <- Swish'(z) g in place (zbar of the layer below), db += g, g -> dst.
+// wgrad_first: the weight gradient (which needs only this wave's zbar columns) runs before the dgrad, Swish' last.
+template <bool NEXT_TR, int IT>
+__device__ __forceinline__ void bwd_hidden(wrsrc_t W, wrsrc_t Wnext, WPre& pre, const float* zb, const float* hb, float* dst,
+                                           int fb, int il, int q, f32x4 (&dW)[IT][8], const f32x4 (&z)[IT][2],
+                                           f32x4 (&db)[IT], f32x4 (&g)[IT][2], bool wgrad_first) {
+  f32x4 unused[IT][2];
+  zero_tiles(g);
+  if (!wgrad_first) {
+    gemm128<true, 0, IT>(W, pre, zb, fb, il, q, g, nullptr, unused);
+    prefetch_w<NEXT_TR>(Wnext, fb, il, q, pre);
+    wgrad_swish<8, IT>(zb, hb, ACT_P, fb, il, q, dW, z, g);
+  } else {
+    wgrad<8, IT>(zb, hb, ACT_P, fb, il, q, dW);
+    gemm128<true, 0, IT>(W, pre, zb, fb, il, q, g, nullptr, unused);
+    prefetch_w<NEXT_TR>(Wnext, fb, il, q, pre);
+    swish_bwd_inplace<IT>(z, g);
+  }
+#pragma unroll
+  for (int it = 0; it < IT; ++it) db[it] += g[it][0];
+  store_act<IT>(dst, fb, il, q, g);
+}
+
+// Euler–Maruyama update of one element x of a sample at time t_raw, a = the network's output for it:
+// x += [(1-l/2) sqrt(beta) a + 1/2 beta x] delta + sqrt(1-l) sqrt(beta) dW, ca = 1 - l/2
+// (SDEs.py:556-561,587-588; sde_scheme.py:82-84,38-40); e = the element's index in x, which also keys its noise.
+__device__ __forceinline__ float em_update(const MlpArgs& A, float ca, float a, float x, float t_raw, int64_t e, int step) {
+  const float s = A.T - t_raw;
+  const float beta = sde_beta(A.b0, A.b1, s);
+  const float sb = sqrtf(beta);
+  const float zz = A.z ? A.z[e] : philox_normal1(A.rng, A.rng_step + (uint64_t)step, RNG_STREAM_DW, (uint64_t)e);
+  const float mu = ca * (sb * a) - (-0.5f * beta * x);
+  return x + (mu * A.delta + (sqrtf(1.0f - A.lmbd) * sb) * (A.sqrt_delta * zz));
+}
+
+// Sliced-score-matching terms of one output o of one sample: returns its share of the sample's loss and sets the
+// cotangents of a and adot (wgt = 1/batch, 0 for a dead row).  p = u_o in the general form, v_o in the SGM closed form:
+//   general (MSGM): loss_b = sum_o adot_o u_o + cst_b + 1/2 a_o^2, u = (d mu/d a)^T v = G(y)^T v
+//   SGM: loss_b = sum_o v_o (sqrt(beta) adot_o + 1/2 beta v_o) + 1/2 a_o^2     SDEs.py:631-646
+__device__ __forceinline__ float ssm_terms(bool general, float a, float ad, float p, float beta, float sb, float wgt,
+                                           float& ab, float& adb) {
+  ab = a * wgt;
+  if (general) { adb = p * wgt; return ad * p + 0.5f * a * a; }
+  adb = sb * p * wgt;
+  return p * (sb * ad + 0.5f * beta * p) + 0.5f * a * a;
+}
+// The 16 threads (ol = 0..15) of a sample add up their terms; thread ol == 0 adds cst, counts the sample and stores it.
+__device__ __forceinline__ void ssm_sample_loss(const MlpArgs& A, float lj, int ol, bool live, int64_t smp, const float* cst_lds,
+                                                float& loss_acc) {
+#pragma unroll
+  for (int m = 8; m > 0; m >>= 1) lj += __shfl_xor(lj, m, 64);
+  if (ol == 0 && live) {
+    if (A.u && A.cst) lj += *cst_lds;
+    loss_acc += lj;
+    if (A.loss_per) A.loss_per[smp] = lj;
+  }
+}
+
+// Epilogue of a training workgroup: the resident dW2 / dW3 (lane (k = 16kt+il, q), reg r -> row fb+16it+4q+r) and the
+// bias gradients of the hidden layers (primal cotangents summed over the 16 sample lanes) go to its slab.
+template <int IT>
+__device__ __forceinline__ void store_hidden_grads(float* slab, const MlpLayout& L, int fb, int il, int q,
+                                                   const f32x4 (&dW2)[IT][8], const f32x4 (&dW3)[IT][8],
+                                                   const f32x4 (&db1)[IT], const f32x4 (&db2)[IT], const f32x4 (&db3)[IT]) {
+#pragma unroll
+  for (int it = 0; it < IT; ++it)
+#pragma unroll
+    for (int kt = 0; kt < 8; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = fb + 16 * it + 4 * q + r, col = 16 * kt + il;
+        slab[L.oW2 + row * HID + col] = dW2[it][kt][r];
+        slab[L.oW3 + row * HID + col] = dW3[it][kt][r];
+      }
+#pragma unroll
+  for (int it = 0; it < IT; ++it)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float s1 = db1[it][r], s2 = db2[it][r], s3 = db3[it][r];
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); s3 += __shfl_xor(s3, o, 64); }
+      if (il == 0) {
+        const int feat = fb + 16 * it + 4 * q + r;
+        slab[L.ob1 + feat] = s1; slab[L.ob2 + feat] = s2; slab[L.ob3 + feat] = s3;
+      }
+    }
+}
+// The workgroup's loss: the 16 sample leaders (threads 0, 16, .. 240 of the loss phase) meet in RED, in a fixed order.
+__device__ __forceinline__ void store_loss_sum(float* RED, int tid, float loss_acc, float* dst) {
+  if (tid < 256 && (tid & 15) == 0) RED[tid >> 4] = loss_acc;
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.f;
+    for (int j = 0; j < 16; ++j) s += RED[j];
+    *dst = s;
+  }
+}
+
 template <int MODE, bool WIDE, int NW, bool TINY = false>
 __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
   constexpr int NT = 64 * NW;         // threads
@@ -415,105 +610,23 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
   f32x4 dW2[IT][8], dW3[IT][8], dW1[IT][KT1], dW4[IT][OT], db1[IT], db2[IT], db3[IT];
   float loss_acc = 0.f;
   if (MODE == MODE_TRAIN) {
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { dW2[it][k] = f32x4{0, 0, 0, 0}; dW3[it][k] = f32x4{0, 0, 0, 0}; }
-#pragma unroll
-      for (int k = 0; k < KT1; ++k) dW1[it][k] = f32x4{0, 0, 0, 0};
-#pragma unroll
-      for (int k = 0; k < OT; ++k) dW4[it][k] = f32x4{0, 0, 0, 0};
-      db1[it] = f32x4{0, 0, 0, 0}; db2[it] = f32x4{0, 0, 0, 0}; db3[it] = f32x4{0, 0, 0, 0};
-    }
+    zero_tiles(dW2); zero_tiles(dW3); zero_tiles(dW1); zero_tiles(dW4);
+    zero_tiles(db1); zero_tiles(db2); zero_tiles(db3);
   }
 
-  // ---- input pipeline: the tile's y / v / u / t / cst chunks (contiguous in global memory) are fetched into
-  // registers ONE TILE AHEAD (raw_issue), parked in LDS a phase later (raw_commit) and turned into the layer-1
-  // operand h0 at the end of the previous tile (build_h0) — no global-load latency sits on the tile's critical path.
+  // input pipeline (see raw_issue): one thread per sample row builds h0
   constexpr int NR = (SPT * LO::DMAX + NT - 1) / NT;
   float* RAW0 = lds + LO::RAW;
-  float pf_y[NR], pf_v[NR], pf_u[NR], pf_t = 0.f, pf_c = 0.f;
-  const int64_t etot = A.B * d;
-  auto raw_issue = [&](int64_t tl, int step = 0) {
-    const int64_t e0 = tl * SPT * d;                 // tl past the last tile => e0 >= etot => zeros
-    const int cnt = SPT * d;
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int e = tid + NT * k;
-      const bool ok = e < cnt && e0 + e < etot;
-      // EM loop: x was rewritten by THIS workgroup a sweep ago — device-scope load so no stale L1 line is served
-      if (MODE == MODE_EM) pf_y[k] = ok ? __hip_atomic_load(A.y + e0 + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-      else pf_y[k] = ok ? A.y[e0 + e] : 0.f;
-      if (MODE == MODE_TRAIN) {
-        pf_v[k] = ok ? A.v[e0 + e] : 0.f;
-        pf_u[k] = (ok && A.u) ? A.u[e0 + e] : 0.f;
-      }
-    }
-    if (tid < SPT) {
-      const int64_t smp = tl * SPT + tid;
-      pf_t = smp < A.B ? (A.t ? A.t[smp] : ((MODE == MODE_EM && A.ts) ? A.ts[step] : A.t_scalar)) : 0.f;
-      if (MODE == MODE_TRAIN) pf_c = (smp < A.B && A.u && A.cst) ? A.cst[smp] : 0.f;
-    }
-  };
-  auto raw_commit = [&](float* R) {
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int e = tid + NT * k;
-      if (e < SPT * LO::DMAX) {
-        R[LO::RY + e] = pf_y[k];
-        if (MODE == MODE_TRAIN) { R[LO::RV + e] = pf_v[k]; R[LO::RU + e] = pf_u[k]; }
-      }
-    }
-    if (tid < SPT) { R[LO::RT + tid] = pf_t; if (MODE == MODE_TRAIN) R[LO::RC + tid] = pf_c; }
-  };
-  // h0 (and its tangent) of tile tl from its raw buffer; run by SPT threads, one per sample row l.
-  // premodule none: h0 = [y, t], h0dot = [v, 0]                     NN.py:113-119
-  // NormalizeLogRadius: h0 = [y/r, log r, t], r = |y| + 1e-6          NN.py:56-70
-  auto build_h0 = [&](float* H0b, const float* R, int64_t tl, int l) {   // l = row (sample) of the tile
-    const int64_t smp = tl * SPT + l;
-    const bool live = smp < A.B;
-    float* hp = H0b + l * SM_P;
-    float* ht = H0b + (16 + l) * SM_P;   // tangent row (train only)
-    float tt = 0.f;
-    if (live) {
-      tt = R[LO::RT + l];
-      if (MODE == MODE_EM) tt = A.T - tt;                                 // s = T - t  SDEs.py:556-557
-    }
-    const float* yr = R + LO::RY + l * d;
-    const float* vr = R + LO::RV + l * d;
-    if (A.P.premodule == 0) {
-      for (int i = 0; i < d; ++i) {
-        hp[i] = yr[i];
-        if (MODE == MODE_TRAIN) ht[i] = vr[i];
-      }
-      hp[d] = tt;
-      if (MODE == MODE_TRAIN) ht[d] = 0.f;
-    } else {
-      float ss = 0.f, yv = 0.f;
-      for (int i = 0; i < d; ++i) {
-        const float yi = live ? yr[i] : 1.0f;
-        ss += yi * yi;
-        if (MODE == MODE_TRAIN) yv += yi * vr[i];
-      }
-      const float nr = sqrtf(ss);
-      const float r = nr + 1e-6f;
-      const float rdot = yv / nr;                                          // d|y| along v
-      for (int i = 0; i < d; ++i) {
-        const float yi = live ? yr[i] : 1.0f;
-        hp[i] = yi / r;
-        if (MODE == MODE_TRAIN) ht[i] = vr[i] / r - yi * rdot / (r * r);
-      }
-      hp[d] = logf(r);
-      hp[d + 1] = tt;
-      if (MODE == MODE_TRAIN) { ht[d] = rdot / r; ht[d + 1] = 0.f; }
-    }
-  };
+  RawRegs<NR> pf;
+  auto issue = [&](int64_t tl, int step = 0) { raw_issue<MODE, LO, NT, true>(A, pf, tid, tid, tl, step); };
+  auto commit = [&](float* R) { raw_commit<MODE, LO, NT, true>(pf, R, tid, tid); };
+  auto h0_row = [&](float* H0b, const float* R, int64_t tl, int l) { build_h0<MODE, LO, 1, SM_P>(A, H0b, R, tl, l, 0); };
 
   // ---- prologue.  The first tile's inputs and the first weight fragments go out first; the one-time staging of
   // the small layers and biases is written as fixed-trip loops with all global loads ahead of the LDS stores, so its
   // latency is ONE L2 round trip, not one per element (at the C2 sampler size a workgroup only has 4 tiles to
   // amortise this over).
-  raw_issue(blockIdx.x);
+  issue(blockIdx.x);
   const wrsrc_t R2 = make_wrsrc(A.P.W2), R3 = make_wrsrc(A.P.W3);
   WPre pre;
   prefetch_w<false>(R2, fb, il, q, pre);
@@ -544,9 +657,9 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
     }
     for (int i = tid; i < 2 * 32 * SM_P; i += NT) H0[i] = 0.f;
   }
-  raw_commit(RAW0);
+  commit(RAW0);
   __syncthreads();
-  if (tid < SPT) build_h0(H0, RAW0, blockIdx.x, tid);
+  if (tid < SPT) h0_row(H0, RAW0, blockIdx.x, tid);
   __syncthreads();
 
   // layer 1 (K = in_dim, weights from LDS) of the tile whose h0 sits in H0b: z1 stays in registers (train: needed
@@ -557,8 +670,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
   f32x4 z1[IT][2];
   auto layer1 = [&](const float* H0b, float* dst) {
     f32x4 h1[IT][2];
-#pragma unroll
-    for (int it = 0; it < IT; ++it) { z1[it][0] = f32x4{0, 0, 0, 0}; z1[it][1] = f32x4{0, 0, 0, 0}; }
+    zero_tiles(z1);
     for (int s = 0; s < A.in4; ++s) {
       const float bP = H0b[il * SM_P + 4 * s + q];
       const float bT = H0b[(16 + il) * SM_P + 4 * s + q];
@@ -581,7 +693,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
   // Waves w and w + NW/2 share a SIMD and would otherwise walk through the backward phases in lockstep (both in their
   // LDS-latency head, both in their VALU tail).  The second one runs its weight-gradient product BEFORE its dgrad, so
   // one wave's heads and tails fall under the other's MFMAs.
-  const bool late = MLP_STAGGER && NW == 8 && w >= NW / 2;
+  const bool late = NW == 8 && w >= NW / 2;
 
   // Work items are (step, tile) with the tile index fastest; training / forward / single-step EM have one step.
   // EM loop (n_steps > 1): rows never interact (sde_scheme.py:82-86), so a workgroup takes its tiles through ALL
@@ -604,26 +716,17 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
     cur ^= 1;
 
     // ---- phase 2: layer 2 --------------------------------------------------
-#pragma unroll
-    for (int it = 0; it < IT; ++it) { z2[it][0] = f32x4{0, 0, 0, 0}; z2[it][1] = f32x4{0, 0, 0, 0}; }
-    if (MODE != MODE_TRAIN) raw_issue(ntile, nstep);
-    gemm128<false, (TRN ? 1 : 2), IT>(R2, pre, Xc, fb, il, q, z2, B2s, h);
-    prefetch_w<false>(R3, fb, il, q, pre);         // head of the next gemm's weights
-    bias_swish<TRN, IT>(z2, h, B2s, fb, q, GemmTail<IT>::FIRST);
+    if (MODE != MODE_TRAIN) issue(ntile, nstep);
+    fwd_hidden<TRN, false, IT>(R2, R3, pre, Xc, B2s, fb, il, q, z2, h);
     store_act<IT>(Yc, fb, il, q, h);
-    if (MODE != MODE_TRAIN) raw_commit(Rn);
+    if (MODE != MODE_TRAIN) commit(Rn);
     lds_barrier();
     STAMP(2);
 
     // ---- phase 3: layer 3, then this wave's K-slice of layer 4 -------------
-#pragma unroll
-    for (int it = 0; it < IT; ++it) { z3[it][0] = f32x4{0, 0, 0, 0}; z3[it][1] = f32x4{0, 0, 0, 0}; }
-    if (MODE != MODE_TRAIN) { if (tid < SPT) build_h0(H0n, Rn, ntile, tid); }   // next item's layer-1 operand
-    else raw_issue(ntile);                                   // train: next tile's inputs, in flight during the gemm
-    gemm128<false, (TRN ? 1 : 2), IT>(R3, pre, Yc, fb, il, q, z3, B3s, h);
-    if (MODE == MODE_TRAIN) prefetch_w<true>(R3, fb, il, q, pre);  // W3^T for dgrad
-    else prefetch_w<false>(R2, fb, il, q, pre);                    // next tile's layer 2
-    bias_swish<TRN, IT>(z3, h, B3s, fb, q, GemmTail<IT>::FIRST);
+    if (MODE != MODE_TRAIN) { if (tid < SPT) h0_row(H0n, Rn, ntile, tid); }   // next item's layer-1 operand
+    else issue(ntile);                                       // train: next tile's inputs, in flight during the gemm
+    fwd_hidden<TRN, TRN, IT>(R3, TRN ? R3 : R2, pre, Yc, B3s, fb, il, q, z3, h);   // then W3^T for dgrad / next tile's layer 2
     if (MODE == MODE_TRAIN) store_act<IT>(Z, fb, il, q, h);   // h3 is the dW4 operand later
     {
       // partial[o][col] = sum_{k in this wave's FW features} W4[o][k] h3[k][col]; B operand = registers
@@ -646,7 +749,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
         }
       }
     }
-    if (MODE == MODE_TRAIN) raw_commit(Rn);
+    if (MODE == MODE_TRAIN) commit(Rn);
     lds_barrier();
     STAMP(3);
 
@@ -662,19 +765,8 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
 #pragma unroll
           for (int ww = 0; ww < NW; ++ww) a += PART[(ww * 32 + c) * PP + o];
           const int64_t e = smp * d + o;
-          if (MODE == MODE_FWD) {
-            A.out[e] = a;
-          } else {
-            // x += [(1-l/2) sqrt(beta) a + 1/2 beta x] delta + sqrt(1-l) sqrt(beta) dW
-            // (SDEs.py:556-561,587-588; sde_scheme.py:82-84,38-40)
-            const float s = A.T - Rc[LO::RT + c];               // this item's time (ts[step] in the EM loop)
-            const float beta = sde_beta(A.b0, A.b1, s);
-            const float sb = sqrtf(beta);
-            const float x = Rc[LO::RY + idx];
-            const float zz = A.z ? A.z[e] : philox_normal1(A.rng, A.rng_step + (uint64_t)step, RNG_STREAM_DW, (uint64_t)e);
-            const float mu = ca * (sb * a) - (-0.5f * beta * x);
-            A.out[e] = x + (mu * A.delta + (sqrtf(1.0f - A.lmbd) * sb) * (A.sqrt_delta * zz));
-          }
+          // EM: the sample's time is this item's (ts[step] in the EM loop)
+          A.out[e] = MODE == MODE_FWD ? a : em_update(A, ca, a, Rc[LO::RY + idx], Rc[LO::RT + c], e, step);
         }
       }
       if (n_steps > 1) __syncthreads();   // + vmcnt(0): this tile's new x must have left the CU before it is re-read
@@ -700,40 +792,23 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
           float a = B4s[o], ad = 0.f;
 #pragma unroll
           for (int ww = 0; ww < NW; ++ww) { a += PART[(ww * 32 + c) * PP + o]; ad += PART[(ww * 32 + 16 + c) * PP + o]; }
-          float adb;
-          if (A.u) {
-            // general form: loss_b = sum_o adot_o u_o + cst_b + 1/2 a_o^2, u = (d mu/d a)^T v  (MSGM: G(y)^T v)
-            const float uo = oo ? Rc[LO::RU + c * d + o] : 0.f;
-            lj += ad * uo + 0.5f * a * a;
-            adb = uo * wgt;
-          } else {
-            const float vo = oo ? Rc[LO::RV + c * d + o] : 0.f;
-            // SGM: loss_b = sum_o v_o (sqrt(beta) adot_o + 1/2 beta v_o) + 1/2 a_o^2     SDEs.py:631-646
-            lj += vo * (sb * ad + 0.5f * beta * vo) + 0.5f * a * a;
-            adb = sb * vo * wgt;
-          }
-          const float ab = a * wgt;
+          const float p = oo ? Rc[(A.u ? LO::RU : LO::RV) + c * d + o] : 0.f;
+          float ab, adb;
+          lj += ssm_terms(A.u != nullptr, a, ad, p, beta, sb, wgt, ab, adb);
           ABAR[c * SM_P + o] = ab;
           ABAR[(16 + c) * SM_P + o] = adb;
           DB4[c * DPAD + o] += ab;
         }
-#pragma unroll
-        for (int m = 8; m > 0; m >>= 1) lj += __shfl_xor(lj, m, 64);
-        if (ol == 0 && live) {
-          if (A.u && A.cst) lj += Rc[LO::RC + c];
-          loss_acc += lj;
-          if (A.loss_per) A.loss_per[smp] = lj;
-        }
+        ssm_sample_loss(A, lj, ol, live, smp, Rc + LO::RC + c, loss_acc);
       }
       // next tile's layer-1 operand, by a wave that has no part in the loss when there are eight
-      if (tid >= NT - 64 && tid < NT - 64 + 16) build_h0(H0n, Rn, ntile, tid - (NT - 64));
+      if (tid >= NT - 64 && tid < NT - 64 + 16) h0_row(H0n, Rn, ntile, tid - (NT - 64));
       lds_barrier();
       STAMP(4);
 
       // ---- phase 5: layer-4 backward, dW4, Swish' on layer 3 --------------
       f32x4 g[IT][2];
-#pragma unroll
-      for (int it = 0; it < IT; ++it) { g[it][0] = f32x4{0, 0, 0, 0}; g[it][1] = f32x4{0, 0, 0, 0}; }
+      zero_tiles(g);
       for (int s = 0; s < A.d4; ++s) {
         const float bP = ABAR[il * SM_P + 4 * s + q];
         const float bT = ABAR[(16 + il) * SM_P + 4 * s + q];
@@ -750,41 +825,15 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
       lds_barrier();
       STAMP(5);
 
-      // ---- phase 6: dgrad layer 3 (W3^T), dW3, Swish' on layer 2 -----------
-#pragma unroll
-      for (int it = 0; it < IT; ++it) { g[it][0] = f32x4{0, 0, 0, 0}; g[it][1] = f32x4{0, 0, 0, 0}; }
-      if (!late) {
-        gemm128<true, 0, IT>(R3, pre, U, fb, il, q, g, nullptr, h);
-        prefetch_w<true>(R2, fb, il, q, pre);        // W2^T for the next dgrad
-        wgrad_swish<8, IT>(U, Yc, ACT_P, fb, il, q, dW3, z2, g);
-      } else {                                         // the SIMD's other wave: weight gradient first (it only needs
-        wgrad<8, IT>(U, Yc, ACT_P, fb, il, q, dW3);    // this wave's zbar3 columns), dgrad second, Swish' last
-        gemm128<true, 0, IT>(R3, pre, U, fb, il, q, g, nullptr, h);
-        prefetch_w<true>(R2, fb, il, q, pre);
-        swish_bwd_inplace<IT>(z2, g);
-      }
-#pragma unroll
-      for (int it = 0; it < IT; ++it) db2[it] += g[it][0];
-      store_act<IT>(Z, fb, il, q, g);                      // h3 is dead after phase 5
+      // ---- phase 6: dgrad layer 3 (W3^T, then W2^T goes out for the next dgrad), dW3, Swish' on layer 2; zbar2 -> Z
+      // (h3 is dead after phase 5)
+      bwd_hidden<true, IT>(R3, R2, pre, U, Yc, Z, fb, il, q, dW3, z2, db2, g, late);
       lds_barrier();
       STAMP(6);
 
-      // ---- phase 7: dgrad layer 2 (W2^T), dW2, Swish' on layer 1 -----------
-#pragma unroll
-      for (int it = 0; it < IT; ++it) { g[it][0] = f32x4{0, 0, 0, 0}; g[it][1] = f32x4{0, 0, 0, 0}; }
-      if (!late) {
-        gemm128<true, 0, IT>(R2, pre, Z, fb, il, q, g, nullptr, h);
-        prefetch_w<false>(R2, fb, il, q, pre);       // next tile's layer 2
-        wgrad_swish<8, IT>(Z, Xc, ACT_P, fb, il, q, dW2, z1, g);
-      } else {
-        wgrad<8, IT>(Z, Xc, ACT_P, fb, il, q, dW2);
-        gemm128<true, 0, IT>(R2, pre, Z, fb, il, q, g, nullptr, h);
-        prefetch_w<false>(R2, fb, il, q, pre);
-        swish_bwd_inplace<IT>(z1, g);
-      }
-#pragma unroll
-      for (int it = 0; it < IT; ++it) db1[it] += g[it][0];
-      store_act<IT>(U, fb, il, q, g);                      // zbar3 is dead after phase 6
+      // ---- phase 7: dgrad layer 2 (W2^T, then the next tile's layer 2 goes out), dW2, Swish' on layer 1; zbar1 -> U
+      // (zbar3 is dead after phase 6)
+      bwd_hidden<false, IT>(R2, R2, pre, Z, Xc, U, fb, il, q, dW2, z1, db1, g, late);
       STAMP(7);
       // dW1 reads only THIS wave's columns of zbar1 (just written by this wave) and h0: no barrier in between
       wgrad<KT1, IT>(U, H0c, SM_P, fb, il, q, dW1);
@@ -800,19 +849,9 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
     STAMP(9);
     float* slab = A.slabs + (int64_t)blockIdx.x * slab_stride(A.n_params);
     const int in_dim = A.in_dim;
-    const int64_t oW1 = 0, ob1 = oW1 + (int64_t)HID * in_dim, oW2 = ob1 + HID, ob2 = oW2 + HID * HID,
-                  oW3 = ob2 + HID, ob3 = oW3 + HID * HID, oW4 = ob3 + HID, ob4 = oW4 + (int64_t)d * HID;
-    // dW2 / dW3: lane (k = 16kt+il, q), reg r -> row 32w+16it+4q+r
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-      for (int kt = 0; kt < 8; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = fb + 16 * it + 4 * q + r, col = 16 * kt + il;
-          slab[oW2 + row * HID + col] = dW2[it][kt][r];
-          slab[oW3 + row * HID + col] = dW3[it][kt][r];
-        }
+    const MlpLayout L(d, in_dim);
+    store_hidden_grads<IT>(slab, L, fb, il, q, dW2, dW3, db1, db2, db3);
+    // dW1: lane (k = 16kt+il, q), reg r -> row 32w+16it+4q+r
 #pragma unroll
     for (int it = 0; it < IT; ++it)
 #pragma unroll
@@ -820,7 +859,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = fb + 16 * it + 4 * q + r, col = 16 * kt + il;
-          if (col < in_dim) slab[oW1 + (int64_t)row * in_dim + col] = dW1[it][kt][r];
+          if (col < in_dim) slab[L.oW1 + (int64_t)row * in_dim + col] = dW1[it][kt][r];
         }
     // dW4 held transposed: lane (o = 16ot+il, q), reg r -> feature 32w+16it+4q+r
 #pragma unroll
@@ -830,34 +869,15 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int feat = fb + 16 * it + 4 * q + r, o = 16 * ot + il;
-          if (o < d) slab[oW4 + (int64_t)o * HID + feat] = dW4[it][ot][r];
+          if (o < d) slab[L.oW4 + (int64_t)o * HID + feat] = dW4[it][ot][r];
         }
-    // biases: sum the primal cotangents over the 16 sample lanes
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s1 = db1[it][r], s2 = db2[it][r], s3 = db3[it][r];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); s3 += __shfl_xor(s3, o, 64); }
-        if (il == 0) {
-          const int feat = fb + 16 * it + 4 * q + r;
-          slab[ob1 + feat] = s1; slab[ob2 + feat] = s2; slab[ob3 + feat] = s3;
-        }
-      }
     __syncthreads();
     if (tid < d) {
       float s = 0.f;
       for (int j = 0; j < 16; ++j) s += DB4[j * DPAD + tid];
-      slab[ob4 + tid] = s;
+      slab[L.ob4 + tid] = s;
     }
-    if (tid < 256 && (tid & 15) == 0) RED[tid >> 4] = loss_acc;
-    __syncthreads();
-    if (tid == 0) {
-      float s = 0.f;
-      for (int j = 0; j < 16; ++j) s += RED[j];
-      slab[A.n_params] = s;
-    }
+    store_loss_sum(RED, tid, loss_acc, slab + A.n_params);
     STAMP(10);
     STAMP_FLUSH;
   }
@@ -881,9 +901,10 @@ struct MlpLdsXW {
   static constexpr bool TRAIN = MODE == 2;
   static constexpr int SPT = TRAIN ? 16 : 32;      // samples per tile
   // raw input buffer: y | v (pitch d), t, cst; u is read straight from global memory by the loss phase
+  static constexpr int DMAX = HID;                 // raw rows are packed (pitch d), sized for d <= DMAX
   static constexpr int RY = 0;
-  static constexpr int RV = RY + SPT * HID;
-  static constexpr int RT = RV + (TRAIN ? SPT * HID : 0);
+  static constexpr int RV = RY + SPT * DMAX;
+  static constexpr int RT = RV + (TRAIN ? SPT * DMAX : 0);
   static constexpr int RC = RT + 32;
   static constexpr int RAWN = RC + 16;
   static constexpr int X = 0;
@@ -979,92 +1000,21 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
   float db4[8];                       // thread (sample c, output lane ol) of the loss phase: outputs 16 ot + ol
   float loss_acc = 0.f;
   if (TRN) {
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { dW2[it][k] = f32x4{0, 0, 0, 0}; dW3[it][k] = f32x4{0, 0, 0, 0}; }
-      db1[it] = f32x4{0, 0, 0, 0}; db2[it] = f32x4{0, 0, 0, 0}; db3[it] = f32x4{0, 0, 0, 0};
-    }
+    zero_tiles(dW2); zero_tiles(dW3);
+    zero_tiles(db1); zero_tiles(db2); zero_tiles(db3);
 #pragma unroll
     for (int k = 0; k < 8; ++k) db4[k] = 0.f;
   }
 
-  // ---- input pipeline, as in k_mlp: fetched one tile ahead into registers, parked in LDS a phase later
-  constexpr int NR = SPT * HID / NT;
-  float pf_y[NR], pf_v[NR], pf_t = 0.f, pf_c = 0.f;
-  const int64_t etot = A.B * d;
-  auto raw_issue = [&](int64_t tl, int step = 0) {
-    const int64_t e0 = tl * SPT * d;
-    const int cnt = SPT * d;
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int e = (w << 6) + lane_v + NT * k;
-      const bool ok = e < cnt && e0 + e < etot;
-      if (MODE == MODE_EM) pf_y[k] = ok ? __hip_atomic_load(A.y + e0 + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-      else pf_y[k] = ok ? A.y[e0 + e] : 0.f;
-      if (TRN) pf_v[k] = ok ? A.v[e0 + e] : 0.f;
-    }
-    if (tid < SPT) {
-      const int64_t smp = tl * SPT + tid;
-      pf_t = smp < A.B ? (A.t ? A.t[smp] : ((MODE == MODE_EM && A.ts) ? A.ts[step] : A.t_scalar)) : 0.f;
-      if (TRN) pf_c = (smp < A.B && A.u && A.cst) ? A.cst[smp] : 0.f;
-    }
-  };
-  auto raw_commit = [&](float* R) {
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int e = (w << 6) + lane_v + NT * k;
-      R[LO::RY + e] = pf_y[k];
-      if (TRN) R[LO::RV + e] = pf_v[k];
-    }
-    if (tid < SPT) { R[LO::RT + tid] = pf_t; if (TRN) R[LO::RC + tid] = pf_c; }
-  };
-  // h0 (and its tangent) of tile tl, by ALL threads: GS = NT / SPT threads per sample row, the norm of
-  // NormalizeLogRadius meets by shuffle within the group.  Same formulas as k_mlp's build_h0 (NN.py:56-70,113-119).
-  constexpr int GS = NT / SPT;
-  auto build_h0 = [&](float* H0b, const float* R, int64_t tl) {
+  // input pipeline (see raw_issue); u is not staged: the loss phase reads it from global memory.  ALL threads build
+  // h0, GS = NT / SPT per sample row.
+  constexpr int NR = SPT * LO::DMAX / NT, GS = NT / SPT;
+  RawRegs<NR> pf;
+  auto issue = [&](int64_t tl, int step = 0) { raw_issue<MODE, LO, NT, false>(A, pf, (w << 6) + lane_v, tid, tl, step); };
+  auto commit = [&](float* R) { raw_commit<MODE, LO, NT, false>(pf, R, (w << 6) + lane_v, tid); };
+  auto h0_rows = [&](float* H0b, const float* R, int64_t tl) {
     const int tv = (w << 6) + lane_v;
-    const int l = tv / GS, sub = tv % GS;
-    const int64_t smp = tl * SPT + l;
-    const bool live = smp < A.B;
-    float* hp = H0b + l * XP;
-    float* ht = H0b + (16 + l) * XP;
-    float tt = 0.f;
-    if (live) {
-      tt = R[LO::RT + l];
-      if (MODE == MODE_EM) tt = A.T - tt;
-    }
-    const float* yr = R + LO::RY + l * d;
-    const float* vr = R + LO::RV + l * d;
-    if (A.P.premodule == 0) {
-      for (int i = sub; i < d; i += GS) {
-        hp[i] = yr[i];
-        if (TRN) ht[i] = vr[i];
-      }
-      if (sub == 0) { hp[d] = tt; if (TRN) ht[d] = 0.f; }
-    } else {
-      float ss = 0.f, yv = 0.f;
-      for (int i = sub; i < d; i += GS) {
-        const float yi = live ? yr[i] : 1.0f;
-        ss += yi * yi;
-        if (TRN) yv += yi * vr[i];
-      }
-#pragma unroll
-      for (int m = GS / 2; m > 0; m >>= 1) { ss += __shfl_xor(ss, m, 64); if (TRN) yv += __shfl_xor(yv, m, 64); }
-      const float nr = sqrtf(ss);
-      const float r = nr + 1e-6f;
-      const float rdot = yv / nr;
-      for (int i = sub; i < d; i += GS) {
-        const float yi = live ? yr[i] : 1.0f;
-        hp[i] = yi / r;
-        if (TRN) ht[i] = vr[i] / r - yi * rdot / (r * r);
-      }
-      if (sub == 0) {
-        hp[d] = logf(r);
-        hp[d + 1] = tt;
-        if (TRN) { ht[d] = rdot / r; ht[d + 1] = 0.f; }
-      }
-    }
+    build_h0<MODE, LO, GS, XP>(A, H0b, R, tl, tv / GS, tv % GS);
   };
 
   // ---- weight fragments.  W1 has pitch in_dim, W4 has d rows.  A lane whose element lies outside the matrix (a column
@@ -1103,7 +1053,7 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
   };
 
   // ---- prologue
-  raw_issue(blockIdx.x);
+  issue(blockIdx.x);
   WPre pre;
   prefetch_w<false>(R2, fb, il, q, pre);
   if (tid < HID) {
@@ -1111,16 +1061,15 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
     B4s[tid] = tid < d ? A.P.b4[tid] : 0.f;
   }
   for (int i = tid; i < 2 * 32 * XP; i += NT) H0[i] = 0.f;
-  raw_commit(RAW0);
+  commit(RAW0);
   __syncthreads();
-  build_h0(H0, RAW0, blockIdx.x);
+  h0_rows(H0, RAW0, blockIdx.x);
   __syncthreads();
 
   f32x4 z1[IT][2];
   auto layer1 = [&](const float* H0b, float* dst) {
     f32x4 h1[IT][2];
-#pragma unroll
-    for (int it = 0; it < IT; ++it) { z1[it][0] = f32x4{0, 0, 0, 0}; z1[it][1] = f32x4{0, 0, 0, 0}; }
+    zero_tiles(z1);
     gemm_xw<IT, KT1>(af1, H0b, XP, il, q, z1, ng1, IT);
     bias_swish<TRN, IT>(z1, h1, B1s, fb, q, 0);
     store_act<IT>(dst, fb, il, q, h1);
@@ -1132,13 +1081,13 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
   const float ca = 1.0f - 0.5f * A.lmbd;
   int cur = 0;
   float* slab = TRN ? A.slabs + (int64_t)blockIdx.x * slab_stride(A.n_params) : nullptr;
-  const int64_t oW4 = (int64_t)HID * in_dim + HID + 2 * ((int64_t)HID * HID + HID);
+  const MlpLayout L(d, in_dim);
   // the slab's dW1 / dW4 words by buffer loads / stores (one per-lane offset per row; a masked-off word gets an offset
   // past the slab, where a load reads 0 and a store is dropped)
   const wrsrc_t RS = __builtin_amdgcn_make_buffer_rsrc(slab, 0, TRN ? (int)(slab_stride(A.n_params) * 4) : 0, 0x00020000);
   // dW1[fb + 4q][il] (+ r rows, + (it, kt) scalar) and dW4[o = il][fb + 4q] (+ (it, kt) scalar)
   auto vo1 = [&] { return (((fb + 4 * (lane_v >> 4)) * in_dim + (lane_v & 15)) * 4); };
-  auto vo4 = [&] { return (int)((oW4 + (int64_t)(lane_v & 15) * HID + fb + 4 * (lane_v >> 4)) * 4); };
+  auto vo4 = [&] { return (int)((L.oW4 + (int64_t)(lane_v & 15) * HID + fb + 4 * (lane_v >> 4)) * 4); };
   const int n_steps = (MODE == MODE_EM && A.n_steps > 1) ? A.n_steps : 1;
   int step = 0;
   for (int64_t tile = blockIdx.x; tile < n_tiles;) {
@@ -1157,33 +1106,23 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
     cur ^= 1;
 
     // ---- layer 2
-#pragma unroll
-    for (int it = 0; it < IT; ++it) { z2[it][0] = f32x4{0, 0, 0, 0}; z2[it][1] = f32x4{0, 0, 0, 0}; }
-    if (!TRN) raw_issue(ntile, nstep);
-    gemm128<false, (TRN ? 1 : 2), IT>(R2, pre, Xc, fb, il, q, z2, B2s, h);
-    prefetch_w<false>(R3, fb, il, q, pre);
-    bias_swish<TRN, IT>(z2, h, B2s, fb, q, GemmTail<IT>::FIRST);
+    if (!TRN) issue(ntile, nstep);
+    fwd_hidden<TRN, false, IT>(R2, R3, pre, Xc, B2s, fb, il, q, z2, h);
     store_act<IT>(Yc, fb, il, q, h);
-    if (!TRN) raw_commit(Rn);
+    if (!TRN) commit(Rn);
     lds_barrier();
 
     // ---- layer 3; h3 -> Z (train) / Xc (inference: h1 is dead)
-#pragma unroll
-    for (int it = 0; it < IT; ++it) { z3[it][0] = f32x4{0, 0, 0, 0}; z3[it][1] = f32x4{0, 0, 0, 0}; }
-    if (!TRN) build_h0(H0n, Rn, ntile);
-    else raw_issue(ntile);
-    gemm128<false, (TRN ? 1 : 2), IT>(R3, pre, Yc, fb, il, q, z3, B3s, h);
-    if (TRN) prefetch_w<true>(R3, fb, il, q, pre);
-    else prefetch_w<false>(R2, fb, il, q, pre);
-    bias_swish<TRN, IT>(z3, h, B3s, fb, q, GemmTail<IT>::FIRST);
+    if (!TRN) h0_rows(H0n, Rn, ntile);
+    else issue(ntile);
+    fwd_hidden<TRN, TRN, IT>(R3, TRN ? R3 : R2, pre, Yc, B3s, fb, il, q, z3, h);   // then W3^T for dgrad / next tile's layer 2
     float* H3 = TRN ? Z : Xc;
     store_act<IT>(H3, fb, il, q, h);
-    if (TRN) raw_commit(Rn);
+    if (TRN) commit(Rn);
     lds_barrier();
 
     // ---- layer 4: this wave's output row tiles 16(w + 4it), K = 128
-#pragma unroll
-    for (int it = 0; it < IT; ++it) { z4[it][0] = f32x4{0, 0, 0, 0}; z4[it][1] = f32x4{0, 0, 0, 0}; }
+    zero_tiles(z4);
     gemm_xw<IT, 8>(af4, H3, ACT_P, il, q, z4, 8, nit4);
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
@@ -1209,17 +1148,7 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
             if (o < d && smp < A.B) {
               const float a = z4[it][ck][r];
               const int64_t e = smp * d + o;
-              if (MODE == MODE_FWD) {
-                A.out[e] = a;
-              } else {
-                const float s = A.T - Rc[LO::RT + c];
-                const float beta = sde_beta(A.b0, A.b1, s);
-                const float sb = sqrtf(beta);
-                const float x = Rc[LO::RY + c * d + o];
-                const float zz = A.z ? A.z[e] : philox_normal1(A.rng, A.rng_step + (uint64_t)step, RNG_STREAM_DW, (uint64_t)e);
-                const float mu = ca * (sb * a) - (-0.5f * beta * x);
-                A.out[e] = x + (mu * A.delta + (sqrtf(1.0f - A.lmbd) * sb) * (A.sqrt_delta * zz));
-              }
+              A.out[e] = MODE == MODE_FWD ? a : em_update(A, ca, a, Rc[LO::RY + c * d + o], Rc[LO::RT + c], e, step);
             }
           }
       }
@@ -1263,36 +1192,22 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
           const int o = 16 * ot + ol;
           const bool oo = o < d;
           const float a = oo ? U[c * ACT_P + o] : 0.f, ad = oo ? U[(16 + c) * ACT_P + o] : 0.f;
-          float adb;
-          if (A.u) {
-            lj += ad * uo[ot] + 0.5f * a * a;
-            adb = uo[ot] * wgt;
-          } else {
-            const float vo = oo ? Rc[LO::RV + c * d + o] : 0.f;
-            lj += vo * (sb * ad + 0.5f * beta * vo) + 0.5f * a * a;
-            adb = sb * vo * wgt;
-          }
-          const float ab = a * wgt;
+          const float p = A.u ? uo[ot] : (oo ? Rc[LO::RV + c * d + o] : 0.f);
+          float ab, adb;
+          lj += ssm_terms(A.u != nullptr, a, ad, p, beta, sb, wgt, ab, adb);
           ABAR[c * ACT_P + o] = ab;
           ABAR[(16 + c) * ACT_P + o] = adb;
           db4[ot] += ab;
         }
-#pragma unroll
-        for (int m = 8; m > 0; m >>= 1) lj += __shfl_xor(lj, m, 64);
-        if (ol == 0 && live) {
-          if (A.u && A.cst) lj += Rc[LO::RC + c];
-          loss_acc += lj;
-          if (A.loss_per) A.loss_per[smp] = lj;
-        }
+        ssm_sample_loss(A, lj, ol, live, smp, Rc + LO::RC + c, loss_acc);
       }
-      build_h0(H0n, Rn, ntile);                          // next tile's layer-1 operand
+      h0_rows(H0n, Rn, ntile);                           // next tile's layer-1 operand
       lds_barrier();
 
       // ---- layer-4 backward: dgrad (W4^T, K = d), dW4 into the slab, Swish' on layer 3
       const bool first = tile == (int64_t)blockIdx.x;
       f32x4 g[IT][2];
-#pragma unroll
-      for (int it = 0; it < IT; ++it) { g[it][0] = f32x4{0, 0, 0, 0}; g[it][1] = f32x4{0, 0, 0, 0}; }
+      zero_tiles(g);
       gemm_xw<IT, 8>(af4t, ABAR, ACT_P, il, q, g, nk4, IT);
       // dW4^T[feat][o] += h3 . abar through the slab, in blocks of two 16-output tiles: lane (o = 16kt + il, q),
       // register r -> feature fb + 16it + 4q + r
@@ -1323,26 +1238,12 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
       store_act<IT>(U, fb, il, q, g);
       lds_barrier();
 
-      // ---- dgrad layer 3 (W3^T), dW3, Swish' on layer 2
-#pragma unroll
-      for (int it = 0; it < IT; ++it) { g[it][0] = f32x4{0, 0, 0, 0}; g[it][1] = f32x4{0, 0, 0, 0}; }
-      gemm128<true, 0, IT>(R3, pre, U, fb, il, q, g, nullptr, h);
-      prefetch_w<true>(R2, fb, il, q, pre);
-      wgrad_swish<8, IT>(U, Yc, ACT_P, fb, il, q, dW3, z2, g);
-#pragma unroll
-      for (int it = 0; it < IT; ++it) db2[it] += g[it][0];
-      store_act<IT>(Z, fb, il, q, g);
+      // ---- dgrad layer 3 (W3^T), dW3, Swish' on layer 2; zbar2 -> Z
+      bwd_hidden<true, IT>(R3, R2, pre, U, Yc, Z, fb, il, q, dW3, z2, db2, g, false);
       lds_barrier();
 
-      // ---- dgrad layer 2 (W2^T), dW2, Swish' on layer 1; dW1 (K = in_dim) into the slab; next tile's layer 1
-#pragma unroll
-      for (int it = 0; it < IT; ++it) { g[it][0] = f32x4{0, 0, 0, 0}; g[it][1] = f32x4{0, 0, 0, 0}; }
-      gemm128<true, 0, IT>(R2, pre, Z, fb, il, q, g, nullptr, h);
-      prefetch_w<false>(R2, fb, il, q, pre);
-      wgrad_swish<8, IT>(Z, Xc, ACT_P, fb, il, q, dW2, z1, g);
-#pragma unroll
-      for (int it = 0; it < IT; ++it) db1[it] += g[it][0];
-      store_act<IT>(U, fb, il, q, g);
+      // ---- dgrad layer 2 (W2^T), dW2, Swish' on layer 1, zbar1 -> U; dW1 (K = in_dim) into the slab; next tile's layer 1
+      bwd_hidden<false, IT>(R2, R2, pre, Z, Xc, U, fb, il, q, dW2, z1, db1, g, false);
       // dW1 (this wave's own zbar1 columns: no barrier in between) through the slab, in blocks of one row tile x three
       // k-tiles (48 columns of h0; the columns past in_dim are zeros and are not stored):
       // lane (k = 16kt + il, q), register r -> row fb + 16it + 4q + r
@@ -1379,47 +1280,18 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
 
   // ---- epilogue (train): the rest of this workgroup's gradient slab (dW1 and dW4 are already there)
   if (TRN) {
-    const int64_t ob1 = (int64_t)HID * in_dim, oW2 = ob1 + HID, ob2 = oW2 + HID * HID,
-                  oW3 = ob2 + HID, ob3 = oW3 + HID * HID, ob4 = oW4 + (int64_t)d * HID;
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-      for (int kt = 0; kt < 8; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = fb + 16 * it + 4 * q + r, col = 16 * kt + il;
-          slab[oW2 + row * HID + col] = dW2[it][kt][r];
-          slab[oW3 + row * HID + col] = dW3[it][kt][r];
-        }
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s1 = db1[it][r], s2 = db2[it][r], s3 = db3[it][r];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); s3 += __shfl_xor(s3, o, 64); }
-        if (il == 0) {
-          const int feat = fb + 16 * it + 4 * q + r;
-          slab[ob1 + feat] = s1; slab[ob2 + feat] = s2; slab[ob3 + feat] = s3;
-        }
-      }
+    store_hidden_grads<IT>(slab, L, fb, il, q, dW2, dW3, db1, db2, db3);
     __syncthreads();
     {
       const int c = tid >> 4, ol = tid & 15;
 #pragma unroll
       for (int ot = 0; ot < 8; ++ot) X[c * HID + 16 * ot + ol] = db4[ot];   // X is free: 16 x 128 per-sample-lane sums
     }
-    if ((tid & 15) == 0) RED[tid >> 4] = loss_acc;
-    __syncthreads();
+    store_loss_sum(RED, tid, loss_acc, slab + A.n_params);   // (its barrier also covers X)
     if (tid < d) {
       float s = 0.f;
       for (int j = 0; j < 16; ++j) s += X[j * HID + tid];
-      slab[ob4 + tid] = s;
-    }
-    if (tid == 0) {
-      float s = 0.f;
-      for (int j = 0; j < 16; ++j) s += RED[j];
-      slab[A.n_params] = s;
+      slab[L.ob4 + tid] = s;
     }
   }
 }
@@ -1478,24 +1350,19 @@ static const int MLP_MAX_GRID = 256;
 // Waves per workgroup.  Training at narrow width runs 8 waves x 16 features: two waves per SIMD, so one wave's
 // Swish / LDS / barrier latencies are covered by the other's MFMAs (each holds half of the dW accumulators).  The
 // wide carve (d > 15) has no LDS left for eight layer-4 K-slices and stays at 4 waves x 32 features.
-#ifndef MLP_NW_TRAIN
-#define MLP_NW_TRAIN 8
-#endif
-#ifndef MLP_NW_FWD
-#define MLP_NW_FWD 4
-#endif
 template <int MODE, bool WIDE>
-struct MlpCfg { static constexpr int NW = WIDE ? 4 : (MODE == MODE_TRAIN ? MLP_NW_TRAIN : MLP_NW_FWD); };
+struct MlpCfg { static constexpr int NW = WIDE ? 4 : (MODE == MODE_TRAIN ? 8 : 4); };
 
-template <int MODE, bool WIDE, bool TINY>
-static void set_lds_attr() {
+// Launch kernel K with LDS bytes of dynamic LDS; the first launch raises the kernel's dynamic-LDS limit to that.
+template <void (*K)(MlpArgs), int LDS, int BLOCK>
+static int launch_kernel(const MlpArgs& A, int grid, hipStream_t st) {
   static const int once = [] {
-    constexpr int NW = MlpCfg<MODE, WIDE>::NW;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mlp<MODE, WIDE, NW, TINY>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, MlpLds<MODE, WIDE, NW, TINY>::BYTES);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     return 0;
   }();
   (void)once;
+  hipLaunchKernelGGL(K, dim3(grid), dim3(BLOCK), LDS, st, A);
+  return msgm_check_launch();
 }
 
 // workgroups that fit one CU with this carve (inference modes: 2, or 3 with the tiny carve, 1 with the extra-wide one)
@@ -1505,28 +1372,13 @@ static int64_t mlp_wg_per_cu(const MlpArgs& A) { return mlp_xwide(A) ? 1 : (mlp_
 
 template <int MODE>
 static int launch_mlp(const MlpArgs& A, int grid, hipStream_t st) {
-  if (mlp_xwide(A)) {
-    static const int once = [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mlp_xw<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                MlpLdsXW<MODE>::BYTES);
-      return 0;
-    }();
-    (void)once;
-    hipLaunchKernelGGL((k_mlp_xw<MODE>), dim3(grid), dim3(256), MlpLdsXW<MODE>::BYTES, st, A);
-    return msgm_check_launch();
-  }
-  const bool wide = A.in_dim > 16 || A.P.d > 16;
+  if (mlp_xwide(A)) return launch_kernel<k_mlp_xw<MODE>, MlpLdsXW<MODE>::BYTES, 256>(A, grid, st);
   constexpr int nw_w = MlpCfg<MODE, true>::NW, nw_n = MlpCfg<MODE, false>::NW;
-  constexpr size_t lds_wide = MlpLds<MODE, true, nw_w>::BYTES, lds_narrow = MlpLds<MODE, false, nw_n>::BYTES;
-  if (wide) { set_lds_attr<MODE, true, false>(); hipLaunchKernelGGL((k_mlp<MODE, true, nw_w, false>), dim3(grid), dim3(64 * nw_w), lds_wide, st, A); }
-  else if (MODE != MODE_TRAIN && mlp_tiny(A)) {
-    constexpr bool T = MODE != MODE_TRAIN;     // never instantiated for training
-    constexpr size_t lds_tiny = MlpLds<MODE, false, nw_n, T>::BYTES;
-    set_lds_attr<MODE, false, T>();
-    hipLaunchKernelGGL((k_mlp<MODE, false, nw_n, T>), dim3(grid), dim3(64 * nw_n), lds_tiny, st, A);
-  }
-  else { set_lds_attr<MODE, false, false>(); hipLaunchKernelGGL((k_mlp<MODE, false, nw_n, false>), dim3(grid), dim3(64 * nw_n), lds_narrow, st, A); }
-  return msgm_check_launch();
+  if (A.in_dim > 16 || A.P.d > 16)
+    return launch_kernel<k_mlp<MODE, true, nw_w, false>, MlpLds<MODE, true, nw_w>::BYTES, 64 * nw_w>(A, grid, st);
+  constexpr bool T = MODE != MODE_TRAIN;     // the tiny carve is never instantiated for training
+  if (T && mlp_tiny(A)) return launch_kernel<k_mlp<MODE, false, nw_n, T>, MlpLds<MODE, false, nw_n, T>::BYTES, 64 * nw_n>(A, grid, st);
+  return launch_kernel<k_mlp<MODE, false, nw_n, false>, MlpLds<MODE, false, nw_n>::BYTES, 64 * nw_n>(A, grid, st);
 }
 
 static int fill_common(MlpArgs& A, const msgm_mlp_params_t* P, int64_t B) {
@@ -1538,11 +1390,22 @@ static int fill_common(MlpArgs& A, const msgm_mlp_params_t* P, int64_t B) {
   return MSGM_OK;
 }
 
+// the arguments of a reverse-SDE Euler–Maruyama step on x (in place)
+static int fill_em(MlpArgs& A, float* x, const msgm_sde_t* sde, float t, float delta, float lmbd, const float* z,
+                   const uint64_t* rng, uint64_t rng_step) {
+  if (!x || !sde) return MSGM_E_BADARG;
+  if (sde->kind != MSGM_SDE_SGM) return MSGM_E_UNSUPPORTED;
+  A.y = x; A.out = x; A.t = nullptr; A.t_scalar = t;
+  A.b0 = sde->beta_min; A.b1 = sde->beta_max; A.T = sde->T;
+  A.delta = delta; A.sqrt_delta = (float)sqrt((double)delta); A.lmbd = lmbd;
+  A.z = z; A.rng = rng; A.rng_step = rng_step;
+  return MSGM_OK;
+}
+
 extern "C" {
 
 int64_t msgm_mlp_num_params(int32_t d, int32_t premodule) {
-  const int64_t in_dim = d + 1 + (premodule ? 1 : 0);
-  return HID * in_dim + HID + 2 * ((int64_t)HID * HID + HID) + (int64_t)d * HID + d;
+  return MlpLayout(d, d + 1 + (premodule ? 1 : 0)).n_params;
 }
 
 size_t msgm_mlp_ssm_workspace(int32_t d, int32_t premodule) {
@@ -1566,12 +1429,9 @@ int msgm_mlp_em_step(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm
   MlpArgs A{};
   int rc = fill_common(A, P, B);
   if (rc) return rc;
-  if (!x || !sde || (!z && !rng)) return MSGM_E_BADARG;
-  if (sde->kind != MSGM_SDE_SGM) return MSGM_E_UNSUPPORTED;
-  A.y = x; A.out = x; A.t = nullptr; A.t_scalar = t;
-  A.b0 = sde->beta_min; A.b1 = sde->beta_max; A.T = sde->T;
-  A.delta = delta; A.sqrt_delta = (float)sqrt((double)delta); A.lmbd = lmbd;
-  A.z = z; A.rng = rng; A.rng_step = rng_step;
+  if (!z && !rng) return MSGM_E_BADARG;
+  rc = fill_em(A, x, sde, t, delta, lmbd, z, rng, rng_step);
+  if (rc) return rc;
   const int64_t tiles = (B + 31) / 32;
   const int64_t cap = mlp_wg_per_cu(A) * MLP_MAX_GRID;
   return launch_mlp<MODE_EM>(A, (int)(tiles < cap ? tiles : cap), S(stream));
@@ -1582,14 +1442,11 @@ int msgm_mlp_em_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm
   MlpArgs A{};
   int rc = fill_common(A, P, B);
   if (rc) return rc;
-  if (!x || !sde || !ts || !rng || n_steps < 1) return MSGM_E_BADARG;
-  if (sde->kind != MSGM_SDE_SGM) return MSGM_E_UNSUPPORTED;
+  if (!ts || !rng || n_steps < 1) return MSGM_E_BADARG;
+  rc = fill_em(A, x, sde, 0.f, delta, lmbd, nullptr, rng, rng_step0);
+  if (rc) return rc;
   const int64_t tiles = (B + 31) / 32;
   if (tiles < 2) return MSGM_E_UNSUPPORTED;              // a workgroup needs two tiles to prefetch one ahead
-  A.y = x; A.out = x; A.t = nullptr; A.t_scalar = 0.f;
-  A.b0 = sde->beta_min; A.b1 = sde->beta_max; A.T = sde->T;
-  A.delta = delta; A.sqrt_delta = (float)sqrt((double)delta); A.lmbd = lmbd;
-  A.z = nullptr; A.rng = rng; A.rng_step = rng_step0;
   A.n_steps = n_steps; A.ts = ts;
   const int64_t cap = mlp_wg_per_cu(A) * MLP_MAX_GRID;
   const int64_t grid = tiles / 2 < cap ? tiles / 2 : cap;
