@@ -665,6 +665,115 @@ __global__ void __launch_bounds__(256, (PT == 4 && !DB && NCO == 4) ? CT_WIDE_MI
   }
 }
 
+// ------------------------------------------------------------------ dgrad of a stride-2 3x3 pad-1 convolution: parity classes
+// The input cotangent of y = conv(x, k = 3, s = 2, p = 1) is the transposed gather i = (o + 1 - k) / 2 (mode 1): of the nine
+// taps an output pixel has only those whose (o + 1 - k) is even, so the strided implicit GEMM spends its MFMAs on fragments
+// that are three quarters zero (15-21 TFLOP/s as written).  By the parity (py, px) of the output pixel (2y + py, 2x + px)
+// the gather splits into four DENSE stride-1 sub-convolutions of gy over the offsets (dy, dx) in {0, 1}^2:
+//   py = 0: kh = 1 reads gy row y;            py = 1: kh = 2 reads row y, kh = 0 reads row y + 1       (columns alike)
+// i.e. 1, 2, 2 and 4 taps — nine in all, none masked.  A workgroup stages the (8 + 1) x (16 + 1) halo of an 8 x 16 gy tile
+// once per 32-channel chunk (zero-filled outside the image) and computes all four classes of its 16 x 32 output pixels from
+// it: wave w owns gy rows 2w, 2w + 1 (two MFMA column tiles), 32 output channels per workgroup, every activation fragment
+// (ds_read_b128, pitch CT_P: conflict-free) feeds the 1-4 classes that use its offset.  The weights are the Wd image the
+// strided gather reads ([tap][CinP][CoutK], tap = kh * 3 + kw): no new pack job.  Same epilogue contract as k_conv_gemm (bias
+// / per-sample bias, accumulate, residual; no channel statistics) and a fixed summation order: chunk, offset, group, class.
+// Host-side contract (conv_route): one source, C % 32 == 0, Cout % 32 == 0, Ho = 2 Hi, Wo = 2 Wi, no tap masks, no input transform.
+#define DS_TH 8
+#define DS_TW 16
+__global__ void __launch_bounds__(256, 3) k_dgrad_s2(ConvArgs A, int tiles_x, int tiles_y, int n_cob) {
+  constexpr int HW = DS_TW + 1, halo = (DS_TH + 1) * HW, n_items = halo * (CT_KC / 4), NST = (n_items + 255) / 256;
+  __shared__ __attribute__((aligned(16))) float ds_lds[halo * CT_P];
+  const int tid = threadIdx.x, lane = tid & 63, il = lane & 15, q = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const ConvGeom g = A.g;                  // g.Hi x g.Wi: the gy grid; g.Ho = 2 g.Hi, g.Wo = 2 g.Wi: the cotangent's grid
+  int t = blockIdx.x;
+  const int cob = t % n_cob; t /= n_cob;
+  const int tx_i = t % tiles_x; t /= tiles_x;
+  const int ty_i = t % tiles_y, n = t / tiles_y, y0 = ty_i * DS_TH, x0 = tx_i * DS_TW;
+  const int co0 = cob * 32, C = A.C[0];
+  f32x4 acc[4][2][2];                      // [parity class 2 py + px][16 output channels][pixel tile]
+#pragma unroll
+  for (int cls = 0; cls < 4; ++cls)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int pt = 0; pt < 2; ++pt) acc[cls][c][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float* base = A.src[0] + (size_t)n * g.Hi * g.Wi * C;
+  const float* wl = A.Wp + (size_t)(co0 + il) * A.Ktot + 4 * q;
+  const size_t tap_stride = (size_t)A.CoutP * A.Ktot, co_stride = (size_t)16 * A.Ktot;
+  for (int c0 = 0; c0 < C; c0 += CT_KC) {
+    if (c0) __syncthreads();               // every wave is done with the previous chunk's halo
+    f32x4 st[NST];
+#pragma unroll
+    for (int k = 0; k < NST; ++k) {
+      const int idx = tid + 256 * k, hp = idx >> 3, hy = hp / HW, hx = hp - hy * HW;
+      const int iy = y0 + hy, ix = x0 + hx;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (idx < n_items && iy < g.Hi && ix < g.Wi)
+        v = *reinterpret_cast<const f32x4*>(base + ((size_t)iy * g.Wi + ix) * C + c0 + 4 * (idx & 7));
+      st[k] = v;
+    }
+#pragma unroll
+    for (int k = 0; k < NST; ++k) {
+      const int idx = tid + 256 * k;
+      if (idx < n_items) *reinterpret_cast<f32x4*>(ds_lds + (idx >> 3) * CT_P + 4 * (idx & 7)) = st[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int off = 0; off < 4; ++off) {
+      const int dy = off >> 1, dx = off & 1;
+#pragma unroll
+      for (int grp = 0; grp < 2; ++grp) {
+        f32x4 b[2];
+#pragma unroll
+        for (int pt = 0; pt < 2; ++pt)
+          b[pt] = *reinterpret_cast<const f32x4*>(ds_lds + ((2 * w + pt + dy) * HW + il + dx) * CT_P + 16 * grp + 4 * q);
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls) {
+          const int py = cls >> 1, px = cls & 1;
+          if (dy > py || dx > px) continue;                 // compile-time: an even row / column has the centre tap only
+          const int kh = py ? (dy ? 0 : 2) : 1, kw = px ? (dx ? 0 : 2) : 1;
+          const float* wp = wl + (size_t)(kh * 3 + kw) * tap_stride + c0 + 16 * grp;
+          f32x4 a[2];
+#pragma unroll
+          for (int c = 0; c < 2; ++c) a[c] = *reinterpret_cast<const f32x4*>(wp + c * co_stride);
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+              for (int pt = 0; pt < 2; ++pt) acc[cls][c][pt] = mfma16c(a[c][r], b[pt][r], acc[cls][c][pt]);
+        }
+      }
+    }
+  }
+  // the epilogue's bounds checks are branches behind the last MFMAs: their wait states are written out
+  asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  const bool primal = n < A.n_bias;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int co = co0 + 16 * c + 4 * q;
+    f32x4 add = {0.f, 0.f, 0.f, 0.f};
+    if (primal && A.bias) add = *reinterpret_cast<const f32x4*>(A.bias + co);
+    if (A.samp_bias && n < A.n_samp) add += *reinterpret_cast<const f32x4*>(A.samp_bias + (size_t)n * A.Cout + co);
+#pragma unroll
+    for (int pt = 0; pt < 2; ++pt) {
+      const int yy = y0 + 2 * w + pt, xx = x0 + il;
+      if (yy >= g.Hi || xx >= g.Wi) continue;
+#pragma unroll
+      for (int cls = 0; cls < 4; ++cls) {
+        const size_t m = ((size_t)n * g.Ho + 2 * yy + (cls >> 1)) * g.Wo + 2 * xx + (cls & 1);
+        float* op = A.out + m * A.Cout + co;
+        f32x4 v = acc[cls][c][pt] + add;
+        if (A.accumulate) v += *reinterpret_cast<const f32x4*>(op);
+        if (A.residual) v += *reinterpret_cast<const f32x4*>(A.residual + (op - A.out));
+        *reinterpret_cast<f32x4*>(op) = v;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ 1x1 convolutions: pixel-stationary streaming kernel
 // A 1x1 (stride 1) convolution is a plain GEMM out[p][co] = sum_c x[p][c] W[co][c] with K = Cin of only 32..256: per
 // 32-channel chunk the halo-tile kernel above has 2 (tap, group) pairs = 64 MFMAs per wave between two barriers, and it
@@ -2350,6 +2459,134 @@ __global__ void __launch_bounds__(256, WW_LB) k_wgrad_wino(WgradArgs A, int tile
   }
 }
 
+// ------------------------------------------------------------------ wgrad of the U-Net's first / last 3x3 convolution (vector ALU)
+// 3 -> 32 and 32 -> 3 channels, 3x3 "same": 864 weight gradients over millions of pixels — one read of gy and of the input
+// (0.3 GB at the C4 shapes) and a handful of FMAs per byte.  On the MFMA tile kernel (k_wgrad_tile<8, 16, 9, RAG>) the three
+// channels fill 3 of 16 tile columns and the element-wise staging of the ragged side sets the speed (404 us per call).  Here
+// the 32-channel tensor is the STREAM ("big": gy of the first conv, the input of the last one) and the 3-channel one the
+// WINDOW ("small"):   acc[(dy, dx)][s] = sum_p big[p][b] * small[p + (dy, dx)][s],   (dy, dx) in {-1, 0, 1}^2.
+// Thread (b = tid & 31, row = tid >> 5) owns channel b of the big tensor on one 16-pixel row of an 8 x 16 tile, with all 27
+// (offset, s) sums in registers: its 16 stream values come straight from global memory (a wave reads two 128-byte pixel
+// rows per load), the window slides along the row through registers and takes one new column (three ds_read_b128 of the
+// zero-filled 10 x 18 x 4 halo in LDS, the same address for the 32 lanes of a row: a broadcast) per pixel.
+// GYBIG (first conv): big = gy [.][32], small = input [.][3], tap = offset.  !GYBIG (last conv): big = input, small = gy,
+// and m = p - (kh - 1, kw - 1) makes the offset of tap t that of 8 - t.
+// Same plan, slabs and slot order as k_wgrad_tile (a workgroup walks tiles_per_wg tiles, adds its eight rows in LDS in a
+// fixed order and stores one slab; bias by-product over the primal rows n < n_bias): no atomics, same bits every run.
+template <bool GYBIG>
+__global__ void __launch_bounds__(256) k_wgrad3(WgradArgs A, int tiles_x, int tiles_y, int tiles_per_wg, int n_tiles) {
+  constexpr int TH = 8, TW = 16, HW = TW + 2, halo = (TH + 2) * HW, NB = GYBIG ? 1 : 3, NR = 27 + 2 * NB;
+  __shared__ __attribute__((aligned(16))) float w3_halo[halo * 4];
+  __shared__ float w3_red[TH][NR][32];
+  const int tid = threadIdx.x, b = tid & 31;
+  const int row = __builtin_amdgcn_readfirstlane(tid >> 6) * 2 + ((tid >> 5) & 1);
+  const ConvGeom g = A.g;                       // stride 1, "same": one H x W grid for both tensors
+  const float* big = GYBIG ? A.gy : A.src;
+  const float* small = GYBIG ? A.src : A.gy;
+  const int t_beg = blockIdx.x * tiles_per_wg, t_end = min(t_beg + tiles_per_wg, n_tiles);
+  // bias by-product: ONE long sum of same-sized terms per channel (and, for the output conv, only three numbers to be judged
+  // by), where a serial fp32 chain loses the most — accumulated in double in the thread and across the tile rows, rounded
+  // to fp32 once per slab
+  float acc[9][3];
+  double bacc[NB];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) { acc[j][0] = 0.f; acc[j][1] = 0.f; acc[j][2] = 0.f; }
+#pragma unroll
+  for (int s = 0; s < NB; ++s) bacc[s] = 0.0;
+  for (int tile = t_beg; tile < t_end; ++tile) {
+    int t = tile;
+    const int tx_i = t % tiles_x; t /= tiles_x;
+    const int ty_i = t % tiles_y, n = t / tiles_y, y0 = ty_i * TH, x0 = tx_i * TW;
+    const bool primal = A.dbias && n < A.n_bias;           // uniform over the workgroup
+    // this thread's 16 stream values (zero outside the image)
+    float gv[TW];
+    {
+      const int y = y0 + row;
+      const float* bp = big + (((size_t)n * g.Ho + y) * g.Wo + x0) * 32 + b;
+#pragma unroll
+      for (int x = 0; x < TW; ++x) gv[x] = (y < g.Ho && x0 + x < g.Wo) ? bp[x * 32] : 0.f;
+    }
+    if (tile != t_beg) __syncthreads();         // every row is done with the previous tile's halo
+    if (tid < halo) {
+      const int hy = tid / HW, hx = tid - hy * HW, iy = y0 + hy - 1, ix = x0 + hx - 1;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (iy >= 0 && iy < g.Ho && ix >= 0 && ix < g.Wo) {
+        const float* sp = small + (((size_t)n * g.Ho + iy) * g.Wo + ix) * 3;
+        v[0] = sp[0]; v[1] = sp[1]; v[2] = sp[2];
+      }
+      *reinterpret_cast<f32x4*>(w3_halo + tid * 4) = v;
+    }
+    __syncthreads();
+    if (primal) {                               // a loop of its own: inside the FMA loop it cost that loop its schedule
+#pragma unroll
+      for (int x = 0; x < TW; ++x) {
+        if (GYBIG) bacc[0] += (double)gv[x];
+        else {
+          const f32x4 c = *reinterpret_cast<const f32x4*>(w3_halo + ((row + 1) * HW + x + 1) * 4);   // gy of pixel (row, x); zero outside the image
+#pragma unroll
+          for (int s = 0; s < 3; ++s) bacc[s] += (double)c[s];
+        }
+      }
+    }
+    // the window at pixel (row, x): halo rows row .. row + 2, columns x .. x + 2
+    f32x4 win[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      win[i][0] = *reinterpret_cast<const f32x4*>(w3_halo + ((row + i) * HW + 0) * 4);
+      win[i][1] = *reinterpret_cast<const f32x4*>(w3_halo + ((row + i) * HW + 1) * 4);
+    }
+#pragma unroll
+    for (int x = 0; x < TW; ++x) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) win[i][2] = *reinterpret_cast<const f32x4*>(w3_halo + ((row + i) * HW + x + 2) * 4);
+      const float gx = gv[x];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+          for (int s = 0; s < 3; ++s) acc[i * 3 + j][s] = __builtin_fmaf(gx, win[i][j][s], acc[i * 3 + j][s]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { win[i][0] = win[i][1]; win[i][1] = win[i][2]; }
+    }
+  }
+  // ---- the eight rows meet in LDS and are added in row order; one slab store per element
+#pragma unroll
+  for (int j = 0; j < 9; ++j)
+#pragma unroll
+    for (int s = 0; s < 3; ++s) w3_red[row][j * 3 + s][b] = acc[j][s];
+#pragma unroll
+  for (int s = 0; s < NB; ++s) {               // a double as two floats (48 bits of it)
+    const float hi = (float)bacc[s];
+    w3_red[row][27 + 2 * s][b] = hi;
+    w3_red[row][28 + 2 * s][b] = (float)(bacc[s] - (double)hi);
+  }
+  __syncthreads();
+  float* slab = A.slab + (size_t)blockIdx.x * A.slab_stride;
+  const int img = 9 * A.CoutP * A.C;
+  for (int e = tid; e < (27 + NB) * 32; e += 256) {
+    const int k = e >> 5, bb = e & 31;
+    float s = 0.f;
+    if (k < 27) {
+#pragma unroll
+      for (int r = 0; r < TH; ++r) s += w3_red[r][k][bb];
+    } else {
+      double d = 0.0;
+#pragma unroll
+      for (int r = 0; r < TH; ++r) d += (double)w3_red[r][27 + 2 * (k - 27)][bb] + (double)w3_red[r][28 + 2 * (k - 27)][bb];
+      s = (float)d;
+    }
+    if (k < 27) {
+      const int j = k / 3, sc = k - 3 * j;
+      if (GYBIG) slab[(j * A.CoutP + bb) * 3 + sc] = s;                    // dW[tap j][co = bb][c = sc]
+      else slab[((8 - j) * A.CoutP + sc) * 32 + bb] = s;                   // dW[tap 8 - j][co = sc][c = bb]
+    } else if (A.dbias) {
+      if (GYBIG) slab[img + bb] = s;
+      else if (bb == 0) slab[img + (k - 27)] = s;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ wgrad of 1x1 convolutions: pixel-streaming kernel
 // dW[co][c] = sum_p gy[p][co] x[p][c] with the pixel as the reduction index: 2 Cout C / (4 (Cout + C)) = 8..48 FLOPs per
 // byte, i.e. HBM-bound below ~128 x 128 channels and MFMA-bound above.  k_wgrad_tile<., ., 1> splits dW into 32 x 32
@@ -2881,7 +3118,8 @@ int msgm_conv_forward_b6(const msgm_conv_geom_t* geom, const float* src0, int32_
 // Which kernel serves a forward convolution, and with what tiling — ONE decision shared by the launcher and by
 // msgm_conv_chanstats_slots (the channel-statistics by-product is laid out per (tile, wave) of that tiling).
 struct ConvRoute {
-  int kind;                 // 0 implicit GEMM from L2, 1 pixel-stationary 1x1, 2 halo tile, 3 / 4 vector-ALU first / last conv
+  int kind;                 // 0 implicit GEMM from L2, 1 pixel-stationary 1x1, 2 halo tile, 3 / 4 vector-ALU first / last conv,
+                            // 5 parity-class dgrad of a stride-2 3x3 convolution
   int pt, kg;               // 1x1: 16-pixel tiles per wave, 16-channel input groups
   bool wide, two_d; int nco, TH, TW, tiles_x, tiles_y;      // halo tile
 };
@@ -2889,10 +3127,17 @@ struct ConvRoute {
 static bool conv_small_shape(const msgm_conv_geom_t* geom, bool has1, bool masks) {
   return conv_same(geom) && geom->KH == 3 && geom->KW == 3 && !geom->ups && geom->Ho > 1 && !has1 && !masks;
 }
+// the transposed gather of a 3x3 stride-2 pad-1 convolution onto the exact 2x grid (its dgrad at even sizes): k_dgrad_s2
+static bool conv_dgrad_s2_shape(const msgm_conv_geom_t* geom, int32_t C0, bool has1, int32_t Cout, int32_t CoutP, bool masks) {
+  return geom->mode == 1 && geom->KH == 3 && geom->KW == 3 && geom->strideH == 2 && geom->strideW == 2 && geom->padH == 1 &&
+         geom->padW == 1 && !geom->ups && geom->Ho == 2 * geom->Hi && geom->Wo == 2 * geom->Wi && !has1 && !masks &&
+         C0 % 32 == 0 && Cout % 32 == 0 && CoutP == Cout;
+}
 static ConvRoute conv_route(const msgm_conv_geom_t* geom, int32_t C0, bool has1, int32_t C1, int32_t Cout, int32_t CoutP,
                             bool masks, bool both_extra = false /* accumulate AND residual */, bool any_size = false) {
   ConvRoute r{};
   const int64_t Mtot = (int64_t)geom->N * geom->Ho * geom->Wo;
+  if (conv_dgrad_s2_shape(geom, C0, has1, Cout, CoutP, masks)) { r.kind = 5; return r; }
   if (conv_small_shape(geom, has1, masks)) {
     if (C0 <= 4 && Cout == 32 && CoutP == 32) { r.kind = 3; return r; }      // forward, or (mode 1) the dgrad of the output conv
     if (C0 == 32 && Cout <= 4 && geom->mode == 0) { r.kind = 4; return r; }
@@ -2942,7 +3187,7 @@ static int conv_route_slots(const ConvRoute& r, const msgm_conv_geom_t* geom, in
   if (r.kind == 1) { const int P = geom->Ho * geom->Wo; return P % (16 * r.pt) == 0 ? P / (16 * r.pt) : 0; }
   if (r.kind == 2) return r.tiles_x * r.tiles_y * 4;
   if (r.kind == 3) { const int P = geom->Ho * geom->Wo; return P % 64 == 0 ? P / 64 : 0; }
-  if (r.kind == 4) return 0;
+  if (r.kind == 4 || r.kind == 5) return 0;
   const int P = geom->Ho * geom->Wo, px = 16 * r.pt;      // implicit GEMM: a wave owns 16 NT consecutive pixels
   return P % px == 0 ? P / px : 0;
 }
@@ -3016,6 +3261,14 @@ int msgm_conv_forward_fused(const msgm_conv_geom_t* geom, const float* src0, int
       case 3: hipLaunchKernelGGL((k_conv3x3_cout_small<3>), grid, dim3(256), lds, S(stream), A, tiles_x, tiles_y); break;
       default: hipLaunchKernelGGL((k_conv3x3_cout_small<4>), grid, dim3(256), lds, S(stream), A, tiles_x, tiles_y); break;
     }
+    return msgm_check_launch();
+  }
+  // dgrad of a stride-2 3x3 convolution: four dense parity classes from one staged gy halo
+  if (rt.kind == 5) {
+    const int tiles_x = (geom->Wi + DS_TW - 1) / DS_TW, tiles_y = (geom->Hi + DS_TH - 1) / DS_TH, n_cob = Cout / 32;
+    const int64_t wgs = (int64_t)geom->N * tiles_x * tiles_y * n_cob;
+    if (wgs >= (1ll << 31)) return MSGM_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_dgrad_s2, dim3((unsigned)wgs), dim3(256), 0, S(stream), A, tiles_x, tiles_y, n_cob);
     return msgm_check_launch();
   }
   // 1x1 stride-1 convolution (forward or dgrad): pixel-stationary streaming kernel, no LDS
@@ -3298,7 +3551,12 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
     const bool rag = (C & 3) || (Cout & 3);
     if (two_d) {
       if (taps == 9) {
-        if (rag) WT_LAUNCH2(8, 16, 9, true);
+        if (rag && !geom->ups && !tapmask_c32 && !tapmask_co32 && ((C == 3 && Cout == 32) || (C == 32 && Cout == 3))) {
+          // the U-Net's first / last convolution: vector-ALU stream over the 32-channel tensor (same tiles, slabs and slot order)
+          if (C == 3) hipLaunchKernelGGL(k_wgrad3<true>, grid, dim3(256), 0, S(stream), A, tiles_x, tiles_y, per, n_tiles);
+          else hipLaunchKernelGGL(k_wgrad3<false>, grid, dim3(256), 0, S(stream), A, tiles_x, tiles_y, per, n_tiles);
+        }
+        else if (rag) WT_LAUNCH2(8, 16, 9, true);
         else if (tapmask_c32 || tapmask_co32) return MSGM_E_UNSUPPORTED;   // k_wgrad_tile9 has no tap masks (they come from 3-tap 1-D convs)
         else if (pl.wino) {
           const size_t ldsw = (size_t)(WW_DBUF ? 2 : 1) * (32 * WT_GP + 32 * WW_IP) * sizeof(float);
