@@ -267,6 +267,49 @@ __global__ void __launch_bounds__(256) k_conv_gemm(ConvArgs A) {
   }
 }
 
+// ------------------------------------------------------------------ phases shared by the forward / dgrad kernels
+// Spatial tile t of a sample-major [N][tiles_y][tiles_x] grid of TH x TW tiles: its sample and the pixel of its corner.
+template <int TH, int TW>
+__device__ __forceinline__ void tile_origin(int t, int tiles_x, int tiles_y, int& n, int& y0, int& x0) {
+  const int tx_i = t % tiles_x; t /= tiles_x;
+  const int ty_i = t % tiles_y;
+  n = t / tiles_y; y0 = ty_i * TH; x0 = tx_i * TW;
+}
+// Epilogue contract of every forward kernel, for a lane's 4 consecutive output channels co .. co + 3 (`full`: all four exist
+// and Cout % 4 == 0, so 16-byte accesses): the addend is bias (rows n < n_bias) + per-sample bias (rows n < n_samp) ...
+__device__ __forceinline__ f32x4 conv_addend(const ConvArgs& A, int n, int co, bool full) {
+  const bool primal = n < A.n_bias;
+  f32x4 add = {0.f, 0.f, 0.f, 0.f};
+  if (primal && A.bias) {
+    if (full) add = *reinterpret_cast<const f32x4*>(A.bias + co);
+    else
+#pragma unroll
+      for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] = A.bias[co + r];
+  }
+  if (A.samp_bias && n < A.n_samp) {
+    const float* sbp = A.samp_bias + (size_t)n * A.Cout + co;
+    if (full) add += *reinterpret_cast<const f32x4*>(sbp);
+    else
+#pragma unroll
+      for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] += sbp[r];
+  }
+  return add;
+}
+// ... and the store of one pixel's quad v at op: accumulate, residual, vector or ragged store; a full quad also feeds the
+// channel-statistics sums cs / css with its FINAL values.
+__device__ __forceinline__ void conv_store_quad(const ConvArgs& A, float* op, f32x4 v, bool full, int co, f32x4& cs, f32x4& css) {
+  if (full) {
+    if (A.accumulate) v += *reinterpret_cast<const f32x4*>(op);
+    if (A.residual) v += *reinterpret_cast<const f32x4*>(A.residual + (op - A.out));
+    *reinterpret_cast<f32x4*>(op) = v;
+    cs += v; css += v * v;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (co + r < A.Cout) op[r] = (A.accumulate ? op[r] + v[r] : v[r]) + (A.residual ? A.residual[(op - A.out) + r] : 0.f);
+  }
+}
+
 // ------------------------------------------------------------------ stride-1 "same" convolutions: halo tile in LDS
 // k_conv_gemm re-reads every input pixel once per tap from L2 (9x for 3x3) and, at small Cout, that fragment
 // traffic — not the MFMA pipe — sets its speed.  For stride-1, pad=(K-1)/2 convolutions (the bulk of both U-Nets,
@@ -302,14 +345,8 @@ __global__ void __launch_bounds__(256) k_conv_gemm(ConvArgs A) {
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 template <int TH, int TW, int NCO, int KS, int PT = 2, bool DB = true, bool B6 = false>
-#ifndef CT_MINWG
-#define CT_MINWG 1
-#endif
-#ifndef CT_WIDE_MINWG
-#define CT_WIDE_MINWG 1
-#endif
-__global__ void __launch_bounds__(256, (PT == 4 && !DB && NCO == 4) ? CT_WIDE_MINWG : CT_MINWG) k_conv_tile(ConvArgs A, int flip, int tiles_x, int tiles_y, int tiles_per_wg, int n_tiles,
-                                                             int n_cob, int n_tgrp) {
+__global__ void __launch_bounds__(256, 1) k_conv_tile(ConvArgs A, int flip, int tiles_x, int tiles_y, int tiles_per_wg, int n_tiles,
+                                                      int n_cob, int n_tgrp) {
   extern __shared__ __attribute__((aligned(16))) float ct_lds[];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const ConvGeom g = A.g;
@@ -357,14 +394,9 @@ __global__ void __launch_bounds__(256, (PT == 4 && !DB && NCO == 4) ? CT_WIDE_MI
   const int padH = g.padH, padW = g.padW;
   const int up = g.ups ? 1 : 0;          // Upsample folded into the gather (model/unet.py:60-73)
   const int ctot_all = A.C[0] + (A.nsrc > 1 ? A.C[1] : 0);
-  auto tile_origin = [&](int t, int& n, int& y0, int& x0) {
-    const int tx_i = t % tiles_x; t /= tiles_x;
-    const int ty_i = t % tiles_y;
-    n = t / tiles_y; y0 = ty_i * TH; x0 = tx_i * TW;
-  };
   auto stage_load = [&](f32x4* dst, int t, int s, int c0, int K0, int K1) __attribute__((always_inline)) {
     int n, y0, x0;
-    tile_origin(t, n, y0, x0);
+    tile_origin<TH, TW>(t, tiles_x, tiles_y, n, y0, x0);
     const int C = A.C[s];
     const float* base = A.src[s] + (size_t)n * g.Hi * g.Wi * C;
     // folded GroupNorm(+SiLU): this thread's 4 channels are the same for every k (256 % 8 == 0), so a and b are
@@ -394,11 +426,7 @@ __global__ void __launch_bounds__(256, (PT == 4 && !DB && NCO == 4) ? CT_WIDE_MI
         const int hy = hp / HW, hx = hp - hy * HW;
         const int iy = y0 + hy - padH, ix = x0 + hx - padW;     // on the (2x nearest-upsampled, if ups) input grid
         const int c = c0 + 4 * c4;
-#ifdef CT_EXP_NOSTAGE    // diagnostic: no halo loads / index arithmetic
-        if (false) {
-#else
         if (iy >= 0 && iy < (g.Hi << up) && ix >= 0 && ix < (g.Wi << up) && c < C) {
-#endif
           v = *reinterpret_cast<const f32x4*>(base + ((size_t)(iy >> up) * g.Wi + (ix >> up)) * C + c);
           valid |= 1u << k;                                    // a real pixel: zero padding stays zero
         }
@@ -579,15 +607,9 @@ __global__ void __launch_bounds__(256, (PT == 4 && !DB && NCO == 4) ? CT_WIDE_MI
         continue;
       }
       f32x4 b[PT];
-#ifndef CT_EXP_NOLDS    // diagnostic: -DCT_EXP_NOLDS feeds the MFMAs from registers (no activation reads)
 #pragma unroll
       for (int pt = 0; pt < PT; ++pt)
         b[pt] = *reinterpret_cast<const f32x4*>(cur + ((pty_of(pt) + oy) * HW + ptx_of(pt) + ox) * CT_P + 16 * grp + 4 * q);
-#else
-#pragma unroll
-      for (int pt = 0; pt < PT; ++pt) b[pt] = a[pt % NCO];
-      (void)oy; (void)ox;
-#endif
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -598,22 +620,20 @@ __global__ void __launch_bounds__(256, (PT == 4 && !DB && NCO == 4) ? CT_WIDE_MI
     }
 
     // ---- epilogue of a finished tile (same contract as k_conv_gemm)
-#ifdef CT_EXP_NOEPI      // diagnostic: one lane stores one value
-    if (last_chunk && tid == 0 && tile == t_beg) A.out[0] = acc[0][0][0] + acc[NCO - 1][PT - 1][3];
-    if (false) {
-#else
     if (last_chunk) {
-#endif
       int n, y0, x0;
-      tile_origin(tile, n, y0, x0);
-      const bool primal = n < A.n_bias;
+      tile_origin<TH, TW>(tile, tiles_x, tiles_y, n, y0, x0);
       const bool vec = (A.Cout & 3) == 0;                 // 16-B accesses along the output channels
 #pragma unroll
       for (int c = 0; c < NCO; ++c) {
         const int co = co0 + 16 * c + 4 * q;
         if (co >= A.Cout) continue;
         const bool full = vec && (co + 3 < A.Cout);
-        // bias / per-sample bias of this lane's 4 channels: fetched once, shared by its two pixels
+        // bias / per-sample bias of this lane's 4 channels, fetched once for its PT pixels: conv_addend's code, kept written out —
+        // through the function the <16, 16, 4, 3, 4, false> form measured 1.4-2.4 % slower at the C4 shapes and the 1-D NCO = 4 forms
+        // 0.4-0.9 %, by value or by reference alike (same registers, 27 more instructions; the rows of build "tile_shared_addend"
+        // in profiles/conv_shared/bench_conv_shared.json)
+        const bool primal = n < A.n_bias;
         f32x4 add = {0.f, 0.f, 0.f, 0.f};
         if (primal && A.bias) {
           if (full) add = *reinterpret_cast<const f32x4*>(A.bias + co);
@@ -633,18 +653,7 @@ __global__ void __launch_bounds__(256, (PT == 4 && !DB && NCO == 4) ? CT_WIDE_MI
         for (int pt = 0; pt < PT; ++pt) {
           if (!((y0 + pty_of(pt) < g.Ho) && (x0 + ptx_of(pt) < g.Wo))) continue;
           const size_t m = ((size_t)n * g.Ho + y0 + pty_of(pt)) * g.Wo + x0 + ptx_of(pt);
-          f32x4 v = acc[c][pt] + add;
-          float* op = A.out + m * A.Cout + co;
-          if (full) {
-            if (A.accumulate) v += *reinterpret_cast<const f32x4*>(op);
-            if (A.residual) v += *reinterpret_cast<const f32x4*>(A.residual + (op - A.out));
-            *reinterpret_cast<f32x4*>(op) = v;
-            cs += v; css += v * v;
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (co + r < A.Cout) op[r] = (A.accumulate ? op[r] + v[r] : v[r]) + (A.residual ? A.residual[(op - A.out) + r] : 0.f);
-          }
+          conv_store_quad(A, A.out + m * A.Cout + co, acc[c][pt] + add, full, co, cs, css);
         }
         if (A.cstat) cstat_store(A, n, (tile - n * tiles_x * tiles_y) * 4 + w, co, cs, css, il);   // Cout % 4 == 0 (host)
       }
@@ -686,10 +695,9 @@ __global__ void __launch_bounds__(256, 3) k_dgrad_s2(ConvArgs A, int tiles_x, in
   const int tid = threadIdx.x, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const ConvGeom g = A.g;                  // g.Hi x g.Wi: the gy grid; g.Ho = 2 g.Hi, g.Wo = 2 g.Wi: the cotangent's grid
-  int t = blockIdx.x;
-  const int cob = t % n_cob; t /= n_cob;
-  const int tx_i = t % tiles_x; t /= tiles_x;
-  const int ty_i = t % tiles_y, n = t / tiles_y, y0 = ty_i * DS_TH, x0 = tx_i * DS_TW;
+  const int t = blockIdx.x, cob = t % n_cob;
+  int n, y0, x0;
+  tile_origin<DS_TH, DS_TW>(t / n_cob, tiles_x, tiles_y, n, y0, x0);
   const int co0 = cob * 32, C = A.C[0];
   f32x4 acc[4][2][2];                      // [parity class 2 py + px][16 output channels][pixel tile]
 #pragma unroll
@@ -750,13 +758,11 @@ __global__ void __launch_bounds__(256, 3) k_dgrad_s2(ConvArgs A, int tiles_x, in
   // the epilogue's bounds checks are branches behind the last MFMAs: their wait states are written out
   asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
-  const bool primal = n < A.n_bias;
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     const int co = co0 + 16 * c + 4 * q;
-    f32x4 add = {0.f, 0.f, 0.f, 0.f};
-    if (primal && A.bias) add = *reinterpret_cast<const f32x4*>(A.bias + co);
-    if (A.samp_bias && n < A.n_samp) add += *reinterpret_cast<const f32x4*>(A.samp_bias + (size_t)n * A.Cout + co);
+    const f32x4 add = conv_addend(A, n, co, true);          // Cout % 32 == 0 (host): every quad is full
+    f32x4 cs = {0.f, 0.f, 0.f, 0.f}, css = cs;              // (no channel statistics here: the sums fold away)
 #pragma unroll
     for (int pt = 0; pt < 2; ++pt) {
       const int yy = y0 + 2 * w + pt, xx = x0 + il;
@@ -764,11 +770,7 @@ __global__ void __launch_bounds__(256, 3) k_dgrad_s2(ConvArgs A, int tiles_x, in
 #pragma unroll
       for (int cls = 0; cls < 4; ++cls) {
         const size_t m = ((size_t)n * g.Ho + 2 * yy + (cls >> 1)) * g.Wo + 2 * xx + (cls & 1);
-        float* op = A.out + m * A.Cout + co;
-        f32x4 v = acc[cls][c][pt] + add;
-        if (A.accumulate) v += *reinterpret_cast<const f32x4*>(op);
-        if (A.residual) v += *reinterpret_cast<const f32x4*>(A.residual + (op - A.out));
-        *reinterpret_cast<f32x4*>(op) = v;
+        conv_store_quad(A, A.out + m * A.Cout + co, acc[cls][c][pt] + add, true, co, cs, css);
       }
     }
   }
@@ -792,7 +794,8 @@ __global__ void __launch_bounds__(256, 3) k_dgrad_s2(ConvArgs A, int tiles_x, in
 // (64 -> 192 channels at 1024 x 1024 pixels: 0.27 ms without the stores, 0.46 ms with them).  Here every per-tile load
 // (weight ring, bias + per-sample bias, residual) is unconditional (clamped index or a 0/1 factor), is issued a tile
 // ahead, BEFORE the previous tile's stores, and nothing in the loop waits on a store.
-// What is left (diagnostic builds -DC1_EXP_NOMFMA / -DC1_EXP_COALESCED / -DC1_EXP_NOSTORE, 64 -> 192 channels): the memory
+// What is left (measured with diagnostic builds whose switches are gone from the source: no MFMAs / fully coalesced stores /
+// no stores, 64 -> 192 channels): the memory
 // streams alone take 0.35 ms with these 64-byte-per-pixel store segments (0.27 ms if every store wrote 1 KB contiguous), the
 // MFMAs alone 0.27 ms, both together 0.43 ms — three waves per SIMD do not overlap the two completely.
 // Host-side contract (conv_route): Cout % 16 == 0, P % (16 PT) == 0 (a wave's pixels belong to one sample), C0 % 16 == 0
@@ -892,15 +895,10 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs A, int P /* pixels per
         }
       }
       __builtin_amdgcn_sched_barrier(0);     // keep the requests HERE, D pairs ahead of their use (the scheduler sinks them)
-#ifdef C1_EXP_NOMFMA       // diagnostic (WRONG results): the kernel's memory streams without its matrix work
-#pragma unroll
-      for (int pt = 0; pt < PT; ++pt) acc[pt] += a * b[pt][g];
-#else
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int pt = 0; pt < PT; ++pt) acc[pt] = mfma16c(a[r], b[pt][g][r], acc[pt]);
-#endif
     }
     // ---- epilogue of this tile: lane (pixel il of tile pt, channels 16ct + 4q .. +3).
     // Output stores go out as FULL 128-byte lines: two consecutive channel tiles (32 channels = 128 bytes per pixel) meet in
@@ -914,17 +912,10 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs A, int P /* pixels per
     for (int pt = 0; pt < PT; ++pt) {
       f32x4 v = acc[pt] + add;
       if (EXTRA) v += exv[pt];
-#if defined(C1_EXP_NOSTORE)    // diagnostic: what the kernel costs without its output stores
-      if (v[0] == 12345.678f) *reinterpret_cast<f32x4*>(A.out + orow + pt * ptstep + 16 * ct) = v;
-#elif defined(C1_EXP_COALESCED)    // diagnostic (WRONG results): the same bytes as fully coalesced 1-KB stores
-      *reinterpret_cast<f32x4*>(A.out + ((size_t)(m0 / 16 + pt) * (A.Cout / 16) + ct) * 256 + lane * 4) = v;
-#else
       if (paired) *reinterpret_cast<f32x4*>(wl + (16 * pt + il) * C1_LP + 16 * half + 4 * q) = v;
       else *reinterpret_cast<f32x4*>(A.out + orow + pt * ptstep + 16 * ct) = v;
-#endif
       cs += v; css += v * v;
     }
-#if !defined(C1_EXP_NOSTORE) && !defined(C1_EXP_COALESCED)
     if (LDS_OUT && half == 1) {                             // both halves are in LDS: rows out, 8 pixels per instruction
       const size_t obase = (size_t)m0 * A.Cout + 16 * (ct - 1) + 4 * (lane & 7);
 #pragma unroll
@@ -935,8 +926,66 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs A, int P /* pixels per
         if (j & 1) __builtin_amdgcn_sched_barrier(0);      // two rows in flight, not all 2 PT (registers)
       }
     }
-#endif
     if (A.cstat) cstat_store(A, n, (int)((m0 % P) / (16 * PT)), 16 * ct + 4 * q, cs, css, il);
+  }
+}
+
+// ------------------------------------------------------------------ 18 x 18 halo of a 16 x 16 tile, pad 1, one 32-channel chunk
+// Staging shared by the kernels whose workgroup is one 16 x 16 output tile of a 3x3 "same" convolution (the Winograd sampler
+// forms and k_conv3x3_cout_small): thread tid moves the 16-byte items tid + 256 k, item = (halo pixel idx >> 3, channel quad
+// idx & 7).  halo18_load requests them all (channels c0 .. c0 + 31 of a source with C channels, sample n, tile corner (y0, x0);
+// up = 1: the source is read 2x nearest-upsampled; zero outside the image and past C) together with the folded GroupNorm's
+// a, b of this thread's quad (aff0: offset of the source's channel 0 of sample n in in_scale / in_shift); halo18_store applies
+// act(a x + b) to the real pixels (zero padding stays zero) and writes the tile at pitch CT_P.  All loads are issued before the
+// transform: applied inside the bounds check of each load, every load waited for the previous one's data (see k_conv_tile).
+// k_conv_tile keeps its own generalisation of this (any tile shape, K0 / K1 halves, DB-dependent placement of the affine fetch,
+// bf16-split planes, re-derived indices): each of those exists for a measured register reason recorded in its comments.
+constexpr int H18_HW = 18, H18_ITEMS = H18_HW * H18_HW * (CT_KC / 4), H18_NST = (H18_ITEMS + 255) / 256;
+__device__ __forceinline__ void halo18_load(const ConvArgs& A, const ConvGeom& g, const float* src, int C, int up, int c0, size_t aff0, int n, int y0, int x0,
+                                            int tid, f32x4 (&st)[H18_NST], unsigned& valid, f32x4& ga, f32x4& gb) {
+  const float* base = src + (size_t)n * g.Hi * g.Wi * C;
+  const int cq = c0 + 4 * (tid & 7);
+  ga = f32x4{1.f, 1.f, 1.f, 1.f}; gb = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (A.in_scale && cq < C) {
+    const size_t o = aff0 + cq;
+    ga = *reinterpret_cast<const f32x4*>(A.in_scale + o);
+    gb = *reinterpret_cast<const f32x4*>(A.in_shift + o);
+  }
+  valid = 0;
+#pragma unroll
+  for (int k = 0; k < H18_NST; ++k) {
+    const int idx = tid + 256 * k;
+    f32x4 v = {0, 0, 0, 0};
+    if (idx < H18_ITEMS) {
+      const int hp = idx >> 3, hy = hp / H18_HW, hx = hp - hy * H18_HW;        // division by the constant 18
+      const int iy = y0 + hy - 1, ix = x0 + hx - 1;
+      const int c = c0 + 4 * (idx & 7);
+      if (iy >= 0 && iy < (g.Hi << up) && ix >= 0 && ix < (g.Wi << up) && c < C) {
+        v = *reinterpret_cast<const f32x4*>(base + ((size_t)(iy >> up) * g.Wi + (ix >> up)) * C + c);
+        valid |= 1u << k;
+      }
+    }
+    st[k] = v;
+  }
+}
+__device__ __forceinline__ void halo18_store(const ConvArgs& A, float* buf, int tid, f32x4 (&st)[H18_NST], unsigned valid, f32x4 ga, f32x4 gb) {
+  if (A.in_scale) {
+#pragma unroll
+    for (int k = 0; k < H18_NST; ++k) {
+      if ((valid >> k) & 1u) {
+        f32x4 v = st[k] * ga + gb;
+        if (A.in_act == 1) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = v[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[r]));
+        }
+        st[k] = v;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < H18_NST; ++k) {
+    const int idx = tid + 256 * k;
+    if (idx < H18_ITEMS) *reinterpret_cast<f32x4*>(buf + (idx >> 3) * CT_P + 4 * (idx & 7)) = st[k];
   }
 }
 
@@ -948,8 +997,8 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs A, int P /* pixels per
 // (uniform addresses: s_load), one thread per output pixel:
 //   k_conv3x3_cin_small : <= 4 input channels read straight from global memory / L1 (27 floats per pixel), CO accumulators;
 //                         optional channel-statistics by-product (full-wave DPP reduction);
-//   k_conv3x3_cout_small: <= 4 output channels; the 32-channel input halo tile is staged in LDS exactly as k_conv_tile does
-//                         (same fused GroupNorm + SiLU input transform), each thread reads its 9 x 32 inputs as ds_read_b128.
+//   k_conv3x3_cout_small: <= 4 output channels; the 32-channel input halo tile is staged in LDS by halo18_load / halo18_store
+//                         (the fused GroupNorm + SiLU input transform of the Winograd sampler kernels), each thread reads its 9 x 32 inputs as ds_read_b128.
 // Forward only (mode 0); same bias / per-sample bias / accumulate / residual contract as the other forward kernels.
 __device__ __forceinline__ float wave64_sum_to_last(float v) {        // lane 63 ends with the sum over the wave
   v = row16_sum(v);
@@ -1016,50 +1065,14 @@ __global__ void __launch_bounds__(256) k_conv3x3_cout_small(ConvArgs A, int tile
   extern __shared__ __attribute__((aligned(16))) float cs_lds[];      // [18 * 18][CT_P]
   const ConvGeom g = A.g;
   const int tid = threadIdx.x;
-  constexpr int HW = 18, n_items = HW * HW * 8;
-  int t = blockIdx.x;
-  const int tx_i = t % tiles_x; t /= tiles_x;
-  const int ty_i = t % tiles_y, n = t / tiles_y, y0 = ty_i * 16, x0 = tx_i * 16;
-  const float* base = A.src[0] + (size_t)n * g.Hi * g.Wi * 32;
-  // ---- halo tile of the 32 input channels, GroupNorm(+SiLU) applied while staging (zero padding stays zero)
-  f32x4 ga = {1.f, 1.f, 1.f, 1.f}, gb = {0.f, 0.f, 0.f, 0.f};
-  const int c4 = tid & 7;
-  if (A.in_scale) {
-    ga = *reinterpret_cast<const f32x4*>(A.in_scale + (size_t)n * 32 + 4 * c4);
-    gb = *reinterpret_cast<const f32x4*>(A.in_shift + (size_t)n * 32 + 4 * c4);
-  }
-  constexpr int NST = (n_items + 255) / 256;
-  f32x4 st[NST];
-  unsigned valid = 0;
-#pragma unroll
-  for (int k = 0; k < NST; ++k) {                           // all the loads first, then the transform (see k_conv_tile)
-    const int idx = tid + 256 * k;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (idx < n_items) {
-      const int hp = idx >> 3, hy = hp / HW, hx = hp - hy * HW;
-      const int iy = y0 + hy - 1, ix = x0 + hx - 1;
-      if (iy >= 0 && iy < g.Hi && ix >= 0 && ix < g.Wi) {
-        v = *reinterpret_cast<const f32x4*>(base + ((size_t)iy * g.Wi + ix) * 32 + 4 * c4);
-        valid |= 1u << k;
-      }
-    }
-    st[k] = v;
-  }
-#pragma unroll
-  for (int k = 0; k < NST; ++k) {
-    const int idx = tid + 256 * k;
-    if (idx < n_items) {
-      f32x4 v = st[k];
-      if (A.in_scale && ((valid >> k) & 1u)) {
-        v = v * ga + gb;
-        if (A.in_act == 1) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = v[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[r]));
-        }
-      }
-      *reinterpret_cast<f32x4*>(cs_lds + (idx >> 3) * CT_P + 4 * c4) = v;
-    }
-  }
+  constexpr int HW = H18_HW;
+  int n, y0, x0;
+  tile_origin<16, 16>(blockIdx.x, tiles_x, tiles_y, n, y0, x0);
+  // ---- halo tile of the 32 input channels (one source, not upsampled), GroupNorm(+SiLU) applied while staging
+  f32x4 st[H18_NST], ga, gb;
+  unsigned valid;
+  halo18_load(A, g, A.src[0], 32, 0, 0, (size_t)n * 32, n, y0, x0, tid, st, valid, ga, gb);
+  halo18_store(A, cs_lds, tid, st, valid, ga, gb);
   __syncthreads();
   const int py = tid >> 4, px = tid & 15;
   float acc[CO];
@@ -1131,6 +1144,55 @@ __device__ __forceinline__ void wino_patch_load(f32x4 (&d)[4][4], const float* _
   }
 }
 
+// V = B^T d B of a lane's 4x4 patch (4 channels), in place: the one input transform of every Winograd forward kernel.
+__device__ __forceinline__ void wino_input_transform(f32x4 (&d)[4][4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x4 r0 = d[0][j] - d[2][j], r1 = d[1][j] + d[2][j], r2 = d[2][j] - d[1][j], r3 = d[1][j] - d[3][j];
+    d[0][j] = r0; d[1][j] = r1; d[2][j] = r2; d[3][j] = r3;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const f32x4 c0_ = d[i][0] - d[i][2], c1_ = d[i][1] + d[i][2], c2_ = d[i][2] - d[i][1], c3_ = d[i][1] - d[i][3];
+    d[i][0] = c0_; d[i][1] = c1_; d[i][2] = c2_; d[i][3] = c3_;
+  }
+}
+// Transformed weights through LDS, laid out as the A fragments themselves: one 1-KB piece per (position, co tile), lane-linear.
+// wino_wfill copies the 16 pieces of one half-group (8 positions x 2 co tiles) by LDS-DMA, wave w pieces 4w .. 4w + 3 (piece =
+// 2 (position in the half) + co tile); src: this lane's fragment of the half's first position, co tile 0 —
+// U[pos][co0 + il][k .. k + 3], k = 4 q of the group.
+__device__ __forceinline__ void wino_wfill(const float* src, float* dst, int w, size_t pos_stride, size_t a_co_stride) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int pw = 4 * w + j;
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(pw >> 1) * pos_stride + (pw & 1) * a_co_stride),
+                                     (__attribute__((address_space(3))) void*)(dst + pw * 256), 16, 0, 0);
+  }
+}
+// M_p += U_p V_p for the NPOS positions pos0 .. pos0 + NPOS - 1 whose pieces start at wb (this lane's slot of the first): the
+// fragments are read one position ahead, r = 0..3 inside a position and co tile 0 before tile 1 (the order every Winograd kernel
+// keeps: equal results bit for bit); the scheduling fence keeps one position's reads in flight, not all of them.
+template <int NPOS>
+__device__ __forceinline__ void wino_mfma_lds(f32x4 (&acc)[16][2], const f32x4 (&d)[4][4], const float* wb, int pos0) {
+  f32x4 a0 = *reinterpret_cast<const f32x4*>(wb), a1 = *reinterpret_cast<const f32x4*>(wb + 256);
+#pragma unroll
+  for (int pl = 0; pl < NPOS; ++pl) {
+    const f32x4 x0 = a0, x1 = a1;
+    if (pl < NPOS - 1) {
+      a0 = *reinterpret_cast<const f32x4*>(wb + (2 * pl + 2) * 256);
+      a1 = *reinterpret_cast<const f32x4*>(wb + (2 * pl + 3) * 256);
+    }
+    const int pos = pos0 + pl;
+    const f32x4 b = d[pos >> 2][pos & 3];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      acc[pos][0] = mfma16c(x0[r], b[r], acc[pos][0]);
+      acc[pos][1] = mfma16c(x1[r], b[r], acc[pos][1]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // Output transform Y = A^T M A per (tile, co quad) and the epilogue of k_conv_tile (bias / per-sample bias / accumulate /
 // residual / channel statistics), 2x2 pixels x 4 consecutive output channels per lane and co tile; shared by every
 // Winograd kernel, so their results agree bit for bit for the same accumulators.
@@ -1139,27 +1201,13 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs& A, const f32x4 (&a
                                               int co0, int slot, int lane) {
   const ConvGeom g = A.g;
   const int il = lane & 15, q = lane >> 4;
-  const bool primal = n < A.n_bias;
   const bool vec = (A.Cout & 3) == 0;
 #pragma unroll
   for (int c = 0; c < NCO; ++c) {
     const int co = co0 + 16 * c + 4 * q;
     if (co >= A.Cout) continue;
     const bool full = vec && (co + 3 < A.Cout);
-    f32x4 add = {0.f, 0.f, 0.f, 0.f};
-    if (primal && A.bias) {
-      if (full) add = *reinterpret_cast<const f32x4*>(A.bias + co);
-      else
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] = A.bias[co + r];
-    }
-    if (A.samp_bias && n < A.n_samp) {
-      const float* sbp = A.samp_bias + (size_t)n * A.Cout + co;
-      if (full) add += *reinterpret_cast<const f32x4*>(sbp);
-      else
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (co + r < A.Cout) add[r] += sbp[r];
-    }
+    const f32x4 add = conv_addend(A, n, co, full);
     f32x4 t0[4], t1[4];
 #pragma unroll
     for (int nu = 0; nu < 4; ++nu) {
@@ -1177,18 +1225,7 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs& A, const f32x4 (&a
         const int oy = y0 + 2 * ty + dy, ox = x0 + 2 * tx + dx;
         if (oy >= g.Ho || ox >= g.Wo) continue;
         const size_t m = ((size_t)n * g.Ho + oy) * g.Wo + ox;
-        f32x4 v = Y[dy][dx] + add;
-        float* op = A.out + m * A.Cout + co;
-        if (full) {
-          if (A.accumulate) v += *reinterpret_cast<const f32x4*>(op);
-          if (A.residual) v += *reinterpret_cast<const f32x4*>(A.residual + (op - A.out));
-          *reinterpret_cast<f32x4*>(op) = v;
-          cs += v; css += v * v;
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (co + r < A.Cout) op[r] = (A.accumulate ? op[r] + v[r] : v[r]) + (A.residual ? A.residual[(op - A.out) + r] : 0.f);
-        }
+        conv_store_quad(A, A.out + m * A.Cout + co, Y[dy][dx] + add, full, co, cs, css);
       }
     // the wave's 16 Winograd tiles = 64 pixels: one statistics slot, as the direct kernel's 16x16 tiles (Cout % 4 == 0, host)
     if (A.cstat) cstat_store(A, n, slot, co, cs, css, il);
@@ -1204,7 +1241,7 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs& A, const f32x4 (&a
 // measured in tests/test_conv_gpu.py).  No tangent-specific code (tangent rows are batch rows).  The training step's forward
 // and dgrad (flipped, transposed kernel image), which carry no folded input transform, run on k_conv_wino_pipe below.
 //   * workgroup = 16x16 output pixels = 8x8 Winograd tiles x 32 output channels, the (16+2)^2 halo of a 32-channel chunk
-//     staged in LDS exactly as k_conv_tile does (same fused GroupNorm(+SiLU) input transform, two sources, folded
+//     staged in LDS by halo18_load / halo18_store (k_conv_tile's fused GroupNorm(+SiLU) input transform, two sources, folded
 //     2x upsample);
 //   * wave w owns 16 tiles (lane&15) for ALL 16 transform positions: per 16-channel group a lane reads its 4x4 patch of
 //     4 channels (16 ds_read_b128), transforms it in registers (B^T d B: 32 additions per channel) and the 16 results
@@ -1220,15 +1257,14 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs& A, const f32x4 (&a
 //     lane-linear, conflict-free ds_read_b128), double-buffered: the DMA of half-group s + 1 is issued right after the barrier
 //     that opens half-group s and has that half-group's 64 MFMAs per wave (2 k cycles) to land.  LDS = halo 46.7 KB + 2 x 16 KB.
 template <int NCO, bool WL = false>
-__global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, int tiles_y, int n_tiles, int n_cob, int n_tgrp) {
+__global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, int tiles_y, int n_tiles, int n_cob) {
   extern __shared__ __attribute__((aligned(16))) float cw_lds[];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const ConvGeom g = A.g;
-  constexpr int HW = 18, halo = 18 * 18;
+  constexpr int HW = H18_HW, halo = HW * HW;
   float* cur = cw_lds;
   const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;            // XCD-aware order, as k_conv_tile
   const int cob = loc % n_cob, tile = (loc / n_cob) * 8 + xcd;
-  (void)n_tgrp;
   if (tile >= n_tiles) return;
   const int co0 = cob * (NCO * 16);
   // this lane's Winograd tile inside the 16x16 output tile: 8x8 tiles, wave w owns tile rows 2w, 2w+1
@@ -1243,57 +1279,15 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, i
   int nch[CONV_MAX_SRC];
 #pragma unroll
   for (int s = 0; s < CONV_MAX_SRC; ++s) nch[s] = s < A.nsrc ? (A.C[s] + CT_KC - 1) / CT_KC : 0;
-  constexpr int MAXST = (halo * (CT_KC / 4) + 255) / 256;
-  constexpr int n_items = halo * (CT_KC / 4);
   const int up = g.ups ? 1 : 0;
   const int ctot_all = A.C[0] + (A.nsrc > 1 ? A.C[1] : 0);
   int n, y0, x0;
-  { int t = tile; const int tx_i = t % tiles_x; t /= tiles_x; const int ty_i = t % tiles_y; n = t / tiles_y; y0 = ty_i * 16; x0 = tx_i * 16; }
+  tile_origin<16, 16>(tile, tiles_x, tiles_y, n, y0, x0);
   auto stage = [&](int s_, int c0) __attribute__((always_inline)) {    // global -> (transform) -> LDS, one 32-channel chunk
-    const int C = A.C[s_];
-    const float* base = A.src[s_] + (size_t)n * g.Hi * g.Wi * C;
-    f32x4 ga = {1.f, 1.f, 1.f, 1.f}, gb = {0.f, 0.f, 0.f, 0.f};
-    const int cq = c0 + 4 * (tid & 7);
-    if (A.in_scale && cq < C) {
-      const size_t o = (size_t)n * ctot_all + (s_ ? A.C[0] : 0) + cq;
-      ga = *reinterpret_cast<const f32x4*>(A.in_scale + o);
-      gb = *reinterpret_cast<const f32x4*>(A.in_shift + o);
-    }
-    f32x4 st[MAXST];
-    unsigned valid = 0;
-#pragma unroll
-    for (int k = 0; k < MAXST; ++k) {                       // all the loads first (see k_conv_tile's stage_load)
-      const int idx = tid + 256 * k;
-      f32x4 v = {0, 0, 0, 0};
-      if (idx < n_items) {
-        const int hp = idx >> 3, hy = hp / HW, hx = hp - hy * HW;        // division by the constant 18
-        const int iy = y0 + hy - 1, ix = x0 + hx - 1;
-        const int c = c0 + 4 * (idx & 7);
-        if (iy >= 0 && iy < (g.Hi << up) && ix >= 0 && ix < (g.Wi << up) && c < C) {
-          v = *reinterpret_cast<const f32x4*>(base + ((size_t)(iy >> up) * g.Wi + (ix >> up)) * C + c);
-          valid |= 1u << k;
-        }
-      }
-      st[k] = v;
-    }
-    if (A.in_scale) {
-#pragma unroll
-      for (int k = 0; k < MAXST; ++k) {
-        if ((valid >> k) & 1u) {
-          f32x4 v = st[k] * ga + gb;
-          if (A.in_act == 1) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = v[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[r]));
-          }
-          st[k] = v;
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < MAXST; ++k) {
-      const int idx = tid + 256 * k;
-      if (idx < n_items) *reinterpret_cast<f32x4*>(cur + (idx >> 3) * CT_P + 4 * (idx & 7)) = st[k];
-    }
+    f32x4 st[H18_NST], ga, gb;
+    unsigned valid;
+    halo18_load(A, g, A.src[s_], A.C[s_], up, c0, (size_t)n * ctot_all + (s_ ? A.C[0] : 0), n, y0, x0, tid, st, valid, ga, gb);
+    halo18_store(A, cur, tid, st, valid, ga, gb);
   };
 
   const size_t a_co_stride = (size_t)16 * A.Ktot, pos_stride = (size_t)A.CoutP * A.Ktot;
@@ -1301,16 +1295,10 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, i
     static_assert(NCO == 2, "the LDS weight image is laid out for two output-channel tiles");
     float* wbuf = cw_lds + halo * CT_P;                       // [2 buffers][8 positions][2 co tiles][64 lanes][4]
     auto ngrp_of = [&](int s_, int c_) { const int rem = A.C[s_] - c_ * CT_KC; return rem >= CT_KC ? 2 : ((rem + 15) >> 4); };
-    // the 16 pieces of one half-group: wave w copies pieces 4w .. 4w+3 (piece = 2 (position in the half) + co tile); lane
-    // (il, q) brings U[pos][co0 + 16 c + il][k .. k+3], k = 4 q of the group — exactly its A fragment
+    // half `half` of group g_ of chunk (s_, c_) into buffer b
     auto wfill = [&](int s_, int c_, int g_, int half, int b) __attribute__((always_inline)) {
-      const float* src = A.Wp + (size_t)(co0 + il) * A.Ktot + A.koff[s_] + c_ * CT_KC + 16 * g_ + 4 * q + (size_t)(8 * half) * pos_stride;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int pw = 4 * w + j;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(pw >> 1) * pos_stride + (pw & 1) * a_co_stride),
-                                         (__attribute__((address_space(3))) void*)(wbuf + b * 4096 + pw * 256), 16, 0, 0);
-      }
+      wino_wfill(A.Wp + (size_t)(co0 + il) * A.Ktot + A.koff[s_] + c_ * CT_KC + 16 * g_ + 4 * q + (size_t)(8 * half) * pos_stride,
+                 wbuf + b * 4096, w, pos_stride, a_co_stride);
     };
     int cs = 0, cc = 0, grp = 0, step = 0;
     wfill(0, 0, 0, 0, 0);
@@ -1337,35 +1325,9 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, i
         if (half == 0) {
           // ---- the lane's 4x4 patch (4 channels) and its transform V = B^T d B, in place
           wino_patch_load<HW>(d, cur + pbase + 16 * grp, tx == 7);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const f32x4 r0 = d[0][j] - d[2][j], r1 = d[1][j] + d[2][j], r2 = d[2][j] - d[1][j], r3 = d[1][j] - d[3][j];
-            d[0][j] = r0; d[1][j] = r1; d[2][j] = r2; d[3][j] = r3;
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const f32x4 c0_ = d[i][0] - d[i][2], c1_ = d[i][1] + d[i][2], c2_ = d[i][2] - d[i][1], c3_ = d[i][1] - d[i][3];
-            d[i][0] = c0_; d[i][1] = c1_; d[i][2] = c2_; d[i][3] = c3_;
-          }
+          wino_input_transform(d);
         }
-        const float* wb = wbuf + (step & 1) * 4096 + lane * 4;
-        f32x4 a0 = *reinterpret_cast<const f32x4*>(wb), a1 = *reinterpret_cast<const f32x4*>(wb + 256);
-#pragma unroll
-        for (int pl = 0; pl < 8; ++pl) {
-          const f32x4 x0 = a0, x1 = a1;
-          if (pl < 7) {
-            a0 = *reinterpret_cast<const f32x4*>(wb + (2 * pl + 2) * 256);
-            a1 = *reinterpret_cast<const f32x4*>(wb + (2 * pl + 3) * 256);
-          }
-          const int pos = 8 * half + pl;
-          const f32x4 b = d[pos >> 2][pos & 3];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            acc[pos][0] = mfma16c(x0[r], b[r], acc[pos][0]);
-            acc[pos][1] = mfma16c(x1[r], b[r], acc[pos][1]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        wino_mfma_lds<8>(acc, d, wbuf + (step & 1) * 4096 + lane * 4, 8 * half);
         ++step;
       }
       if (!more) break;
@@ -1390,16 +1352,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, i
         // ---- the lane's 4x4 patch (4 channels) and its transform V = B^T d B, in place
         f32x4 d[4][4];
         wino_patch_load<HW>(d, cur + pbase + 16 * grp, tx == 7);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const f32x4 r0 = d[0][j] - d[2][j], r1 = d[1][j] + d[2][j], r2 = d[2][j] - d[1][j], r3 = d[1][j] - d[3][j];
-          d[0][j] = r0; d[1][j] = r1; d[2][j] = r2; d[3][j] = r3;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const f32x4 c0_ = d[i][0] - d[i][2], c1_ = d[i][1] + d[i][2], c2_ = d[i][2] - d[i][1], c3_ = d[i][1] - d[i][3];
-          d[i][0] = c0_; d[i][1] = c1_; d[i][2] = c2_; d[i][3] = c3_;
-        }
+        wino_input_transform(d);
         __builtin_amdgcn_sched_barrier(0);
         // ---- 16 positions: M_p += U_p V_p
 #pragma unroll
@@ -1439,7 +1392,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, i
 // LDS: 64 KB weights + 2 x 46.7 KB halo = 155 KB.  Same staging options and epilogue as k_conv_wino.
 __global__ void __launch_bounds__(256, 1) k_conv_wino_p32(ConvArgs A, int tiles_x, int tiles_y, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) float cw_lds[];
-  constexpr int NCO = 2, HW = 18, halo = 18 * 18;
+  constexpr int NCO = 2, HW = H18_HW, halo = HW * HW;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const ConvGeom g = A.g;
   float* wbuf = cw_lds;                                     // [2 groups][16 positions][2 co tiles][64 lanes][4]
@@ -1460,67 +1413,17 @@ __global__ void __launch_bounds__(256, 1) k_conv_wino_p32(ConvArgs A, int tiles_
                                        (__attribute__((address_space(3))) void*)(wbuf + pw * 256), 16, 0, 0);
     }
   }
-  constexpr int MAXST = (halo * (CT_KC / 4) + 255) / 256;
-  constexpr int n_items = halo * (CT_KC / 4);
   const int up = g.ups ? 1 : 0;
   const int C = A.C[0];
-  f32x4 st[MAXST];
-  f32x4 ga = {1.f, 1.f, 1.f, 1.f}, gb = {0.f, 0.f, 0.f, 0.f};
-  unsigned valid = 0;
-  auto origin = [&](int tile, int& n, int& y0, int& x0) {
-    const int tx_i = tile % tiles_x; tile /= tiles_x;
-    const int ty_i = tile % tiles_y; n = tile / tiles_y; y0 = ty_i * 16; x0 = tx_i * 16;
-  };
+  f32x4 st[H18_NST], ga, gb;
+  unsigned valid;
   auto stage_load = [&](int tile) __attribute__((always_inline)) {
     int n, y0, x0;
-    origin(tile, n, y0, x0);
-    const float* base = A.src[0] + (size_t)n * g.Hi * g.Wi * C;
-    const int cq = 4 * (tid & 7);
-    ga = f32x4{1.f, 1.f, 1.f, 1.f}; gb = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (A.in_scale && cq < C) {
-      const size_t o = (size_t)n * C + cq;
-      ga = *reinterpret_cast<const f32x4*>(A.in_scale + o);
-      gb = *reinterpret_cast<const f32x4*>(A.in_shift + o);
-    }
-    valid = 0;
-#pragma unroll
-    for (int k = 0; k < MAXST; ++k) {
-      const int idx = tid + 256 * k;
-      f32x4 v = {0, 0, 0, 0};
-      if (idx < n_items) {
-        const int hp = idx >> 3, hy = hp / HW, hx = hp - hy * HW;
-        const int iy = y0 + hy - 1, ix = x0 + hx - 1;
-        const int c = 4 * (idx & 7);
-        if (iy >= 0 && iy < (g.Hi << up) && ix >= 0 && ix < (g.Wi << up) && c < C) {
-          v = *reinterpret_cast<const f32x4*>(base + ((size_t)(iy >> up) * g.Wi + (ix >> up)) * C + c);
-          valid |= 1u << k;
-        }
-      }
-      st[k] = v;
-    }
-  };
-  auto stage_store = [&](float* buf) __attribute__((always_inline)) {
-    if (A.in_scale) {
-#pragma unroll
-      for (int k = 0; k < MAXST; ++k) {
-        if ((valid >> k) & 1u) {
-          f32x4 v = st[k] * ga + gb;
-          if (A.in_act == 1) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = v[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[r]));
-          }
-          st[k] = v;
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < MAXST; ++k) {
-      const int idx = tid + 256 * k;
-      if (idx < n_items) *reinterpret_cast<f32x4*>(buf + (idx >> 3) * CT_P + 4 * (idx & 7)) = st[k];
-    }
+    tile_origin<16, 16>(tile, tiles_x, tiles_y, n, y0, x0);
+    halo18_load(A, g, A.src[0], C, up, 0, (size_t)n * C, n, y0, x0, tid, st, valid, ga, gb);
   };
   stage_load(t);
-  stage_store(hb0);
+  halo18_store(A, hb0, tid, st, valid, ga, gb);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");        // weights and the first halo are in LDS
   float* cur = hb0;
   float* nxt = hb1;
@@ -1543,39 +1446,14 @@ __global__ void __launch_bounds__(256, 1) k_conv_wino_p32(ConvArgs A, int tiles_
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) d[i][j] = *reinterpret_cast<const f32x4*>(cur + pbase + (i * HW + j) * CT_P + 16 * grp);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4 r0 = d[0][j] - d[2][j], r1 = d[1][j] + d[2][j], r2 = d[2][j] - d[1][j], r3 = d[1][j] - d[3][j];
-        d[0][j] = r0; d[1][j] = r1; d[2][j] = r2; d[3][j] = r3;
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const f32x4 c0_ = d[i][0] - d[i][2], c1_ = d[i][1] + d[i][2], c2_ = d[i][2] - d[i][1], c3_ = d[i][1] - d[i][3];
-        d[i][0] = c0_; d[i][1] = c1_; d[i][2] = c2_; d[i][3] = c3_;
-      }
-      const float* wb = wbuf + grp * (16 * 2 * 256) + lane * 4;
-      f32x4 a0 = *reinterpret_cast<const f32x4*>(wb), a1 = *reinterpret_cast<const f32x4*>(wb + 256);
-#pragma unroll
-      for (int pos = 0; pos < 16; ++pos) {
-        const f32x4 x0_ = a0, x1_ = a1;
-        if (pos < 15) {
-          a0 = *reinterpret_cast<const f32x4*>(wb + (2 * pos + 2) * 256);
-          a1 = *reinterpret_cast<const f32x4*>(wb + (2 * pos + 3) * 256);
-        }
-        const f32x4 b = d[pos >> 2][pos & 3];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          acc[pos][0] = mfma16c(x0_[r], b[r], acc[pos][0]);
-          acc[pos][1] = mfma16c(x1_[r], b[r], acc[pos][1]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      wino_input_transform(d);
+      wino_mfma_lds<16>(acc, d, wbuf + grp * (16 * 2 * 256) + lane * 4, 0);
     }
     // ---- output transform and epilogue (as k_conv_wino)
     int n, y0, x0;
-    origin(t, n, y0, x0);
+    tile_origin<16, 16>(t, tiles_x, tiles_y, n, y0, x0);
     wino_epilogue<NCO>(A, acc, n, y0, x0, ty, tx, 0, (t - n * tiles_x * tiles_y) * 4 + w, lane);
-    if (more) stage_store(nxt);
+    if (more) halo18_store(A, nxt, tid, st, valid, ga, gb);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");               // the other buffer is complete; this one is free
     float* sw = cur; cur = nxt; nxt = sw;
   }
@@ -1625,13 +1503,8 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
 
   // half `half` of channel group grp_'s weights for output-channel block cob_: as k_conv_wino's WL form
   auto wfill = [&](int cob_, int grp_, int half) __attribute__((always_inline)) {
-    const float* src = A.Wp + (size_t)(cob_ * (NCO * 16) + il) * A.Ktot + 16 * grp_ + 4 * q + (size_t)(8 * half) * pos_stride;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int pw = 4 * w + j;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(pw >> 1) * pos_stride + (pw & 1) * a_co_stride),
-                                       (__attribute__((address_space(3))) void*)(wbuf + half * 4096 + pw * 256), 16, 0, 0);
-    }
+    wino_wfill(A.Wp + (size_t)(cob_ * (NCO * 16) + il) * A.Ktot + 16 * grp_ + 4 * q + (size_t)(8 * half) * pos_stride,
+               wbuf + half * 4096, w, pos_stride, a_co_stride);
   };
   // channel group grp_'s halo of tile tile_ into stage b: wave w copies pieces w, w + 4, ... (6 for wave 0, 5 for the others)
   // (branch-free: the source of each lane is a select between its pixel and the zero row)
@@ -1707,17 +1580,11 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
             d[i][3] = *reinterpret_cast<const f32x4*>(rp + 16);
           }
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const f32x4 r0 = d[0][j] - d[2][j], r1 = d[1][j] + d[2][j], r2 = d[2][j] - d[1][j], r3 = d[1][j] - d[3][j];
-          d[0][j] = r0; d[1][j] = r1; d[2][j] = r2; d[3][j] = r3;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const f32x4 c0_ = d[i][0] - d[i][2], c1_ = d[i][1] + d[i][2], c2_ = d[i][2] - d[i][1], c3_ = d[i][1] - d[i][3];
-          d[i][0] = c0_; d[i][1] = c1_; d[i][2] = c2_; d[i][3] = c3_;
-        }
+        wino_input_transform(d);
       }
+      // (wino_mfma_lds<8>'s loop, kept written out: through the function this kernel measured up to 0.5 % slower at the 1024-row
+      // shapes, outside the parent's own spread on two of six; the rows of build "pipe_shared_mfma_loop" in
+      // profiles/conv_shared/bench_conv_shared.json)
       const float* wb = wbuf + half * 4096 + lane * 4;
       f32x4 a0 = *reinterpret_cast<const f32x4*>(wb), a1 = *reinterpret_cast<const f32x4*>(wb + 256);
 #pragma unroll
@@ -1896,9 +1763,6 @@ __global__ void __launch_bounds__(256) k_conv_wgrad(WgradArgs A) {
 // 4 * (channel quad & 7) spreads the eight channel quads over all 32 banks and keeps groups of 4 consecutive pixels (the
 // 16-byte MFMA fragments) intact.  Readers apply the same XOR (an involution).
 #define WT_SWZ(ch) ((((ch) >> 2) & 7) << 2)
-#ifndef WT_DBUF
-#define WT_DBUF(TAPS) ((TAPS) == 9)
-#endif
 // RAG: channel counts that are not multiples of 4 (the U-Net's input conv has 1 or 3 input channels, its output conv 1 or 3
 // output channels): the staging loads go element by element with a channel mask instead of 16 bytes at a time.  Those two
 // layers ran on k_conv_wgrad at 1.2 ms each per C4 step (rocprofv3), 1.8 % of it.
@@ -2002,7 +1866,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
   // LDS buffering: the 3x3 variant is register-bound to two workgroups per CU and keeps two LDS buffers (one barrier
   // per tile); the others have registers for three and keep ONE buffer (34 KB) so that three fit — the next tile
   // still travels global -> registers under this tile's MFMAs, only its LDS store waits for an extra barrier.
-  constexpr bool DBUF = WT_DBUF(TAPS);
+  constexpr bool DBUF = TAPS == 9;
   stage_load(t_beg);
   stage_store(0);
   __syncthreads();
@@ -2073,7 +1937,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
   // stores by a single wave per workgroup: 10-15 % of a workgroup's time at 8 tiles per workgroup.)
   float* red = wt_lds;
   constexpr int TR = TAPS == 9 ? 4 : (TAPS == 3 ? 2 : 1);   // taps per round: TR * 4 waves * 1024 floats fit the staging area
-  constexpr int STG = (WT_DBUF(TAPS) ? 2 : 1) * BUF;
+  constexpr int STG = (TAPS == 9 ? 2 : 1) * BUF;
   static_assert(TR * 4096 <= (STG > 4096 ? STG : 4096), "reduction scratch exceeds the staging area");
   __syncthreads();
 #pragma unroll
@@ -2264,16 +2128,10 @@ __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x
 // 16 MFMAs, hidden under the other waves' MFMAs — and the 16 sums of one (co, c) element end in ONE lane, so A^T M A runs
 // in registers.  Input rows pitch WW_IP = 188 = -4 (mod 64): the b64 patch reads of a half-wave (16 channels x 2 blocks
 // 2 floats apart) fall on 32 distinct bank pairs.  ~200 VGPRs (at the 168 of three workgroups per CU the compiler spills
-// 44-176 bytes), so two workgroups per CU (WW_LB) and a double-buffered LDS staging area (2 x 40 KB, one barrier per tile):
+// 44-176 bytes), so two workgroups per CU and a double-buffered LDS staging area (2 x 40 KB, one barrier per tile):
 // C4 3x3 wgrad family 17.7 -> 13.2 ms per step (tools/bench_wgrad3x3.py; single buffer 13.4, three workgroups 14.3).
 #define WW_IP 188
-#ifndef WW_LB
-#define WW_LB 2
-#endif
-#ifndef WW_DBUF
-#define WW_DBUF 1
-#endif
-__global__ void __launch_bounds__(256, WW_LB) k_wgrad_wino(WgradArgs A, int tiles_x, int tiles_y, int tiles_per_wg, int n_tiles) {
+__global__ void __launch_bounds__(256, 2) k_wgrad_wino(WgradArgs A, int tiles_x, int tiles_y, int tiles_per_wg, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) float wt_lds[];
   constexpr int TH = 8, TW = 16, HW = TW + 2, halo = (TH + 2) * HW, IP = WW_IP;
   static_assert(IP >= halo && IP % 2 == 0, "input row pitch");
@@ -2416,14 +2274,9 @@ __global__ void __launch_bounds__(256, WW_LB) k_wgrad_wino(WgradArgs A, int tile
 #pragma unroll
       for (int x = 0; x < 16; ++x) acc[x] = mfma16c(U[x], V[x], acc[x]);
     }
-    if (WW_DBUF) {                                          // two buffers: the next tile goes into the other one, one barrier
-      if (more) stage_store(cur ^ 1);
-      __syncthreads();
-      cur ^= 1;
-    } else {
-      __syncthreads();                                      // every wave is done reading the buffer
-      if (more) { stage_store(0); __syncthreads(); }
-    }
+    if (more) stage_store(cur ^ 1);                         // two buffers: the next tile goes into the other one, one barrier
+    __syncthreads();
+    cur ^= 1;
   }
   if (do_bias) {
     bsum += __shfl_xor(bsum, 1, 64);
@@ -2940,6 +2793,22 @@ static bool conv_same(const msgm_conv_geom_t* g) {
          (g->KH & 1) && (g->KW & 1) && g->KH <= 3 && g->KW <= 3 && g->padH == (g->KH - 1) / 2 && g->padW == (g->KW - 1) / 2;
 }
 
+// Compute units of the current device (grid sizing of the persistent kernels), queried once.
+static int conv_n_cu() {
+  static const int n_cu = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
+  return n_cu;
+}
+// More than 64 KB of dynamic LDS has to be opted into per kernel (160 KB per CU on gfx950): the first call for kernel K raises
+// its limit to BYTES.
+template <auto K, int BYTES = 160 * 1024>
+static void conv_raise_lds_limit() {
+  static const int once = [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
+    return 0;
+  }();
+  (void)once;
+}
+
 extern "C" {
 
 // is this (geometry, channels) served by the halo-tile kernel?
@@ -3019,17 +2888,12 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
   if (!conv_wino_eligible(geom, C0, A.C[1], CoutP, 16) || !tile16_chanstats(A)) return MSGM_E_UNSUPPORTED;
   const int tiles_x = geom->Wo / 16, tiles_y = geom->Ho / 16;
   const int n_tiles = tiles_x * tiles_y * geom->N, gy = CoutP / 32;
-  static const int n_cu = [] { int d = 0, n = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
   if (!A.in_scale) {
     // no folded input transform (every training forward and dgrad): the pipelined stream of channel groups, two
     // workgroups per CU, each walking (tile, output-channel block) items of one XCD
-    static const int once_pipe = [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_wino_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, WP_LDS_BYTES);
-      return 0;
-    }();
-    (void)once_pipe;
+    conv_raise_lds_limit<&k_conv_wino_pipe, WP_LDS_BYTES>();
     const int items_per_xcd = gy * ((n_tiles + 7) / 8);
-    const int wg_per_xcd = std::min(items_per_xcd, std::max(1, 2 * n_cu / 8));
+    const int wg_per_xcd = std::min(items_per_xcd, std::max(1, 2 * conv_n_cu() / 8));
     hipLaunchKernelGGL(k_conv_wino_pipe, dim3((unsigned)(8 * wg_per_xcd)), dim3(256), WP_LDS_BYTES, S(stream), A, tiles_x, tiles_y, n_tiles, gy);
     return msgm_check_launch();
   }
@@ -3041,25 +2905,17 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
   constexpr int p32_min = 1024;                            // >= 4 tiles per workgroup (B = 32: 18.6 -> 18.5 ms)
   if (!src1 && Ktot == 32 && CoutP == 32 && n_tiles >= p32_min) {
     // one persistent workgroup per CU (>= 8 tiles each): weights resident in LDS, halo double-buffered
-    static const int once32 = [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_wino_p32), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      return 0;
-    }();
-    (void)once32;
+    conv_raise_lds_limit<&k_conv_wino_p32>();
     const size_t lds32 = ((size_t)2 * 16 * 2 * 256 + 2 * 18 * 18 * CT_P) * sizeof(float);
-    hipLaunchKernelGGL(k_conv_wino_p32, dim3((unsigned)n_cu), dim3(256), lds32, S(stream), A, tiles_x, tiles_y, n_tiles);
+    hipLaunchKernelGGL(k_conv_wino_p32, dim3((unsigned)conv_n_cu()), dim3(256), lds32, S(stream), A, tiles_x, tiles_y, n_tiles);
     return msgm_check_launch();
   }
   if (Ktot < 64) {
-    hipLaunchKernelGGL((k_conv_wino<2, false>), grid, dim3(256), lds, S(stream), A, tiles_x, tiles_y, n_tiles, gy, n_tiles);
+    hipLaunchKernelGGL((k_conv_wino<2, false>), grid, dim3(256), lds, S(stream), A, tiles_x, tiles_y, n_tiles, gy);
     return msgm_check_launch();
   }
-  static const int once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_wino<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return 0;
-  }();
-  (void)once;
-  hipLaunchKernelGGL((k_conv_wino<2, true>), grid, dim3(256), lds + 2 * 4096 * sizeof(float), S(stream), A, tiles_x, tiles_y, n_tiles, gy, n_tiles);
+  conv_raise_lds_limit<&k_conv_wino<2, true>>();
+  hipLaunchKernelGGL((k_conv_wino<2, true>), grid, dim3(256), lds + 2 * 4096 * sizeof(float), S(stream), A, tiles_x, tiles_y, n_tiles, gy);
   return msgm_check_launch();
 }
 
@@ -3104,12 +2960,8 @@ int msgm_conv_forward_b6(const msgm_conv_geom_t* geom, const float* src0, int32_
   const int n_tgrp = (n_tiles + per - 1) / per;
   dim3 grid((unsigned)(8 * gy * ((n_tgrp + 7) / 8)));
   const size_t lds = (size_t)18 * 18 * 52 * sizeof(float);
-  static const int once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_tile<16, 16, 4, 3, 4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_tile<16, 16, 2, 3, 4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return 0;
-  }();
-  (void)once;
+  conv_raise_lds_limit<&k_conv_tile<16, 16, 4, 3, 4, false, true>>();
+  conv_raise_lds_limit<&k_conv_tile<16, 16, 2, 3, 4, false, true>>();
   if (nco == 4) hipLaunchKernelGGL((k_conv_tile<16, 16, 4, 3, 4, false, true>), grid, dim3(256), lds, S(stream), A, 0, tiles_x, tiles_y, per, n_tiles, gy, n_tgrp);
   else hipLaunchKernelGGL((k_conv_tile<16, 16, 2, 3, 4, false, true>), grid, dim3(256), lds, S(stream), A, 0, tiles_x, tiles_y, per, n_tiles, gy, n_tgrp);
   return msgm_check_launch();
@@ -3392,8 +3244,8 @@ static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n
     p.n_tiles = p.tiles_x * p.tiles_y * geom->N;
     p.yblocks = ((Cout + 31) / 32) * ((C + 31) / 32);
     p.wino = wino && two_d && taps == 9 && aligned;
-    // k_wgrad_wino: WW_LB resident workgroups per CU (registers), so one full round of them on the 256 CUs; the others:
-    const int wg_target = p.wino ? 256 * WW_LB : 768;                         // = 3 resident workgroups per CU (k_wgrad_tile9 and the 1- / 3-tap forms); r3 measured 768 / 1024 / 1536 / 3072: 124.0 / 126.4 / 124.7 / 124.9 ms per C4 step (r2, two workgroups per CU: 1024 was best)
+    // k_wgrad_wino: 2 resident workgroups per CU (registers), so one full round of them on the 256 CUs; the others:
+    const int wg_target = p.wino ? 256 * 2 : 768;                         // = 3 resident workgroups per CU (k_wgrad_tile9 and the 1- / 3-tap forms); r3 measured 768 / 1024 / 1536 / 3072: 124.0 / 126.4 / 124.7 / 124.9 ms per C4 step (r2, two workgroups per CU: 1024 was best)
     int wgs = wg_target / p.yblocks;                       // ~4 workgroups per CU overall
     if (wgs < 1) wgs = 1;
     int per = (p.n_tiles + wgs - 1) / wgs;
@@ -3498,12 +3350,7 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
     dim3 grid((unsigned)pl.wgs, (unsigned)pl.yblocks);
 #define W1_LAUNCH(MT_, NT_, WM_)                                                                                      \
   do {                                                                                                               \
-    static const int once = [] {                                                                                     \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad1x1<MT_, NT_, WM_>),                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                             \
-      return 0;                                                                                                      \
-    }();                                                                                                             \
-    (void)once;                                                                                                      \
+    conv_raise_lds_limit<&k_wgrad1x1<MT_, NT_, WM_>>();                                                              \
     hipLaunchKernelGGL((k_wgrad1x1<MT_, NT_, WM_>), grid, dim3(256), lds, S(stream), A, Mtot, Mbias, pl.per, (long)pl.n_tiles1); \
   } while (0)
     const int key = pl.wm * 10000 + pl.mt * 100 + pl.nt;
@@ -3533,19 +3380,13 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
     const int tiles_x = pl.tiles_x, tiles_y = pl.tiles_y, n_tiles = pl.n_tiles, yblocks = pl.yblocks, per = pl.per, wgs = pl.wgs;
     const int halo = (TH + geom->KH - 1) * (TW + geom->KW - 1);
     const int IP = ((halo + 2) & ~7) + 5;
-    size_t lds = (size_t)(WT_DBUF(taps) ? 2 : 1) * (32 * WT_GP + 32 * IP) * sizeof(float);
+    size_t lds = (size_t)(taps == 9 ? 2 : 1) * (32 * WT_GP + 32 * IP) * sizeof(float);
     if (lds < 4096 * sizeof(float)) lds = 4096 * sizeof(float);
     dim3 grid((unsigned)wgs, (unsigned)yblocks);
-    // more than 64 KB of dynamic LDS has to be opted into per kernel (160 KB per CU on gfx950)
 #define WT_LAUNCH(TH_, TW_, TP_) WT_LAUNCH2(TH_, TW_, TP_, false)
 #define WT_LAUNCH2(TH_, TW_, TP_, RAG_)                                                                              \
   do {                                                                                                               \
-    static const int once = [] {                                                                                     \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_tile<TH_, TW_, TP_, RAG_>),                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                             \
-      return 0;                                                                                                      \
-    }();                                                                                                             \
-    (void)once;                                                                                                      \
+    conv_raise_lds_limit<&k_wgrad_tile<TH_, TW_, TP_, RAG_>>();                                                      \
     hipLaunchKernelGGL((k_wgrad_tile<TH_, TW_, TP_, RAG_>), grid, dim3(256), lds, S(stream), A, tiles_x, tiles_y, per, n_tiles); \
   } while (0)
     const bool rag = (C & 3) || (Cout & 3);
@@ -3559,12 +3400,8 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
         else if (rag) WT_LAUNCH2(8, 16, 9, true);
         else if (tapmask_c32 || tapmask_co32) return MSGM_E_UNSUPPORTED;   // k_wgrad_tile9 has no tap masks (they come from 3-tap 1-D convs)
         else if (pl.wino) {
-          const size_t ldsw = (size_t)(WW_DBUF ? 2 : 1) * (32 * WT_GP + 32 * WW_IP) * sizeof(float);
-          static const int once = [] {                      // more than 64 KB of dynamic LDS is opted into per kernel
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_wino), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            return 0;
-          }();
-          (void)once;
+          const size_t ldsw = (size_t)2 * (32 * WT_GP + 32 * WW_IP) * sizeof(float);
+          conv_raise_lds_limit<&k_wgrad_wino>();
           hipLaunchKernelGGL(k_wgrad_wino, grid, dim3(256), ldsw, S(stream), A, tiles_x, tiles_y, per, n_tiles);
         } else {
           const size_t lds9 = (size_t)(32 * WT_GP + 32 * IP) * sizeof(float);

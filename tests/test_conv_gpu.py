@@ -300,7 +300,9 @@ def test_stride2_pair_op_fwd_bwd(kind, N, Cin, Cout, L):
                                                    (2, 16, 144, 96, True, True, True),
                                                    # >= 2048 tiles of a 32 -> 32 layer: the persistent form (weights resident in LDS), with a
                                                    # tile count that does not divide over the workgroups, and with the folded upsample
-                                                   (130, 64, 32, 32, False, False, True), (520, 32, 32, 32, False, True, False)])
+                                                   (130, 64, 32, 32, False, False, True), (520, 32, 32, 32, False, True, False),
+                                                   # 1040 tiles: just past the persistent form's threshold (1024), ragged last round
+                                                   (65, 64, 32, 32, False, False, True)])
 def test_winograd_forward_equals_direct_conv(N, H, Ci, Co, two, ups, aff):
     """Winograd F(2x2,3x3) forward (sampler path) vs the direct halo-tile kernel on the same inputs and fused options:
     second source, folded 2x upsample, GroupNorm(+SiLU) input transform, bias, per-sample bias, residual.  Both are fp32;
