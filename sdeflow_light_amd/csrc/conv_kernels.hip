@@ -2124,17 +2124,40 @@ __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x
 // k_wgrad_tile9: a workgroup owns a 32 co x 32 c block, walks 8 x 16-pixel tiles (32 Winograd blocks, the 10 x 18 halo), and
 // wave (m, kt) owns the 16 x 16 output tile (m, kt) at all 16 positions (64 accumulator registers); k-step s takes four
 // blocks, one per lane group q (the MFMA's reduction index): block row s >> 1, column 4 (s & 1) + q.  Lane (il, q) transforms
-// the gy block of channel 16 m + il (A operand) and the input patch of channel 16 kt + il (B operand) itself — ~50 VALU per
-// 16 MFMAs, hidden under the other waves' MFMAs — and the 16 sums of one (co, c) element end in ONE lane, so A^T M A runs
-// in registers.  Input rows pitch WW_IP = 188 = -4 (mod 64): the b64 patch reads of a half-wave (16 channels x 2 blocks
-// 2 floats apart) fall on 32 distinct bank pairs.  ~200 VGPRs (at the 168 of three workgroups per CU the compiler spills
-// 44-176 bytes), so two workgroups per CU and a double-buffered LDS staging area (2 x 40 KB, one barrier per tile):
-// C4 3x3 wgrad family 17.7 -> 13.2 ms per step (tools/bench_wgrad3x3.py; single buffer 13.4, three workgroups 14.3).
+// the gy block of channel 16 m + il (A operand) and the input patch of channel 16 kt + il (B operand) itself and the 16 sums
+// of one (co, c) element end in ONE lane, so A^T M A runs in registers.
+//   * The halves of G are kept out of the k-loop: the loop accumulates with U' = D U D = (D G) g (D G)^T, D = diag(1, 2, 2, 1)
+//     (sums and differences only), and position (i, j) is scaled by 1 / (D_ii D_jj) once, before A^T M A.  A power of two
+//     commutes with every fp32 rounding (short of subnormal partial sums), so the bits are those of the unscaled form.
+//   * The operands of k-step s + 1 are read and transformed among the MFMAs of step s (two register sets), so that no MFMA
+//     waits for a VALU result issued just before it.
+//   * Everything of the staging that depends on the thread only (pixel, channel quad, halo offsets, LDS addresses) is
+//     computed once; per tile only the two image bases change, and the tile coordinates advance by increments.  (A wave-
+//     uniform branch to an unchecked load sequence for tiles whose halo lies inside the image was built and measured: the
+//     kernel with it is SLOWER on every shape, 10.80 against 10.48 ms per C4 step, also where no tile takes it — 254 instead
+//     of 243 registers; profiles/wgrad_diet/unchecked_path.txt.  It is not here.)
+// Input rows: channel ch at WW_ROW(ch) = 188 ch + 2 ((ch >> 3) & 1) + 4 (ch >> 4).  hipcc reads a patch row (four floats, 8-byte
+// aligned) with one ds_read2_b64: groups of 16 lanes = the 16 channels of one block column, banks modulo 32.  188 = -4 (mod 32)
+// alone puts channels il and il + 8 on the same bank pair; the 2-float shift of every second group of eight rows separates
+// them.  The transposed staging stores (a half-wave = 8 channel quads x 4 halo pixels; quad c4 starts 16 c4 (mod 32) banks on)
+// were 4-way conflicting at a plain pitch of 188; the two shifts leave them at most 2-way.  Measured, one call each of three
+// shapes (profiles/wgrad_diet/pmc_lds.txt): SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.54 at the plain pitch, 0.49 with the
+// 4 (ch >> 4) term alone, 0.23 with both.
+// Registers: 243 VGPRs, scratch 0 (profiles/wgrad_diet/kernel_regs.txt), of the 256 that two workgroups per CU allow: after
+// ANY edit of this kernel or a compiler change run `python tools/kernel_regs.py conv_kernels k_wgrad_wino` and check
+// that scratch is still 0.  Two workgroups per CU and a double-buffered LDS staging area (2 x 40 KB, one barrier per tile).
 #define WW_IP 188
+#define WW_ROW(ch) ((ch) * WW_IP + 2 * (((ch) >> 3) & 1) + 4 * ((ch) >> 4))
+// hipcc left to itself computes each operand right before its MFMA, with hazard padding between them; the groups below make
+// it emit one MFMA of step s, then three or four of step s + 1's LDS reads and transform instructions, and so on (the
+// instruction order of both forms and their timing: profiles/wgrad_diet/asm_counts.txt, bench_steps.txt)
+#define WW_GAP(n) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x102, n, 0);
+#define WW_GAP4 WW_GAP(3) WW_GAP(3) WW_GAP(3) WW_GAP(4)
+#define WW_SCHED(s) if ((s) < 7) { WW_GAP4 WW_GAP4 WW_GAP4 WW_GAP4 }
 __global__ void __launch_bounds__(256, 2) k_wgrad_wino(WgradArgs A, int tiles_x, int tiles_y, int tiles_per_wg, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) float wt_lds[];
   constexpr int TH = 8, TW = 16, HW = TW + 2, halo = (TH + 2) * HW, IP = WW_IP;
-  static_assert(IP >= halo && IP % 2 == 0, "input row pitch");
+  static_assert(IP >= halo && IP % 2 == 0 && WW_ROW(31) + halo <= 32 * IP, "input row pitch");
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const int m = w >> 1, kt = w & 1;                         // this wave's 16 x 16 output tile of every position
   const ConvGeom g = A.g;
@@ -2148,135 +2171,158 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_wino(WgradArgs A, int tiles_x,
 #pragma unroll
   for (int x = 0; x < 16; ++x) acc[x] = f32x4{0, 0, 0, 0};
   constexpr int MAXIN = (halo * 8 + 255) / 256;
+  static_assert(MAXIN == 6 && halo * 8 > 5 * 256, "six staged halo quads per thread, the sixth partial");
   f32x4 sg[4], si[MAXIN];
   const int up = g.ups ? 1 : 0;
-  constexpr int n_in = halo * 8;
-  auto stage_load = [&](int tile) {
-    int bx = tile;
-    const int tx_i = bx % tiles_x; bx /= tiles_x;
-    const int ty_i = bx % tiles_y;
-    const int n = bx / tiles_y;
-    const int y0 = ty_i * TH, x0 = tx_i * TW;
+  // staging, per thread: element k is (pixel sp + 32 k, channel quad c4) of the gy tile and of the halo
+  const int c4 = tid & 7, sp = tid >> 3;
+  const int Hs = g.Hi << up, Ws = g.Wi << up;
+  const bool co_ok = co0 + 4 * c4 < A.Cout, c_ok = c0 + 4 * c4 < A.C;
+  const bool last_in = sp + 32 * (MAXIN - 1) < halo;        // the sixth halo quad exists for this thread
+  const int goff = ((sp >> 4) * g.Wo + (sp & 15)) * A.Cout + co0 + 4 * c4;   // + k * gstep, from the tile's first pixel
+  const int gstep = 2 * g.Wo * A.Cout;
+  int ioff[MAXIN];                                          // from the input pixel under the tile's first pixel (on the source grid)
+  unsigned hyp = 0, hxp = 0;                                // halo row (4 bits) and column (5 bits) of element k
+#pragma unroll
+  for (int k = 0; k < MAXIN; ++k) {
+    const int hp = sp + 32 * k, hy = hp / HW, hx = hp - hy * HW;
+    ioff[k] = (((hy - g.padH) >> up) * g.Wi + ((hx - g.padW) >> up)) * A.C + c0 + 4 * c4;   // tile origins are even: the shift splits
+    hyp |= (unsigned)hy << (4 * k);
+    hxp |= (unsigned)hx << (5 * k);
+  }
+  const int gst = 4 * c4 * WT_GP + (sp ^ WT_SWZ(4 * c4));   // + 32 k + r WT_GP: the swizzle stays below bit 5
+  const int ist = 32 * WT_GP + WW_ROW(4 * c4) + sp;         // + 32 k + r IP
+  int ld_tx, ld_ty, ld_n;                                   // the tile the next stage_load takes
+  {
+    int bx = t_beg;
+    ld_tx = bx % tiles_x; bx /= tiles_x;
+    ld_ty = bx % tiles_y;
+    ld_n = bx / tiles_y;
+  }
+  auto stage_load = [&]() {                                 // returns the tile's sample
+    const int n = ld_n, y0 = ld_ty * TH, x0 = ld_tx * TW;
+    const float* gb = A.gy + (((size_t)n * g.Ho + y0) * g.Wo + x0) * A.Cout;
+    const float* sb = A.src + (((size_t)n * g.Hi + (y0 >> up)) * g.Wi + (x0 >> up)) * A.C;
+    const int iy0 = y0 - g.padH, ix0 = x0 - g.padW;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const int idx = tid + 256 * k;
-      const int p = idx >> 3, c4 = idx & 7;
-      const int py = p / TW, px = p - py * TW;
-      const int oy = y0 + py, ox = x0 + px, co = co0 + 4 * c4;
+      const bool ok = co_ok & (y0 + (sp >> 4) + 2 * k < g.Ho) & (x0 + (sp & 15) < g.Wo);   // one test, one branch per load
       f32x4 v = {0, 0, 0, 0};
-      if (oy < g.Ho && ox < g.Wo && co < A.Cout)
-        v = *reinterpret_cast<const f32x4*>(A.gy + (((size_t)n * g.Ho + oy) * g.Wo + ox) * A.Cout + co);
+      if (ok) v = *reinterpret_cast<const f32x4*>(gb + goff + k * gstep);
       sg[k] = v;
     }
 #pragma unroll
     for (int k = 0; k < MAXIN; ++k) {
-      const int idx = tid + 256 * k;
+      const int iy = iy0 + (int)((hyp >> (4 * k)) & 15u), ix = ix0 + (int)((hxp >> (5 * k)) & 31u);   // on the 2x grid if ups
+      const bool ok = c_ok & (k < MAXIN - 1 || last_in) & ((unsigned)iy < (unsigned)Hs) & ((unsigned)ix < (unsigned)Ws);
       f32x4 v = {0, 0, 0, 0};
-      if (idx < n_in) {
-        const int hp = idx >> 3, c4 = idx & 7;
-        const int hy = hp / HW, hx = hp - hy * HW;
-        const int iy = y0 + hy - g.padH, ix = x0 + hx - g.padW, c = c0 + 4 * c4;
-        if (iy >= 0 && iy < (g.Hi << up) && ix >= 0 && ix < (g.Wi << up) && c < A.C)
-          v = *reinterpret_cast<const f32x4*>(A.src + (((size_t)n * g.Hi + (iy >> up)) * g.Wi + (ix >> up)) * A.C + c);
-      }
+      if (ok) v = *reinterpret_cast<const f32x4*>(sb + ioff[k]);
       si[k] = v;
     }
+    if (++ld_tx == tiles_x) { ld_tx = 0; if (++ld_ty == tiles_y) { ld_ty = 0; ++ld_n; } }
+    return n;
   };
   auto stage_store = [&](int b) {
-    float* gT = wt_lds + b * BUF;
-    float* iT = gT + 32 * WT_GP;
+    float* gT = wt_lds + b * BUF + gst;
+    float* iT = wt_lds + b * BUF + ist;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int idx = tid + 256 * k;
-      const int p = idx >> 3, c4 = idx & 7;
+    for (int k = 0; k < 4; ++k)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) gT[(4 * c4 + r) * WT_GP + (p ^ WT_SWZ(4 * c4))] = sg[k][r];
-    }
+      for (int r = 0; r < 4; ++r) gT[r * WT_GP + 32 * k] = sg[k][r];
 #pragma unroll
-    for (int k = 0; k < MAXIN; ++k) {
-      const int idx = tid + 256 * k;
-      if (idx < n_in) {
-        const int hp = idx >> 3, c4 = idx & 7;
+    for (int k = 0; k < MAXIN; ++k)
+      if (k < MAXIN - 1 || last_in) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) iT[(4 * c4 + r) * IP + hp] = si[k][r];
+        for (int r = 0; r < 4; ++r) iT[r * IP + 32 * k] = si[k][r];
       }
-    }
   };
   const bool do_bias = A.dbias != nullptr && cblk == 0;
-  const int tiles_per_sample = tiles_x * tiles_y;
   float bsum = 0.f;                                        // thread (co = tid>>3, 16-pixel part = tid&7)
-  stage_load(t_beg);
+  int n_cur = stage_load();
   stage_store(0);
   __syncthreads();
+  // MFMA operands, per lane: block (bi, bj = 4 e + q) of k-step s = 2 bi + e has its gy pixel pair at 32 bi + (8 e + 2 q), the
+  // row below 16 on; the swizzle XORs bits 2..4, so (8 e + 2 q) and the 16 go through it and 32 bi stays an offset
   const int gsw = WT_SWZ(16 * m + il);
+  int gq[4];                                                // gy pair of (e, lower row): gq[e + 2 * lower]
+#pragma unroll
+  for (int j = 0; j < 4; ++j) gq[j] = (16 * m + il) * WT_GP + ((8 * (j & 1) + 16 * (j >> 1) + 2 * q) ^ gsw);
+  int ibq = 32 * WT_GP + WW_ROW(16 * kt + il) + 2 * q;     // patch of block (bi, 4 e + q): + (2 bi + a) HW + 8 e, four floats
+  int flip = BUF;
+  auto operands = [&](int s, float* U, float* V) {
+    const int bi = s >> 1, e = s & 1;
+    // U' = (D G) g (D G)^T of the gy block
+    const f32x2 g0 = *reinterpret_cast<const f32x2*>(wt_lds + gq[e] + 32 * bi);
+    const f32x2 g1 = *reinterpret_cast<const f32x2*>(wt_lds + gq[2 + e] + 32 * bi);
+    float gr[4][2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      gr[0][b] = g0[b];
+      gr[1][b] = g0[b] + g1[b];
+      gr[2][b] = g0[b] - g1[b];
+      gr[3][b] = g1[b];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      U[4 * i + 0] = gr[i][0];
+      U[4 * i + 1] = gr[i][0] + gr[i][1];
+      U[4 * i + 2] = gr[i][0] - gr[i][1];
+      U[4 * i + 3] = gr[i][1];
+    }
+    // V = B^T d B of the 4 x 4 input patch (halo rows 2 bi .. 2 bi + 3, columns 2 bj .. 2 bj + 3)
+    float d[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const float* rp = wt_lds + ibq + (2 * bi + a) * HW + 8 * e;
+      const f32x2 lo = *reinterpret_cast<const f32x2*>(rp), hi = *reinterpret_cast<const f32x2*>(rp + 2);
+      d[a][0] = lo[0]; d[a][1] = lo[1]; d[a][2] = hi[0]; d[a][3] = hi[1];
+    }
+    float t[4][4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      t[0][b] = d[0][b] - d[2][b];
+      t[1][b] = d[1][b] + d[2][b];
+      t[2][b] = d[2][b] - d[1][b];
+      t[3][b] = d[3][b] - d[1][b];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      V[4 * i + 0] = t[i][0] - t[i][2];
+      V[4 * i + 1] = t[i][1] + t[i][2];
+      V[4 * i + 2] = t[i][2] - t[i][1];
+      V[4 * i + 3] = t[i][3] - t[i][1];
+    }
+  };
   int cur = 0;
   for (int tile = t_beg; tile < t_end; ++tile) {
     const bool more = tile + 1 < t_end;
-    if (more) stage_load(tile + 1);
-    const float* gT = wt_lds + cur * BUF;
-    const float* ga = gT + (16 * m + il) * WT_GP;          // + (pixel ^ swizzle of this lane's channel)
-    const float* ib = gT + 32 * WT_GP + (16 * kt + il) * IP;
-    if (do_bias && tile / tiles_per_sample < A.n_bias) {   // as k_wgrad_tile9: same bits
-      const float* gr = gT + (tid >> 3) * WT_GP + 16 * (tid & 7);
+    int n_nxt = n_cur;
+    if (more) n_nxt = stage_load();
+    if (do_bias && n_cur < A.n_bias) {                     // as k_wgrad_tile9: same bits
+      const float* gr = wt_lds + cur * BUF + (tid >> 3) * WT_GP + 16 * (tid & 7);
       f32x4 t4 = *reinterpret_cast<const f32x4*>(gr);
       t4 += *reinterpret_cast<const f32x4*>(gr + 4);
       t4 += *reinterpret_cast<const f32x4*>(gr + 8);
       t4 += *reinterpret_cast<const f32x4*>(gr + 12);
       bsum += (t4[0] + t4[1]) + (t4[2] + t4[3]);
     }
+    float U[2][16], V[2][16];
+    operands(0, U[0], V[0]);
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
-      const int bi = s >> 1, bj = 4 * (s & 1) + q;          // this lane's 2 x 2 block of the 8 x 16 tile
-      // U = G g G^T of the gy block (pixel pairs stay contiguous under the swizzle: it XORs bits 2..4 of the pixel)
-      const int p0 = 2 * bi * TW + 2 * bj;
-      const f32x2 g0 = *reinterpret_cast<const f32x2*>(ga + (p0 ^ gsw));
-      const f32x2 g1 = *reinterpret_cast<const f32x2*>(ga + ((p0 + TW) ^ gsw));
-      float gr[4][2];
+      if (s < 7) operands(s + 1, U[(s + 1) & 1], V[(s + 1) & 1]);   // among the MFMAs below (see WW_SCHED)
 #pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        gr[0][b] = g0[b];
-        gr[1][b] = 0.5f * (g0[b] + g1[b]);
-        gr[2][b] = 0.5f * (g0[b] - g1[b]);
-        gr[3][b] = g1[b];
-      }
-      float U[16];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        U[4 * i + 0] = gr[i][0];
-        U[4 * i + 1] = 0.5f * (gr[i][0] + gr[i][1]);
-        U[4 * i + 2] = 0.5f * (gr[i][0] - gr[i][1]);
-        U[4 * i + 3] = gr[i][1];
-      }
-      // V = B^T d B of the 4 x 4 input patch (halo rows 2 bi .. 2 bi + 3, columns 2 bj .. 2 bj + 3)
-      float d[4][4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const float* rp = ib + (2 * bi + a) * HW + 2 * bj;
-        const f32x2 lo = *reinterpret_cast<const f32x2*>(rp), hi = *reinterpret_cast<const f32x2*>(rp + 2);
-        d[a][0] = lo[0]; d[a][1] = lo[1]; d[a][2] = hi[0]; d[a][3] = hi[1];
-      }
-      float t[4][4];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        t[0][b] = d[0][b] - d[2][b];
-        t[1][b] = d[1][b] + d[2][b];
-        t[2][b] = d[2][b] - d[1][b];
-        t[3][b] = d[3][b] - d[1][b];
-      }
-      float V[16];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        V[4 * i + 0] = t[i][0] - t[i][2];
-        V[4 * i + 1] = t[i][1] + t[i][2];
-        V[4 * i + 2] = t[i][2] - t[i][1];
-        V[4 * i + 3] = t[i][3] - t[i][1];
-      }
-#pragma unroll
-      for (int x = 0; x < 16; ++x) acc[x] = mfma16c(U[x], V[x], acc[x]);
+      for (int x = 0; x < 16; ++x) acc[x] = mfma16c(U[s & 1][x], V[s & 1][x], acc[x]);
+      WW_SCHED(s)
     }
     if (more) stage_store(cur ^ 1);                         // two buffers: the next tile goes into the other one, one barrier
     __syncthreads();
     cur ^= 1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gq[j] += flip;
+    ibq += flip;
+    flip = -flip;
+    n_cur = n_nxt;
   }
   if (do_bias) {
     bsum += __shfl_xor(bsum, 1, 64);
@@ -2285,28 +2331,35 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_wino(WgradArgs A, int tiles_x,
     const int co = co0 + (tid >> 3);
     if ((tid & 7) == 0 && co < A.Cout) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)9 * A.CoutP * A.C + co] = bsum;
   }
-  // dW = A^T M A per (co, c) element, all in this lane's registers
+  // dW = A^T M A per (co, c) element, all in this lane's registers; M (i, j) = M' (i, j) / (D_ii D_jj)
   const int c = c0 + 16 * kt + il;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
+    float M[16];
+#pragma unroll
+    for (int x = 0; x < 16; ++x) {
+      const int i = x >> 2, j = x & 3;
+      const float sc = ((i == 1 || i == 2) ? 0.5f : 1.f) * ((j == 1 || j == 2) ? 0.5f : 1.f);
+      M[x] = sc == 1.f ? acc[x][r] : sc * acc[x][r];
+    }
     float R[3][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float s12 = acc[4 + j][r] + acc[8 + j][r];
-      R[0][j] = acc[j][r] + s12;
-      R[1][j] = acc[4 + j][r] - acc[8 + j][r];
-      R[2][j] = s12 + acc[12 + j][r];
+      const float s12 = M[4 + j] + M[8 + j];
+      R[0][j] = M[j] + s12;
+      R[1][j] = M[4 + j] - M[8 + j];
+      R[2][j] = s12 + M[12 + j];
     }
     const int co = co0 + 16 * m + 4 * q + r;
     if (co < A.Cout && c < A.C) {
-      float* sp = A.slab + (size_t)blockIdx.x * A.slab_stride + (size_t)co * A.C + c;
+      float* sp_ = A.slab + (size_t)blockIdx.x * A.slab_stride + (size_t)co * A.C + c;
       const size_t tap = (size_t)A.CoutP * A.C;
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh) {
         const float s12 = R[kh][1] + R[kh][2];
-        sp[(3 * kh + 0) * tap] = R[kh][0] + s12;
-        sp[(3 * kh + 1) * tap] = R[kh][1] - R[kh][2];
-        sp[(3 * kh + 2) * tap] = s12 + R[kh][3];
+        sp_[(3 * kh + 0) * tap] = R[kh][0] + s12;
+        sp_[(3 * kh + 1) * tap] = R[kh][1] - R[kh][2];
+        sp_[(3 * kh + 2) * tap] = s12 + R[kh][3];
       }
     }
   }
