@@ -1667,6 +1667,126 @@ struct WgradArgs {
   float* slab; long slab_stride;
 };
 
+// ------------------------------------------------------------------ phases shared by the weight-gradient kernels
+// The staged tile of the LDS-tile kernels (k_wgrad_tile, k_wgrad_tile9, k_wgrad_wino), sized here for the kernels AND the host:
+// gy^T [32 channels][WT_GP] | input^T [32 channels][pitch], one such buffer per tile in flight.
+constexpr int WT_GP = 132;
+// gy^T rows are [channel][pixel ^ WT_SWZ(channel)]: the transposed store of a staged float4 (lane = 4 channels of one pixel, 8
+// lanes per pixel) put 32 lanes on 8 banks (pitch 132 = 4 mod 32: channel quads c4 and c4 + 2 collide, 4-way) — measured
+// SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.52 in the 3x3 wgrad (profiles/r03/pmc_c4_step.json).  XOR-ing the pixel with
+// 4 * (channel quad & 7) spreads the eight channel quads over all 32 banks and keeps groups of 4 consecutive pixels (the
+// 16-byte MFMA fragments) intact.  Readers apply the same XOR (an involution).
+#define WT_SWZ(ch) ((((ch) >> 2) & 7) << 2)
+// taps along x of k_wgrad_tile<TH, ., TAPS>: a 1-D row (TH = 1) has all its taps there, a 2-D tile only those of a 3x3
+__host__ __device__ constexpr int wt_kw(int TH, int TAPS) { return TH == 1 ? TAPS : (TAPS == 9 ? 3 : 1); }
+__host__ __device__ constexpr int wt_halo(int TH, int TW, int KH, int KW) { return (TH + KH - 1) * (TW + KW - 1); }
+// pitch of an input channel row: = 5 (mod 8) keeps the (channel il, pixel 4q) scalar reads at <= 3 lanes per bank
+// (brute-forced; 3 (mod 8) is equivalent) and makes the 3x3 buffer 80.1 KB, so TWO such workgroups share a CU
+__host__ __device__ constexpr int wt_in_pitch(int halo) { return ((halo + 2) & ~7) + 5; }
+__host__ __device__ constexpr int wt_buf_floats(int in_pitch) { return 32 * WT_GP + 32 * in_pitch; }
+// staging buffers of k_wgrad_tile<., ., TAPS>: see "LDS buffering" there
+__host__ __device__ constexpr int wt_tile_bufs(int TAPS) { return TAPS == 9 ? 2 : 1; }
+
+// A workgroup's share of the work in the three LDS-tile kernels: blockIdx.y is the 32 co x 32 c block (coblk, cblk) of dW at
+// (co0, c0), blockIdx.x the tiles [t_beg, t_end) of the sample-major tile grid; an empty range means the caller returns.
+struct WgradShare { int coblk, cblk, co0, c0, t_beg, t_end; };
+__device__ __forceinline__ WgradShare wgrad_share(const WgradArgs& A, int tiles_per_wg, int n_tiles) {
+  const int cblocks = (A.C + 31) / 32;
+  const int coblk = blockIdx.y / cblocks, cblk = blockIdx.y - coblk * cblocks;
+  const int t_beg = blockIdx.x * tiles_per_wg;
+  return WgradShare{coblk, cblk, coblk * 32, cblk * 32, t_beg, min(t_beg + tiles_per_wg, n_tiles)};
+}
+
+// Staging of tile `tile` of k_wgrad_tile / k_wgrad_tile9, global -> registers: thread tid takes items tid + 256 k, item =
+// (pixel idx >> 3, channel quad idx & 7), of the gy tile (TH x TW = 128 pixels, sg) and of the input halo ((TH + KH - 1) x
+// (TW + KW - 1) pixels, si), 16 bytes each and zero outside the image or the channel range.  RAG: channel counts that are no
+// multiples of 4 — the loads go element by element with a channel mask.  The input is read on the 2x grid of a folded upsample.
+// (Measured against each kernel's own lambda, profiles/wgrad_shared/bench_load_variants.txt: no form beyond its parent-vs-parent
+// margin; the 1-D 3-tap form is 0.5 % = 1.3 us slower through the function than with its own lines, margins 1.8 / 2.6 us.)
+template <int TH, int TW, int KH, int KW, bool RAG, int MAXIN>
+__device__ __forceinline__ void wtile_load(const WgradArgs& A, int tile, int tiles_x, int tiles_y, int co0, int c0, int tid,
+                                           f32x4 (&sg)[4], f32x4 (&si)[MAXIN]) {
+  constexpr int HW = TW + KW - 1, n_in = wt_halo(TH, TW, KH, KW) * 8;
+  const ConvGeom& g = A.g;
+  const int up = g.ups ? 1 : 0;          // input nearest-upsampled 2x on the fly (folded Upsample)
+  int n, y0, x0;
+  tile_origin<TH, TW>(tile, tiles_x, tiles_y, n, y0, x0);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {                           // gy: 128 pixels x 8 column quads
+    const int idx = tid + 256 * k;
+    const int p = idx >> 3, c4 = idx & 7;
+    const int py = p / TW, px = p - py * TW;
+    const int oy = y0 + py, ox = x0 + px, co = co0 + 4 * c4;
+    f32x4 v = {0, 0, 0, 0};
+    if (oy < g.Ho && ox < g.Wo && co < A.Cout) {
+      const float* gp = A.gy + (((size_t)n * g.Ho + oy) * g.Wo + ox) * A.Cout + co;
+      if (!RAG) v = *reinterpret_cast<const f32x4*>(gp);
+      else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) if (co + r < A.Cout) v[r] = gp[r];
+      }
+    }
+    sg[k] = v;
+  }
+#pragma unroll
+  for (int k = 0; k < MAXIN; ++k) {
+    const int idx = tid + 256 * k;
+    f32x4 v = {0, 0, 0, 0};
+    if (idx < n_in) {
+      const int hp = idx >> 3, c4 = idx & 7;
+      const int hy = hp / HW, hx = hp - hy * HW;
+      const int iy = y0 + hy - g.padH, ix = x0 + hx - g.padW, c = c0 + 4 * c4;   // on the 2x grid if ups
+      if (iy >= 0 && iy < (g.Hi << up) && ix >= 0 && ix < (g.Wi << up) && c < A.C) {
+        const float* sp = A.src + (((size_t)n * g.Hi + (iy >> up)) * g.Wi + (ix >> up)) * A.C + c;
+        if (!RAG) v = *reinterpret_cast<const f32x4*>(sp);
+        else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) if (c + r < A.C) v[r] = sp[r];
+        }
+      }
+    }
+    si[k] = v;
+  }
+}
+// The way back, registers -> LDS (transposed: gy^T [channel][pixel ^ WT_SWZ(channel)] at pitch WT_GP, input^T [channel][halo
+// pixel] at the input pitch), is NOT a function: k_wgrad_tile and k_wgrad_tile9 each keep the same dozen lines as a lambda.
+// Through one function (two buffer pointers or one, called directly or from a lambda) hipcc allocates k_wgrad_tile9 to 168
+// VGPRs + 92 / 48 bytes of scratch where the copy has 160 + 0, and it runs 20-30 % slower; k_wgrad_tile<8, 16, 9, true> 1.4 %
+// slower (428.6 -> 434.4 us, parent-vs-parent 1.3 us), back to the parent's time with the store alone put back
+// (profiles/wgrad_shared/kernel_regs.txt, bench_variants.txt).
+
+// Bias gradient as a by-product of a staged gy^T tile (rows at pitch WT_GP, 128 pixels): thread (co = tid >> 3, part = tid & 7)
+// adds its 16 pixels into bsum.  Every kernel that uses it gives the same bits: the order is fixed here — four 16-byte reads
+// added lane-wise, then (0 + 1) + (2 + 3).  (The XOR swizzle permutes groups of four pixels within the row: which pixels a
+// part holds differs per channel, the union of the eight parts does not.)
+__device__ __forceinline__ void wgrad_bias_add(const float* gT, int tid, float& bsum) {
+  const float* gr = gT + (tid >> 3) * WT_GP + 16 * (tid & 7);
+  f32x4 t4 = *reinterpret_cast<const f32x4*>(gr);
+  t4 += *reinterpret_cast<const f32x4*>(gr + 4);
+  t4 += *reinterpret_cast<const f32x4*>(gr + 8);
+  t4 += *reinterpret_cast<const f32x4*>(gr + 12);
+  bsum += (t4[0] + t4[1]) + (t4[2] + t4[3]);
+}
+// ... and its end: the eight parts of a channel meet (xor 1, 2, 4) and part 0 stores the workgroup's partial behind the slab's
+// `taps` tap images.
+__device__ __forceinline__ void wgrad_bias_store(const WgradArgs& A, float bsum, int tid, int co0, int taps) {
+  bsum += __shfl_xor(bsum, 1, 64);
+  bsum += __shfl_xor(bsum, 2, 64);
+  bsum += __shfl_xor(bsum, 4, 64);
+  const int co = co0 + (tid >> 3);
+  if ((tid & 7) == 0 && co < A.Cout) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)taps * A.CoutP * A.C + co] = bsum;
+}
+
+// Guarded slab store of lane (il, q)'s four values of an MFMA 16 x 16 result tile of tap `tap`: rows co = co_base + 4 q + r,
+// column c, into the slab of workgroup column blockIdx.x.
+__device__ __forceinline__ void wgrad_slab_store(const WgradArgs& A, int tap, int co_base, int q, int c, f32x4 v) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int co = co_base + 4 * q + r;
+    if (co < A.Cout && c < A.C) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)(tap * A.CoutP + co) * A.C + c] = v[r];
+  }
+}
+
 // One workgroup = one (position chunk, tap, co block of 16*MT, c block of 16*KT).
 // Reduction over positions: A lane (co, q) <- gy[m+q][co], B lane (c, q) <- in[src(m+q)][c].
 template <int MT, int KT>
@@ -1725,7 +1845,9 @@ __global__ void __launch_bounds__(256) k_conv_wgrad(WgradArgs A) {
     while (ow >= g.Wo) { ow -= g.Wo; ++oh; }
     while (oh >= g.Ho) { oh -= g.Ho; ++n; }
   }
-  // cross-wave sum, then one slab store per element per workgroup
+  // cross-wave sum, then one slab store per element per workgroup.  The store is wgrad_slab_store's lines, kept here: collecting
+  // the four sums into an f32x4 for the function first measured 400.0 -> 403.0 us (parent-vs-parent 0.9 us) on the C4 step's
+  // 32 -> 32 stride-2 wgrad (profiles/wgrad_shared/bench_variants.txt); with its own lines the kernel is the parent's machine code
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -1756,33 +1878,21 @@ __global__ void __launch_bounds__(256) k_conv_wgrad(WgradArgs A) {
 // index — the pixel — is contiguous for the MFMA fragments), then every tap reads its shifted window from LDS.
 // Each wave reduces its own 32 pixels; the four partial sums meet in LDS at the end and go to the workgroup's slab with
 // one store per element.
-#define WT_GP 132
-// gy^T rows are [channel][pixel ^ WT_SWZ(channel)]: the transposed store of a staged float4 (lane = 4 channels of one pixel, 8
-// lanes per pixel) put 32 lanes on 8 banks (pitch 132 = 4 mod 32: channel quads c4 and c4 + 2 collide, 4-way) — measured
-// SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.52 in the 3x3 wgrad (profiles/r03/pmc_c4_step.json).  XOR-ing the pixel with
-// 4 * (channel quad & 7) spreads the eight channel quads over all 32 banks and keeps groups of 4 consecutive pixels (the
-// 16-byte MFMA fragments) intact.  Readers apply the same XOR (an involution).
-#define WT_SWZ(ch) ((((ch) >> 2) & 7) << 2)
 // RAG: channel counts that are not multiples of 4 (the U-Net's input conv has 1 or 3 input channels, its output conv 1 or 3
 // output channels): the staging loads go element by element with a channel mask instead of 16 bytes at a time.  Those two
-// layers ran on k_conv_wgrad at 1.2 ms each per C4 step (rocprofv3), 1.8 % of it.
+// layers ran on k_conv_wgrad at 1.2 ms each per C4 step (rocprofv3), 1.8 % of it.  The 3x3 form is launched with RAG only:
+// aligned 3x3 shapes go to k_wgrad_tile9 / k_wgrad_wino below, and <8, 16, 9, false> is not instantiated.
 template <int TH, int TW, int TAPS, bool RAG = false>
 __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x, int tiles_y, int tiles_per_wg, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) float wt_lds[];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
-  const ConvGeom g = A.g;
-  constexpr int KW = (TH == 1) ? TAPS : (TAPS == 9 ? 3 : 1), KH = TAPS / KW;    // compile-time: constant index arithmetic
-  constexpr int HH = TH + KH - 1, HW = TW + KW - 1, halo = HH * HW;
-  // pitch of an input channel row: = 5 (mod 8) keeps the (channel il, pixel 4q) scalar reads at <= 3 lanes per bank
-  // (brute-forced; 3 (mod 8) is equivalent) and makes the 3x3 buffer 80.1 KB, so TWO such workgroups share a CU
-  constexpr int IP = ((halo + 2) & ~7) + 5;
-  constexpr int BUF = 32 * WT_GP + 32 * IP;               // one staging buffer: gy^T [32][WT_GP] | input^T [32][IP]
+  constexpr int KW = wt_kw(TH, TAPS), KH = TAPS / KW;      // compile-time: constant index arithmetic
+  constexpr int HW = TW + KW - 1, halo = wt_halo(TH, TW, KH, KW), IP = wt_in_pitch(halo);
+  constexpr int BUF = wt_buf_floats(IP);                  // one staging buffer: gy^T [32][WT_GP] | input^T [32][IP]
   auto gyT = [&](int b) { return wt_lds + b * BUF; };
   auto inT = [&](int b) { return wt_lds + b * BUF + 32 * WT_GP; };
-  const int cblocks = (A.C + 31) / 32;
-  const int coblk = blockIdx.y / cblocks, cblk = blockIdx.y - coblk * cblocks;
-  const int co0 = coblk * 32, c0 = cblk * 32;
-  const int t_beg = blockIdx.x * tiles_per_wg, t_end = min(t_beg + tiles_per_wg, n_tiles);
+  const WgradShare ws = wgrad_share(A, tiles_per_wg, n_tiles);
+  const int coblk = ws.coblk, cblk = ws.cblk, co0 = ws.co0, c0 = ws.c0, t_beg = ws.t_beg, t_end = ws.t_end;
   if (t_beg >= t_end) return;
 
   f32x4 acc[TAPS][2][2];
@@ -1791,53 +1901,10 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
 #pragma unroll
     for (int m = 0; m < 2; ++m) { acc[t][m][0] = f32x4{0, 0, 0, 0}; acc[t][m][1] = f32x4{0, 0, 0, 0}; }
 
-  constexpr int MAXIN = ((TH == 1 ? 1 : TH + 2) * (TW + 2) * 8 + 255) / 256;   // 1-D convolutions have no vertical halo
+  constexpr int n_in = halo * 8, MAXIN = (n_in + 255) / 256;
   f32x4 sg[4], si[MAXIN];
-  const int up = g.ups ? 1 : 0;          // input nearest-upsampled 2x on the fly (folded Upsample)
-  const int n_in = halo * 8;
-  auto stage_load = [&](int tile) {
-    int bx = tile;
-    const int tx_i = bx % tiles_x; bx /= tiles_x;
-    const int ty_i = bx % tiles_y;
-    const int n = bx / tiles_y;
-    const int y0 = ty_i * TH, x0 = tx_i * TW;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                           // gy: 128 pixels x 8 column quads
-      const int idx = tid + 256 * k;
-      const int p = idx >> 3, c4 = idx & 7;
-      const int py = p / TW, px = p - py * TW;
-      const int oy = y0 + py, ox = x0 + px, co = co0 + 4 * c4;
-      f32x4 v = {0, 0, 0, 0};
-      if (oy < g.Ho && ox < g.Wo && co < A.Cout) {
-        const float* gp = A.gy + (((size_t)n * g.Ho + oy) * g.Wo + ox) * A.Cout + co;
-        if (!RAG) v = *reinterpret_cast<const f32x4*>(gp);
-        else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (co + r < A.Cout) v[r] = gp[r];
-        }
-      }
-      sg[k] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < MAXIN; ++k) {
-      const int idx = tid + 256 * k;
-      f32x4 v = {0, 0, 0, 0};
-      if (idx < n_in) {
-        const int hp = idx >> 3, c4 = idx & 7;
-        const int hy = hp / HW, hx = hp - hy * HW;
-        const int iy = y0 + hy - g.padH, ix = x0 + hx - g.padW, c = c0 + 4 * c4;   // on the 2x grid if ups
-        if (iy >= 0 && iy < (g.Hi << up) && ix >= 0 && ix < (g.Wi << up) && c < A.C) {
-          const float* sp = A.src + (((size_t)n * g.Hi + (iy >> up)) * g.Wi + (ix >> up)) * A.C + c;
-          if (!RAG) v = *reinterpret_cast<const f32x4*>(sp);
-          else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (c + r < A.C) v[r] = sp[r];
-          }
-        }
-      }
-      si[k] = v;
-    }
-  };
+  auto stage_load = [&](int tile) { wtile_load<TH, TW, KH, KW, RAG>(A, tile, tiles_x, tiles_y, co0, c0, tid, sg, si); };
+  // registers -> LDS: this kernel's own lines, see the note after wtile_load
   auto stage_store = [&](int b) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -1856,7 +1923,6 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
       }
     }
   };
-
   unsigned tmask = (1u << TAPS) - 1u;
   if (cblk < 16 && A.tm_c[cblk]) tmask &= A.tm_c[cblk];
   if (coblk < 16 && A.tm_o[coblk]) tmask &= A.tm_o[coblk];
@@ -1866,7 +1932,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
   // LDS buffering: the 3x3 variant is register-bound to two workgroups per CU and keeps two LDS buffers (one barrier
   // per tile); the others have registers for three and keep ONE buffer (34 KB) so that three fit — the next tile
   // still travels global -> registers under this tile's MFMAs, only its LDS store waits for an extra barrier.
-  constexpr bool DBUF = TAPS == 9;
+  constexpr bool DBUF = wt_tile_bufs(TAPS) == 2;
   stage_load(t_beg);
   stage_store(0);
   __syncthreads();
@@ -1876,14 +1942,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
     if (more) stage_load(tile + 1);
     const float* gT = gyT(cur);
     const float* iT = inT(cur);
-    if (do_bias && tile / tiles_per_sample < A.n_bias) {   // bias gradient as a by-product of the staged gy tile
-      const float* gr = gT + (tid >> 3) * WT_GP + 16 * (tid & 7);
-      f32x4 t4 = *reinterpret_cast<const f32x4*>(gr);
-      t4 += *reinterpret_cast<const f32x4*>(gr + 4);
-      t4 += *reinterpret_cast<const f32x4*>(gr + 8);
-      t4 += *reinterpret_cast<const f32x4*>(gr + 12);
-      bsum += (t4[0] + t4[1]) + (t4[2] + t4[3]);
-    }
+    if (do_bias && tile / tiles_per_sample < A.n_bias) wgrad_bias_add(gT, tid, bsum);   // by-product of the staged gy tile
     // (Round 3 tried a branch-free tap loop — no per-tap `continue`, the next tap's LDS fragments requested ahead: hipcc then
     // keeps more fragments live, spills 19 registers at the 256-register budget of two workgroups per CU, and the C4 step
     // got SLOWER, 125.7 -> 133.6 ms.  The per-tap branch stays; the second resident wave covers the LDS latency.)
@@ -1924,21 +1983,15 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
       __syncthreads();
     }
   }
-  if (do_bias) {
-    bsum += __shfl_xor(bsum, 1, 64);
-    bsum += __shfl_xor(bsum, 2, 64);
-    bsum += __shfl_xor(bsum, 4, 64);
-    const int co = co0 + (tid >> 3);
-    if ((tid & 7) == 0 && co < A.Cout) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)TAPS * A.CoutP * A.C + co] = bsum;
-  }
+  if (do_bias) wgrad_bias_store(A, bsum, tid, co0, TAPS);
   // cross-wave reduction through LDS (reuse the staging area): up to four taps per round — every wave parks its partial
   // tiles of the round's taps, one barrier, then wave w adds the four partials of tap (round base + w) in wave order and
   // stores that tap's 32 x 32 block.  (One tap per round with wave 0 doing every store was 18 barriers and 144 scattered
   // stores by a single wave per workgroup: 10-15 % of a workgroup's time at 8 tiles per workgroup.)
   float* red = wt_lds;
-  constexpr int TR = TAPS == 9 ? 4 : (TAPS == 3 ? 2 : 1);   // taps per round: TR * 4 waves * 1024 floats fit the staging area
-  constexpr int STG = (TAPS == 9 ? 2 : 1) * BUF;
-  static_assert(TR * 4096 <= (STG > 4096 ? STG : 4096), "reduction scratch exceeds the staging area");
+  constexpr int STG = wt_tile_bufs(TAPS) * BUF;            // the staging area, and with it:
+  constexpr int TR = TAPS < STG / 4096 ? TAPS : STG / 4096;   // taps per round, TR * 4 waves * 1024 floats (4 / 2 / 1 for 9 / 3 / 1 taps)
+  static_assert(TR >= 1, "reduction scratch exceeds the staging area");
   __syncthreads();
 #pragma unroll
   for (int t0 = 0; t0 < TAPS; t0 += TR) {
@@ -1962,14 +2015,15 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-          for (int kt = 0; kt < 2; ++kt)
+          for (int kt = 0; kt < 2; ++kt) {
+            f32x4 sum;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int idx = tt * 4096 + ((m * 2 + kt) * 4 + r) * 64 + lane;
-              const float sum = (red[idx] + red[1024 + idx]) + (red[2048 + idx] + red[3072 + idx]);
-              const int co = co0 + 16 * m + 4 * q + r, c = c0 + 16 * kt + il;
-              if (co < A.Cout && c < A.C) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)(t * A.CoutP + co) * A.C + c] = sum;
+              sum[r] = (red[idx] + red[1024 + idx]) + (red[2048 + idx] + red[3072 + idx]);
             }
+            wgrad_slab_store(A, t, co0 + 16 * m, q, c0 + 16 * kt + il, sum);
+          }
       }
     }
     __syncthreads();
@@ -1985,62 +2039,27 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
 //   * ~130 VGPRs: three workgroups (12 waves) per CU instead of two (8);
 //   * a tap row's fragments overlap: pixels 4q..4q+3 shifted by kw = 0..2 are 6 consecutive halo values, read once per
 //     (pixel group, kh) — 9 LDS read pairs per 36 MFMAs.
-// Same staging (coalesced 16-byte global loads one tile ahead, transposed [channel][pixel] LDS images), ONE LDS buffer
-// (40 KB), same slab / bias outputs as k_wgrad_tile<8, 16, 9>.  Aligned channel counts, no tap masks, no folded upsample
-// restrictions beyond the old kernel's.
+// Same staging (wtile_load: coalesced 16-byte global loads one tile ahead; transposed [channel][pixel] LDS images), ONE LDS
+// buffer (40 KB), same slab / bias outputs as k_wgrad_tile.  It serves every aligned 3x3 shape (channel counts that are
+// multiples of 4, folded upsample included) and has no tap masks; k_wgrad_tile<8, 16, 9> remains for ragged channel counts only.
 __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x, int tiles_y, int tiles_per_wg, int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) float wt_lds[];
   constexpr int TH = 8, TW = 16, KW = 3, KH = 3, TAPS = 9;
-  constexpr int HH = TH + KH - 1, HW = TW + KW - 1, halo = HH * HW;
-  constexpr int IP = ((halo + 2) & ~7) + 5;
+  constexpr int HW = TW + KW - 1, halo = wt_halo(TH, TW, KH, KW), IP = wt_in_pitch(halo);
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const int m = w >> 1, kt = w & 1;                         // this wave's 16 x 16 output tile of every tap
-  const ConvGeom g = A.g;
   float* gT = wt_lds;                                       // gy^T    [32][WT_GP]
   float* iT = wt_lds + 32 * WT_GP;                          // input^T [32][IP]
-  const int cblocks = (A.C + 31) / 32;
-  const int coblk = blockIdx.y / cblocks, cblk = blockIdx.y - coblk * cblocks;
-  const int co0 = coblk * 32, c0 = cblk * 32;
-  const int t_beg = blockIdx.x * tiles_per_wg, t_end = min(t_beg + tiles_per_wg, n_tiles);
+  const WgradShare ws = wgrad_share(A, tiles_per_wg, n_tiles);
+  const int cblk = ws.cblk, co0 = ws.co0, c0 = ws.c0, t_beg = ws.t_beg, t_end = ws.t_end;
   if (t_beg >= t_end) return;
   f32x4 acc[TAPS];
 #pragma unroll
   for (int t = 0; t < TAPS; ++t) acc[t] = f32x4{0, 0, 0, 0};
-  constexpr int MAXIN = (halo * 8 + 255) / 256;
+  constexpr int n_in = halo * 8, MAXIN = (n_in + 255) / 256;
   f32x4 sg[4], si[MAXIN];
-  const int up = g.ups ? 1 : 0;
-  constexpr int n_in = halo * 8;
-  auto stage_load = [&](int tile) {
-    int bx = tile;
-    const int tx_i = bx % tiles_x; bx /= tiles_x;
-    const int ty_i = bx % tiles_y;
-    const int n = bx / tiles_y;
-    const int y0 = ty_i * TH, x0 = tx_i * TW;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int idx = tid + 256 * k;
-      const int p = idx >> 3, c4 = idx & 7;
-      const int py = p / TW, px = p - py * TW;
-      const int oy = y0 + py, ox = x0 + px, co = co0 + 4 * c4;
-      f32x4 v = {0, 0, 0, 0};
-      if (oy < g.Ho && ox < g.Wo && co < A.Cout)
-        v = *reinterpret_cast<const f32x4*>(A.gy + (((size_t)n * g.Ho + oy) * g.Wo + ox) * A.Cout + co);
-      sg[k] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < MAXIN; ++k) {
-      const int idx = tid + 256 * k;
-      f32x4 v = {0, 0, 0, 0};
-      if (idx < n_in) {
-        const int hp = idx >> 3, c4 = idx & 7;
-        const int hy = hp / HW, hx = hp - hy * HW;
-        const int iy = y0 + hy - g.padH, ix = x0 + hx - g.padW, c = c0 + 4 * c4;
-        if (iy >= 0 && iy < (g.Hi << up) && ix >= 0 && ix < (g.Wi << up) && c < A.C)
-          v = *reinterpret_cast<const f32x4*>(A.src + (((size_t)n * g.Hi + (iy >> up)) * g.Wi + (ix >> up)) * A.C + c);
-      }
-      si[k] = v;
-    }
-  };
+  auto stage_load = [&](int tile) { wtile_load<TH, TW, KH, KW, false>(A, tile, tiles_x, tiles_y, co0, c0, tid, sg, si); };
+  // registers -> LDS: this kernel's own lines, see the note after wtile_load
   auto stage_store = [&]() {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -2071,14 +2090,7 @@ __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x
   for (int tile = t_beg; tile < t_end; ++tile) {
     const bool more = tile + 1 < t_end;
     if (more) stage_load(tile + 1);
-    if (do_bias && tile / tiles_per_sample < A.n_bias) {
-      const float* gr = gT + (tid >> 3) * WT_GP + 16 * (tid & 7);
-      f32x4 t4 = *reinterpret_cast<const f32x4*>(gr);
-      t4 += *reinterpret_cast<const f32x4*>(gr + 4);
-      t4 += *reinterpret_cast<const f32x4*>(gr + 8);
-      t4 += *reinterpret_cast<const f32x4*>(gr + 12);
-      bsum += (t4[0] + t4[1]) + (t4[2] + t4[3]);
-    }
+    if (do_bias && tile / tiles_per_sample < A.n_bias) wgrad_bias_add(gT, tid, bsum);
 #pragma unroll
     for (int pg = 0; pg < 8; ++pg) {
       const f32x4 a = *reinterpret_cast<const f32x4*>(ga + ((16 * pg + 4 * q) ^ gsw));
@@ -2097,21 +2109,9 @@ __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x
     __syncthreads();                                        // every wave is done reading the buffer
     if (more) { stage_store(); __syncthreads(); }
   }
-  if (do_bias) {
-    bsum += __shfl_xor(bsum, 1, 64);
-    bsum += __shfl_xor(bsum, 2, 64);
-    bsum += __shfl_xor(bsum, 4, 64);
-    const int co = co0 + (tid >> 3);
-    if ((tid & 7) == 0 && co < A.Cout) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)TAPS * A.CoutP * A.C + co] = bsum;
-  }
-  const int c = c0 + 16 * kt + il;
+  if (do_bias) wgrad_bias_store(A, bsum, tid, co0, TAPS);
 #pragma unroll
-  for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int co = co0 + 16 * m + 4 * q + r;
-      if (co < A.Cout && c < A.C) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)(t * A.CoutP + co) * A.C + c] = acc[t][r];
-    }
+  for (int t = 0; t < TAPS; ++t) wgrad_slab_store(A, t, co0 + 16 * m, q, c0 + 16 * kt + il, acc[t]);
 }
 
 // ------------------------------------------------------------------ wgrad of 3x3 "same" convolutions, Winograd F(3x3, 2x2)
@@ -2161,11 +2161,9 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_wino(WgradArgs A, int tiles_x,
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const int m = w >> 1, kt = w & 1;                         // this wave's 16 x 16 output tile of every position
   const ConvGeom g = A.g;
-  constexpr int BUF = 32 * WT_GP + 32 * IP;                 // one staging buffer: gy^T [32][WT_GP] | input^T [32][IP]
-  const int cblocks = (A.C + 31) / 32;
-  const int coblk = blockIdx.y / cblocks, cblk = blockIdx.y - coblk * cblocks;
-  const int co0 = coblk * 32, c0 = cblk * 32;
-  const int t_beg = blockIdx.x * tiles_per_wg, t_end = min(t_beg + tiles_per_wg, n_tiles);
+  constexpr int BUF = wt_buf_floats(IP);                    // one staging buffer: gy^T [32][WT_GP] | input^T [32][IP]
+  const WgradShare ws = wgrad_share(A, tiles_per_wg, n_tiles);
+  const int cblk = ws.cblk, co0 = ws.co0, c0 = ws.c0, t_beg = ws.t_beg, t_end = ws.t_end;
   if (t_beg >= t_end) return;
   f32x4 acc[16];
 #pragma unroll
@@ -2192,13 +2190,10 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_wino(WgradArgs A, int tiles_x,
   }
   const int gst = 4 * c4 * WT_GP + (sp ^ WT_SWZ(4 * c4));   // + 32 k + r WT_GP: the swizzle stays below bit 5
   const int ist = 32 * WT_GP + WW_ROW(4 * c4) + sp;         // + 32 k + r IP
-  int ld_tx, ld_ty, ld_n;                                   // the tile the next stage_load takes
-  {
-    int bx = t_beg;
-    ld_tx = bx % tiles_x; bx /= tiles_x;
-    ld_ty = bx % tiles_y;
-    ld_n = bx / tiles_y;
-  }
+  // This kernel's staging is its own, not wtile_load: thread-only terms hoisted, tile coordinates advanced by
+  // increments, WW_ROW row shifts — each kept on a measurement (see the head comment; profiles/wgrad_diet).
+  int ld_tx, ld_ty, ld_n;                                   // the tile the next stage_load takes, in units of tiles (<1, 1>)
+  tile_origin<1, 1>(t_beg, tiles_x, tiles_y, ld_n, ld_ty, ld_tx);
   auto stage_load = [&]() {                                 // returns the tile's sample
     const int n = ld_n, y0 = ld_ty * TH, x0 = ld_tx * TW;
     const float* gb = A.gy + (((size_t)n * g.Ho + y0) * g.Wo + x0) * A.Cout;
@@ -2298,14 +2293,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_wino(WgradArgs A, int tiles_x,
     const bool more = tile + 1 < t_end;
     int n_nxt = n_cur;
     if (more) n_nxt = stage_load();
-    if (do_bias && n_cur < A.n_bias) {                     // as k_wgrad_tile9: same bits
-      const float* gr = wt_lds + cur * BUF + (tid >> 3) * WT_GP + 16 * (tid & 7);
-      f32x4 t4 = *reinterpret_cast<const f32x4*>(gr);
-      t4 += *reinterpret_cast<const f32x4*>(gr + 4);
-      t4 += *reinterpret_cast<const f32x4*>(gr + 8);
-      t4 += *reinterpret_cast<const f32x4*>(gr + 12);
-      bsum += (t4[0] + t4[1]) + (t4[2] + t4[3]);
-    }
+    if (do_bias && n_cur < A.n_bias) wgrad_bias_add(wt_lds + cur * BUF, tid, bsum);   // the function k_wgrad_tile9 calls: same bits
     float U[2][16], V[2][16];
     operands(0, U[0], V[0]);
 #pragma unroll
@@ -2324,13 +2312,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_wino(WgradArgs A, int tiles_x,
     flip = -flip;
     n_cur = n_nxt;
   }
-  if (do_bias) {
-    bsum += __shfl_xor(bsum, 1, 64);
-    bsum += __shfl_xor(bsum, 2, 64);
-    bsum += __shfl_xor(bsum, 4, 64);
-    const int co = co0 + (tid >> 3);
-    if ((tid & 7) == 0 && co < A.Cout) A.slab[(size_t)blockIdx.x * A.slab_stride + (size_t)9 * A.CoutP * A.C + co] = bsum;
-  }
+  if (do_bias) wgrad_bias_store(A, bsum, tid, co0, 9);
   // dW = A^T M A per (co, c) element, all in this lane's registers; M (i, j) = M' (i, j) / (D_ii D_jj)
   const int c = c0 + 16 * kt + il;
 #pragma unroll
@@ -2400,9 +2382,8 @@ __global__ void __launch_bounds__(256) k_wgrad3(WgradArgs A, int tiles_x, int ti
 #pragma unroll
   for (int s = 0; s < NB; ++s) bacc[s] = 0.0;
   for (int tile = t_beg; tile < t_end; ++tile) {
-    int t = tile;
-    const int tx_i = t % tiles_x; t /= tiles_x;
-    const int ty_i = t % tiles_y, n = t / tiles_y, y0 = ty_i * TH, x0 = tx_i * TW;
+    int n, y0, x0;
+    tile_origin<TH, TW>(tile, tiles_x, tiles_y, n, y0, x0);
     const bool primal = A.dbias && n < A.n_bias;           // uniform over the workgroup
     // this thread's 16 stream values (zero outside the image)
     float gv[TW];
@@ -3251,7 +3232,8 @@ int msgm_conv_forward_fused(const msgm_conv_geom_t* geom, const float* src0, int
 
 // launch geometry shared by the launcher and the workspace query
 struct WgradPlan { bool tile; int wgs, per, tiles_x, tiles_y, n_tiles, yblocks; int64_t nchunks, chunk; int64_t bias_slots, bias_chunk;
-                   bool one; int mt, nt, wm, px; int64_t n_tiles1; bool wino; };
+                   bool one; int mt, nt, wm, px; int64_t n_tiles1; bool wino;
+                   int th, tw; size_t lds; };          // tile: tile height and width; tile / one: dynamic LDS bytes of the MFMA kernel
 // The pixel-streaming 1x1 wgrad (k_wgrad1x1): instance (MT, NT, WM) for (Cout, C), or mt = 0
 static void wgrad1x1_shape(int C, int Cout, int* mt, int* nt, int* wm) {
   *mt = 0; *nt = 0; *wm = 4;
@@ -3275,6 +3257,7 @@ static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n
       p.one = true;
       const int COB = 16 * p.mt * p.wm, Wd = COB + C;
       p.px = w1_px(Wd);                                     // = k_wgrad1x1's PX
+      p.lds = (size_t)2 * p.px * (Wd + 4) * sizeof(float);  // two buffers of PX rows at k_wgrad1x1's PITCH
       p.yblocks = Cout / COB;
       p.n_tiles1 = (Mtot + p.px - 1) / p.px;
       int wgs = 512 / p.yblocks;                            // two resident workgroups per CU (2 x 33 KB of LDS each)
@@ -3292,11 +3275,14 @@ static WgradPlan wgrad_plan(const msgm_conv_geom_t* geom, int C, int Cout, int n
            (taps == 1 || taps == 3 || (taps == 9 && geom->Ho > 1)) && (geom->Ho > 1 || geom->KH == 1);
   if (p.tile) {
     const bool two_d = geom->Ho > 1;
-    const int TH = two_d ? 8 : 1, TW = two_d ? 16 : 128;
-    p.tiles_x = (geom->Wo + TW - 1) / TW; p.tiles_y = (geom->Ho + TH - 1) / TH;
+    p.th = two_d ? 8 : 1; p.tw = two_d ? 16 : 128;
+    p.tiles_x = (geom->Wo + p.tw - 1) / p.tw; p.tiles_y = (geom->Ho + p.th - 1) / p.th;
     p.n_tiles = p.tiles_x * p.tiles_y * geom->N;
     p.yblocks = ((Cout + 31) / 32) * ((C + 31) / 32);
     p.wino = wino && two_d && taps == 9 && aligned;
+    // k_wgrad_wino: two buffers at its own pitch; k_wgrad_tile9 (aligned 3x3): one; k_wgrad_tile: wt_tile_bufs (k_wgrad3 takes none)
+    const int kw = wt_kw(p.th, taps), ip = wt_in_pitch(wt_halo(p.th, p.tw, taps / kw, kw));
+    p.lds = sizeof(float) * (p.wino ? 2 * wt_buf_floats(WW_IP) : (taps == 9 && aligned ? 1 : wt_tile_bufs(taps)) * wt_buf_floats(ip));
     // k_wgrad_wino: 2 resident workgroups per CU (registers), so one full round of them on the 256 CUs; the others:
     const int wg_target = p.wino ? 256 * 2 : 768;                         // = 3 resident workgroups per CU (k_wgrad_tile9 and the 1- / 3-tap forms); r3 measured 768 / 1024 / 1536 / 3072: 124.0 / 126.4 / 124.7 / 124.9 ms per C4 step (r2, two workgroups per CU: 1024 was best)
     int wgs = wg_target / p.yblocks;                       // ~4 workgroups per CU overall
@@ -3398,8 +3384,7 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
   if (pl.one) {
     if (tapmask_c32 || tapmask_co32) return MSGM_E_UNSUPPORTED;      // a 1x1 kernel has no taps to mask
     const long Mtot = (long)geom->N * geom->Ho * geom->Wo, Mbias = dbias ? (long)n_bias * geom->Ho * geom->Wo : 0;
-    const int COB = 16 * pl.mt * pl.wm;
-    const size_t lds = (size_t)2 * pl.px * (COB + C + 4) * sizeof(float);
+    const size_t lds = pl.lds;
     dim3 grid((unsigned)pl.wgs, (unsigned)pl.yblocks);
 #define W1_LAUNCH(MT_, NT_, WM_)                                                                                      \
   do {                                                                                                               \
@@ -3428,14 +3413,10 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
     return msgm_check_launch();
   }
   if (pl.tile) {
-    const bool two_d = geom->Ho > 1;
-    const int TH = two_d ? 8 : 1, TW = two_d ? 16 : 128;
-    const int tiles_x = pl.tiles_x, tiles_y = pl.tiles_y, n_tiles = pl.n_tiles, yblocks = pl.yblocks, per = pl.per, wgs = pl.wgs;
-    const int halo = (TH + geom->KH - 1) * (TW + geom->KW - 1);
-    const int IP = ((halo + 2) & ~7) + 5;
-    size_t lds = (size_t)(taps == 9 ? 2 : 1) * (32 * WT_GP + 32 * IP) * sizeof(float);
-    if (lds < 4096 * sizeof(float)) lds = 4096 * sizeof(float);
-    dim3 grid((unsigned)wgs, (unsigned)yblocks);
+    const bool two_d = pl.th > 1;
+    const int tiles_x = pl.tiles_x, tiles_y = pl.tiles_y, n_tiles = pl.n_tiles, per = pl.per, wgs = pl.wgs;
+    const size_t lds = pl.lds;
+    dim3 grid((unsigned)wgs, (unsigned)pl.yblocks);
 #define WT_LAUNCH(TH_, TW_, TP_) WT_LAUNCH2(TH_, TW_, TP_, false)
 #define WT_LAUNCH2(TH_, TW_, TP_, RAG_)                                                                              \
   do {                                                                                                               \
@@ -3453,12 +3434,10 @@ static int wgrad_impl(const msgm_conv_geom_t* geom, const float* gy, const float
         else if (rag) WT_LAUNCH2(8, 16, 9, true);
         else if (tapmask_c32 || tapmask_co32) return MSGM_E_UNSUPPORTED;   // k_wgrad_tile9 has no tap masks (they come from 3-tap 1-D convs)
         else if (pl.wino) {
-          const size_t ldsw = (size_t)2 * (32 * WT_GP + 32 * WW_IP) * sizeof(float);
           conv_raise_lds_limit<&k_wgrad_wino>();
-          hipLaunchKernelGGL(k_wgrad_wino, grid, dim3(256), ldsw, S(stream), A, tiles_x, tiles_y, per, n_tiles);
+          hipLaunchKernelGGL(k_wgrad_wino, grid, dim3(256), lds, S(stream), A, tiles_x, tiles_y, per, n_tiles);
         } else {
-          const size_t lds9 = (size_t)(32 * WT_GP + 32 * IP) * sizeof(float);
-          hipLaunchKernelGGL(k_wgrad_tile9, grid, dim3(256), lds9, S(stream), A, tiles_x, tiles_y, per, n_tiles);
+          hipLaunchKernelGGL(k_wgrad_tile9, grid, dim3(256), lds, S(stream), A, tiles_x, tiles_y, per, n_tiles);
         }
       }
       else if (taps == 3) WT_LAUNCH(8, 16, 3); else WT_LAUNCH(8, 16, 1);
@@ -3543,13 +3522,20 @@ int msgm_act_dual_backward(int32_t act, const float* z, float* g, int64_t half, 
   return msgm_check_launch();
 }
 
+// Column sums of N samples x P positions: ~1024 (sample, chunk) workgroups of at least 64 positions; returns the chunks per sample
+static int colsum_chunks(int N, int P, int* chunk) {
+  const int nch = (1024 + N - 1) / N;
+  int ch = (P + nch - 1) / nch;
+  if (ch < 64) ch = 64;
+  if (ch > P) ch = P;
+  *chunk = ch;
+  return (P + ch - 1) / ch;
+}
+
 size_t msgm_colsum_workspace(int32_t N, int32_t P, int32_t C) {
   if (N <= 0 || P <= 0 || C <= 0) return 0;
-  int nch = (1024 + N - 1) / N;
-  int chunk = (P + nch - 1) / nch;
-  if (chunk < 64) chunk = 64;
-  if (chunk > P) chunk = P;
-  nch = (P + chunk - 1) / chunk;
+  int chunk;
+  const int nch = colsum_chunks(N, P, &chunk);
   return nch > 1 ? (size_t)nch * N * C * sizeof(float) : 0;
 }
 
@@ -3557,11 +3543,8 @@ size_t msgm_colsum_workspace(int32_t N, int32_t P, int32_t C) {
 int msgm_colsum_det(const float* x, float* Sout, int32_t N, int32_t P, int32_t C, void* workspace, size_t workspace_bytes,
                     msgm_stream_t stream) {
   if (!x || !Sout || N <= 0 || P <= 0 || C <= 0) return MSGM_E_BADARG;
-  int nch = (1024 + N - 1) / N;
-  int chunk = (P + nch - 1) / nch;
-  if (chunk < 64) chunk = 64;
-  if (chunk > P) chunk = P;
-  nch = (P + chunk - 1) / chunk;
+  int chunk;
+  const int nch = colsum_chunks(N, P, &chunk);
   if (nch == 1) {
     hipLaunchKernelGGL(k_colsum, dim3(N, 1), dim3(256), 0, S(stream), x, Sout, P, C, chunk);
     return msgm_check_launch();

@@ -10,32 +10,18 @@ the same random values where the call accumulates), so a skipped store shows.  T
 every k_conv_tile form, k_dgrad_s2, k_conv3x3_cout_small, k_conv_wino (register / LDS weights), k_conv_wino_p32 and
 k_conv_wino_pipe.  The kernel name printed with a case is what this script EXPECTS conv_route / msgm_conv_forward_wino to pick
 for it (their conditions, restated here), not something observed: check it against a kernel trace if the routing changes.
-A diagnostic: it swaps the library under ops.* by setting _lib._lib and takes the C4 call list from tests/test_wino_pipe_gpu.py."""
-import ctypes, importlib.util, json, os, statistics, sys, time
+A diagnostic: it swaps the library under ops.* (tools/parent_compare.py, shared with wgrad_vs_parent.py) and takes the C4 call
+list from tests/test_wino_pipe_gpu.py."""
+import sys, time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from parent_compare import load, use, test_module, timed_rounds, timing_line, write_timing, timing_args
 from sdeflow_light_amd import _lib, ops  # noqa: E402
 
 DEV = "cuda"
-
-
-def load(path):
-    h = ctypes.CDLL(path)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(h, name)
-        fn.restype, fn.argtypes = res, args
-    return h
-
-
 NEW = _lib.lib()
-PARENT = load(os.path.abspath(sys.argv[1]))
-
-
-def use(h):
-    _lib._lib = h                       # ops.* resolves the library through _lib.lib()
+PARENT = load(sys.argv[1])
 
 
 class Case:
@@ -142,13 +128,6 @@ def small_cases():
     return cases
 
 
-def _test_module(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
 def wino_kernel(C0, C1, CoutP, N, H, aff):
     if not aff:
         return "k_conv_wino_pipe"
@@ -160,7 +139,7 @@ def wino_kernel(C0, C1, CoutP, N, H, aff):
 def wino_cases():
     cases = []
     use(NEW)
-    calls = _test_module("test_wino_pipe_gpu")._c4_winograd_calls()          # what one C4 training step sends to the Winograd entry
+    calls = test_module("test_wino_pipe_gpu")._c4_winograd_calls()          # what one C4 training step sends to the Winograd entry
     for i, (C0, C1, Cout, CoutP, H, ups, acc, res, bias, samp, stats) in enumerate(calls):
         for N in (2, 13):
             for aff in (None, "identity"):
@@ -237,55 +216,21 @@ def time_cases():
 
 
 def timing(path, variants):
-    """Per case: ROUNDS + 1 rounds of (parent, parent again, this tree, then every variant library), each the median of REPS
-    event-timed launches after WARM untimed ones; the first round is a warm-up and is dropped.  The yardstick is the parent
-    against itself: pp = the largest |parent - parent again| of one round.  A build holds when |its median - the parent's median|
-    <= pp; beyond that it is reported as faster or SLOWER, with the rounds in the JSON."""
+    """Every case of time_cases() through parent_compare.timed_rounds (parent / parent again / this tree / variants, alternated;
+    the yardstick is the parent against itself), the rounds in the JSON."""
     ROUNDS, REPS, WARM = 7, 20, 5
-    builds = [("new", NEW)] + [(n, load(os.path.abspath(f))) for n, f in variants]
     rows = []
     for c in time_cases():
         out, cs = c.run(NEW)                               # buffers reused by every timed launch
-
-        def med(h):
-            for _ in range(WARM):
-                c.run(h, out, cs)
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(REPS)]
-            for a, b in ev:
-                a.record(); c.run(h, out, cs); b.record()
-            torch.cuda.synchronize()
-            return statistics.median(a.elapsed_time(b) for a, b in ev) * 1e3
-        p1, p2, t = [], [], {n: [] for n, _ in builds}
-        for r in range(ROUNDS + 1):
-            x1, x2 = med(PARENT), med(PARENT)
-            xs = [med(h) for _, h in builds]
-            if r:                                          # round 0: warm-up
-                p1.append(x1); p2.append(x2)
-                for (n, _), x in zip(builds, xs):
-                    t[n].append(x)
-        mp = statistics.median(p1 + p2)
-        pp = max(abs(a - b) for a, b in zip(p1, p2))
-        row = dict(kernel=c.kernel, case=c.desc, parent_us=[round(x, 2) for x in p1], parent_again_us=[round(x, 2) for x in p2],
-                   parent_median_us=round(mp, 2), parent_vs_parent_max_us=round(pp, 2), builds={})
-        line = f"{c.kernel:<34} parent {mp:9.2f} us (pp {pp:5.2f})"
-        for n, _ in builds:
-            d = statistics.median(t[n]) - mp
-            verdict = "holds" if abs(d) <= pp else ("faster" if d < 0 else "SLOWER")
-            row["builds"][n] = dict(us=[round(x, 2) for x in t[n]], median_us=round(statistics.median(t[n]), 2),
-                                    minus_parent_us=round(d, 2), percent=round(100 * d / mp, 2), verdict=verdict)
-            line += f" | {n} {d:+7.2f} us ({100 * d / mp:+.2f} %) {verdict}"
-        rows.append(row)
-        print(line, flush=True)
+        row = timed_rounds(lambda h: c.run(h, out, cs), PARENT, [("new", NEW)] + variants, ROUNDS, REPS, WARM)
+        rows.append(dict(kernel=c.kernel, case=c.desc, **row))
+        print(timing_line(c.kernel, row), flush=True)
     if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), rounds=ROUNDS, reps=REPS, warmup=WARM, dropped_warmup_rounds=1,
-                           variants=[n for n, _ in variants], cases=rows), f, indent=1)
+        write_timing(path, rows, variants, ROUNDS, REPS, WARM)
     return 0
 
 
 if __name__ == "__main__":
     if "--time" in sys.argv:
-        rest = sys.argv[sys.argv.index("--time") + 1:]
-        sys.exit(timing(next((a for a in rest if "=" not in a), None), [a.split("=", 1) for a in rest if "=" in a]))
+        sys.exit(timing(*timing_args(sys.argv)))
     sys.exit(1 if bitwise() else 0)

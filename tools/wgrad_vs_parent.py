@@ -1,49 +1,122 @@
 #!/usr/bin/env python3
-"""GPU box: the Winograd 3x3 weight gradient (k_wgrad_wino) of this tree's library against another build of it (the parent
-commit's libmsgm_hip.so, built into a scratch path), both loaded into one process, as tools/conv_vs_parent.py does for the
-forward kernels:
+"""GPU box: every weight-gradient kernel of this tree's library against another build of it (the parent commit's
+libmsgm_hip.so, built into a scratch path), both loaded into one process, as tools/conv_vs_parent.py does for the forward
+kernels (the shared parts: tools/parent_compare.py):
     python tools/wgrad_vs_parent.py <parent.so> [B]                          bitwise: slabs, dW and dbias, torch.equal
-    python tools/wgrad_vs_parent.py <parent.so> [B] --time [name=variant.so ...]
+    python tools/wgrad_vs_parent.py <parent.so> [B] [--only NAME[,NAME]] [--skip NAME[,NAME]] --time [out.json] [name=variant.so ...]
                                                                              timing: parent / parent again / this tree (/ further
-                                                                             builds, e.g. a rejected form), alternated
-The cases are every distinct 3x3 stride-1 wgrad call of one eager C4 training step at batch B (default 256; recorded as
-tools/bench_wgrad3x3.py records them) and the shapes of tests/test_wgrad_wino_paths_gpu.py.  Bitwise goes through the raw ABI
-(msgm_conv_wgrad_det with a workspace of its own, NaN-filled first, so the slabs can be compared and a skipped store shows)
-and through ops.conv_wgrad under DeferredReduces; timing goes through ops.conv_wgrad (slot reduction included)."""
-import ctypes, importlib.util, os, statistics, sys, time
+                                                                             builds, e.g. a rejected form), alternated; --only keeps
+                                                                             the cases whose expected kernel contains a NAME, --skip
+                                                                             drops them (e.g. kernels whose machine code is the parent's)
+Bitwise cases: every distinct conv_wgrad call of one eager C4 training step at batch B (default 256) and SMALL below — each
+kernel at the smallest shapes at which it can go wrong.  Each goes through the raw ABI (msgm_conv_wgrad_det with a workspace
+of its own, NaN-filled first, so the slabs can be compared and a skipped store shows) and through ops.conv_wgrad under
+DeferredReduces.  Timing (ops.conv_wgrad, slot reduction included): the step's calls and timed_extra() below.  The kernel printed with a case is what this script EXPECTS
+wgrad_plan / wgrad_impl to pick (their conditions, restated in expect()), not something observed."""
+import ctypes, sys, time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from parent_compare import load, use, same, test_module, timed_rounds, timing_line, write_timing, timing_args
 from sdeflow_light_amd import _lib, ops  # noqa: E402
 
 DEV = "cuda"
-args = [a for a in sys.argv[1:] if a != "--time"]
 TIME = "--time" in sys.argv
-VARIANTS = [a.split("=", 1) for a in args if "=" in a]
-args = [a for a in args if "=" not in a]
+args = sys.argv[1:sys.argv.index("--time")] if TIME else sys.argv[1:]
+ONLY = args.pop(args.index("--only") + 1).split(",") if "--only" in args else [""]
+SKIP = args.pop(args.index("--skip") + 1).split(",") if "--skip" in args else []
+args = [a for a in args if a not in ("--only", "--skip")]
 B = int(args[1]) if len(args) > 1 else 256
-
-
-def load(path):
-    h = ctypes.CDLL(path)
-    for name, (res, at) in _lib.SIGNATURES.items():
-        fn = getattr(h, name)
-        fn.restype, fn.argtypes = res, at
-    return h
-
-
 NEW = _lib.lib()
-PARENT = load(os.path.abspath(args[0]))
+PARENT = load(args[0])
 
 
-def use(h):
-    _lib._lib = h                       # ops.* resolves the library through _lib.lib()
+def expect(g, C, Cout, nb, wino, masks):
+    taps, two_d, aligned = g.KH * g.KW, g.Ho > 1, C % 4 == 0 and Cout % 4 == 0
+    same_ = (g.mode == 0 and g.strideH == 1 and g.strideW == 1 and (g.Hi << g.ups) == g.Ho and (g.Wi << g.ups) == g.Wo and g.KH in (1, 3)
+             and g.KW in (1, 3) and g.padH == (g.KH - 1) // 2 and g.padW == (g.KW - 1) // 2)
+    if taps == 1 and same_ and not g.ups and (nb * g.Ho * g.Wo) % 16 == 0 and C in (32, 64, 128, 256):
+        if Cout == 32 and C <= 128:
+            return f"k_wgrad1x1<1,{C // 32},2>"
+        if Cout % 64 == 0:
+            return f"k_wgrad1x1<{1 if C == 256 else (3 if Cout % 192 == 0 else (2 if Cout % 128 == 0 else 1))},{C // 16},4>"
+    if not (same_ and (aligned or (taps == 9 and two_d)) and g.Ho * g.Wo >= 64 and (taps in (1, 3) or (taps == 9 and two_d))
+            and (two_d or g.KH == 1)):
+        return "k_conv_wgrad<2,4>"
+    if two_d and taps == 9:
+        if not aligned:
+            if not g.ups and not masks and (C, Cout) in ((3, 32), (32, 3)):
+                return f"k_wgrad3<{'true' if C == 3 else 'false'}>"
+            return "k_wgrad_tile<8,16,9,true>"
+        return "k_wgrad_wino" if wino else "k_wgrad_tile9"
+    return f"k_wgrad_tile<{'8,16' if two_d else '1,128'},{taps}>"
+
+
+class Case:
+    """One conv_wgrad call: geometry (the 13 fields of msgm_conv_geom_t), channels, place in the packed image, bias gradient,
+    tap masks, Winograd preference; the inputs are drawn once from a seeded generator."""
+
+    def __init__(self, geom, C, Cout, koff=0, Ktot=None, CoutP=None, nb=0, wino=False, mc=None, mo=None, cnt=1, seed=0):
+        self.geom = g = _lib.ConvGeomT(*geom)
+        self.C, self.Cout, self.koff, self.nb, self.wino, self.mc, self.mo, self.cnt = C, Cout, koff, nb, bool(wino), mc, mo, cnt
+        self.Ktot, self.CoutP = Ktot or ops.pad16(koff + C), CoutP or ops.pad16(Cout)
+        self.taps = g.KH * g.KW
+        self.kernel = expect(g, C, Cout, nb, wino, mc or mo)
+        gen = torch.Generator(device=DEV).manual_seed(seed)
+        self.gy = torch.randn(g.N * g.Ho * g.Wo * Cout, device=DEV, generator=gen)
+        self.x = torch.randn(g.N * g.Hi * g.Wi * C, device=DEV, generator=gen)
+        self.base = torch.randn(self.taps * self.CoutP * self.Ktot, device=DEV, generator=gen)
+        self.db0 = torch.randn(Cout, device=DEV, generator=gen) if nb else None
+        self.flops = 2.0 * self.taps * g.N * g.Ho * g.Wo * C * Cout
+        self.desc = (f"{self.kernel:<26} N={g.N} {g.Hi}x{g.Wi}->{g.Ho}x{g.Wo} k{g.KH}x{g.KW} s{g.strideW} ups={g.ups} C={C} koff={koff} "
+                     f"Cout={Cout}/{self.CoutP} Ktot={self.Ktot} n_bias={nb} masks={mc or mo} wino={int(self.wino)} x{cnt}")
+
+    def fresh(self):
+        return self.base.clone(), (self.db0.clone() if self.nb else None)
+
+    def raw(self, h):
+        """msgm_conv_wgrad_det on a NaN-filled workspace: (slabs, dW, dbias)."""
+        L = _lib
+        need = int(h.msgm_conv_wgrad_workspace(self.geom, self.C, self.Cout, self.CoutP, self.nb, int(self.wino)))
+        ws = torch.full((need // 4,), float("nan"), device=DEV)
+        dWp, db = self.fresh()
+        mc = (ctypes.c_uint16 * len(self.mc))(*self.mc) if self.mc else None
+        mo = (ctypes.c_uint16 * len(self.mo))(*self.mo) if self.mo else None
+        rc = h.msgm_conv_wgrad_det(self.geom, L.ptr(self.gy), L.ptr(self.x), self.C, self.koff, L.ptr(dWp), self.Cout, self.CoutP,
+                                   self.Ktot, L.ptr(db), self.nb, mc, mo, L.ptr(ws), ws.numel() * 4, int(self.wino), L.stream())
+        assert rc == 0, rc
+        torch.cuda.synchronize()
+        return ws, dWp, db
+
+    def via_ops(self, h, deferred, dWp=None, db=None):
+        use(h)
+        if dWp is None:
+            dWp, db = self.fresh()
+        call = lambda: ops.conv_wgrad(self.geom, self.gy, self.x, self.C, self.koff, dWp, self.Cout, self.CoutP, self.Ktot,  # noqa: E731
+                                      dbias=db, n_bias=self.nb, tapmask_c32=self.mc, tapmask_co32=self.mo, wino=self.wino)
+        if deferred:
+            with ops.DeferredReduces.on(DEV):
+                call()
+        else:
+            call()
+        return dWp, db
+
+
+def geom2d(N, H, W, k=3, ups=0, stride=1):
+    """A "same" k x k convolution with H x W output (input at half the size under the folded upsample), or — stride 2 —
+    a 3x3 pad-1 convolution of an H x W input."""
+    if stride == 2:
+        return (N, H, W, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 3, 3, 2, 1, 2, 1, 0, 0)
+    p = (k - 1) // 2
+    return (N, H >> ups, W >> ups, H, W, k, k, 1, p, 1, p, 0, ups)
+
+
+def geom1d(N, L, k):
+    return (N, 1, L, 1, L, 1, k, 1, 0, 1, (k - 1) // 2, 0, 0)
 
 
 def step_calls():
-    """(N, Hi, Wi, Ho, Wo, ups, C, koff, Cout, CoutP, Ktot, has_bias, n_bias) -> launches per step, of the calls routed to wino."""
+    """Every distinct conv_wgrad call of one eager C4 training step at batch B, with its number of launches."""
     from sdeflow_light_amd.NNUnet import VorticityUNet
     from sdeflow_light_amd.SDEs import SGMsde, PluginReverseSDE
     from sdeflow_light_amd.train import UNetScoreTrainer
@@ -59,9 +132,8 @@ def step_calls():
     seen, orig = {}, ops.conv_wgrad
 
     def spy(geom, gy, src, C, koff, dWp, Cout, CoutP, Ktot, dbias=None, n_bias=0, tapmask_c32=None, tapmask_co32=None, wino=False):
-        if wino and geom.KH == 3 and geom.KW == 3 and geom.strideH == 1 and geom.strideW == 1 and C % 4 == 0 and Cout % 4 == 0:
-            key = (geom.N, geom.Hi, geom.Wi, geom.Ho, geom.Wo, geom.ups, C, koff, Cout, CoutP, Ktot, dbias is not None, n_bias)
-            seen[key] = seen.get(key, 0) + 1
+        key = (tuple(getattr(geom, f) for f, _ in geom._fields_), C, Cout, koff, Ktot, CoutP, n_bias if dbias is not None else 0, bool(wino))
+        seen[key] = seen.get(key, 0) + 1
         return orig(geom, gy, src, C, koff, dWp, Cout, CoutP, Ktot, dbias=dbias, n_bias=n_bias, tapmask_c32=tapmask_c32,
                     tapmask_co32=tapmask_co32, wino=wino)
 
@@ -71,70 +143,82 @@ def step_calls():
     ops.conv_wgrad = orig
     del tr, gen, net
     torch.cuda.empty_cache()
-    return sorted(seen.items(), key=lambda kv: (-kv[0][3], kv[0][6], kv[0][8], kv[0][7]))
+    rows = sorted(seen.items(), key=lambda kv: (-kv[0][0][3], kv[0][0][5], kv[0][1], kv[0][2], kv[0][3]))
+    return [Case(k[0], k[1], k[2], koff=k[3], Ktot=k[4], CoutP=k[5], nb=k[6], wino=k[7], cnt=n, seed=100 + i) for i, (k, n) in enumerate(rows)]
 
 
-def test_calls():
-    spec = importlib.util.spec_from_file_location("paths", os.path.join(ROOT, "tests", "test_wgrad_wino_paths_gpu.py"))
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    out = []
-    for (N, nb, H, W, ups, srcC, Cout) in m.CASES:
-        Hi, Wi = (H // 2, W // 2) if ups else (H, W)
-        Ktot, koff = ops.pad16(sum(srcC)), 0
+def wino_test_rows():
+    """The rows of tests/test_wgrad_wino_paths_gpu.py and the 9 x 11 row of tests/test_wgrad_wino_gpu.py, one call per source."""
+    rows = list(test_module("test_wgrad_wino_paths_gpu").CASES) + [c for c in test_module("test_wgrad_wino_gpu").CASES if c[2:4] == (9, 11)]
+    for (N, nb, H, W, ups, srcC, Cout) in rows:
+        koff = 0
         for s, C in enumerate(srcC):
-            out.append(((N, Hi, Wi, H, W, int(ups), C, koff, Cout, ops.pad16(Cout), Ktot, s == 0, nb if s == 0 else 0), 1))
+            yield dict(geom=geom2d(N, H, W, ups=int(ups)), C=C, Cout=Cout, koff=koff, Ktot=ops.pad16(sum(srcC)), nb=nb if s == 0 else 0)
             koff += C
-    return out
 
 
-class Case:
-    def __init__(self, key, cnt, seed):
-        (self.N, self.Hi, self.Wi, self.Ho, self.Wo, self.ups, self.C, self.koff, self.Cout, self.CoutP, self.Ktot, self.has_b,
-         self.nb) = key
-        self.cnt = cnt
-        g = torch.Generator(device=DEV).manual_seed(seed)
-        self.geom = ops.conv_geom(self.N, self.Hi, self.Wi, self.Ho, self.Wo, 3, 3, 1, 1, 0, self.ups)
-        self.gy = torch.randn(self.N * self.Ho * self.Wo * self.Cout, device=DEV, generator=g)
-        self.x = torch.randn(self.N * self.Hi * self.Wi * self.C, device=DEV, generator=g)
-        self.base = torch.randn(9 * self.CoutP * self.Ktot, device=DEV, generator=g)
-        self.db0 = torch.randn(self.Cout, device=DEV, generator=g) if self.has_b else None
-        self.desc = (f"N={self.N} {self.Hi}x{self.Wi}->{self.Ho}x{self.Wo} ups={self.ups} C={self.C} koff={self.koff} Cout={self.Cout}/"
-                     f"{self.CoutP} Ktot={self.Ktot} bias={int(self.has_b)} n_bias={self.nb} x{cnt}")
-
-    def raw(self, h):
-        """msgm_conv_wgrad_det on a NaN-filled workspace: (slabs, dW, dbias)."""
-        L = _lib
-        nbias = self.nb if self.has_b else 0
-        need = int(h.msgm_conv_wgrad_workspace(self.geom, self.C, self.Cout, self.CoutP, nbias, 1))
-        ws = torch.full((need // 4,), float("nan"), device=DEV)
-        dWp, db = self.base.clone(), (self.db0.clone() if self.has_b else None)
-        rc = h.msgm_conv_wgrad_det(self.geom, L.ptr(self.gy), L.ptr(self.x), self.C, self.koff, L.ptr(dWp), self.Cout, self.CoutP,
-                                   self.Ktot, L.ptr(db), nbias, None, None, L.ptr(ws), ws.numel() * 4, 1, L.stream())
-        assert rc == 0, rc
-        torch.cuda.synchronize()
-        return ws, dWp, db
-
-    def via_ops(self, h, deferred, dWp=None, db=None):
-        use(h)
-        if dWp is None:
-            dWp, db = self.base.clone(), (self.db0.clone() if self.has_b else None)
-        call = lambda: ops.conv_wgrad(self.geom, self.gy, self.x, self.C, self.koff, dWp, self.Cout, self.CoutP, self.Ktot,  # noqa: E731
-                                      dbias=db, n_bias=self.nb if self.has_b else 0, wino=True)
-        if deferred:
-            with ops.DeferredReduces.on(DEV):
-                call()
-        else:
-            call()
-        return dWp, db
+# The stride-2 pair op's tap masks as convnet.py builds them (Stride2PairOp: bit t = tap t present, per 32 channels of the paired
+# axis): a conv with 32 input channels has [x[2j] | x[2j+1]] = 64 paired inputs, a transposed conv with 32 outputs 64 paired outputs
+MASK_CONV, MASK_CONVT = [0b110, 0b011], [0b011, 0b110]
 
 
-def same(a, b):
-    if a is None or b is None:
-        return a is None and b is None
-    # slabs: every slot either kernel writes is finite; NaN marks what neither wrote, and must sit at the same places
-    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b))
+def small_cases():
+    rows = [
+        # k_conv_wgrad<2, 4>: the stride-2 3x3 of test_conv2d_fwd_bwd; 80 -> 45 channels (partial 64- / 32-channel blocks) over
+        # 6 x 48 = 288 positions = chunks of 256 + 32 (position 256 is inside a row of 6); a "same" 3x3 on 6 x 6 = 36 < 64 pixels
+        dict(geom=geom2d(2, 16, 12, stride=2), C=32, Cout=32, nb=2),
+        dict(geom=geom2d(6, 16, 12, stride=2), C=80, Cout=45, nb=3),
+        dict(geom=geom2d(9, 6, 6), C=40, Cout=24, nb=4),
+        dict(geom=geom2d(2, 6, 6), C=32, Cout=32, koff=16, Ktot=48),
+        # k_wgrad_tile<8, 16, 9, true>: ragged channel counts; 20 x 24 = 3 x 2 ragged tiles; one tile in all; three tiles
+        dict(geom=geom2d(2, 20, 24), C=1, Cout=32, nb=1),
+        dict(geom=geom2d(2, 20, 24), C=32, Cout=1, nb=1),
+        dict(geom=geom2d(2, 16, 16), C=3, Cout=48, nb=2),
+        dict(geom=geom2d(2, 20, 24, ups=1), C=1, Cout=32, nb=1),
+        dict(geom=geom2d(1, 8, 16), C=1, Cout=32, nb=1),
+        dict(geom=geom2d(1, 8, 40), C=32, Cout=1, nb=1),
+        # k_wgrad_tile<8, 16, 1>: a 2-D 1x1 the streaming kernel declines (48 input channels); one tile; three tiles
+        dict(geom=geom2d(2, 16, 16, k=1), C=48, Cout=32, nb=1),
+        dict(geom=geom2d(1, 8, 16, k=1), C=48, Cout=64, nb=1),
+        dict(geom=geom2d(3, 8, 16, k=1), C=48, Cout=32, koff=16, Ktot=64),
+        # k_wgrad_tile<8, 16, 3>: three vertical taps, through the raw geometry only (ops.conv_geom cannot express it)
+        dict(geom=(2, 16, 16, 16, 16, 3, 1, 1, 1, 1, 0, 0, 0), C=32, Cout=32, nb=1),
+        dict(geom=(1, 8, 16, 8, 16, 3, 1, 1, 1, 1, 0, 0, 0), C=36, Cout=44, nb=1),
+        # k_wgrad_tile<1, 128, 3>: L = 100 (one ragged tile per sample; three tiles, one tile), the pair op's masks, a second source
+        # at a K offset; L = 37 < 64 positions falls to k_conv_wgrad
+        dict(geom=geom1d(3, 100, 3), C=32, Cout=32, nb=2),
+        dict(geom=geom1d(1, 100, 3), C=64, Cout=128, nb=1),
+        dict(geom=geom1d(3, 100, 3), C=64, Cout=32, nb=2, mc=MASK_CONV),
+        dict(geom=geom1d(2, 100, 3), C=32, Cout=64, nb=1, mo=MASK_CONVT),
+        dict(geom=geom1d(2, 300, 3), C=32, Cout=32, koff=32, Ktot=64),
+        dict(geom=geom1d(2, 37, 3), C=64, Cout=128, nb=1),
+        dict(geom=geom1d(2, 37, 3), C=64, Cout=32, nb=1, mc=MASK_CONV),
+        # k_wgrad_tile<1, 128, 1>: 48 input channels (the streaming kernel declines)
+        dict(geom=geom1d(3, 100, 1), C=48, Cout=32, nb=2),
+        dict(geom=geom1d(1, 100, 1), C=48, Cout=64, koff=16, Ktot=64),
+        dict(geom=geom1d(2, 37, 1), C=48, Cout=32, nb=1),
+    ]
+    # k_wgrad_tile9 (wino = 0) and k_wgrad_wino (wino = 1)
+    rows += [dict(r, wino=w) for r in wino_test_rows() for w in (0, 1)]
+    # k_wgrad3<true / false>: the shapes of test_wgrad3_parity
+    rows += [dict(geom=geom2d(2, H, H), C=C, Cout=Co, nb=1) for H in (16, 24) for (C, Co) in ((3, 32), (32, 3))]
+    return [Case(seed=900 + i, **r) for i, r in enumerate(rows)]
+
+
+def timed_extra():
+    """A shape of a size a user would run for every changed kernel that the C4 step does not launch (dual batch 512; the 1-D
+    shapes are those of the 1-D U-Net at batch 1024)."""
+    rows = [dict(r, wino=0) for r in (dict(geom=geom2d(2 * B, H, H), C=C, Cout=C, nb=B) for H, C in ((64, 32), (32, 64), (16, 128)))]   # k_wgrad_tile9
+    rows += [
+        dict(geom=geom2d(2 * B, 64, 64), C=1, Cout=32, nb=B),                   # k_wgrad_tile<8,16,9,true>
+        dict(geom=geom2d(2 * B, 64, 64), C=32, Cout=1, nb=B),
+        dict(geom=geom2d(2 * B, 32, 32, k=1), C=48, Cout=64, nb=B),             # k_wgrad_tile<8,16,1>
+        dict(geom=(2 * B, 32, 32, 32, 32, 3, 1, 1, 1, 1, 0, 0, 0), C=64, Cout=64, nb=B),   # k_wgrad_tile<8,16,3>
+        dict(geom=geom1d(2048, 512, 3), C=64, Cout=64, nb=1024),                 # k_wgrad_tile<1,128,3>
+        dict(geom=geom1d(2048, 256, 3), C=128, Cout=64, nb=1024, mc=[0b110, 0b110, 0b011, 0b011]),
+        dict(geom=geom1d(2048, 1024, 1), C=48, Cout=32, nb=1024),                # k_wgrad_tile<1,128,1>
+    ]
+    return [Case(seed=700 + i, **r) for i, r in enumerate(rows)]
 
 
 def bitwise(cases):
@@ -157,50 +241,26 @@ def bitwise(cases):
     return bad
 
 
-def timing(cases):
-    """Per case: ROUNDS + 1 rounds of (parent, parent again, this tree, then every variant), each the median of REPS event-timed
-    calls after WARM untimed ones; round 0 is dropped.  pp = the largest |parent - parent again| of one round."""
+def timing(cases, path, variants):
     ROUNDS, REPS, WARM = 5, 20, 3
-    builds = [("new", NEW)] + [(n, load(os.path.abspath(f))) for n, f in VARIANTS]
-    tot = {n: 0.0 for n, _ in builds}
-    totp = 0.0
+    rows, tot = [], {}
     for c in cases:
-        dWp, db = c.base.clone(), (c.db0.clone() if c.has_b else None)
-
-        def med(h):
-            for _ in range(WARM):
-                c.via_ops(h, False, dWp, db)
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(REPS)]
-            for a, b in ev:
-                a.record(); c.via_ops(h, False, dWp, db); b.record()
-            torch.cuda.synchronize()
-            return statistics.median(a.elapsed_time(b) for a, b in ev) * 1e3
-        p1, p2, t = [], [], {n: [] for n, _ in builds}
-        for r in range(ROUNDS + 1):
-            x1, x2 = med(PARENT), med(PARENT)
-            xs = [med(h) for _, h in builds]
-            if r:
-                p1.append(x1); p2.append(x2)
-                for (n, _), x in zip(builds, xs):
-                    t[n].append(x)
-        mp = statistics.median(p1 + p2)
-        pp = max(abs(a - b) for a, b in zip(p1, p2))
-        fl = 2.0 * 9 * c.N * c.Ho * c.Wo * c.C * c.Cout
-        line = f"{c.desc:<86} parent {mp:7.1f} us {fl / mp / 1e6:6.1f} TFLOP/s as written (pp {pp:4.1f})"
-        totp += c.cnt * mp
-        for n, _ in builds:
-            x = statistics.median(t[n])
-            tot[n] += c.cnt * x
-            line += f" | {n} {x:7.1f} us {fl / x / 1e6:6.1f} ({100 * (x - mp) / mp:+.1f} %)"
-        print(line, flush=True)
-    print(f"per step (launches x median): parent {totp / 1e3:.2f} ms" + "".join(f", {n} {v / 1e3:.2f} ms" for n, v in tot.items()))
+        dWp, db = c.fresh()
+        row = timed_rounds(lambda h: c.via_ops(h, False, dWp, db), PARENT, [("new", NEW)] + variants, ROUNDS, REPS, WARM)
+        rows.append(dict(kernel=c.kernel, case=c.desc, launches_per_step=c.cnt, **row))
+        print(f"{timing_line(c.kernel, row)}   {c.flops / row['parent_median_us'] / 1e6:6.1f} TFLOP/s as written   {c.desc[27:]}", flush=True)
+        for n, us in [("parent", row["parent_median_us"])] + [(n, b["median_us"]) for n, b in row["builds"].items()]:
+            tot[n] = tot.get(n, 0.0) + c.cnt * us
+    print("launches x median over these cases: " + ", ".join(f"{n} {v / 1e3:.2f} ms" for n, v in tot.items()))
+    if path:
+        write_timing(path, rows, variants, ROUNDS, REPS, WARM)
     return 0
 
 
 if __name__ == "__main__":
-    step = [Case(k, n, 100 + i) for i, (k, n) in enumerate(step_calls())]
-    print(f"{len(step)} distinct Winograd 3x3 wgrad calls, {sum(c.cnt for c in step)} per step (dual batch {2 * B})", flush=True)
+    keep = lambda c: any(n in c.kernel for n in ONLY) and not any(n in c.kernel for n in SKIP)   # noqa: E731
+    step = step_calls()
+    print(f"{len(step)} distinct conv_wgrad calls, {sum(c.cnt for c in step)} per C4 step (dual batch {2 * B})", flush=True)
     if TIME:
-        sys.exit(timing(step))
-    small = [Case(k, n, 900 + i) for i, (k, n) in enumerate(test_calls())]
-    sys.exit(1 if bitwise(step + small) else 0)
+        sys.exit(timing([c for c in step + timed_extra() if keep(c)], *timing_args(sys.argv)))
+    sys.exit(1 if bitwise([c for c in step + small_cases() if keep(c)]) else 0)
