@@ -631,6 +631,19 @@ int msgm_attention_dual_mh_backward(const float* qkv, const float* att, const fl
 int msgm_rbf_kernel(const float* x, const float* y, int64_t Nx, int64_t Ny, int32_t d, float* K, double* sum,
                     msgm_stream_t stream);
 
+/* 1-D Gaussian kernel density of the multiplicative SDE's latent radii (SDEs.py:239-240, 503-509): what
+ * sklearn's KernelDensity(kernel='gaussian', bandwidth=h).fit(r).score_samples(q) returns with its default exact sum,
+ *   out[m] = -log(Ns) - log(h) - log(2 pi)/2 + logsumexp_i( -((q[m] - r[i]) / h)^2 / 2 ),     q [M], r [Ns], out [M], fp32.
+ * Evaluated in log space relative to the nearest sample, so a query any number of bandwidths away from every sample
+ * gets a finite (large negative) value; q, r and (q - r) / h must be finite in fp32.  The samples are split into slabs
+ * whose per-(slab, query) partial (nearest distance, sum) pairs go to `workspace` and are folded in slab order by a
+ * second launch: no atomics, bitwise repeatable.  msgm_kde_workspace() gives the bytes for the slab count the call
+ * prefers; a smaller workspace (at least 8 M bytes) is accepted and means fewer, longer slabs.
+ * M <= 0, Ns <= 0, h not finite or not positive -> MSGM_E_BADARG; M > 65535 * 256 -> MSGM_E_UNSUPPORTED. */
+size_t msgm_kde_workspace(int64_t M, int64_t Ns);
+int msgm_kde_logpdf(const float* q, int64_t M, const float* r, int64_t Ns, double h, float* out, void* workspace,
+                    size_t workspace_bytes, msgm_stream_t stream);
+
 /* [cos(t f_j), sin(t f_j)], f_j = exp(-ln(max_period) j/half) (model/nn_utils.py:130-148). */
 int msgm_timestep_embedding(const float* t, float* emb, int32_t B, int32_t dim, float max_period, msgm_stream_t stream);
 

@@ -9,8 +9,12 @@ What runs where
 * schedule accessors kept for API compatibility (``beta``, ``mean_weight``,
   ``var``, ``f``, ``g`` ...) are one-line tensor expressions evaluated on the
   tensor's own device — the hot path never calls them;
-* out of scope: the sklearn-KDE latent density
-  (``log_latent_pdf``), plotting / validation branches, ``ssm_intT``.
+* reporting path: the latent log-densities and the ELBO slice estimate.  The
+  multiplicative SDE's latent density is a 1-D Gaussian kernel density of the
+  radii (a host-side sklearn ``KernelDensity`` upstream, SDEs.py:240): here one
+  log-space kernel on the device (``ops.kde_logpdf``);
+* out of scope: plotting / validation branches, ``ssm_intT``,
+  non-Gaussian KDE kernels.
 
 RNG: the reference draws from torch's global generator (CPU mt19937 for t,
 device generator for the rest, SDEs.py:688,141,515).  Here every draw comes
@@ -216,15 +220,34 @@ class SGMsde(SDE):
 
 class MSGMsde(SDE):
     """Multiplicative SDE dY = G(Y) o dB (SDEs.py:221-509), dense rank-3
-    tensor or sparse nearest-neighbour rotation tensor.  The KDE of the radial
-    law (sklearn, SDEs.py:240) is out of scope; the ECDF latent sampler is kept."""
+    tensor or sparse nearest-neighbour rotation tensor.
+
+    The radial law of the latent is a 1-D Gaussian kernel density of the mapped
+    radii ``r_T`` with bandwidth ``0.1 * std(r_T)`` (SDEs.py:239-240).  It serves
+    ``log_latent_pdf`` (the ELBO's latent term), ``cst_log_dens`` and the
+    ``norm_sampler="kde"`` latent sampler; ``norm_sampler="ecdf"`` (the default)
+    samples radii by empirical quantiles instead.
+
+    The density is needed lazily.  Upstream fits the sklearn estimator in every
+    constructor call, so sklearn refuses a bandwidth that is not a positive
+    number (one row, or all radii equal) at construction, and an unknown
+    ``kernel`` there too.  Here construction succeeds for such inputs — training
+    and ECDF sampling do not need the density — and ``log_latent_pdf``,
+    ``cst_log_dens`` and the KDE sampler raise ``MsgmError`` when first used.
+    Only ``kernel='gaussian'`` is built.
+
+    Upstream's defects of this density are mirrored, not fixed: the missing
+    ``|x|^(d-1) / S_(d-1)`` factor (see the WARNING comments at SDEs.py:504-505)
+    and, with ``norm_map="log"``, a density fitted on ``log(r + 1e-6)`` but
+    queried with the raw norm (SDEs.py:236, 506) — queries then sit many
+    bandwidths from every sample and the log-density is large and negative."""
 
     def __init__(self, y0, beta_min=0.1, beta_max=20.0, T=1.0, t_epsilon=0.001, denseTensor=True,
                  norm_sampler="ecdf", norm_map=None, kernel='gaussian', plot_validate=False,
                  num_steps_forward=100, device='cpu', estim_cst_norm_dens_r_T=True, G=None):
         super().__init__(beta_min, beta_max, T, t_epsilon, num_steps_forward, device)
-        if norm_sampler != "ecdf":
-            raise MsgmError("only norm_sampler='ecdf' is built (the KDE branch is broken upstream, SDEs.py:444)")
+        if norm_sampler not in ("ecdf", "kde"):
+            raise MsgmError("norm_sampler must be 'ecdf' or 'kde'")
         self.sparseTensor = not denseTensor
         self.kind = L.SDE_MSGM_DENSE if denseTensor else L.SDE_MSGM_SPARSE
         self.norm_correction = True
@@ -232,6 +255,9 @@ class MSGMsde(SDE):
         self.norm_map = norm_map
         if norm_map == "log":
             self.r_T = torch.log(self.r_T + 1e-6)
+        # SDEs.py:239 (unbiased std of the mapped radii); NaN when there is a single row
+        self.bandwidth = 0.1 * torch.std(self.r_T).item() if self.r_T.numel() > 1 else float("nan")
+        self.kernel = kernel
         self.r_T = self.r_T.to(self.device)
         self.norm_sampler = norm_sampler
         self.dim = y0.shape[1]
@@ -243,13 +269,18 @@ class MSGMsde(SDE):
             self.name_SDE += "_sparseTens"
             self.sparse_G(self.dim)
             self.L_G = 0.5 * torch.eye(self.dim, device=self.device)
+        if norm_sampler != "ecdf":
+            self.name_SDE += norm_sampler + kernel                                          # SDEs.py:252-253
         if norm_map == "log":
             self.name_SDE += "logNorm"
-        self.cst_log_dens = 0
+        self.estim_cst_norm_dens_r_T = bool(estim_cst_norm_dens_r_T or plot_validate)       # SDEs.py:256-257
+        self._cst_log_dens = None
 
     def to(self, device):
         new = super().to(device)
         new.r_T = self.r_T.to(device)
+        if self._cst_log_dens is not None:
+            new._cst_log_dens = self._cst_log_dens.to(device)
         if self.sparseTensor:
             for k in ("G_I", "G_J", "G_K", "G_V"):
                 setattr(new, k, getattr(self, k).to(device))
@@ -322,13 +353,31 @@ class MSGMsde(SDE):
         from .sde_scheme import msgm_forward_perturb
         return msgm_forward_perturb(self, t, y0, noise_main=noise_main, noise_short=noise_short)
 
-    def gen_radial_distribution(self, num_samples, u=None):
-        if u is None:
-            u = torch.empty(num_samples, dtype=torch.float32, device=self.device)
+    def gen_radial_distribution(self, num_samples, u=None, z=None):
+        """Radii of the latent (SDEs.py:438-465).  'ecdf': empirical quantiles of ``r_T`` at ``u``.  'kde': what
+        ``KernelDensity.sample`` draws for a Gaussian kernel, ``r_T[floor(u Ns)] + h z``, negative radii set to 0
+        unless the radii are log-mapped (upstream's own branch cannot run: undefined global at SDEs.py:444).
+        ``u`` (uniform) and ``z`` (normal), each (num_samples,), inject the draws; otherwise they come from the
+        SDE's Philox stream, which advances once per call."""
+        kde = self.norm_sampler == "kde"
+        if kde:
+            self._kde_check()
+        if u is None or (kde and z is None):
             rng = self.philox(self.device)
-            ops.fill_uniform(u, rng, L.RNG_STREAM_ROWS)
+            if u is None:
+                u = ops.fill_uniform(torch.empty(num_samples, dtype=torch.float32, device=self.device), rng, L.RNG_STREAM_ROWS)
+            if kde and z is None:
+                z = ops.fill_normal(torch.empty(num_samples, dtype=torch.float32, device=self.device), rng,
+                                    L.RNG_STREAM_USER + 2)
             rng.advance(1)
-        r = torch.quantile(self.r_T, u).reshape(num_samples, 1)                # SDEs.py:442
+        if kde:
+            Ns = self.r_T.numel()
+            i = torch.floor(u.reshape(-1) * Ns).long().clamp_(max=Ns - 1)
+            r = (self.r_T[i] + self.bandwidth * z.reshape(-1)).reshape(num_samples, 1)
+            if self.norm_map != "log":
+                r = r.clamp_min(0.)                                                # SDEs.py:445-447
+        else:
+            r = torch.quantile(self.r_T, u).reshape(num_samples, 1)                # SDEs.py:442
         if self.norm_map == "log":
             r = torch.exp(r) - 1e-6
         return r
@@ -342,8 +391,40 @@ class MSGMsde(SDE):
         r_x = torch.linalg.norm(x.detach().to(self.device), dim=1).reshape(x.shape[0], 1)
         return r_x * randu_on_sphere((x.shape[0], self.dim), self.device, rng=self.philox(self.device))
 
+    def _kde_check(self):
+        if self.kernel != 'gaussian':
+            raise MsgmError(f"only the Gaussian kernel density is built (kernel={self.kernel!r})")
+        if not (math.isfinite(self.bandwidth) and self.bandwidth > 0.):
+            raise MsgmError(f"the kernel density of the radii needs a positive bandwidth 0.1 * std(r_T), got "
+                            f"{self.bandwidth} (one row, or all radii equal)")
+
+    @property
+    def cst_log_dens(self):
+        """log of the density's integral over [min r_T, max r_T] by a 1000-point Riemann sum (SDEs.py:258-265) — a device
+        scalar, computed when first needed; 0 without ``estim_cst_norm_dens_r_T``."""
+        if not self.estim_cst_norm_dens_r_T:
+            return 0
+        if self._cst_log_dens is None or self._cst_log_dens.device != self.r_T.device:
+            self._kde_check()
+            r = self.r_T.contiguous()
+            lo, hi = r.min(), r.max()
+            # torch.linspace(lo, hi, 1000) as the CPU computes it — fp32 fma(step, k, lo) from the left half, fma(-step,
+            # 999 - k, hi) from the right — without reading lo / hi on the host.  Bit-exactness matters: upstream's
+            # dr = grid[1] - grid[0] is an fp32 difference of neighbours and carries their rounding.
+            step = ((hi - lo) / 999.).double()
+            k = torch.arange(1000, dtype=torch.float64, device=r.device)
+            grid = torch.where(k < 500, lo.double() + step * k, hi.double() - step * (999. - k)).float()
+            dens = torch.exp(ops.kde_logpdf(grid, r, self.bandwidth))
+            self._cst_log_dens = torch.log(dens.sum() * (grid[1] - grid[0]))
+        return self._cst_log_dens
+
     def log_latent_pdf(self, yT):
-        raise MsgmError("log_latent_pdf (sklearn KDE) is outside the accelerated hot path")
+        """Log-density (M,) of the latent's radius |yT| under the kernel density of ``r_T``, minus ``cst_log_dens``
+        (SDEs.py:503-509): row norm + one log-space KDE kernel on the device, no host synchronisation."""
+        self._kde_check()
+        cst = self.cst_log_dens
+        lp = ops.kde_logpdf(ops.row_norm(yT.detach().contiguous().float()), self.r_T.contiguous(), self.bandwidth)
+        return lp - cst
 
 
 # ---------------------------------------------------------------------------
@@ -552,20 +633,24 @@ class PluginReverseSDE(nn.Module):
     def cond_latent_sample(self, t_, T, x):
         return self.base_sde.cond_latent_sample(t_, T, x)
 
-    def elbo_random_t_slice(self, x, u=None, eps=None, u_v=None, eps_T=None):
-        """ELBO slice estimate lp(y_T) - ssm(x) T (SDEs.py:708-721) for the additive SDE; the loss term runs on the
-        same fused kernels as training.  ``u``/``eps``/``u_v`` inject the draws of ``ssm`` and ``eps_T`` the noise
-        of ``cond_latent_sample`` (parity tests).  The multiplicative SDE's latent density is a sklearn KDE
-        (SDEs.py:503-509) and stays out of scope."""
-        if self.base_sde.kind != L.SDE_SGM:
-            raise MsgmError("ELBO evaluation of the multiplicative SDE needs its KDE latent density (out of scope)")
+    def elbo_random_t_slice(self, x, u=None, eps=None, u_v=None, eps_T=None, y=None, t_given=None, yT=None):
+        """ELBO slice estimate lp(y_T) - ssm(x) T (SDEs.py:708-721); the loss term runs on the same fused kernels as
+        training.  The latent term is the standard normal's log-density for the additive SDE and the kernel density
+        of the radii for the multiplicative one (``MSGMsde.log_latent_pdf``).  For parity tests ``u``/``eps``/``u_v``
+        inject the draws of ``ssm``, ``y``/``t_given`` are forwarded to it, ``eps_T`` is the noise of the additive
+        SDE's ``cond_latent_sample`` and ``yT`` replaces that draw altogether."""
+        base = self.base_sde
+        if base.kind != L.SDE_SGM:
+            base._kde_check()                          # refuse before any work is queued
         x = x.contiguous().float()
-        qt = 1.0 / self.base_sde.T_float()
+        qt = 1.0 / base.T_float()
         with torch.no_grad():
-            loss_ssm = self.ssm(x, u=u, eps=eps, u_v=u_v).detach() / qt
-            t_ = torch.empty(x.shape[0], 1, device=x.device)
-            yT = self.base_sde.cond_latent_sample(t_, self.base_sde.T_float(), x, eps=eps_T)
-            lp = self.base_sde.log_latent_pdf(yT).view(x.size(0), -1).sum(1)
+            loss_ssm = self.ssm(x, u=u, eps=eps, u_v=u_v, y=y, t_given=t_given).detach() / qt
+            if yT is None:
+                t_ = torch.empty(x.shape[0], 1, device=x.device)
+                yT = (base.cond_latent_sample(t_, base.T_float(), x, eps=eps_T) if base.kind == L.SDE_SGM
+                      else base.cond_latent_sample(t_, base.T_float(), x))
+            lp = base.log_latent_pdf(yT).view(x.size(0), -1).sum(1)
         return lp - loss_ssm
 
 

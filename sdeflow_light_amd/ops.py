@@ -892,6 +892,27 @@ def rbf_kernel(x: torch.Tensor, y: torch.Tensor, want_matrix: bool = False, want
     return Kmat, ssum
 
 
+def kde_logpdf(q: torch.Tensor, r: torch.Tensor, h: float, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Log-density (M,) at the queries q (M,) of the 1-D Gaussian kernel density with bandwidth h fitted on the samples
+    r (Ns,) — sklearn's KernelDensity(bandwidth=h).fit(r).score_samples(q).  ``workspace`` (fp32, at least 2 M elements)
+    replaces the per-device cached one; a small one makes the kernel use fewer, longer sample slabs."""
+    if q.dim() != 1 or r.dim() != 1 or q.numel() == 0 or r.numel() == 0:
+        raise MsgmError("kde_logpdf: non-empty q (M,) and r (Ns,) expected")
+    if q.device != r.device:
+        raise MsgmError("kde_logpdf: q and r must be on the same device")
+    h = float(h)
+    if not (math.isfinite(h) and h > 0.0):
+        raise MsgmError(f"kde_logpdf: the bandwidth must be a finite positive number (got {h})")
+    M, Ns = q.numel(), r.numel()
+    ws = workspace if workspace is not None else scratch(q.device, int(lib().msgm_kde_workspace(M, Ns)), "kde")
+    if ws.device != q.device or ws.numel() < 2 * M:
+        raise MsgmError("kde_logpdf: the workspace must hold at least 2 M floats on the queries' device")
+    out = torch.empty(M, dtype=torch.float32, device=q.device)
+    check(lib().msgm_kde_logpdf(ptr(f32(q, "q")), M, ptr(f32(r, "r")), Ns, h, ptr(out), ptr(f32(ws, "workspace")),
+                                ws.numel() * 4, stream()), "msgm_kde_logpdf")
+    return out
+
+
 def attention_supported(T, C) -> bool:
     return bool(lib().msgm_attention_supported(int(T), int(C)))
 

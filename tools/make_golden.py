@@ -787,6 +787,54 @@ def g20_mlp_wide():
     save("g20_mlp_wide", **out)
 
 
+def g21_kde():
+    """Latent log-density and ELBO of the multiplicative SDE: the sklearn KernelDensity of the radii (SDEs.py:239-265,
+    503-509) on CPU.  Density cases (a) norm_map=None with cst_log_dens estimated, (b) norm_map="log" without (the driver's
+    configuration, MSGM_higherDim.py:57): Ns = 257 rows of d = 4, a query batch of 65 rows of which some are scaled by
+    10 and by 0.01 (far outside the samples).  lp64 is the estimator's own float64 output at the fp32 row norms, before
+    upstream's cast to float32.  ELBO cases shaped like g14: ssm_loss(t, x, y) with the probe forced, yT from
+    cond_latent_sample, elbo = lp - per * T (SDEs.py:708-721)."""
+    torch.manual_seed(21)
+    out = {}
+    for tag, norm_map, estim in (("a", None, True), ("b", "log", False)):
+        y0 = torch.randn(257, 4) * 1.5
+        base = MSGMsde(y0, beta_min=0.1, beta_max=20.0, t_epsilon=1e-3, T=Tparam(), num_steps_forward=4, device="cpu",
+                       estim_cst_norm_dens_r_T=estim, norm_sampler="ecdf", norm_map=norm_map, denseTensor=False,
+                       plot_validate=False)
+        yT = torch.randn(65, 4) * 1.5
+        yT[40:52] *= 10.0
+        yT[52:] *= 0.01
+        r_yT = torch.linalg.norm(yT, dim=1).reshape(-1, 1)
+        out.update({f"{tag}_y0": y0, f"{tag}_r_T": base.r_T, f"{tag}_bandwidth": np.float64(base.kde.bandwidth),
+                    f"{tag}_cst_log_dens": torch.as_tensor(base.cst_log_dens, dtype=torch.float32).reshape(1),
+                    f"{tag}_yT": yT, f"{tag}_lp": base.log_latent_pdf(yT),
+                    f"{tag}_lp64": np.asarray(base.kde.score_samples(r_yT.numpy()), dtype=np.float64)})
+    B = 48
+    for tag, d, dense, pre in (("sp", 6, False, "NormalizeLogRadius"), ("dn", 4, True, None)):
+        net = MLP(d, premodule=pre)
+        y0 = torch.randn(64, d) * 1.5
+        base = msgm(y0, dense=dense, nsf=4)
+        rev = PluginReverseSDE(base, net, Tparam())
+        x = torch.randn(B, d) * 1.5
+        t_ = torch.rand(B, 1).clamp_min(1e-3)
+        y = torch.randn(B, d) * 1.3
+        u_v = torch.rand(B, d)
+        o = torch.rand
+        torch.rand = lambda *a, **k: u_v.clone()
+        try:
+            per = rev.ssm_loss(t_, x, y.clone().requires_grad_(True)).detach()
+        finally:
+            torch.rand = o
+        yT = rev.cond_latent_sample(t_, base.T, x)
+        lp = base.log_latent_pdf(yT).view(B, -1).sum(1)
+        out.update({f"{tag}::" + k: v for k, v in sd_np(rev.state_dict()).items()})
+        out.update({f"{tag}_y0": y0, f"{tag}_x": x, f"{tag}_t": t_, f"{tag}_y": y, f"{tag}_u_v": u_v, f"{tag}_per": per,
+                    f"{tag}_yT": yT, f"{tag}_lp": lp, f"{tag}_elbo": lp - per * rev.T})
+        if dense:
+            out["dn_G"] = base.G
+    save("g21_kde", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
