@@ -18,11 +18,7 @@
 // The kernel body is the single-head one at channel count D; a workgroup serves one (sample, head) pair, reads rows of
 // stride 3C from column 3Dh and writes rows of stride C from column Dh.  MH = false is the single-head build (strides
 // compile-time 3C / C, no head index).
-#include "common.h"
-
-__device__ __forceinline__ f32x4 mfma16a(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
+#include "attention_common.h"
 
 template <int CT, int QT, bool MH = false>   // C = 16*CT channels (per head); QT tiles of 16 queries per wave
 __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv, float* __restrict__ out, int T, int nqb, float scale,
@@ -30,14 +26,13 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv,
   constexpr int C = 16 * CT, KP = C + 4;
   constexpr int NV = (64 * C / 4) / 256;                  // float4 per thread per matrix and key block
   static_assert(NV >= 1 && (64 * C / 4) % 256 == 0, "key block does not divide over the workgroup's threads");
-  const int LD = MH ? 3 * C * nh : 3 * C, LA = MH ? C * nh : C;   // qkv / out row strides
   extern __shared__ __attribute__((aligned(16))) float at_lds[];
   float* Ks = at_lds;
   float* Vs = at_lds + 64 * KP;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const int pr = blockIdx.x / nqb, qb = blockIdx.x - pr * nqb;     // (sample, head) pair, query block of 64*QT
-  const int smp = MH ? pr / nh : pr, hd = MH ? pr - smp * nh : 0;
-  const float* base = qkv + (size_t)smp * T * LD + 3 * C * hd;
+  const AttnHead H = attn_head<MH, C>(pr, nh);
+  const float* base = qkv + (size_t)H.smp * T * H.LD + H.qcol;
   const int q0 = (qb * 4 + w) * 16 * QT;                  // first query of this wave
 
   f32x4 qf[QT][CT], o[QT][CT];
@@ -46,7 +41,7 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv,
   for (int qt = 0; qt < QT; ++qt) {
 #pragma unroll
     for (int g = 0; g < CT; ++g) {
-      qf[qt][g] = *reinterpret_cast<const f32x4*>(base + (size_t)(q0 + 16 * qt + il) * LD + 16 * g + 4 * q);
+      qf[qt][g] = *reinterpret_cast<const f32x4*>(base + (size_t)(q0 + 16 * qt + il) * H.LD + 16 * g + 4 * q);
       o[qt][g] = f32x4{0, 0, 0, 0};
     }
     m[qt] = -INFINITY; l[qt] = 0.f;
@@ -56,8 +51,8 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv,
   auto gload = [&](int kb) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int idx = tid + 256 * i, key = idx / (C / 4), c4 = idx - key * (C / 4);
-      const float* p = base + (size_t)(kb * 64 + key) * LD + 4 * c4;
+      const AttnSlot s = attn_slot<C, 256>(tid, i);
+      const float* p = base + (size_t)(kb * 64 + s.row) * H.LD + 4 * s.c4;
       pk[i] = *reinterpret_cast<const f32x4*>(p + C);
       pv[i] = *reinterpret_cast<const f32x4*>(p + 2 * C);
     }
@@ -68,9 +63,9 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv,
     __syncthreads();                                       // the previous block's readers are done
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int idx = tid + 256 * i, key = idx / (C / 4), c4 = idx - key * (C / 4);
-      *reinterpret_cast<f32x4*>(Ks + key * KP + 4 * c4) = pk[i];
-      *reinterpret_cast<f32x4*>(Vs + key * KP + 4 * c4) = pv[i];
+      const AttnSlot s = attn_slot<C, 256>(tid, i);
+      *reinterpret_cast<f32x4*>(Ks + s.row * KP + 4 * s.c4) = pk[i];
+      *reinterpret_cast<f32x4*>(Vs + s.row * KP + 4 * s.c4) = pv[i];
     }
     __syncthreads();
     if (kb + 1 < nkb) gload(kb + 1);
@@ -87,7 +82,7 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv,
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-          for (int qt = 0; qt < QT; ++qt) s[qt][kt] = mfma16a(a[r], qf[qt][g][r], s[qt][kt]);
+          for (int qt = 0; qt < QT; ++qt) s[qt][kt] = mfma16(a[r], qf[qt][g][r], s[qt][kt]);
       }
     }
     // ---- online softmax: this lane's query, its 16 keys of the block (+ the other three key groups by shuffle)
@@ -98,9 +93,7 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv,
       for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) { s[qt][kt][r] *= scale; mb = fmaxf(mb, s[qt][kt][r]); }
-      mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
-      mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
-      const float mn = fmaxf(m[qt], mb);
+      const float mn = fmaxf(m[qt], quad_max(mb));
       const float alpha = __expf(m[qt] - mn);
       m[qt] = mn;
       float ls = 0.f;
@@ -123,76 +116,69 @@ __global__ void __launch_bounds__(256) k_attn_fwd(const float* __restrict__ qkv,
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-          for (int qt = 0; qt < QT; ++qt) o[qt][ct] = mfma16a(a[r], s[qt][kt][r], o[qt][ct]);
+          for (int qt = 0; qt < QT; ++qt) o[qt][ct] = mfma16(a[r], s[qt][kt][r], o[qt][ct]);
       }
   }
   // ---- normalise and store: lane (query il, q) holds channels 16ct + 4q + r
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    float lt = l[qt];
-    lt += __shfl_xor(lt, 16, 64);
-    lt += __shfl_xor(lt, 32, 64);
-    const float inv = 1.0f / lt;
-    float* orow = out + ((size_t)smp * T + q0 + 16 * qt + il) * LA + C * hd;
+    const float inv = 1.0f / quad_sum(l[qt]);
+    float* orow = out + ((size_t)H.smp * T + q0 + 16 * qt + il) * H.LA + H.acol;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) *reinterpret_cast<f32x4*>(orow + 16 * ct + 4 * q) = o[qt][ct] * inv;
   }
 }
 
-static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
 template <int CT, int QT, bool MH = false>
 static int launch_attn(const float* qkv, float* out, int64_t N, int T, float scale, hipStream_t st, int nh = 1) {
   constexpr int C = 16 * CT;
   constexpr size_t lds = (size_t)2 * 64 * (C + 4) * sizeof(float);
-  static const int once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fwd<CT, QT, MH>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    return 0;
-  }();
-  (void)once;
+  static const int once = attn_allow_lds(&k_attn_fwd<CT, QT, MH>, lds); (void)once;
   const int nqb = T / (64 * QT);
   hipLaunchKernelGGL((k_attn_fwd<CT, QT, MH>), dim3((unsigned)(N * nh * nqb)), dim3(256), lds, st, qkv, out, T, nqb, scale, nh);
   return msgm_check_launch();
 }
 
-template <int CT>
-static int launch_attn_mh(const float* qkv, float* out, int64_t N, int T, int nh, float scale, hipStream_t st) {
-  return T % 128 == 0 ? launch_attn<CT, 2, true>(qkv, out, N, T, scale, st, nh) : launch_attn<CT, 1, true>(qkv, out, N, T, scale, st, nh);
+// D -> <CT, QT>, once: 128 queries per workgroup when T allows — except at D = 128, where the second query tile costs the second
+// resident wave per SIMD (357 registers): 89 vs 102 TFLOP/s at T = 256.  D = 16 is multi-head only.
+template <bool MH>
+static int attn_fwd_go(const float* qkv, float* out, int64_t N, int T, int D, int nh, float scale, hipStream_t st) {
+  const bool two = T % 128 == 0;
+  if constexpr (MH)
+    if (D == 16) return two ? launch_attn<1, 2, MH>(qkv, out, N, T, scale, st, nh) : launch_attn<1, 1, MH>(qkv, out, N, T, scale, st, nh);
+  if (D == 32) return two ? launch_attn<2, 2, MH>(qkv, out, N, T, scale, st, nh) : launch_attn<2, 1, MH>(qkv, out, N, T, scale, st, nh);
+  if (D == 64) return two ? launch_attn<4, 2, MH>(qkv, out, N, T, scale, st, nh) : launch_attn<4, 1, MH>(qkv, out, N, T, scale, st, nh);
+  if (D == 128) return launch_attn<8, 1, MH>(qkv, out, N, T, scale, st, nh);
+  return MSGM_E_UNSUPPORTED;
+}
+
+// the shapes the kernels take: D channels per head (16 only through the multi-head entries), T a multiple of 64
+static bool attn_shape_ok(int32_t T, int32_t heads, int32_t D, bool mh) {
+  return heads >= 1 && heads <= 64 && ((mh && D == 16) || D == 32 || D == 64 || D == 128) && T >= 64 && T % 64 == 0;
+}
+
+// both forward entries; one head runs the single-head instantiations through either (same kernels, same bits; D = 16 has none)
+static int attn_forward(const float* qkv, float* out, int64_t N, int32_t T, int32_t heads, int32_t D, bool mh, float scale,
+                        msgm_stream_t stream) {
+  if (!qkv || !out || N <= 0 || T <= 0 || heads <= 0 || D <= 0) return MSGM_E_BADARG;
+  if (!attn_shape_ok(T, heads, D, mh) || N * heads * (int64_t)(T / 64) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
+  if (!mh || (heads == 1 && attn_shape_ok(T, 1, D, false))) return attn_fwd_go<false>(qkv, out, N, T, D, 1, scale, S(stream));
+  return attn_fwd_go<true>(qkv, out, N, T, D, heads, scale, S(stream));
 }
 
 extern "C" {
 
-int msgm_attention_supported(int32_t T, int32_t C) {
-  return (C == 32 || C == 64 || C == 128) && T >= 64 && T % 64 == 0;
-}
+int msgm_attention_supported(int32_t T, int32_t C) { return attn_shape_ok(T, 1, C, false); }
 
 int msgm_attention_forward(const float* qkv, float* out, int64_t N, int32_t T, int32_t C, float scale, msgm_stream_t stream) {
-  if (!qkv || !out || N <= 0 || T <= 0 || C <= 0) return MSGM_E_BADARG;
-  if (!msgm_attention_supported(T, C) || N * (int64_t)(T / 64) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
-  // 128 queries per workgroup when T allows — except at C = 128, where the second query tile costs the second
-  // resident wave per SIMD (357 registers): 89 vs 102 TFLOP/s at T = 256
-  const bool two = T % 128 == 0;
-  if (C == 32) return two ? launch_attn<2, 2>(qkv, out, N, T, scale, S(stream)) : launch_attn<2, 1>(qkv, out, N, T, scale, S(stream));
-  if (C == 64) return two ? launch_attn<4, 2>(qkv, out, N, T, scale, S(stream)) : launch_attn<4, 1>(qkv, out, N, T, scale, S(stream));
-  return launch_attn<8, 1>(qkv, out, N, T, scale, S(stream));
+  return attn_forward(qkv, out, N, T, 1, C, false, scale, stream);
 }
 
-int msgm_attention_mh_supported(int32_t T, int32_t heads, int32_t D) {
-  return heads >= 1 && heads <= 64 && (D == 16 || D == 32 || D == 64 || D == 128) && T >= 64 && T % 64 == 0;
-}
+int msgm_attention_mh_supported(int32_t T, int32_t heads, int32_t D) { return attn_shape_ok(T, heads, D, true); }
 
 int msgm_attention_mh_forward(const float* qkv, float* out, int64_t N, int32_t T, int32_t heads, int32_t D, float scale,
                               msgm_stream_t stream) {
-  if (!qkv || !out || N <= 0 || T <= 0 || heads <= 0 || D <= 0) return MSGM_E_BADARG;
-  if (!msgm_attention_mh_supported(T, heads, D) || N * heads * (int64_t)(T / 64) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
-  // one head: the single-head entry (the same kernels, so the same bits)
-  if (heads == 1 && msgm_attention_supported(T, D)) return msgm_attention_forward(qkv, out, N, T, D, scale, stream);
-  // 128 queries per workgroup when T allows, except at D = 128 (the register argument of msgm_attention_forward)
-  if (D == 16) return launch_attn_mh<1>(qkv, out, N, T, heads, scale, S(stream));
-  if (D == 32) return launch_attn_mh<2>(qkv, out, N, T, heads, scale, S(stream));
-  if (D == 64) return launch_attn_mh<4>(qkv, out, N, T, heads, scale, S(stream));
-  return launch_attn<8, 1, true>(qkv, out, N, T, scale, S(stream), heads);
+  return attn_forward(qkv, out, N, T, heads, D, true, scale, stream);
 }
 
 }  // extern "C"

@@ -32,13 +32,13 @@
 // channel count D, run over (sample, head) PAIRS pr = sample*H + h: rows of stride 3C / C from column 3Dh / Dh, the row
 // scalars (lse, rbar, c, delta) and the query-gradient slabs indexed by pair instead of sample.  MH = false is the
 // single-head build: compile-time strides, no head index, the code the single-head entries always ran.
-#include "common.h"
+#include "attention_common.h"
 
-__device__ __forceinline__ f32x4 mfma16t(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
+// Head addressing is attention_common.h's (attn_head, attn_mh_row).  k_attn_dual_fwd / k_attn_dual_bwd keep their OWN lines for
+// the staging-slot decode (the sampler's attn_slot), the shuffle pairs (quad_max / quad_sum) and the XCD-aware decode: each
+// was timed alone against the parent (profiles/unet_shared/bench_train_attn_phases.txt), all outputs bit-identical, no scratch:
+// attn_slot: k_attn_dual_bwd<2,4,*,true> +0.59 % (parent vs parent 0.22 %); quad_*: k_attn_dual_fwd<8,1,16,4> +0.52 % (0.31 %),
+// 156 -> 160 VGPRs in <2,1,64,4>; a shared decode: +0.18 % / +0.16 % on two rows (0.11 % / 0.08 %).  The decode is there twice.
 // =============================================================================================== forward
 // Transposed formulation (as the sampler kernel): S^T[key][query] = K Q^T, O^T[c][query] += V^T P^T, so a lane owns ONE
 // query (lane&15): running max / sums are per-lane scalars, and e^{S-m} in the C/D layout IS the B operand of the
@@ -48,7 +48,6 @@ __global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restri
                                                         float* __restrict__ lse, float* __restrict__ rbar, int T, int nqb,  // per LDS
                                                         int64_t Bp, float scale, int nh) {                                  // block; NW waves
   constexpr int C = 16 * CT, KP = C + 4, KT = KB / 16, NT = 64 * NW;
-  const int LD = MH ? 3 * C * nh : 3 * C, LA = MH ? C * nh : C;   // qkv / att row strides
   constexpr int NV = (KB * C / 4) / NT;                   // float4 per thread per matrix and key block
   static_assert(NV >= 1 && (KB * C / 4) % NT == 0, "key block does not divide over the workgroup's threads");
   extern __shared__ __attribute__((aligned(16))) float atd_lds[];
@@ -67,8 +66,9 @@ __global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restri
     if (b < full) { const int loc = b >> 3; pr = (loc / nqb) * 8 + (b & 7); qb = loc % nqb; }
     else { const int r = b - full; pr = (int)(NP / 8) * 8 + r / nqb; qb = r % nqb; }
   }
-  const int smp = MH ? pr / nh : pr, hd = MH ? pr - smp * nh : 0;
-  const float* bp = qkv + (size_t)smp * T * LD + 3 * C * hd;   // primal rows of this sample, this head's columns
+  const AttnHead H = attn_head<MH, C>(pr, nh);
+  const int LD = H.LD, LA = H.LA, smp = H.smp;
+  const float* bp = qkv + (size_t)smp * T * LD + H.qcol;   // primal rows of this sample, this head's columns
   const float* bt = bp + (size_t)Bp * T * LD;              // tangent rows
   const int q0 = (qb * NW + w) * 16 * QT;                  // first query of this wave
 
@@ -128,9 +128,9 @@ __global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restri
         for (int r = 0; r < 4; ++r)
 #pragma unroll
           for (int qt = 0; qt < QT; ++qt) {
-            s[qt][kt] = mfma16t(a[r], qf[qt][g][r], s[qt][kt]);
-            sd[qt][kt] = mfma16t(a[r], qd[qt][g][r], sd[qt][kt]);
-            sd[qt][kt] = mfma16t(ad[r], qf[qt][g][r], sd[qt][kt]);
+            s[qt][kt] = mfma16(a[r], qf[qt][g][r], s[qt][kt]);
+            sd[qt][kt] = mfma16(a[r], qd[qt][g][r], sd[qt][kt]);
+            sd[qt][kt] = mfma16(ad[r], qf[qt][g][r], sd[qt][kt]);
           }
       }
     }
@@ -177,9 +177,9 @@ __global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restri
         for (int r = 0; r < 4; ++r)
 #pragma unroll
           for (int qt = 0; qt < QT; ++qt) {
-            o[qt][ct] = mfma16t(a[r], s[qt][kt][r], o[qt][ct]);
-            od[qt][ct] = mfma16t(a[r], sd[qt][kt][r], od[qt][ct]);
-            od[qt][ct] = mfma16t(ad[r], s[qt][kt][r], od[qt][ct]);
+            o[qt][ct] = mfma16(a[r], s[qt][kt][r], o[qt][ct]);
+            od[qt][ct] = mfma16(a[r], sd[qt][kt][r], od[qt][ct]);
+            od[qt][ct] = mfma16(ad[r], s[qt][kt][r], od[qt][ct]);
           }
       }
   }
@@ -191,8 +191,8 @@ __global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restri
     rt += __shfl_xor(rt, 16, 64); rt += __shfl_xor(rt, 32, 64);
     const float inv = 1.0f / lt, rb = rt * inv;
     const size_t row = (size_t)smp * T + q0 + 16 * qt + il;
-    float* orow = att + row * LA + C * hd;
-    float* drow = att + ((size_t)Bp * T + row) * LA + C * hd;
+    float* orow = att + row * LA + H.acol;
+    float* drow = att + ((size_t)Bp * T + row) * LA + H.acol;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       const f32x4 ov = o[qt][ct] * inv;
@@ -217,11 +217,7 @@ __global__ void __launch_bounds__(256) k_attn_dual_delta(const float* __restrict
   const int sl = threadIdx.x & 15;
   float c = 0.f, d = 0.f;
   if (row < rows) {
-    size_t off = (size_t)row * C;
-    if (MH) {
-      const int64_t pr = row / T, t = row - pr * T, smp = pr / nh, hd = pr - smp * nh;
-      off = ((size_t)smp * T + t) * C * nh + (size_t)C * hd;
-    }
+    const size_t off = MH ? attn_mh_row(row / T, row % T, T, C, nh) : (size_t)row * C;
     const float* o = att + off;                            // the tangent half starts rows*C floats later in both layouts
     const float* g = datt + off;
     const float* od = att + (size_t)rows * C + off;
@@ -267,7 +263,6 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
   constexpr int NQ = (QB * C / 4 + NT - 1) / NT;          // float4 per thread per streamed matrix and query block
   constexpr bool QFULL = (QB * C / 4) % NT == 0;          // C <= 32: only a half / quarter of the threads stage a float4
   static_assert(NK >= 1 && NQ >= 1 && (KFULL || NK == 1) && (QFULL || NQ == 1), "tiles do not divide over the workgroup");
-  const int LD = MH ? 3 * C * nh : 3 * C, LA = MH ? C * nh : C;   // qkv / att row strides
   const int64_t NP = MH ? Bp * nh : Bp;                   // (sample, head) pairs
   extern __shared__ __attribute__((aligned(16))) float atb_lds[];
   float* Ks = atb_lds;                                    // [KB][KP] x4, resident
@@ -289,11 +284,12 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
     if (b < full) { const int loc = b >> 3; pr = (loc / nkg) * 8 + (b & 7); kgi = loc % nkg; }
     else { const int r = b - full; pr = (int)(NP / 8) * 8 + r / nkg; kgi = r % nkg; }
   }
-  const int smp = MH ? pr / nh : pr, hd = MH ? pr - smp * nh : 0;
+  const AttnHead H = attn_head<MH, C>(pr, nh);
+  const int LD = H.LD, LA = H.LA, smp = H.smp;
   const int kb = kgi * kseq + ks;
   const size_t half_qkv = (size_t)Bp * T * LD, half_att = (size_t)Bp * T * LA;
-  const float* bp = qkv + (size_t)smp * T * LD + 3 * C * hd;
-  const float* gp = datt + (size_t)smp * T * LA + C * hd;
+  const float* bp = qkv + (size_t)smp * T * LD + H.qcol;
+  const float* gp = datt + (size_t)smp * T * LA + H.acol;
   const size_t srow0 = (size_t)pr * T;                     // row scalars and slabs: per pair
 
   // ---- resident K, Kd, V, Vd tiles of this key block
@@ -362,12 +358,12 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
       const f32x4 bV = *reinterpret_cast<const f32x4*>(Vs + bo), bVd = *reinterpret_cast<const f32x4*>(Vd + bo);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        s = mfma16t(aQ[r], bK[r], s);
-        sd = mfma16t(aQd[r], bK[r], sd);
-        pb = mfma16t(aG[r], bV[r], pb);
-        dd = mfma16t(aGd[r], bV[r], dd);
-        sd = mfma16t(aQ[r], bKd[r], sd);
-        pb = mfma16t(aGd[r], bVd[r], pb);
+        s = mfma16(aQ[r], bK[r], s);
+        sd = mfma16(aQd[r], bK[r], sd);
+        pb = mfma16(aG[r], bV[r], pb);
+        dd = mfma16(aGd[r], bV[r], dd);
+        sd = mfma16(aQ[r], bKd[r], sd);
+        pb = mfma16(aGd[r], bVd[r], pb);
       }
       __builtin_amdgcn_sched_barrier(0);                   // keep one channel group of fragments in flight, not all
     }
@@ -399,12 +395,12 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        dv[ct] = mfma16t(aG[r], p[r], dv[ct]);
-        dvd[ct] = mfma16t(aGd[r], p[r], dvd[ct]);
-        dk[ct] = mfma16t(aQ[r], ds[r], dk[ct]);
-        dkd[ct] = mfma16t(aQ[r], dsd[r], dkd[ct]);
-        dv[ct] = mfma16t(aGd[r], pd[r], dv[ct]);
-        dk[ct] = mfma16t(aQd[r], dsd[r], dk[ct]);
+        dv[ct] = mfma16(aG[r], p[r], dv[ct]);
+        dvd[ct] = mfma16(aGd[r], p[r], dvd[ct]);
+        dk[ct] = mfma16(aQ[r], ds[r], dk[ct]);
+        dkd[ct] = mfma16(aQ[r], dsd[r], dkd[ct]);
+        dv[ct] = mfma16(aGd[r], pd[r], dv[ct]);
+        dk[ct] = mfma16(aQd[r], dsd[r], dk[ct]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -432,18 +428,14 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          dq = mfma16t(a1[r], b1[r], dq);
-          dqd = mfma16t(a1[r], b2[r], dqd);
-          dq = mfma16t(a2[r], b2[r], dq);
+          dq = mfma16(a1[r], b1[r], dq);
+          dqd = mfma16(a1[r], b2[r], dqd);
+          dq = mfma16(a2[r], b2[r], dq);
         }
       }
-#ifdef ATT_EXP_NODQ           // diagnostic (WRONG results): what the query-gradient slab stores cost inside the loop
-      if (dq[0] == 12345.678f) { *reinterpret_cast<f32x4*>(sp) = dq; *reinterpret_cast<f32x4*>(sdp) = dqd; }
-#else
       if (ACC) { dq += pdq; dqd += pdqd; }
       *reinterpret_cast<f32x4*>(sp) = dq;
       *reinterpret_cast<f32x4*>(sdp) = dqd;
-#endif
     }
   }
   // ---- the two query halves of each key group meet through LDS; scaled key / value gradients leave the chip
@@ -459,8 +451,8 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
   __syncthreads();
   if (qs == 0) {
     const size_t row = (size_t)smp * T + kb * KB + 16 * kg + il;     // key of this lane
-    float* kp_ = dqkv + row * LD + 3 * C * hd;
-    float* kt_ = dqkv + half_qkv + row * LD + 3 * C * hd;
+    float* kp_ = dqkv + row * LD + H.qcol;
+    float* kt_ = dqkv + half_qkv + row * LD + H.qcol;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       const f32x4* base = reinterpret_cast<const f32x4*>(scratch) + ((size_t)kg * 4 * CT + 4 * ct) * 64 + lane;
@@ -485,12 +477,7 @@ __global__ void __launch_bounds__(256) k_attn_dq_reduce(const float* __restrict_
     const float* p = slab + ((size_t)n * nkb * T + qr) * C + 4 * c4;
     f32x4 acc = *reinterpret_cast<const f32x4*>(p);
     for (int kb = 1; kb < nkb; ++kb) acc += *reinterpret_cast<const f32x4*>(p + (size_t)kb * T * C);
-    if (MH) {
-      const int64_t nb = n / nh, hd = n - nb * nh;
-      *reinterpret_cast<f32x4*>(dqkv + ((size_t)nb * T + qr) * 3 * C * nh + 3 * C * hd + 4 * c4) = acc * scale;
-    } else {
-      *reinterpret_cast<f32x4*>(dqkv + (size_t)row * 3 * C + 4 * c4) = acc * scale;
-    }
+    *reinterpret_cast<f32x4*>(dqkv + (MH ? attn_mh_row(n, qr, T, 3 * C, nh) : (size_t)row * 3 * C) + 4 * c4) = acc * scale;
   }
 }
 
@@ -499,12 +486,7 @@ template <int CT, int QT, int KB, int NW, bool MH = false>
 static int launch_fwd(const float* qkv, float* att, float* stats, int64_t Bp, int T, float scale, hipStream_t st, int nh = 1) {
   constexpr int C = 16 * CT;
   constexpr size_t lds = (size_t)4 * KB * (C + 4) * sizeof(float);
-  static const int once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dual_fwd<CT, QT, KB, NW, MH>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return 0;
-  }();
-  (void)once;
+  static const int once = attn_allow_lds(&k_attn_dual_fwd<CT, QT, KB, NW, MH>, lds); (void)once;
   const int nqb = T / (16 * NW * QT);
   const int64_t NP = Bp * nh;
   hipLaunchKernelGGL((k_attn_dual_fwd<CT, QT, KB, NW, MH>), dim3((unsigned)(NP * nqb)), dim3(64 * NW), lds, st, qkv, att, stats,
@@ -523,13 +505,7 @@ static int launch_bwd(const float* qkv, const float* att, const float* datt, con
   constexpr size_t lds_epi = (size_t)KG * 4 * CT * 64 * 4 * sizeof(float);        // the cross-wave sum of the key-side gradients
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   static_assert(lds <= 160 * 1024, "backward tiles exceed the CU's LDS");
-  static const int once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dual_bwd<CT, KG, false, MH>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dual_bwd<CT, KG, true, MH>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return 0;
-  }();
+  static const int once = attn_allow_lds(&k_attn_dual_bwd<CT, KG, false, MH>, lds) | attn_allow_lds(&k_attn_dual_bwd<CT, KG, true, MH>, lds);
   (void)once;
   const int64_t NP = Bp * nh;                             // (sample, head) pairs: the backward's "samples"
   const int64_t rows = NP * T;
@@ -558,88 +534,95 @@ static int launch_bwd(const float* qkv, const float* att, const float* datt, con
   return msgm_check_launch();
 }
 
+// ---- what the single-head and the multi-head entries share (D = C / heads channels per head)
+// shapes: D in {32, 64}: T a multiple of 64; D = 128 (the 16x16 / 8x8 attention of the 2-D U-Net): T a multiple of 32; D = 16
+// only through the multi-head entries (mh)
+static bool attn_dual_ok(int32_t T, int32_t heads, int32_t D, bool mh) {
+  if (heads < 1 || heads > 64) return false;
+  if (D == 128) return T >= 32 && T % 32 == 0;
+  return ((mh && D == 16) || D == 32 || D == 64) && T >= 64 && T % 64 == 0;
+}
+
+// backward workspace: row scalars c | delta and the query-gradient slabs, per (sample, head) pair
+static size_t attn_dual_ws(int64_t Bp, int32_t T, int32_t heads, int32_t D, bool mh) {
+  if (!attn_dual_ok(T, heads, D, mh) || Bp <= 0) return 0;
+  const size_t np = (size_t)Bp * heads;
+  return ((size_t)2 * np * T + (size_t)2 * np * (T / attn_bwd_keys(D)) * T * D) * sizeof(float);
+}
+
+// D -> <CT, QT, KB, NW>, once.  D = 128: 64-query workgroups (4 waves) while they fill the chip twice over, else 32-query
+// workgroups (2 waves): at the 32-row shard the T = 256 blocks are only 128 workgroups of 64 queries
+template <bool MH>
+static int attn_dual_fwd_go(const float* qkv, float* att, float* stats, int64_t Bp, int T, int D, int nh, float scale, hipStream_t st) {
+  if (D == 128) {
+    if (T % 64 == 0 && Bp * nh * (int64_t)(T / 64) >= 512) return launch_fwd<8, 1, 16, 4, MH>(qkv, att, stats, Bp, T, scale, st, nh);
+    return launch_fwd<8, 1, 16, 2, MH>(qkv, att, stats, Bp, T, scale, st, nh);
+  }
+  if (D == 64) return launch_fwd<4, 1, 32, 4, MH>(qkv, att, stats, Bp, T, scale, st, nh);
+  if (D == 32) return launch_fwd<2, 1, 64, 4, MH>(qkv, att, stats, Bp, T, scale, st, nh);
+  if constexpr (MH) return launch_fwd<1, 1, 64, 4, MH>(qkv, att, stats, Bp, T, scale, st, nh);
+  return MSGM_E_UNSUPPORTED;
+}
+
+// D -> <CT, KG>, once
+template <bool MH>
+static int attn_dual_bwd_go(const float* qkv, const float* att, const float* datt, const float* stats, float* dqkv, int64_t Bp, int T,
+                            int D, int nh, float scale, float* ws, hipStream_t st) {
+  if (D == 128) return launch_bwd<8, 2, MH>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, st, nh);
+  if (D == 64) return launch_bwd<4, 4, MH>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, st, nh);
+  if (D == 32) return launch_bwd<2, 4, MH>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, st, nh);
+  if constexpr (MH) return launch_bwd<1, 4, MH>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, st, nh);
+  return MSGM_E_UNSUPPORTED;
+}
+
+// both entries of each direction; one head runs the single-head instantiations through either (same bits; D = 16 has none)
+static int attn_dual_forward(const float* qkv, float* att, float* stats, int64_t Bp, int32_t T, int32_t heads, int32_t D, bool mh,
+                             float scale, msgm_stream_t stream) {
+  if (!qkv || !att || !stats || Bp <= 0 || T <= 0 || heads <= 0 || D <= 0) return MSGM_E_BADARG;
+  if (!attn_dual_ok(T, heads, D, mh) || Bp * heads * (int64_t)(T / 32) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
+  if (!mh || (heads == 1 && attn_dual_ok(T, 1, D, false))) return attn_dual_fwd_go<false>(qkv, att, stats, Bp, T, D, 1, scale, S(stream));
+  return attn_dual_fwd_go<true>(qkv, att, stats, Bp, T, D, heads, scale, S(stream));
+}
+
+static int attn_dual_backward(const float* qkv, const float* att, const float* datt, const float* stats, float* dqkv, int64_t Bp,
+                              int32_t T, int32_t heads, int32_t D, bool mh, float scale, void* workspace, size_t workspace_bytes,
+                              msgm_stream_t stream) {
+  if (!qkv || !att || !datt || !stats || !dqkv || !workspace || Bp <= 0 || T <= 0 || heads <= 0 || D <= 0) return MSGM_E_BADARG;
+  if (!attn_dual_ok(T, heads, D, mh) || Bp * heads * (int64_t)(T / 32) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
+  if (workspace_bytes < attn_dual_ws(Bp, T, heads, D, mh)) return MSGM_E_WORKSPACE;
+  float* ws = static_cast<float*>(workspace);
+  if (!mh || (heads == 1 && attn_dual_ok(T, 1, D, false))) return attn_dual_bwd_go<false>(qkv, att, datt, stats, dqkv, Bp, T, D, 1, scale, ws, S(stream));
+  return attn_dual_bwd_go<true>(qkv, att, datt, stats, dqkv, Bp, T, D, heads, scale, ws, S(stream));
+}
+
 extern "C" {
 
-// C in {32, 64}: T a multiple of 64; C = 128 (the 16x16 / 8x8 attention of the 2-D U-Net): T a multiple of 32
-int msgm_attention_dual_supported(int32_t T, int32_t C) {
-  if (C == 128) return T >= 32 && T % 32 == 0;
-  return (C == 32 || C == 64) && T >= 64 && T % 64 == 0;
-}
+int msgm_attention_dual_supported(int32_t T, int32_t C) { return attn_dual_ok(T, 1, C, false); }
+int msgm_attention_dual_mh_supported(int32_t T, int32_t heads, int32_t D) { return attn_dual_ok(T, heads, D, true); }
 
-size_t msgm_attention_dual_workspace(int64_t Bp, int32_t T, int32_t C) {
-  if (!msgm_attention_dual_supported(T, C) || Bp <= 0) return 0;
-  return ((size_t)2 * Bp * T + (size_t)2 * Bp * (T / attn_bwd_keys(C)) * T * C) * sizeof(float);
-}
+size_t msgm_attention_dual_workspace(int64_t Bp, int32_t T, int32_t C) { return attn_dual_ws(Bp, T, 1, C, false); }
+size_t msgm_attention_dual_mh_workspace(int64_t Bp, int32_t T, int32_t heads, int32_t D) { return attn_dual_ws(Bp, T, heads, D, true); }
 
 int msgm_attention_dual_forward(const float* qkv, float* att, float* stats, int64_t Bp, int32_t T, int32_t C, float scale,
                                 msgm_stream_t stream) {
-  if (!qkv || !att || !stats || Bp <= 0 || T <= 0 || C <= 0) return MSGM_E_BADARG;
-  if (!msgm_attention_dual_supported(T, C) || Bp * (int64_t)(T / 32) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
-  if (C == 128) {
-    // 64-query workgroups (4 waves) while they fill the chip twice over, else 32-query workgroups (2 waves): at the 32-row
-    // shard the T = 256 blocks are only 128 workgroups of 64 queries
-    if (T % 64 == 0 && Bp * (int64_t)(T / 64) >= 512) return launch_fwd<8, 1, 16, 4>(qkv, att, stats, Bp, T, scale, S(stream));
-    return launch_fwd<8, 1, 16, 2>(qkv, att, stats, Bp, T, scale, S(stream));
-  }
-  if (C == 32) return launch_fwd<2, 1, 64, 4>(qkv, att, stats, Bp, T, scale, S(stream));
-  return launch_fwd<4, 1, 32, 4>(qkv, att, stats, Bp, T, scale, S(stream));
+  return attn_dual_forward(qkv, att, stats, Bp, T, 1, C, false, scale, stream);
+}
+
+int msgm_attention_dual_mh_forward(const float* qkv, float* att, float* stats, int64_t Bp, int32_t T, int32_t heads, int32_t D,
+                                   float scale, msgm_stream_t stream) {
+  return attn_dual_forward(qkv, att, stats, Bp, T, heads, D, true, scale, stream);
 }
 
 int msgm_attention_dual_backward(const float* qkv, const float* att, const float* datt, const float* stats, float* dqkv,
                                  int64_t Bp, int32_t T, int32_t C, float scale, void* workspace, size_t workspace_bytes,
                                  msgm_stream_t stream) {
-  if (!qkv || !att || !datt || !stats || !dqkv || !workspace || Bp <= 0 || T <= 0 || C <= 0) return MSGM_E_BADARG;
-  if (!msgm_attention_dual_supported(T, C) || Bp * (int64_t)(T / 32) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
-  if (workspace_bytes < msgm_attention_dual_workspace(Bp, T, C)) return MSGM_E_WORKSPACE;
-  float* ws = static_cast<float*>(workspace);
-  if (C == 128) return launch_bwd<8, 2>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream));
-  if (C == 32) return launch_bwd<2, 4>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream));
-  return launch_bwd<4, 4>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream));
-}
-
-// ---- multi-head: D = C / heads channels per head, D in {16, 32, 64, 128}; the T rules of the single-head entries at C = D
-int msgm_attention_dual_mh_supported(int32_t T, int32_t heads, int32_t D) {
-  if (heads < 1 || heads > 64) return 0;
-  if (D == 128) return T >= 32 && T % 32 == 0;
-  return (D == 16 || D == 32 || D == 64) && T >= 64 && T % 64 == 0;
-}
-
-size_t msgm_attention_dual_mh_workspace(int64_t Bp, int32_t T, int32_t heads, int32_t D) {
-  if (!msgm_attention_dual_mh_supported(T, heads, D) || Bp <= 0) return 0;
-  if (heads == 1 && msgm_attention_dual_supported(T, D)) return msgm_attention_dual_workspace(Bp, T, D);
-  const size_t np = (size_t)Bp * heads;                    // row scalars c | delta and the slabs, per (sample, head) pair
-  return ((size_t)2 * np * T + (size_t)2 * np * (T / attn_bwd_keys(D)) * T * D) * sizeof(float);
-}
-
-int msgm_attention_dual_mh_forward(const float* qkv, float* att, float* stats, int64_t Bp, int32_t T, int32_t heads, int32_t D,
-                                   float scale, msgm_stream_t stream) {
-  if (!qkv || !att || !stats || Bp <= 0 || T <= 0 || heads <= 0 || D <= 0) return MSGM_E_BADARG;
-  if (!msgm_attention_dual_mh_supported(T, heads, D) || Bp * heads * (int64_t)(T / 32) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
-  if (heads == 1 && msgm_attention_dual_supported(T, D))   // one head: the single-head entry (same kernels, same bits)
-    return msgm_attention_dual_forward(qkv, att, stats, Bp, T, D, scale, stream);
-  const int64_t np = Bp * heads;
-  if (D == 128) {
-    if (T % 64 == 0 && np * (int64_t)(T / 64) >= 512) return launch_fwd<8, 1, 16, 4, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
-    return launch_fwd<8, 1, 16, 2, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
-  }
-  if (D == 64) return launch_fwd<4, 1, 32, 4, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
-  if (D == 32) return launch_fwd<2, 1, 64, 4, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
-  return launch_fwd<1, 1, 64, 4, true>(qkv, att, stats, Bp, T, scale, S(stream), heads);
+  return attn_dual_backward(qkv, att, datt, stats, dqkv, Bp, T, 1, C, false, scale, workspace, workspace_bytes, stream);
 }
 
 int msgm_attention_dual_mh_backward(const float* qkv, const float* att, const float* datt, const float* stats, float* dqkv,
                                     int64_t Bp, int32_t T, int32_t heads, int32_t D, float scale, void* workspace,
                                     size_t workspace_bytes, msgm_stream_t stream) {
-  if (!qkv || !att || !datt || !stats || !dqkv || !workspace || Bp <= 0 || T <= 0 || heads <= 0 || D <= 0) return MSGM_E_BADARG;
-  if (!msgm_attention_dual_mh_supported(T, heads, D) || Bp * heads * (int64_t)(T / 32) > 0x7fffffffLL) return MSGM_E_UNSUPPORTED;
-  if (workspace_bytes < msgm_attention_dual_mh_workspace(Bp, T, heads, D)) return MSGM_E_WORKSPACE;
-  if (heads == 1 && msgm_attention_dual_supported(T, D))
-    return msgm_attention_dual_backward(qkv, att, datt, stats, dqkv, Bp, T, D, scale, workspace, workspace_bytes, stream);
-  float* ws = static_cast<float*>(workspace);
-  if (D == 128) return launch_bwd<8, 2, true>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream), heads);
-  if (D == 64) return launch_bwd<4, 4, true>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream), heads);
-  if (D == 32) return launch_bwd<2, 4, true>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream), heads);
-  return launch_bwd<1, 4, true>(qkv, att, datt, stats, dqkv, Bp, T, scale, ws, S(stream), heads);
+  return attn_dual_backward(qkv, att, datt, stats, dqkv, Bp, T, heads, D, true, scale, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

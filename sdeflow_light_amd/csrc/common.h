@@ -12,6 +12,20 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 static inline int msgm_check_launch() {
   return hipGetLastError() == hipSuccess ? MSGM_OK : MSGM_E_LAUNCH;
 }
+static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// One step of v_mfma_f32_16x16x4_f32 (exact fp32): c += a (16 x 4, one value per lane) . b (4 x 16).
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+// SiLU and its first two derivatives at z (hardware exp / rcp, as every SiLU of the U-Nets)
+__device__ __forceinline__ void silu012(float z, float& s0, float& s1, float& s2) {
+  const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
+  const float om = 1.0f - sg;
+  s0 = z * sg;
+  s1 = sg * (1.0f + z * om);
+  s2 = sg * om * (2.0f + z * (1.0f - 2.0f * sg));
+}
 
 // Zero-fill as a KERNEL node.  hipMemsetAsync must not be used on this path: inside a captured hipGraph (ROCm 7.2,
 // gfx950) a memset node was observed to lose its ordering against the kernel nodes around it when the replay starts

@@ -24,10 +24,6 @@
 
 #define CONV_MAX_SRC 2
 
-__device__ __forceinline__ f32x4 mfma16c(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 struct ConvGeom {
   int N, Hi, Wi, Ho, Wo;      // Hi/Wi: stored input size (before the optional 2x upsample)
   int KH, KW, strideH, padH, strideW, padW;
@@ -210,7 +206,7 @@ __global__ void __launch_bounds__(256) k_conv_gemm(ConvArgs A) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma16c(fa[mt][r], fb[nt][r], acc[mt][nt]);
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma16(fa[mt][r], fb[nt][r], acc[mt][nt]);
   };
 
   f32x4 a0[MT], b0[NT], a1[MT], b1[NT], a2[MT], b2[NT];
@@ -615,7 +611,7 @@ __global__ void __launch_bounds__(256, 1) k_conv_tile(ConvArgs A, int flip, int 
 #pragma unroll
         for (int c = 0; c < NCO; ++c)
 #pragma unroll
-          for (int pt = 0; pt < PT; ++pt) acc[c][pt] = mfma16c(a[c][r], b[pt][r], acc[c][pt]);
+          for (int pt = 0; pt < PT; ++pt) acc[c][pt] = mfma16(a[c][r], b[pt][r], acc[c][pt]);
       tap = ntap; grp = ngr;
     }
 
@@ -750,7 +746,7 @@ __global__ void __launch_bounds__(256, 3) k_dgrad_s2(ConvArgs A, int tiles_x, in
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-              for (int pt = 0; pt < 2; ++pt) acc[cls][c][pt] = mfma16c(a[c][r], b[pt][r], acc[cls][c][pt]);
+              for (int pt = 0; pt < 2; ++pt) acc[cls][c][pt] = mfma16(a[c][r], b[pt][r], acc[cls][c][pt]);
         }
       }
     }
@@ -898,7 +894,7 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs A, int P /* pixels per
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int pt = 0; pt < PT; ++pt) acc[pt] = mfma16c(a[r], b[pt][g][r], acc[pt]);
+        for (int pt = 0; pt < PT; ++pt) acc[pt] = mfma16(a[r], b[pt][g][r], acc[pt]);
     }
     // ---- epilogue of this tile: lane (pixel il of tile pt, channels 16ct + 4q .. +3).
     // Output stores go out as FULL 128-byte lines: two consecutive channel tiles (32 channels = 128 bytes per pixel) meet in
@@ -1186,8 +1182,8 @@ __device__ __forceinline__ void wino_mfma_lds(f32x4 (&acc)[16][2], const f32x4 (
     const f32x4 b = d[pos >> 2][pos & 3];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      acc[pos][0] = mfma16c(x0[r], b[r], acc[pos][0]);
-      acc[pos][1] = mfma16c(x1[r], b[r], acc[pos][1]);
+      acc[pos][0] = mfma16(x0[r], b[r], acc[pos][0]);
+      acc[pos][1] = mfma16(x1[r], b[r], acc[pos][1]);
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -1372,7 +1368,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, i
 #pragma unroll
           for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int c = 0; c < NCO; ++c) acc[pos][c] = mfma16c(a[c][r], b[r], acc[pos][c]);
+            for (int c = 0; c < NCO; ++c) acc[pos][c] = mfma16(a[c][r], b[r], acc[pos][c]);
           __builtin_amdgcn_sched_barrier(0);          // one position's weight fragments in flight, not all sixteen
         }
       }
@@ -1598,8 +1594,8 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
         const f32x4 b = d[pos >> 2][pos & 3];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          acc[pos][0] = mfma16c(x0_[r], b[r], acc[pos][0]);
-          acc[pos][1] = mfma16c(x1_[r], b[r], acc[pos][1]);
+          acc[pos][0] = mfma16(x0_[r], b[r], acc[pos][0]);
+          acc[pos][1] = mfma16(x1_[r], b[r], acc[pos][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1838,7 +1834,7 @@ __global__ void __launch_bounds__(256) k_conv_wgrad(WgradArgs A) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-      for (int kt = 0; kt < KT; ++kt) acc[mt][kt] = mfma16c(a[mt], b[kt], acc[mt][kt]);
+      for (int kt = 0; kt < KT; ++kt) acc[mt][kt] = mfma16(a[mt], b[kt], acc[mt][kt]);
     m += 16; ow += 16;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) gyp[mt] += gy_step;
@@ -1968,8 +1964,8 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_tile(WgradArgs A, int tiles_x,
         for (int r = 0; r < 4; ++r)
 #pragma unroll
           for (int m = 0; m < 2; ++m) {
-            acc[t][m][0] = mfma16c(a[m][r], b[0][r], acc[t][m][0]);
-            acc[t][m][1] = mfma16c(a[m][r], b[1][r], acc[t][m][1]);
+            acc[t][m][0] = mfma16(a[m][r], b[0][r], acc[t][m][0]);
+            acc[t][m][1] = mfma16(a[m][r], b[1][r], acc[t][m][1]);
           }
       }
     }
@@ -2103,7 +2099,7 @@ __global__ void __launch_bounds__(256, 3) k_wgrad_tile9(WgradArgs A, int tiles_x
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-          for (int kw = 0; kw < 3; ++kw) acc[kh * 3 + kw] = mfma16c(a[r], v[kw + r], acc[kh * 3 + kw]);
+          for (int kw = 0; kw < 3; ++kw) acc[kh * 3 + kw] = mfma16(a[r], v[kw + r], acc[kh * 3 + kw]);
       }
     }
     __syncthreads();                                        // every wave is done reading the buffer
@@ -2300,7 +2296,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_wino(WgradArgs A, int tiles_x,
     for (int s = 0; s < 8; ++s) {
       if (s < 7) operands(s + 1, U[(s + 1) & 1], V[(s + 1) & 1]);   // among the MFMAs below (see WW_SCHED)
 #pragma unroll
-      for (int x = 0; x < 16; ++x) acc[x] = mfma16c(U[s & 1][x], V[s & 1][x], acc[x]);
+      for (int x = 0; x < 16; ++x) acc[x] = mfma16(U[s & 1][x], V[s & 1][x], acc[x]);
       WW_SCHED(s)
     }
     if (more) stage_store(cur ^ 1);                         // two buffers: the next tile goes into the other one, one barrier
@@ -2576,7 +2572,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad1x1(WgradArgs A, long Mtot, lon
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-          for (int n = 0; n < NT; ++n) acc[m][n] = mfma16c(a[m], b[n], acc[m][n]);
+          for (int n = 0; n < NT; ++n) acc[m][n] = mfma16(a[m], b[n], acc[m][n]);
       }
     }
   };
@@ -2650,13 +2646,6 @@ __device__ __forceinline__ void gelu012(float z, float& g0, float& g1, float& g2
   g0 = z * Phi;
   g1 = Phi + z * phi;
   g2 = phi * (2.0f - z * z);
-}
-__device__ __forceinline__ void silu012(float z, float& s0, float& s1, float& s2) {
-  const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
-  const float om = 1.0f - sg;
-  s0 = z * sg;
-  s1 = sg * (1.0f + z * om);
-  s2 = sg * om * (2.0f + z * (1.0f - 2.0f * sg));
 }
 
 template <int ACT>   // 0 GELU, 1 SiLU
@@ -2806,8 +2795,6 @@ __global__ void k_gather_row(const float* __restrict__ x, float* __restrict__ ou
 }
 
 // ============================================================ C ABI
-static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
 static int check_geom(const msgm_conv_geom_t* g) {
   if (!g || g->N <= 0 || g->Hi <= 0 || g->Wi <= 0 || g->Ho <= 0 || g->Wo <= 0 || g->KH <= 0 || g->KW <= 0 ||
       g->strideH <= 0 || g->padH < 0 || g->strideW <= 0 || g->padW < 0 || (g->mode != 0 && g->mode != 1) ||

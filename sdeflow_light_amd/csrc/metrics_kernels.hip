@@ -162,8 +162,6 @@ static inline int64_t kde_slabs(int64_t M, int64_t Ns) {
   return (chunks + per - 1) / per;
 }
 
-static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
 extern "C" {
 
 int msgm_rbf_kernel(const float* x, const float* y, int64_t Nx, int64_t Ny, int32_t d, float* K, double* sum,

@@ -43,10 +43,6 @@ __device__ unsigned long long g_stamps[16];
 // own waitcnt insertion still guards the first use of every in-flight load.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 // row pitch of a gradient slab: n_params + 1 (loss) rounded up to 4 floats, so the reduction reads 16-B vectors
 __host__ __device__ static inline int64_t slab_stride(int64_t n_params) { return (n_params + 1 + 3) & ~(int64_t)3; }
 
@@ -1344,7 +1340,6 @@ __global__ void __launch_bounds__(256) k_slab_reduce(const float* __restrict__ s
 }
 
 // ============================================================ C ABI
-static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static const int MLP_MAX_GRID = 256;
 
 // Waves per workgroup.  Training at narrow width runs 8 waves x 16 features: two waves per SIMD, so one wave's

@@ -626,8 +626,6 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
 }
 
 // ============================================================ C ABI
-static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
 template <typename F>
 static int launch_rows(int64_t B, int64_t n, F&& f) {
   // lanes per row: next power of two >= min(n,64), at least 2

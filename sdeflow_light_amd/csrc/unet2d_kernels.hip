@@ -12,17 +12,6 @@
 #include <stdlib.h>
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ f32x4 mfma16u(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ void silu012u(float z, float& s0, float& s1, float& s2) {
-  const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
-  const float om = 1.0f - sg;
-  s0 = z * sg;
-  s1 = sg * (1.0f + z * om);
-  s2 = sg * om * (2.0f + z * (1.0f - 2.0f * sg));
-}
-
 // ------------------------------------------------------------------ GroupNorm dual
 // Two fully parallel launches per direction (a per-sample workgroup would leave the
 // chip idle at 32 samples/GPU):
@@ -77,50 +66,84 @@ __device__ __forceinline__ f32x4 drop_mul4(const DropKey& k, int b, int P, int C
                (r.w >> 8) >= k.thr ? k.s : 0.f};
 }
 
-// Reduction tail of the reduce kernels: every thread holds V double partials per moment (channels V*cv .. V*cv+V-1 of pixel
-// lane pl; per-thread fp32 sums over one sub-chunk are widened and from there on everything is added in double).  ALL moments
-// go to LDS images [moment][pl][C] at once; after ONE barrier one thread per (moment, group) sums its channels over the pixel
-// lanes in a fixed order and STORES the chunk's value in its slot.
+// ---- the phases the four GroupNorm kernels share
+// gn_lane: a thread's place in the 256-thread workgroup: channel vector cv (channels V*cv .. V*cv+V-1; V = 4 with VEC, else 1)
+// of pixel lane pl, CV vectors per pixel, PL = 256 / CV pixel lanes.  Threads beyond CV*PL (C = 96: 240) are not live: (0, 0).
+struct GnLane { int cv, pl, CV, PL; bool live; };
+template <bool VEC>
+__device__ __forceinline__ GnLane gn_lane(int tid, int C) {
+  const int CV = C / (VEC ? 4 : 1), PL = 256 / CV;
+  const bool live = tid < CV * PL;
+  return GnLane{live ? tid % CV : 0, live ? tid / CV : 0, CV, PL, live};
+}
+
+// gn_src: where channel c of the possibly two-source input lives.  `base` points at that channel in x (pitch C0) or in x1
+// (pitch C - C0) — a channel vector never straddles the sources (C0 % 4 == 0) — so element (sample b, pixel p) is
+// base[(b P + p) pitch]; `half` is the primal -> tangent offset of that source.
+struct GnSrc { const float* base; long half; int pitch; };
+__device__ __forceinline__ GnSrc gn_src(const GnArgs& A, int c) {
+  const int C0 = A.x1 ? A.C0 : A.C;
+  const bool second = c >= C0;
+  const int pitch = second ? A.C - C0 : C0;
+  return GnSrc{(second ? A.x1 : A.x) + (second ? c - C0 : c), (long)A.Bp * A.P * pitch, pitch};
+}
+
+// gn_load_x: the thread's V primal elements at source offset ex and, when dual, their tangents (xd is left untouched
+// otherwise).  VEC: one 16-byte load each.
+template <bool VEC>
+__device__ __forceinline__ void gn_load_x(const GnSrc& sx, long ex, bool dual, float (&x)[VEC ? 4 : 1], float (&xd)[VEC ? 4 : 1]) {
+  if constexpr (VEC) {
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(sx.base + ex);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = xv[k];
+    if (dual) {
+      const f32x4 dv = *reinterpret_cast<const f32x4*>(sx.base + ex + sx.half);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) xd[k] = dv[k];
+    }
+  } else {
+    x[0] = sx.base[ex];
+    if (dual) xd[0] = sx.base[ex + sx.half];
+  }
+}
+
+// gn_group_tail: the LDS tail of the reduce kernels.  red: nm images [pixel lane][C] of double partials, 1024 apart, visible
+// (the caller's ONE barrier); one thread per (moment, group): the pixel lanes in order, the group's channels inside -> dst[g][m].
+__device__ __forceinline__ void gn_group_tail(const double* red, double* dst, int nm, int tid, int C, int G, int PL) {
+  const int cpg = C / G;
+  for (int i = tid; i < nm * G; i += 256) {
+    const int m = i / G, g = i - m * G;
+    const double* r = red + m * 1024 + g * cpg;
+    double t = 0.0;
+    for (int p = 0; p < PL; ++p)
+      for (int cc = 0; cc < cpg; ++cc) t += r[p * C + cc];
+    dst[(size_t)g * 8 + m] = t;
+  }
+}
+
+// Reduce kernels: every thread holds V double partials per moment (per-thread fp32 sums over one sub-chunk are widened and
+// from there on everything is added in double).  ALL moments go to LDS at once and gn_group_tail finishes the chunk.
 template <bool VEC>
 __global__ void __launch_bounds__(256) k_gn_fwd_reduce(GnArgs A) {
   constexpr int V = VEC ? 4 : 1;
   __shared__ double red[4 * 1024];       // all moments at once: ONE barrier in the tail instead of two per moment
   const int tid = threadIdx.x, b = blockIdx.x;
-  const int C = A.C, P = A.P, G = A.G, cpg = C / G;
-  const int CV = C / V, PL = 256 / CV;
-  const bool live = tid < CV * PL;
-  const int cv = live ? tid % CV : 0, pl = live ? tid / CV : 0;
-  // channel V*cv of the (possibly concatenated) input lives in x (pitch C0) or in x1 (pitch C - C0)
-  const int C0 = A.x1 ? A.C0 : C;
-  const bool second = V * cv >= C0;
-  const int pitch = second ? C - C0 : C0, coff = second ? V * cv - C0 : V * cv;
-  const float* xp = (second ? A.x1 : A.x) + (size_t)b * P * pitch + coff;
-  const float* xt = (second ? A.x1 : A.x) + (size_t)(b + A.Bp) * P * pitch + coff;
+  const int C = A.C, P = A.P, G = A.G;
+  const GnLane L = gn_lane<VEC>(tid, C);
+  const GnSrc sx = gn_src(A, V * L.cv);
   const int p0 = blockIdx.y * A.chunk, p1 = min(p0 + A.chunk, P);
   double d0[V], d1[V], d2[V], d3[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) { d0[k] = 0.0; d1[k] = 0.0; d2[k] = 0.0; d3[k] = 0.0; }
-  if (live)
+  if (L.live)
    for (int ps = p0; ps < p1; ps += max(A.sub, 1)) {
     const int pe = min(ps + max(A.sub, 1), p1);
     float s0[V], s1[V], s2[V], s3[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) { s0[k] = 0.f; s1[k] = 0.f; s2[k] = 0.f; s3[k] = 0.f; }
-    for (int p = ps + pl; p < pe; p += PL) {
+    for (int p = ps + L.pl; p < pe; p += L.PL) {
       float xv[V], dv[V];
-      if (VEC) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(xp + (size_t)p * pitch);
-#pragma unroll
-        for (int k = 0; k < V; ++k) xv[k] = t[k];
-        if (A.dual) {
-          const f32x4 u = *reinterpret_cast<const f32x4*>(xt + (size_t)p * pitch);
-#pragma unroll
-          for (int k = 0; k < V; ++k) dv[k] = u[k];
-        }
-      } else {
-        xv[0] = xp[(size_t)p * pitch];
-        if (A.dual) dv[0] = xt[(size_t)p * pitch];
-      }
+      gn_load_x<VEC>(sx, ((long)b * P + p) * sx.pitch, A.dual, xv, dv);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         s0[k] += xv[k]; s1[k] += xv[k] * xv[k];
@@ -130,26 +153,16 @@ __global__ void __launch_bounds__(256) k_gn_fwd_reduce(GnArgs A) {
 #pragma unroll
     for (int k = 0; k < V; ++k) { d0[k] += (double)s0[k]; d1[k] += (double)s1[k]; d2[k] += (double)s2[k]; d3[k] += (double)s3[k]; }
    }
-  double* dst = A.acc + ((size_t)b * GN_SLOTS + blockIdx.y) * G * 8;
-  const int nm = A.dual ? 4 : 2;
-  if (live) {
+  if (L.live) {
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const int e = pl * C + V * cv + k;
+      const int e = L.pl * C + V * L.cv + k;
       red[e] = d0[k]; red[1024 + e] = d1[k];
       if (A.dual) { red[2048 + e] = d2[k]; red[3072 + e] = d3[k]; }
     }
   }
   __syncthreads();
-  // one thread per (moment, group): the pixel lanes in order, the group's channels inside
-  for (int i = tid; i < nm * G; i += 256) {
-    const int m = i / G, g = i - m * G;
-    const double* r = red + m * 1024 + g * cpg;
-    double t = 0.0;
-    for (int p = 0; p < PL; ++p)
-      for (int cc = 0; cc < cpg; ++cc) t += r[p * C + cc];
-    dst[(size_t)g * 8 + m] = t;
-  }
+  gn_group_tail(red, A.acc + ((size_t)b * GN_SLOTS + blockIdx.y) * G * 8, A.dual ? 4 : 2, tid, C, G, L.PL);
 }
 
 // moments of (sample b, group g): the chunk slots added in chunk order.  The loads of up to 4 slots are issued before the
@@ -204,20 +217,25 @@ __global__ void __launch_bounds__(256) k_gn_affine(GnArgs A, float* __restrict__
   }
 }
 
+// gn_consts: the constants of the thread's V channels c0 ..: {mean, inv_std, mean(xdot), a} of each one's group from the f32x4
+// table[row + group] (k_gn_fwd_apply: this sample's LDS copy, row 0; backward: A.stats, row b G) and the affine parameters.
+template <int V> struct GnConsts { float mu[V], inv[V], md[V], a[V], ga[V], be[V]; };
+template <int V>
+__device__ __forceinline__ GnConsts<V> gn_consts(const GnArgs& A, const f32x4* table, size_t row, int c0, int cpg) {
+  GnConsts<V> K;
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    const int c = c0 + k;
+    const f32x4 st = table[row + c / cpg];
+    K.mu[k] = st[0]; K.inv[k] = st[1]; K.md[k] = st[2]; K.a[k] = st[3];
+    K.ga[k] = A.gamma[c]; K.be[k] = A.beta[c];
+  }
+  return K;
+}
+
 // Elementwise pass.  VEC: grid (pixel chunk, sample); a thread owns 4 consecutive channels (its statistics and
 // affine parameters are loaded once) and walks over pixels — 16-B loads/stores, consecutive threads on consecutive
 // addresses.  !VEC (C % 4 != 0): one thread per channel, same walk.
-// element offset of (sample b, pixel p, channel c) of the possibly two-source input: `pitch` / `coff` select the source
-// of this thread's channel vector (a vector never straddles the sources: C0 % 4 == 0), `half` is the primal -> tangent
-// offset of that source
-struct GnSrc { const float* base; long half; int pitch; };
-__device__ __forceinline__ GnSrc gn_src(const GnArgs& A, int c) {
-  const int C0 = A.x1 ? A.C0 : A.C;
-  const bool second = c >= C0;
-  const int pitch = second ? A.C - C0 : C0;
-  return GnSrc{(second ? A.x1 : A.x) + (second ? c - C0 : c), (long)A.Bp * A.P * pitch, pitch};
-}
-
 // DROP (VEC only): the post-SiLU primal and tangent are multiplied by keep * scale of the dropout mask.
 template <bool VEC, bool DROP = false>
 __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
@@ -225,7 +243,6 @@ __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
   constexpr int V = VEC ? 4 : 1;
   __shared__ f32x4 sst[64];
   const int C = A.C, P = A.P, G = A.G, cpg = C / G;
-  const int CV = C / V, PL = 256 / CV;
   const int tid = threadIdx.x, b = blockIdx.y;
   // {mean, inv_std, mean(xdot), a} of this sample's groups, rebuilt by every workgroup from the chunk slots the reduce
   // kernel left (thread g: the slots of group g in chunk order, in double — the arithmetic of the former one-thread-per-
@@ -240,46 +257,27 @@ __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
     if (A.stats && blockIdx.x == 0) *reinterpret_cast<f32x4*>(A.stats + ((size_t)b * G + tid) * 4) = f32x4{mu, inv, md, a};
   }
   __syncthreads();
-  if (tid >= CV * PL) return;
-  const int cv = tid % CV, pl = tid / CV;
+  const GnLane L = gn_lane<VEC>(tid, C);
+  if (!L.live) return;
+  const int cv = L.cv;
   const long tot = (long)A.Bp * P * C;
-  float mu[V], inv[V], md[V], a[V], ga[V], be[V];
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    const int c = V * cv + k;
-    const f32x4 st = sst[c / cpg];
-    mu[k] = st[0]; inv[k] = st[1]; md[k] = st[2]; a[k] = st[3];
-    ga[k] = A.gamma[c]; be[k] = A.beta[c];
-  }
+  const GnConsts<V> K = gn_consts<V>(A, sst, 0, V * cv, cpg);
   const int p0 = blockIdx.x * A.chunk, p1 = min(p0 + A.chunk, P);
   const GnSrc sx = gn_src(A, V * cv);
   DropKey dk;
   if constexpr (DROP) dk = drop_key(A.drng, A.dstream, A.dthr, A.dscale);
-  for (int p = p0 + pl; p < p1; p += PL) {
+  for (int p = p0 + L.pl; p < p1; p += L.PL) {
     const long e = ((long)b * P + p) * C + V * cv;
-    const long ex = ((long)b * P + p) * sx.pitch;
     float x[V], xd[V], y[V], yd[V];
-    if (VEC) {
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(sx.base + ex);
-#pragma unroll
-      for (int k = 0; k < V; ++k) x[k] = xv[k];
-      if (A.dual) {
-        const f32x4 dv = *reinterpret_cast<const f32x4*>(sx.base + ex + sx.half);
-#pragma unroll
-        for (int k = 0; k < V; ++k) xd[k] = dv[k];
-      }
-    } else {
-      x[0] = sx.base[ex];
-      if (A.dual) xd[0] = sx.base[ex + sx.half];
-    }
+    gn_load_x<VEC>(sx, ((long)b * P + p) * sx.pitch, A.dual, x, xd);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const float xh = (x[k] - mu[k]) * inv[k];
-      y[k] = ga[k] * xh + be[k];
-      yd[k] = A.dual ? ga[k] * (inv[k] * ((xd[k] - md[k]) - xh * a[k])) : 0.f;
+      const float xh = (x[k] - K.mu[k]) * K.inv[k];
+      y[k] = K.ga[k] * xh + K.be[k];
+      yd[k] = A.dual ? K.ga[k] * (K.inv[k] * ((xd[k] - K.md[k]) - xh * K.a[k])) : 0.f;
       if (A.silu) {
         float z0, z1, z2;
-        silu012u(y[k], z0, z1, z2);
+        silu012(y[k], z0, z1, z2);
         y[k] = z0; yd[k] = z1 * yd[k];
       }
     }
@@ -308,6 +306,47 @@ __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
 // (derived by hand, checked against autograd in tests/test_unet2d_gpu.py).
 // DROP (VEC only): both incoming cotangents are multiplied by keep * scale as they are loaded (the moments see the masked
 // cotangent), in this kernel and in k_gn_bwd_apply.
+// gn_load_cot: both incoming cotangents (zb: of the output, zdb: of its tangent, `tot` floats later) of the thread's V
+// channels at output offset e = ((b P + p) C + c); DROP multiplies them by the keep * scale of (b, p, c .. c+3).
+template <bool VEC, bool DROP>
+__device__ __forceinline__ void gn_load_cot(const GnArgs& A, const DropKey& dk, long e, long tot, int b, int p, int c,
+                                            float (&zb)[VEC ? 4 : 1], float (&zdb)[VEC ? 4 : 1]) {
+  if constexpr (VEC) {
+    const f32x4 v2 = *reinterpret_cast<const f32x4*>(A.gout + e), v3 = *reinterpret_cast<const f32x4*>(A.gout + e + tot);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { zb[k] = v2[k]; zdb[k] = v3[k]; }
+  } else {
+    zb[0] = A.gout[e]; zdb[0] = A.gout[e + tot];
+  }
+  if constexpr (DROP) {
+    const f32x4 m = drop_mul4(dk, b, A.P, A.C, p, c);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { zb[k] *= m[k]; zdb[k] *= m[k]; }
+  }
+}
+
+// gn_bwd_elem: the backward's per-element chain for channel k of the thread's constants K — xh = xhat, wh = what, the
+// cotangents (zbk, zdbk) pulled back through the SiLU when there is one, X = gamma zbar, W = gamma zdotbar.  The ONE text of
+// it: k_gn_bwd_reduce sums moments of these quantities and k_gn_bwd_apply subtracts them, so both must see the same values.
+struct GnElem { float xh, wh, zbk, zdbk, X, W; };
+template <int V>
+__device__ __forceinline__ GnElem gn_bwd_elem(float x, float xd, const GnConsts<V>& K, int k, int silu, float zb, float zdb) {
+  GnElem E;
+  E.xh = (x - K.mu[k]) * K.inv[k];
+  E.wh = K.inv[k] * ((xd - K.md[k]) - E.xh * K.a[k]);
+  E.zbk = zb; E.zdbk = zdb;
+  if (silu) {
+    float z0, z1, z2;
+    silu012(K.ga[k] * E.xh + K.be[k], z0, z1, z2);
+    const float yd = K.ga[k] * E.wh;
+    const float nzb = E.zbk * z1 + E.zdbk * (z2 * yd);
+    E.zdbk = E.zdbk * z1;
+    E.zbk = nzb;
+  }
+  E.X = K.ga[k] * E.zbk; E.W = K.ga[k] * E.zdbk;
+  return E;
+}
+
 template <bool VEC, bool DROP = false>
 __global__ void __launch_bounds__(256) k_gn_bwd_reduce(GnArgs A) {
   static_assert(VEC || !DROP, "dropout masks are drawn per channel quad");
@@ -316,18 +355,10 @@ __global__ void __launch_bounds__(256) k_gn_bwd_reduce(GnArgs A) {
   __shared__ float red[2 * 1024];
   const int tid = threadIdx.x, b = blockIdx.x;
   const int C = A.C, P = A.P, G = A.G, cpg = C / G;
-  const int CV = C / V, PL = 256 / CV;
-  const bool live = tid < CV * PL;
-  const int cv = live ? tid % CV : 0, pl = live ? tid / CV : 0;
+  const GnLane L = gn_lane<VEC>(tid, C);
+  const int cv = L.cv, pl = L.pl;
   const long tot = (long)A.Bp * P * C;
-  float mu[V], inv[V], md[V], a[V], ga[V], be[V];
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    const int c = V * cv + k;
-    const f32x4 st = *reinterpret_cast<const f32x4*>(A.stats + ((size_t)b * G + c / cpg) * 4);
-    mu[k] = st[0]; inv[k] = st[1]; md[k] = st[2]; a[k] = st[3];
-    ga[k] = A.gamma[c]; be[k] = A.beta[c];
-  }
+  const GnConsts<V> K = gn_consts<V>(A, reinterpret_cast<const f32x4*>(A.stats), (size_t)b * G, V * cv, cpg);
   const int p0 = blockIdx.y * A.chunk, p1 = min(p0 + A.chunk, P);
   const GnSrc sx = gn_src(A, V * cv);
   double dX[V], dXx[V], dW[V], dWx[V], dWw[V];
@@ -336,45 +367,21 @@ __global__ void __launch_bounds__(256) k_gn_bwd_reduce(GnArgs A) {
   for (int k = 0; k < V; ++k) { dX[k] = dXx[k] = dW[k] = dWx[k] = dWw[k] = 0.0; dga[k] = dbe[k] = 0.f; }
   DropKey dk;
   if constexpr (DROP) dk = drop_key(A.drng, A.dstream, A.dthr, A.dscale);
-  if (live)
+  if (L.live)
    for (int ps = p0; ps < p1; ps += max(A.sub, 1)) {
     const int pe = min(ps + max(A.sub, 1), p1);
     float sX[V], sXx[V], sW[V], sWx[V], sWw[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) { sX[k] = sXx[k] = sW[k] = sWx[k] = sWw[k] = 0.f; }
-    for (int p = ps + pl; p < pe; p += PL) {
-      const long e = ((long)b * P + p) * C + V * cv;
-      const long ex = ((long)b * P + p) * sx.pitch;
+    for (int p = ps + pl; p < pe; p += L.PL) {
       float x[V], xd[V], zb[V], zdb[V];
-      if (VEC) {
-        const f32x4 v0 = *reinterpret_cast<const f32x4*>(sx.base + ex), v1 = *reinterpret_cast<const f32x4*>(sx.base + ex + sx.half);
-        const f32x4 v2 = *reinterpret_cast<const f32x4*>(A.gout + e), v3 = *reinterpret_cast<const f32x4*>(A.gout + e + tot);
-#pragma unroll
-        for (int k = 0; k < V; ++k) { x[k] = v0[k]; xd[k] = v1[k]; zb[k] = v2[k]; zdb[k] = v3[k]; }
-      } else {
-        x[0] = sx.base[ex]; xd[0] = sx.base[ex + sx.half]; zb[0] = A.gout[e]; zdb[0] = A.gout[e + tot];
-      }
-      if constexpr (DROP) {
-        const f32x4 m = drop_mul4(dk, b, P, C, p, V * cv);
-#pragma unroll
-        for (int k = 0; k < V; ++k) { zb[k] *= m[k]; zdb[k] *= m[k]; }
-      }
+      gn_load_x<VEC>(sx, ((long)b * P + p) * sx.pitch, true, x, xd);
+      gn_load_cot<VEC, DROP>(A, dk, ((long)b * P + p) * C + V * cv, tot, b, p, V * cv, zb, zdb);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        const float xh = (x[k] - mu[k]) * inv[k];
-        const float wh = inv[k] * ((xd[k] - md[k]) - xh * a[k]);
-        float zbk = zb[k], zdbk = zdb[k];
-        if (A.silu) {
-          float z0, z1, z2;
-          silu012u(ga[k] * xh + be[k], z0, z1, z2);
-          const float yd = ga[k] * wh;
-          const float nzb = zbk * z1 + zdbk * (z2 * yd);
-          zdbk = zdbk * z1;
-          zbk = nzb;
-        }
-        const float X = ga[k] * zbk, W = ga[k] * zdbk;
-        sX[k] += X; sXx[k] += X * xh; sW[k] += W; sWx[k] += W * xh; sWw[k] += W * wh;
-        dga[k] += zbk * xh + zdbk * wh; dbe[k] += zbk;
+        const GnElem E = gn_bwd_elem(x[k], xd[k], K, k, A.silu, zb[k], zdb[k]);
+        sX[k] += E.X; sXx[k] += E.X * E.xh; sW[k] += E.W; sWx[k] += E.W * E.xh; sWw[k] += E.W * E.wh;
+        dga[k] += E.zbk * E.xh + E.zdbk * E.wh; dbe[k] += E.zbk;
       }
     }
 #pragma unroll
@@ -382,9 +389,8 @@ __global__ void __launch_bounds__(256) k_gn_bwd_reduce(GnArgs A) {
       dX[k] += (double)sX[k]; dXx[k] += (double)sXx[k]; dW[k] += (double)sW[k]; dWx[k] += (double)sWx[k]; dWw[k] += (double)sWw[k];
     }
    }
-  double* dst = A.acc + ((size_t)b * GN_SLOTS + blockIdx.y) * G * 8;
   const size_t slot = (size_t)b * gridDim.y + blockIdx.y, nslots = (size_t)gridDim.x * gridDim.y;
-  if (live) {
+  if (L.live) {
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       const int e = pl * C + V * cv + k;
@@ -393,20 +399,12 @@ __global__ void __launch_bounds__(256) k_gn_bwd_reduce(GnArgs A) {
     }
   }
   __syncthreads();
-  // one thread per (moment, group): the pixel lanes in order, the group's channels inside
-  for (int i = tid; i < 5 * G; i += 256) {
-    const int m = i / G, g = i - m * G;
-    const double* r = redd + m * 1024 + g * cpg;
-    double t = 0.0;
-    for (int p = 0; p < PL; ++p)
-      for (int cc = 0; cc < cpg; ++cc) t += r[p * C + cc];
-    dst[(size_t)g * 8 + m] = t;
-  }
+  gn_group_tail(redd, A.acc + ((size_t)b * GN_SLOTS + blockIdx.y) * G * 8, 5, tid, C, G, L.PL);
   // per-channel parameter gradients: the pixel lanes in order, one value per channel into this (sample, chunk)'s slot
   for (int i = tid; i < 2 * C; i += 256) {
     const int which = i / C, c = i - which * C;
     float t = 0.f;
-    for (int p = 0; p < PL; ++p) t += red[which * 1024 + p * C + c];
+    for (int p = 0; p < L.PL; ++p) t += red[which * 1024 + p * C + c];
     A.pslots[((size_t)which * nslots + slot) * C + c] = t;
   }
 }
@@ -440,7 +438,6 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(GnArgs A) {
   static_assert(VEC || !DROP, "dropout masks are drawn per channel quad");
   constexpr int V = VEC ? 4 : 1;
   const int C = A.C, P = A.P, G = A.G, cpg = C / G;
-  const int CV = C / V, PL = 256 / CV;
   const int tid = threadIdx.x, b = blockIdx.y;
   // the five backward moments of this sample's groups: every workgroup adds the reduce kernel's chunk slots itself (thread
   // g, chunk order, double) instead of a finalise launch in between
@@ -452,19 +449,18 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(GnArgs A) {
     for (int m = 0; m < 5; ++m) sm5[tid][m] = (float)a8[m];
   }
   __syncthreads();
-  if (tid >= CV * PL) return;
-  const int cv = tid % CV, pl = tid / CV;
+  const GnLane L = gn_lane<VEC>(tid, C);
+  if (!L.live) return;
+  const int cv = L.cv;
   const long tot = (long)A.Bp * P * C;
   const float rc = 1.0f / ((float)P * (float)cpg);
-  float mu[V], inv[V], md[V], a[V], ga[V], be[V], mX[V], mXx[V], mW[V], pp[V], cc[V];
+  const GnConsts<V> K = gn_consts<V>(A, reinterpret_cast<const f32x4*>(A.stats), (size_t)b * G, V * cv, cpg);
+  float mX[V], mXx[V], mW[V], pp[V], cc[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) {
-    const int c = V * cv + k, g = c / cpg;
-    const f32x4 st = *reinterpret_cast<const f32x4*>(A.stats + ((size_t)b * G + g) * 4);
-    mu[k] = st[0]; inv[k] = st[1]; md[k] = st[2]; a[k] = st[3];
+    const int g = (V * cv + k) / cpg;
     mX[k] = sm5[g][0] * rc; mXx[k] = sm5[g][1] * rc; mW[k] = sm5[g][2] * rc; pp[k] = sm5[g][3] * rc;
     cc[k] = sm5[g][4] * rc;
-    ga[k] = A.gamma[c]; be[k] = A.beta[c];
   }
   const int p0 = blockIdx.x * A.chunk, p1 = min(p0 + A.chunk, P);
   const GnSrc sx = gn_src(A, V * cv);
@@ -474,39 +470,16 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(GnArgs A) {
   const float* rbase2 = A.resid2 ? A.resid2 + V * cv : nullptr;
   DropKey dk;
   if constexpr (DROP) dk = drop_key(A.drng, A.dstream, A.dthr, A.dscale);
-  for (int p = p0 + pl; p < p1; p += PL) {
-    const long e = ((long)b * P + p) * C + V * cv;
+  for (int p = p0 + L.pl; p < p1; p += L.PL) {
     const long ex = ((long)b * P + p) * sx.pitch;
     float x[V], xd[V], zb[V], zdb[V], xb[V], xdb[V];
-    if (VEC) {
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(sx.base + ex), v1 = *reinterpret_cast<const f32x4*>(sx.base + ex + sx.half);
-      const f32x4 v2 = *reinterpret_cast<const f32x4*>(A.gout + e), v3 = *reinterpret_cast<const f32x4*>(A.gout + e + tot);
-#pragma unroll
-      for (int k = 0; k < V; ++k) { x[k] = v0[k]; xd[k] = v1[k]; zb[k] = v2[k]; zdb[k] = v3[k]; }
-    } else {
-      x[0] = sx.base[ex]; xd[0] = sx.base[ex + sx.half]; zb[0] = A.gout[e]; zdb[0] = A.gout[e + tot];
-    }
-    if constexpr (DROP) {
-      const f32x4 m = drop_mul4(dk, b, P, C, p, V * cv);
-#pragma unroll
-      for (int k = 0; k < V; ++k) { zb[k] *= m[k]; zdb[k] *= m[k]; }
-    }
+    gn_load_x<VEC>(sx, ex, true, x, xd);
+    gn_load_cot<VEC, DROP>(A, dk, ((long)b * P + p) * C + V * cv, tot, b, p, V * cv, zb, zdb);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const float xh = (x[k] - mu[k]) * inv[k];
-      const float wh = inv[k] * ((xd[k] - md[k]) - xh * a[k]);
-      float zbk = zb[k], zdbk = zdb[k];
-      if (A.silu) {
-        float z0, z1, z2;
-        silu012u(ga[k] * xh + be[k], z0, z1, z2);
-        const float yd = ga[k] * wh;
-        const float nzb = zbk * z1 + zdbk * (z2 * yd);
-        zdbk = zdbk * z1;
-        zbk = nzb;
-      }
-      const float X = ga[k] * zbk, W = ga[k] * zdbk;
-      xdb[k] = inv[k] * (W - mW[k] - xh * pp[k]);
-      xb[k] = inv[k] * (X - mX[k] - xh * mXx[k]) - inv[k] * (cc[k] * xh + a[k] * xdb[k] + pp[k] * wh);
+      const GnElem E = gn_bwd_elem(x[k], xd[k], K, k, A.silu, zb[k], zdb[k]);
+      xdb[k] = K.inv[k] * (E.W - mW[k] - E.xh * pp[k]);
+      xb[k] = K.inv[k] * (E.X - mX[k] - E.xh * mXx[k]) - K.inv[k] * (cc[k] * E.xh + K.a[k] * xdb[k] + pp[k] * E.wh);
     }
     if (VEC) {
       f32x4 o, od;
@@ -615,8 +588,8 @@ __global__ void __launch_bounds__(256) k_bmm(BmmArgs P) {
         for (int m = 0; m < MT; ++m)
 #pragma unroll
           for (int n = 0; n < NT; ++n) {
-            acc[m][n] = mfma16u(a[m][r], b[n][r], acc[m][n]);
-            if (third) acc3[m][n] = mfma16u(a3[m][r], b[n][r], acc3[m][n]);
+            acc[m][n] = mfma16(a[m][r], b[n][r], acc[m][n]);
+            if (third) acc3[m][n] = mfma16(a3[m][r], b[n][r], acc3[m][n]);
           }
     }
   }
@@ -752,8 +725,8 @@ __global__ void __launch_bounds__(256) k_bmm_lds(BmmArgs P) {
         for (int m = 0; m < 2; ++m)
 #pragma unroll
           for (int n = 0; n < 2; ++n) {
-            acc[m][n] = mfma16u(a[m][r], b[n][r], acc[m][n]);
-            if (third) acc3[m][n] = mfma16u(a3[m][r], b[n][r], acc3[m][n]);
+            acc[m][n] = mfma16(a[m][r], b[n][r], acc[m][n]);
+            if (third) acc3[m][n] = mfma16(a3[m][r], b[n][r], acc3[m][n]);
           }
     }
     if (it + 1 < total) lstore(cur ^ 1, it + 1);          // the other buffer: its readers finished before the last barrier
@@ -807,7 +780,7 @@ __global__ void __launch_bounds__(256) k_bmm_slow(BmmArgs P) {
       const int k = k0 + q;
       const float a = (vi && k < P.K) ? Ab[(size_t)k * P.sAk] : 0.f;
       const float b = (vj && k < P.K) ? Bb[(size_t)k * P.sBk] : 0.f;
-      acc = mfma16u(a, b, acc);
+      acc = mfma16(a, b, acc);
     }
   }
   float* Cb = P.C + (size_t)blockIdx.y * P.sCb;
@@ -1145,7 +1118,15 @@ __global__ void __launch_bounds__(256) k_emb_bank_dgrad(const msgm_emb_job_t* __
 }
 
 // ============================================================ C ABI
-static inline hipStream_t S(msgm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+// the builds of a GroupNorm kernel, picked in ONE place: [0] scalar, [1] VEC (C % 4 == 0), [2] VEC + DROP (gn_set_dropout checks)
+typedef void (*gn_kernel_t)(GnArgs);
+static const gn_kernel_t GN_FWD_REDUCE[3] = {k_gn_fwd_reduce<false>, k_gn_fwd_reduce<true>, k_gn_fwd_reduce<true>};
+static const gn_kernel_t GN_FWD_APPLY[3] = {k_gn_fwd_apply<false>, k_gn_fwd_apply<true>, k_gn_fwd_apply<true, true>};
+static const gn_kernel_t GN_BWD_REDUCE[3] = {k_gn_bwd_reduce<false>, k_gn_bwd_reduce<true>, k_gn_bwd_reduce<true, true>};
+static const gn_kernel_t GN_BWD_APPLY[3] = {k_gn_bwd_apply<false>, k_gn_bwd_apply<true>, k_gn_bwd_apply<true, true>};
+static void gn_launch(const gn_kernel_t (&builds)[3], bool drop, bool vec, dim3 grid, msgm_stream_t stream, const GnArgs& A) {
+  hipLaunchKernelGGL(builds[drop ? 2 : vec ? 1 : 0], grid, dim3(256), 0, S(stream), A);
+}
 
 extern "C" {
 
@@ -1201,28 +1182,33 @@ static int gn_set_dropout(GnArgs& A, const msgm_dropout_t* drop) {
   return MSGM_OK;
 }
 
-static int gn_forward_impl(const float* x, int32_t C0, const float* x1, int32_t C, const float* gamma, const float* beta, float* out,
-                           float* stats, int32_t Bp, int32_t P, int32_t G, int32_t dual, int32_t silu, float eps, void* workspace,
-                           size_t workspace_bytes, msgm_stream_t stream, const msgm_dropout_t* drop = nullptr) {
-  if (!x || !gamma || !beta || !out || !workspace || Bp <= 0 || P <= 0 || C <= 0 || G <= 0) return MSGM_E_BADARG;
-  if (C % G || C > 256 || G > 64 || (x1 && (C0 % 4 || (C - C0) % 4 || C0 <= 0 || C0 >= C))) return MSGM_E_UNSUPPORTED;
-  if (workspace_bytes < msgm_groupnorm_workspace(Bp, G)) return MSGM_E_WORKSPACE;
-  GnArgs A{x, gamma, beta, out, reinterpret_cast<double*>(workspace), stats, P, C, G, Bp, dual, silu, 0, eps,
-           nullptr, nullptr, nullptr, nullptr, x1, C0};
+// forward and msgm_groupnorm_affine: checks of what the caller put into A, chunking, launch of the moment reduce (`vec` build)
+static int gn_forward_reduce(GnArgs& A, size_t workspace_bytes, const msgm_dropout_t* drop, bool vec, msgm_stream_t stream) {
+  const int C = A.C, C0 = A.C0, G = A.G;
+  if (!A.x || !A.gamma || !A.beta || !A.acc || A.Bp <= 0 || A.P <= 0 || C <= 0 || G <= 0) return MSGM_E_BADARG;
+  if (C % G || C > 256 || G > 64 || (A.x1 && (C0 % 4 || (C - C0) % 4 || C0 <= 0 || C0 >= C))) return MSGM_E_UNSUPPORTED;
+  if (workspace_bytes < msgm_groupnorm_workspace(A.Bp, G)) return MSGM_E_WORKSPACE;
   if (drop) {
     const int rc = gn_set_dropout(A, drop);
     if (rc != MSGM_OK) return rc;
   }
-  const int nch = gn_chunks(Bp, P, &A.chunk, &A.sub);
-  if (nch > GN_SLOTS) return MSGM_E_UNSUPPORTED;
-  A.nch = nch;
+  A.nch = gn_chunks(A.Bp, A.P, &A.chunk, &A.sub);
+  if (A.nch > GN_SLOTS) return MSGM_E_UNSUPPORTED;
+  gn_launch(GN_FWD_REDUCE, drop, vec, dim3(A.Bp, A.nch), stream, A);
+  return MSGM_OK;
+}
+
+static int gn_forward_impl(const float* x, int32_t C0, const float* x1, int32_t C, const float* gamma, const float* beta, float* out,
+                           float* stats, int32_t Bp, int32_t P, int32_t G, int32_t dual, int32_t silu, float eps, void* workspace,
+                           size_t workspace_bytes, msgm_stream_t stream, const msgm_dropout_t* drop = nullptr) {
+  if (!out) return MSGM_E_BADARG;
+  GnArgs A{x, gamma, beta, out, reinterpret_cast<double*>(workspace), stats, P, C, G, Bp, dual, silu, 0, eps,
+           nullptr, nullptr, nullptr, nullptr, x1, C0};
   // two launches: chunk moments -> slots, then the apply pass (every workgroup finalises its sample's statistics itself)
-  if (C % 4 == 0) hipLaunchKernelGGL(k_gn_fwd_reduce<true>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
-  else hipLaunchKernelGGL(k_gn_fwd_reduce<false>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
+  const int rc = gn_forward_reduce(A, workspace_bytes, drop, C % 4 == 0, stream);
+  if (rc != MSGM_OK) return rc;
   const int nap = gn_chunks_apply(Bp, P, &A.chunk);
-  if (drop) hipLaunchKernelGGL((k_gn_fwd_apply<true, true>), dim3(nap, Bp), dim3(256), 0, S(stream), A);
-  else if (C % 4 == 0) hipLaunchKernelGGL(k_gn_fwd_apply<true>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
-  else hipLaunchKernelGGL(k_gn_fwd_apply<false>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
+  gn_launch(GN_FWD_APPLY, drop, C % 4 == 0, dim3(nap, Bp), stream, A);
   return msgm_check_launch();
 }
 
@@ -1273,18 +1259,12 @@ int msgm_dropout_mask(const msgm_dropout_t* drop, int32_t Bp, int32_t P, int32_t
 int msgm_groupnorm_affine(const float* x0, int32_t C0, const float* x1, int32_t C1, const float* gamma, const float* beta,
                           float* scale, float* shift, int32_t Bp, int32_t P, int32_t G, float eps, void* workspace,
                           size_t workspace_bytes, msgm_stream_t stream) {
-  if (!x0 || !gamma || !beta || !scale || !shift || !workspace || Bp <= 0 || P <= 0 || C0 <= 0 || G <= 0 || (x1 && C1 <= 0))
-    return MSGM_E_BADARG;
+  if (!scale || !shift || C0 <= 0 || (x1 && C1 <= 0)) return MSGM_E_BADARG;
   const int C = C0 + (x1 ? C1 : 0);
-  if (C % G || C > 256 || G > 64 || (x1 && (C0 % 4 || C1 % 4))) return MSGM_E_UNSUPPORTED;
-  if (workspace_bytes < msgm_groupnorm_workspace(Bp, G)) return MSGM_E_WORKSPACE;
   GnArgs A{x0, gamma, beta, nullptr, reinterpret_cast<double*>(workspace), nullptr, P, C, G, Bp, 0, 0, 0, eps,
            nullptr, nullptr, nullptr, nullptr, x1, C0};
-  const int nch = gn_chunks(Bp, P, &A.chunk, &A.sub);
-  if (nch > GN_SLOTS) return MSGM_E_UNSUPPORTED;
-  A.nch = nch;
-  if (C % 4 == 0 && C0 % 4 == 0) hipLaunchKernelGGL(k_gn_fwd_reduce<true>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
-  else hipLaunchKernelGGL(k_gn_fwd_reduce<false>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
+  const int rc = gn_forward_reduce(A, workspace_bytes, nullptr, C % 4 == 0 && C0 % 4 == 0, stream);
+  if (rc != MSGM_OK) return rc;
   hipLaunchKernelGGL(k_gn_affine, dim3(Bp), dim3(256), 0, S(stream), A, scale, shift);
   return msgm_check_launch();
 }
@@ -1365,9 +1345,7 @@ static int gn_backward_impl(const float* x, int32_t C0, const float* x1, int32_t
   }
   A.resid = residual;
   A.resid2 = residual2;
-  if (drop) hipLaunchKernelGGL((k_gn_bwd_reduce<true, true>), dim3(Bp, nch), dim3(256), 0, S(stream), A);
-  else if (C % 4 == 0) hipLaunchKernelGGL(k_gn_bwd_reduce<true>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
-  else hipLaunchKernelGGL(k_gn_bwd_reduce<false>, dim3(Bp, nch), dim3(256), 0, S(stream), A);
+  gn_launch(GN_BWD_REDUCE, drop, C % 4 == 0, dim3(Bp, nch), stream, A);
   if (pslots_ext) {
     for (int w = 0; w < 2; ++w)
       jobs_out[w] = msgm_reduce_job_t{A.pslots + (size_t)w * nslots * C, w == 0 ? dgamma : dbeta, nullptr, (int64_t)C, (int64_t)C, 0, 0,
@@ -1379,9 +1357,7 @@ static int gn_backward_impl(const float* x, int32_t C0, const float* x1, int32_t
                        nbc);
   }
   const int nap = gn_chunks_apply(Bp, P, &A.chunk);
-  if (drop) hipLaunchKernelGGL((k_gn_bwd_apply<true, true>), dim3(nap, Bp), dim3(256), 0, S(stream), A);
-  else if (C % 4 == 0) hipLaunchKernelGGL(k_gn_bwd_apply<true>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
-  else hipLaunchKernelGGL(k_gn_bwd_apply<false>, dim3(nap, Bp), dim3(256), 0, S(stream), A);
+  gn_launch(GN_BWD_APPLY, drop, C % 4 == 0, dim3(nap, Bp), stream, A);
   return msgm_check_launch();
 }
 

@@ -6,6 +6,7 @@ GPU for everyone), passes raw device pointers through ctypes, and raises
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C_
 import math
 from typing import Optional
@@ -749,34 +750,24 @@ def groupnorm_dual_forward(x, gamma, beta, Bp, P, C, G, dual, silu, stats=None, 
     return out
 
 
-def _gn_backward_slots(x0, C0, x1, C1, gamma, beta, stats, gout, gx0, gx1, dgamma, dbeta, Bp, P, G, silu, eps, residual, d,
-                       residual2=None):
-    """GroupNorm backward inside a DeferredReduces pass: the dgamma / dbeta partials go to the pass's arena and their
-    slot-ordered sums join the pass's ONE batched reduction launch."""
-    import ctypes as C_
+def _gn_backward_in_pass(x0, C0, x1, C1, gamma, beta, stats, gout, gx0, gx1, dgamma, dbeta, Bp, P, G, silu, eps, residual, d,
+                         residual2=None, dropout=None):
+    """GroupNorm backward inside the DeferredReduces pass ``d``: the dgamma / dbeta partials go to the pass's arena and their
+    slot-ordered sums join the pass's ONE batched reduction launch.  ``dropout`` (single source only) picks the dropout entry."""
     C = C0 + C1
     need = int(lib().msgm_groupnorm_param_slots_bytes(Bp, P, C))
     ps, nbytes = d.take(need)
     ws = _gn_ws(Bp, G, x0.device)
     jobs, nj = (L.ReduceJobT * 2)(), C_.c_int32(0)
-    check(lib().msgm_groupnorm_dual_backward_slots(ptr(f32(x0)), C0, ptr(x1), C1, ptr(f32(gamma)), ptr(f32(beta)), ptr(f32(stats)),
-                                                   ptr(f32(gout)), ptr(gx0), ptr(gx1), ptr(dgamma), ptr(dbeta), Bp, P, G,
-                                                   int(bool(silu)), float(eps), ptr(residual), ptr(residual2), ptr(ws), ws.numel() * 8, ps, nbytes,
-                                                   jobs, C_.byref(nj), stream()), "msgm_groupnorm_dual_backward_slots")
-    d.add(jobs, nj.value, (dgamma, dbeta))
-
-
-def _gn_backward_dropout(x, gamma, beta, stats, gout, gx, dgamma, dbeta, Bp, P, C, G, silu, eps, residual, residual2, drop, d):
-    """The slots backward of the dropout map (its parameter reductions join the DeferredReduces pass ``d``)."""
-    need = int(lib().msgm_groupnorm_param_slots_bytes(Bp, P, C))
-    ps, nbytes = d.take(need)
-    ws = _gn_ws(Bp, G, x.device)
-    jobs, nj = (L.ReduceJobT * 2)(), C_.c_int32(0)
-    check(lib().msgm_groupnorm_dual_backward_slots_dropout(ptr(f32(x)), ptr(f32(gamma)), ptr(f32(beta)), ptr(f32(stats)),
-                                                           ptr(f32(gout)), ptr(gx), ptr(dgamma), ptr(dbeta), Bp, P, C, G,
-                                                           int(bool(silu)), float(eps), ptr(residual), ptr(residual2), ptr(ws),
-                                                           ws.numel() * 8, ps, nbytes, jobs, C_.byref(nj), C_.byref(drop), stream()),
-          "msgm_groupnorm_dual_backward_slots_dropout")
+    params = (ptr(f32(gamma)), ptr(f32(beta)), ptr(f32(stats)), ptr(f32(gout)))
+    rest = (int(bool(silu)), float(eps), ptr(residual), ptr(residual2), ptr(ws), ws.numel() * 8, ps, nbytes, jobs, C_.byref(nj))
+    if dropout is None:
+        check(lib().msgm_groupnorm_dual_backward_slots(ptr(f32(x0)), C0, ptr(x1), C1, *params, ptr(gx0), ptr(gx1), ptr(dgamma),
+                                                       ptr(dbeta), Bp, P, G, *rest, stream()), "msgm_groupnorm_dual_backward_slots")
+    else:
+        check(lib().msgm_groupnorm_dual_backward_slots_dropout(ptr(f32(x0)), *params, ptr(gx0), ptr(dgamma), ptr(dbeta), Bp, P, C, G,
+                                                               *rest, C_.byref(dropout), stream()),
+              "msgm_groupnorm_dual_backward_slots_dropout")
     d.add(jobs, nj.value, (dgamma, dbeta))
 
 
@@ -795,18 +786,12 @@ def groupnorm_dual_backward(x, gamma, beta, stats, gout, dgamma, dbeta, Bp, P, C
     if (residual is not None and residual.numel() != x.numel()) or (residual2 is not None and residual2.numel() != x.numel()):
         raise MsgmError("groupnorm backward: residual size")
     d = DeferredReduces.active
-    if dropout is not None:
-        if d is not None and d.device == x.device:
-            _gn_backward_dropout(x, gamma, beta, stats, gout, gx, dgamma, dbeta, Bp, P, C, G, silu, eps, residual, residual2,
-                                 dropout, d)
-        else:
-            with DeferredReduces.on(x.device) as d1:
-                _gn_backward_dropout(x, gamma, beta, stats, gout, gx, dgamma, dbeta, Bp, P, C, G, silu, eps, residual, residual2,
-                                     dropout, d1)
-        return gx
-    if d is not None and d.device == x.device:
-        _gn_backward_slots(x, C, None, 0, gamma, beta, stats, gout, gx, None, dgamma, dbeta, Bp, P, G, silu, eps, residual, d,
-                           residual2=residual2)
+    in_pass = d is not None and d.device == x.device
+    if dropout is not None or in_pass:
+        # the slots form; dropout has no other, so outside a pass on this device it opens one of its own
+        with (contextlib.nullcontext(d) if in_pass else DeferredReduces.on(x.device)) as dp:
+            _gn_backward_in_pass(x, C, None, 0, gamma, beta, stats, gout, gx, None, dgamma, dbeta, Bp, P, G, silu, eps, residual, dp,
+                                 residual2=residual2, dropout=dropout)
         return gx
     ws = _gn_ws(Bp, G, x.device)
     check(lib().msgm_groupnorm_dual_backward(ptr(f32(x)), ptr(f32(gamma)), ptr(f32(beta)), ptr(f32(stats)), ptr(f32(gout)),
@@ -837,7 +822,7 @@ def groupnorm_dual_backward2(x0, C0, x1, C1, gamma, beta, stats, gout, dgamma, d
     gx0, gx1 = torch.empty_like(x0), torch.empty_like(x1)
     d = DeferredReduces.active
     if d is not None and d.device == x0.device:
-        _gn_backward_slots(x0, C0, x1, C1, gamma, beta, stats, gout, gx0, gx1, dgamma, dbeta, Bp, P, G, silu, eps, None, d)
+        _gn_backward_in_pass(x0, C0, x1, C1, gamma, beta, stats, gout, gx0, gx1, dgamma, dbeta, Bp, P, G, silu, eps, None, d)
         return gx0, gx1
     ws = _gn_ws(Bp, G, x0.device)
     check(lib().msgm_groupnorm_dual_backward2(ptr(f32(x0)), C0, ptr(f32(x1)), C1, ptr(f32(gamma)), ptr(f32(beta)), ptr(f32(stats)),

@@ -18,7 +18,7 @@ def cl(x):    # (N,C,H,W) -> [N][H*W][C] flat
     return x.permute(0, 2, 3, 1).contiguous().reshape(-1)
 
 
-@pytest.mark.parametrize("C,H,silu", [(32, 8, True), (64, 4, True), (96, 8, True), (192, 4, True), (256, 4, False), (128, 16, False)])
+@pytest.mark.parametrize("C,H,silu", [(32, 8, True), (64, 4, True), (96, 8, True), (192, 4, True), (256, 4, False), (128, 16, False), (6, 8, True)])
 def test_groupnorm_dual_forward_backward(C, H, silu):
     from sdeflow_light_amd import ops
     torch.manual_seed(C)
