@@ -1189,30 +1189,142 @@ __device__ __forceinline__ void wino_mfma_lds(f32x4 (&acc)[16][2], const f32x4 (
   }
 }
 
-// Output transform Y = A^T M A per (tile, co quad) and the epilogue of k_conv_tile (bias / per-sample bias / accumulate /
-// residual / channel statistics), 2x2 pixels x 4 consecutive output channels per lane and co tile; shared by every
-// Winograd kernel, so their results agree bit for bit for the same accumulators.
+// Output transform Y = A^T M A of one co tile: the lane's 2x2 pixels (p = 2 dy + dx) x 4 consecutive output channels.
 template <int NCO>
-__device__ __forceinline__ void wino_epilogue(const ConvArgs& A, const f32x4 (&acc)[16][NCO], int n, int y0, int x0, int ty, int tx,
+__device__ __forceinline__ void wino_output_transform(const f32x4 (&acc)[16][NCO], int c, f32x4 (&Y)[4]) {
+  f32x4 t0[4], t1[4];
+#pragma unroll
+  for (int nu = 0; nu < 4; ++nu) {
+    t0[nu] = acc[nu][c] + acc[4 + nu][c] + acc[8 + nu][c];
+    t1[nu] = acc[4 + nu][c] - acc[8 + nu][c] - acc[12 + nu][c];
+  }
+  Y[0] = t0[0] + t0[1] + t0[2]; Y[1] = t0[1] - t0[2] - t0[3];
+  Y[2] = t1[0] + t1[1] + t1[2]; Y[3] = t1[1] - t1[2] - t1[3];
+}
+__device__ __attribute__((aligned(16))) float g_wino_zero[4];  // what an out-of-image halo slot or an absent bias row fetches
+
+// The epilogue of an item whose NCO x 16 output channels all exist (Cout % 4 == 0): straight-line for one combination of the
+// options.  With the options tested per pixel (conv_addend / conv_store_quad) hipcc drains vmcnt behind every test and in front
+// of every store: 8 to 18 serial memory round trips per item, each of which also drains the next item's LDS-DMAs.  Here the
+// loads of a co tile (addend rows, accumulate and residual quads of its 4 pixels) are issued together, those of co tile c + 1
+// as soon as the output transform of tile c has freed its accumulators, and the stores of the item follow one another
+// without a wait.  With both accumulate and residual set (10 quads per co tile) the two co tiles run one after the other,
+// each transformed before its loads: requested beside all the accumulators they made hipcc spill in k_conv_wino_pipe.
+// ADD: a bias or per-sample bias row applies to sample n; an absent one of the two reads g_wino_zero and is not added.
+// The arithmetic is conv_addend's and conv_store_quad's, in their order: ((Y + add) + out) + residual, statistics of the result.
+template <int NCO, bool ADD, bool ACC, bool RES>
+__device__ __forceinline__ void wino_epilogue_full(const ConvArgs& A, const f32x4 (&acc)[16][NCO], int n, size_t e00, int co,
+                                                   int slot, int il) {
+  constexpr bool SERIAL = ACC && RES;
+  const size_t row = (size_t)A.g.Wo * A.Cout;
+  const size_t pe[4] = {0, (size_t)A.Cout, row, row + A.Cout};          // pixel p = 2 dy + dx of the lane's 2x2
+  const bool hasb = A.bias && n < A.n_bias, hass = A.samp_bias && n < A.n_samp;
+  f32x4 b[NCO], s[NCO], o[NCO][4], rs[NCO][4], v[NCO][4], cs[NCO], css[NCO];
+  auto loads = [&](int c) __attribute__((always_inline)) {
+    if constexpr (ADD) {
+      b[c] = *reinterpret_cast<const f32x4*>(hasb ? A.bias + co + 16 * c : g_wino_zero);
+      s[c] = *reinterpret_cast<const f32x4*>(hass ? A.samp_bias + (size_t)n * A.Cout + co + 16 * c : g_wino_zero);
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      if constexpr (ACC) o[c][p] = *reinterpret_cast<const f32x4*>(A.out + e00 + pe[p] + 16 * c);
+      if constexpr (RES) rs[c][p] = *reinterpret_cast<const f32x4*>(A.residual + e00 + pe[p] + 16 * c);
+    }
+    __builtin_amdgcn_sched_barrier(0);                     // the loads stay in front of the transform that follows
+  };
+  auto finish = [&](int c) __attribute__((always_inline)) {
+    f32x4 add = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (ADD) {
+      if (hasb) add = b[c];
+      if (hass) add += s[c];
+    }
+    cs[c] = f32x4{0.f, 0.f, 0.f, 0.f}; css[c] = cs[c];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      f32x4 x = v[c][p] + add;
+      if constexpr (ACC) x += o[c][p];
+      if constexpr (RES) x += rs[c][p];
+      v[c][p] = x;
+      cs[c] += x; css[c] += x * x;
+    }
+  };
+  auto stores = [&](int c) __attribute__((always_inline)) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4*>(A.out + e00 + pe[p] + 16 * c) = v[c][p];
+  };
+  // the wave's 16 Winograd tiles = 64 pixels: one statistics slot, as the direct kernel's 16x16 tiles
+  if constexpr (SERIAL) {
+#pragma unroll
+    for (int c = 0; c < NCO; ++c) {
+      wino_output_transform<NCO>(acc, c, v[c]);
+      __builtin_amdgcn_sched_barrier(0);
+      loads(c);
+      finish(c);
+      __builtin_amdgcn_sched_barrier(0);
+      stores(c);
+      if (A.cstat) cstat_store(A, n, slot, co + 16 * c, cs[c], css[c], il);
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < NCO; ++c) {
+      loads(c);
+      wino_output_transform<NCO>(acc, c, v[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < NCO; ++c) finish(c);
+    __builtin_amdgcn_sched_barrier(0);                     // every value is final: the stores go out back to back
+#pragma unroll
+    for (int c = 0; c < NCO; ++c) stores(c);
+    if (A.cstat) {
+#pragma unroll
+      for (int c = 0; c < NCO; ++c) cstat_store(A, n, slot, co + 16 * c, cs[c], css[c], il);
+    }
+  }
+}
+
+// Output transform and the epilogue of k_conv_tile (bias / per-sample bias / accumulate / residual / channel statistics),
+// 2x2 pixels x 4 consecutive output channels per lane and co tile; shared by every Winograd kernel, so their results agree bit
+// for bit for the same accumulators.  The options are uniform over an item: they are branched on once, around the
+// straight-line bodies of wino_epilogue_full; an output-channel block with absent or ragged quads (Cout % 4 != 0, or the
+// block reaches past Cout) keeps the per-quad form.  Ho % 16 == 0 and Wo % 16 == 0 in every caller (conv_wino_eligible), so
+// every pixel of a tile exists and the full bodies carry no bounds tests.
+// The wait states for the VALU reads of the callers' last MFMA results are written out here: the epilogue is a branch
+// target, where hipcc has been seen to insert none.
+// The lane's coordinates (wave w, lane: Winograd tile 16 w + (lane & 15) of the 8x8) are derived here from a lane id the
+// optimiser cannot see through: hoisted out of the callers' loops, the epilogue's per-lane offsets cost them registers.
+template <int NCO>
+__device__ __forceinline__ void wino_epilogue(const ConvArgs& A, const f32x4 (&acc)[16][NCO], int n, int y0, int x0, int w,
                                               int co0, int slot, int lane) {
+  asm volatile("s_nop 15\n\ts_nop 7" : "+v"(lane) :: "memory");
+  __builtin_amdgcn_sched_barrier(0);
   const ConvGeom g = A.g;
-  const int il = lane & 15, q = lane >> 4;
+  const int il = lane & 15, q = lane >> 4, ty = 2 * w + (il >> 3), tx = il & 7;
   const bool vec = (A.Cout & 3) == 0;
+  if (vec && co0 + 16 * NCO <= A.Cout) {
+    const int co = co0 + 4 * q;
+    const size_t e00 = (((size_t)n * g.Ho + (y0 + 2 * ty)) * g.Wo + (x0 + 2 * tx)) * A.Cout + co;
+    const bool add = (A.bias && n < A.n_bias) || (A.samp_bias && n < A.n_samp);
+    // (five bodies, not eight: beside accumulate or residual quads the addend rows ride along, and every further body cost
+    // the sampler kernels registers)
+    switch ((A.accumulate ? 1 : 0) | (A.residual ? 2 : 0)) {
+      case 0:
+        if (add) wino_epilogue_full<NCO, true, false, false>(A, acc, n, e00, co, slot, il);
+        else wino_epilogue_full<NCO, false, false, false>(A, acc, n, e00, co, slot, il);
+        break;
+      case 1: wino_epilogue_full<NCO, true, true, false>(A, acc, n, e00, co, slot, il); break;
+      case 2: wino_epilogue_full<NCO, true, false, true>(A, acc, n, e00, co, slot, il); break;
+      default: wino_epilogue_full<NCO, true, true, true>(A, acc, n, e00, co, slot, il); break;
+    }
+    return;
+  }
 #pragma unroll
   for (int c = 0; c < NCO; ++c) {
     const int co = co0 + 16 * c + 4 * q;
     if (co >= A.Cout) continue;
     const bool full = vec && (co + 3 < A.Cout);
     const f32x4 add = conv_addend(A, n, co, full);
-    f32x4 t0[4], t1[4];
-#pragma unroll
-    for (int nu = 0; nu < 4; ++nu) {
-      t0[nu] = acc[nu][c] + acc[4 + nu][c] + acc[8 + nu][c];
-      t1[nu] = acc[4 + nu][c] - acc[8 + nu][c] - acc[12 + nu][c];
-    }
-    f32x4 Y[2][2];
-    Y[0][0] = t0[0] + t0[1] + t0[2]; Y[0][1] = t0[1] - t0[2] - t0[3];
-    Y[1][0] = t1[0] + t1[1] + t1[2]; Y[1][1] = t1[1] - t1[2] - t1[3];
+    f32x4 Y[4];
+    wino_output_transform<NCO>(acc, c, Y);
     f32x4 cs = {0.f, 0.f, 0.f, 0.f}, css = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy)
@@ -1221,7 +1333,7 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs& A, const f32x4 (&a
         const int oy = y0 + 2 * ty + dy, ox = x0 + 2 * tx + dx;
         if (oy >= g.Ho || ox >= g.Wo) continue;
         const size_t m = ((size_t)n * g.Ho + oy) * g.Wo + ox;
-        conv_store_quad(A, A.out + m * A.Cout + co, Y[dy][dx] + add, full, co, cs, css);
+        conv_store_quad(A, A.out + m * A.Cout + co, Y[2 * dy + dx] + add, full, co, cs, css);
       }
     // the wave's 16 Winograd tiles = 64 pixels: one statistics slot, as the direct kernel's 16x16 tiles (Cout % 4 == 0, host)
     if (A.cstat) cstat_store(A, n, slot, co, cs, css, il);
@@ -1374,7 +1486,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino(ConvArgs A, int tiles_x, i
       }
     }
 
-  wino_epilogue<NCO>(A, acc, n, y0, x0, ty, tx, co0, (tile - n * tiles_x * tiles_y) * 4 + w, lane);
+  wino_epilogue<NCO>(A, acc, n, y0, x0, w, co0, (tile - n * tiles_x * tiles_y) * 4 + w, lane);
 }
 
 // ------------------------------------------------------------------ Winograd, 32 input channels: persistent workgroups
@@ -1448,7 +1560,7 @@ __global__ void __launch_bounds__(256, 1) k_conv_wino_p32(ConvArgs A, int tiles_
     // ---- output transform and epilogue (as k_conv_wino)
     int n, y0, x0;
     tile_origin<16, 16>(t, tiles_x, tiles_y, n, y0, x0);
-    wino_epilogue<NCO>(A, acc, n, y0, x0, ty, tx, 0, (t - n * tiles_x * tiles_y) * 4 + w, lane);
+    wino_epilogue<NCO>(A, acc, n, y0, x0, w, 0, (t - n * tiles_x * tiles_y) * 4 + w, lane);
     if (more) halo18_store(A, nxt, tid, st, valid, ga, gb);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");               // the other buffer is complete; this one is free
     float* sw = cur; cur = nxt; nxt = sw;
@@ -1476,7 +1588,6 @@ __global__ void __launch_bounds__(256, 1) k_conv_wino_p32(ConvArgs A, int tiles_
 constexpr int WP_HPIECES = 21;                                // ceil(18 * 18 pixels * 4 quads / 64 lanes)
 constexpr int WP_HSTAGE = WP_HPIECES * 64 * 4;                // floats per halo stage
 constexpr int WP_LDS_BYTES = (2 * 4096 + 2 * WP_HSTAGE) * (int)sizeof(float);
-__device__ __attribute__((aligned(16))) float g_wino_zero[4];  // what an out-of-image (or padding) halo slot fetches
 
 __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles_x, int tiles_y, int n_tiles, int n_cob) {
   extern __shared__ __attribute__((aligned(16))) float cw_lds[];
@@ -1504,7 +1615,17 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
   };
   // channel group grp_'s halo of tile tile_ into stage b: wave w copies pieces w, w + 4, ... (6 for wave 0, 5 for the others)
   // (branch-free: the source of each lane is a select between its pixel and the zero row)
+  // The decode of a piece's slot does not change during the kernel: halo pixel (hy, hx) and channel quad c of lane l in piece
+  // m = w + 4 j, packed in ONE register per piece (hy << 16 | hx << 2 | c; a slot past the 18 x 18 pixels gets a row outside
+  // every image) and unpacked per group behind an asm the optimiser cannot hoist — kept apart, the decoded values of the six
+  // pieces occupy registers the MFMA loop has no room for.
   const int Hu = g.Hi << up, Wu = g.Wi << up;
+  int hpk[(WP_HPIECES + 3) / 4];
+#pragma unroll
+  for (int j = 0; j < (WP_HPIECES + 3) / 4; ++j) {
+    const int sl = 64 * (w + 4 * j) + lane, P = sl >> 2, c = (sl & 3) ^ ((P >> 1) & 3), hy = P / HW, hx = P - hy * HW;
+    hpk[j] = P < HW * HW ? (hy << 16) | (hx << 2) | c : 0x7fff << 16;
+  }
   auto hfill = [&](int tile_, int grp_, int b) __attribute__((always_inline)) {
     const int n = tile_ / tpi, r = tile_ - n * tpi, ty_i = r / tiles_x, y0 = ty_i * 16, x0 = (r - ty_i * tiles_x) * 16;
     const bool s1 = 16 * grp_ >= A.C[0];                    // channel groups of the second source follow the first's (C0 % 16 == 0)
@@ -1514,9 +1635,10 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
     for (int j = 0; j < (WP_HPIECES + 3) / 4; ++j) {
       const int m = w + 4 * j;
       if (m < WP_HPIECES) {
-        const int sl = 64 * m + lane, P = sl >> 2, c = (sl & 3) ^ ((P >> 1) & 3);
-        const int hy = P / HW, hx = P - hy * HW, iy = y0 + hy - 1, ix = x0 + hx - 1;
-        const bool in = P < HW * HW && (unsigned)iy < (unsigned)Hu && (unsigned)ix < (unsigned)Wu;
+        int pk = hpk[j];
+        asm volatile("" : "+v"(pk));
+        const int c = pk & 3, iy = y0 + (pk >> 16) - 1, ix = x0 + ((pk >> 2) & 31) - 1;
+        const bool in = (unsigned)iy < (unsigned)Hu && (unsigned)ix < (unsigned)Wu;
         const float* p = in ? base + (((iy >> up) * g.Wi + (ix >> up)) * C + 4 * c) : g_wino_zero;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p,
                                          (__attribute__((address_space(3))) void*)(hbuf + b * WP_HSTAGE + m * 256), 16, 0, 0);
@@ -1601,12 +1723,9 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
       }
     }
     if (ngrp_ == 0) {
-      // ---- the item is complete.  Wait states for the VALU reads of the last MFMAs' results are written out: the epilogue is
-      //      a branch target, where hipcc has been seen to insert none
-      asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      // ---- the item is complete (wino_epilogue opens with the wait states for the last MFMAs' results)
       const int n = tile / tpi, r = tile - n * tpi, ty_i = r / tiles_x;
-      wino_epilogue<NCO>(A, acc, n, ty_i * 16, (r - ty_i * tiles_x) * 16, ty, tx, cob * (NCO * 16), r * 4 + w, lane);
+      wino_epilogue<NCO>(A, acc, n, ty_i * 16, (r - ty_i * tiles_x) * 16, w, cob * (NCO * 16), r * 4 + w, lane);
       if (!more) break;
 #pragma unroll
       for (int p = 0; p < 16; ++p)

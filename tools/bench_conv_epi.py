@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""GPU box: what the epilogue options of the 3x3 halo-tile conv cost (plain / residual / accumulate / stats), sampler shapes."""
+"""GPU box: what the epilogue options of the 3x3 halo-tile conv cost (plain / residual / accumulate / stats), sampler shapes.
+The Winograd kernels' epilogue options are timed against the parent build by tools/conv_vs_parent.py --only k_conv_wino --time."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sdeflow_light_amd import ops

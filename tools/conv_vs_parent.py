@@ -5,6 +5,8 @@ libmsgm_hip.so, built into a scratch path), both loaded into one process:
     python tools/conv_vs_parent.py <parent.so> --time [out.json] [name=variant.so ...]
                                                                     timing: parent / parent again / this tree (/ further builds,
                                                                     e.g. a form that was tried and rejected), alternated
+    python tools/conv_vs_parent.py <parent.so> --only k_conv_wino [--time ...]
+                                                                    either mode, only the cases whose kernel name contains the word
 Every case runs on the same inputs through the same entry points (SIGNATURES of _lib.py); outputs start NaN-filled (or from
 the same random values where the call accumulates), so a skipped store shows.  The cases are chosen to reach
 every k_conv_tile form, k_dgrad_s2, k_conv3x3_cout_small, k_conv_wino (register / LDS weights), k_conv_wino_p32 and
@@ -12,7 +14,7 @@ k_conv_wino_pipe.  The kernel name printed with a case is what this script EXPEC
 for it (their conditions, restated here), not something observed: check it against a kernel trace if the routing changes.
 A diagnostic: it swaps the library under ops.* (tools/parent_compare.py, shared with wgrad_vs_parent.py) and takes the C4 call
 list from tests/test_wino_pipe_gpu.py."""
-import sys, time
+import itertools, sys, time
 
 import torch
 
@@ -20,6 +22,11 @@ from parent_compare import load, use, test_module, timed_rounds, timing_line, wr
 from sdeflow_light_amd import _lib, ops  # noqa: E402
 
 DEV = "cuda"
+ONLY = ""
+if "--only" in sys.argv:
+    i = sys.argv.index("--only")
+    ONLY = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
 NEW = _lib.lib()
 PARENT = load(sys.argv[1])
 
@@ -159,6 +166,17 @@ def wino_cases():
     # the persistent 32 -> 32 form: 1040 tiles (a ragged last round), real affine + SiLU
     cases.append(Case("k_conv_wino_p32", N=65, Hi=64, Wi=64, Ho=64, Wo=64, KH=3, KW=3, C0=32, Cout=32, wino=True, bias=True, samp=True,
                       res=True, stats=True, aff=True, act=1, seed=6000))
+    # every body of the shared epilogue (wino_epilogue: each subset of bias / per-sample bias / accumulate / residual, with and
+    # without statistics) on every kernel that calls it; Cout = 30 takes the per-quad path (no statistics: Cout % 4 != 0)
+    rows = [(3, 32, 16, 16, 32, 32, None), (3, 16, 32, 0, 64, 64, None), (3, 16, 16, 0, 30, 32, None),     # k_conv_wino_pipe
+            (3, 32, 32, 0, 32, 32, "identity"), (3, 32, 64, 0, 64, 64, "identity"), (3, 16, 32, 0, 30, 32, "identity"),
+            (256, 32, 32, 0, 32, 32, "identity")]                                                           # 1024 tiles: k_conv_wino_p32
+    for i, (N, H, C0, C1, Cout, CoutP, aff) in enumerate(rows):
+        for k, o in enumerate(itertools.product((False, True), repeat=4)):
+            for stats in ((False, True) if Cout % 4 == 0 and N < 256 else (Cout % 4 == 0,)):
+                cases.append(Case(wino_kernel(C0, C1, CoutP, N, H, aff), N=N, Hi=H, Wi=H, Ho=H, Wo=H, KH=3, KW=3, C0=C0, C1=C1, Cout=Cout,
+                                  CoutP=CoutP, wino=True, bias=o[0], samp=o[1], acc=o[2], res=o[3], stats=stats, aff=aff,
+                                  seed=7000 + 100 * i + k))
     return cases
 
 
@@ -167,6 +185,8 @@ def bitwise():
     n = bad = 0
     for group in (tile_cases, small_cases, wino_cases):
         for c in group():
+            if ONLY not in c.kernel:
+                continue
             o_p, s_p = c.run(PARENT)
             o_n, s_n = c.run(NEW)
             torch.cuda.synchronize()
@@ -188,6 +208,12 @@ def time_cases():
             yield Case(wino_kernel(C0, C1, Co, N, H, aff), N=N, Hi=H, Wi=H, Ho=H, Wo=H, KH=3, KW=3, C0=C0, C1=C1, Cout=Co, wino=True,
                        aff=aff, act=1 if aff else 0, seed=H + C0)
     B = 512                                                # the C4 step: 256 samples, primal + tangent rows
+    # its Winograd shapes through k_conv_wino_pipe, with the option sets of the step: a dgrad or tangent-only call (plain), a
+    # ResBlock's conv1 (bias + per-sample bias) and conv2 (bias + residual), a dgrad that accumulates
+    for (H, C0, C1, Co) in ((64, 32, 0, 32), (64, 64, 32, 32), (32, 64, 0, 64), (32, 128, 64, 64), (16, 128, 0, 128), (16, 128, 128, 128)):
+        for j, o in enumerate((dict(), dict(bias=True, samp=True, stats=True), dict(bias=True, res=True, stats=True), dict(acc=True))):
+            yield Case(wino_kernel(C0, C1, Co, B, H, None), N=B, Hi=H, Wi=H, Ho=H, Wo=H, KH=3, KW=3, C0=C0, C1=C1, Cout=Co, wino=True,
+                       seed=8000 + H + C0 + j, **o)
     full = dict(bias=True, res=True, stats=True)
     for (H, C0, C1, Co) in ((64, 32, 0, 32), (32, 64, 0, 64), (32, 64, 32, 64), (16, 128, 0, 128), (8, 128, 0, 128)):
         nco = 4 if Co % 64 == 0 else 2
@@ -221,6 +247,8 @@ def timing(path, variants):
     ROUNDS, REPS, WARM = 7, 20, 5
     rows = []
     for c in time_cases():
+        if ONLY not in c.kernel:
+            continue
         out, cs = c.run(NEW)                               # buffers reused by every timed launch
         row = timed_rounds(lambda h: c.run(h, out, cs), PARENT, [("new", NEW)] + variants, ROUNDS, REPS, WARM)
         rows.append(dict(kernel=c.kernel, case=c.desc, **row))
