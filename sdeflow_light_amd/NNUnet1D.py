@@ -14,7 +14,7 @@ backward.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -106,6 +106,18 @@ class UNet1D(nn.Module, FlatParamMixin):
         return o
 
     # ------------------------------------------------------------------ pipeline
+    # tape records of _run, in the order _backward meets them reversed.  The embedding MLPs (first on the tape): pre = (logr, zs,
+    # hs_) of the log-radius MLP or None, er = rows that carry an embedding
+    EmbRec = NamedTuple("EmbRec", [("tt", torch.Tensor), ("ze", torch.Tensor), ("he", torch.Tensor), ("emb", torch.Tensor),
+                                   ("pre", Optional[tuple]), ("er", int)])
+    # a ConvBlock1D (ops ka, kb) on srcs at length Lc: conv -> z1 -> GELU -> h1 -> conv -> z2 -> GELU
+    BlockRec = NamedTuple("BlockRec", [("ka", str), ("kb", str), ("srcs", List[torch.Tensor]), ("Lc", int), ("z1", torch.Tensor),
+                                       ("h1", torch.Tensor), ("z2", torch.Tensor)])
+    DownRec = NamedTuple("DownRec", [("k", str), ("h", torch.Tensor), ("Lc", int)])          # op k on h at length Lc
+    # op k on h at length Lc; its output was zero-padded from pad_from to Ls positions (pad_from None: the lengths agreed)
+    UpRec = NamedTuple("UpRec", [("k", str), ("h", torch.Tensor), ("Lc", int), ("pad_from", Optional[int]), ("Ls", int)])
+    FinRec = NamedTuple("FinRec", [("h", torch.Tensor), ("Lc", int)])
+
     def _run(self, h0: torch.Tensor, t: torch.Tensor, N: int, Bp: int, L: int, dual: bool, tape: Optional[list]):
         """h0: [N][L][1] (primal rows then tangent rows).  Returns [N][L] output."""
         o = self._build()
@@ -131,14 +143,14 @@ class UNet1D(nn.Module, FlatParamMixin):
             ops.lincomb(pv, pv, 1.0, emb, 1.0)                      # t_emb + scale_vec        NNUnet1D.py:145
             pre = (logr, zs, hs_)
             emb, er = sv, N
-        rec(("emb", tt, ze, he, emb, pre, er))
+        rec(self.EmbRec(tt, ze, he, emb, pre, er))
 
         def block(ka, kb, srcs, Lc):
             z1, _, _ = o[ka].forward(srcs, N, 1, Lc, Bp, emb=emb, emb_rows=er)
             h1 = act(z1)
             z2, _, _ = o[kb].forward([h1], N, 1, Lc, Bp)
             h2 = act(z2)
-            rec(("block", ka, kb, srcs, Lc, z1, h1, z2))
+            rec(self.BlockRec(ka, kb, srcs, Lc, z1, h1, z2))
             return h2
 
         h, Lc = h0, L
@@ -147,7 +159,7 @@ class UNet1D(nn.Module, FlatParamMixin):
             h = block(f"e{i}a", f"e{i}b", [h], Lc)
             skips.append((h, Lc))
             hd, _, Ld = o[f"d{i}"].forward([h], N, 1, Lc, Bp)
-            rec(("down", f"d{i}", h, Lc))
+            rec(self.DownRec(f"d{i}", h, Lc))
             h, Lc = hd, Ld
         h = block("ma", "mb", [h], Lc)
         for i in range(nl):
@@ -159,11 +171,11 @@ class UNet1D(nn.Module, FlatParamMixin):
                 upp = torch.zeros(N, Ls, C, device=dev)
                 upp[:, :Lu].copy_(up.view(N, Lu, C))
                 pad_from, up = Lu, upp.view(-1)
-            rec(("up", f"u{i}", h, Lc, pad_from, Ls))
+            rec(self.UpRec(f"u{i}", h, Lc, pad_from, Ls))
             h = block(f"x{i}a", f"x{i}b", [up, skip], Ls)
             Lc = Ls
         out, _, _ = o["fin"].forward([h], N, 1, Lc, Bp)
-        rec(("fin", h, Lc))
+        rec(self.FinRec(h, Lc))
         return out
 
     @torch.no_grad()
@@ -208,44 +220,36 @@ class UNet1D(nn.Module, FlatParamMixin):
         o = self._ops
         dev = g.device
         E = self.emb_dim
-        emb_rec = tape[0]
-        emb, pre, er = emb_rec[4], emb_rec[5], emb_rec[6]
+        tt, ze, he, emb, pre, er = tape[0]
         demb = torch.zeros(er * E, device=dev)
         pending_skip = []                      # gradients w.r.t. skip tensors, consumed by the encoder
         dh = g
         for r in reversed(tape[1:]):
-            kind = r[0]
-            if kind == "fin":
-                _, h, Lc = r
-                (dh,) = o["fin"].backward(dh, [h], N, 1, Lc, Bp)
-            elif kind == "block":
-                _, ka, kb, srcs, Lc, z1, h1, z2 = r
-                g2 = ops.act_dual_backward(GELU, z2, dh)
-                (dh1,) = o[kb].backward(g2, [h1], N, 1, Lc, Bp)
-                g1 = ops.act_dual_backward(GELU, z1, dh1)
-                first = ka == "e0a"
-                ds = o[ka].backward(g1, srcs, N, 1, Lc, Bp, emb=emb, demb=demb, need=[not first] + [True] * (len(srcs) - 1),
-                                    emb_rows=er)
-                if len(srcs) == 2:
+            if isinstance(r, self.FinRec):
+                (dh,) = o["fin"].backward(dh, [r.h], N, 1, r.Lc, Bp)
+            elif isinstance(r, self.BlockRec):
+                g2 = ops.act_dual_backward(GELU, r.z2, dh)
+                (dh1,) = o[r.kb].backward(g2, [r.h1], N, 1, r.Lc, Bp)
+                g1 = ops.act_dual_backward(GELU, r.z1, dh1)
+                first = r.ka == "e0a"
+                ds = o[r.ka].backward(g1, r.srcs, N, 1, r.Lc, Bp, emb=emb, demb=demb,
+                                      need=[not first] + [True] * (len(r.srcs) - 1), emb_rows=er)
+                if len(r.srcs) == 2:
                     pending_skip.append(ds[1])
                 dh = ds[0]
-            elif kind == "up":
-                _, ku, h, Lc, pad_from, Ls = r
-                if pad_from is not None:
-                    C = o[ku].Cout
-                    dh = dh.view(N, Ls, C)[:, :pad_from].contiguous().view(-1)
-                (dh,) = o[ku].backward(dh, [h], N, 1, Lc, Bp)
-            elif kind == "down":
-                _, kd, h, Lc = r
+            elif isinstance(r, self.UpRec):
+                if r.pad_from is not None:
+                    dh = dh.view(N, r.Ls, o[r.k].Cout)[:, :r.pad_from].contiguous().view(-1)
+                (dh,) = o[r.k].backward(dh, [r.h], N, 1, r.Lc, Bp)
+            elif isinstance(r, self.DownRec):
                 dskip = pending_skip.pop()
-                (dh,) = o[kd].backward(dh, [h], N, 1, Lc, Bp, dsrc=[dskip], dacc=[True])
+                (dh,) = o[r.k].backward(dh, [r.h], N, 1, r.Lc, Bp, dsrc=[dskip], dacc=[True])
         if pre is not None:                    # log-radius embedding (primal | tangent rows): Linear -> GELU -> Linear
             logr, zs, hs_ = pre
             (dhs,) = o["s2"].backward(demb, [hs_], N, 1, 1, Bp)
             ops.act_dual_backward(GELU, zs, dhs)
             o["s0"].backward(dhs, [logr], N, 1, 1, Bp, need=[False])
         # time MLP (primal rows only): Linear -> GELU -> Linear
-        tt, ze, he = emb_rec[1], emb_rec[2], emb_rec[3]
         (dhe,) = o["t2"].backward(demb[: Bp * E].contiguous(), [he], Bp, 1, 1, Bp)
         zz = torch.cat([ze, torch.zeros_like(ze)])
         gg = torch.cat([dhe, torch.zeros_like(dhe)])
