@@ -1,8 +1,76 @@
 // sde_kernels.hip — HBM-bound elementwise / row-reduced kernels of the SDE
 // hot path (K1 perturb_vp, K2/K3/K4 integrator stages, K13 Adam, helpers).
-// gfx950 only.  Reference lines are cited per kernel (relative to
-// /root/reference).
+// gfx950 only.  Reference lines are cited per kernel (relative to the
+// reference project's root).
+//
+// Phases that more than one kernel runs are ONE __device__ function each ("SDE kernels, shared
+// phases"); the build keeps -ffp-contract=off, so two kernels that call the same function give the same bits.
 #include "common.h"
+#include <type_traits>
+
+// ============================================================ shared pieces
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+// every pointer 16-byte aligned (a null pointer counts as aligned: optional operands)
+template <typename... P>
+__host__ __device__ __forceinline__ bool aligned16(P... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }
+
+// Sum over the GS lanes that share a row.  GS <= 64: a lane group inside a wave (xor tree).  GS = 256: the whole workgroup
+// owns the row (long rows: n >= 2048 — 12288-element images have too few rows per launch to fill the chip with 64-lane
+// groups: 32 rows were 8 workgroups and 67-82 us per launch); wave sums meet through LDS in a fixed order.  The group size
+// depends on n only, never on the batch: a row's sum is the same bits in every batch size.
+template <int GS>
+__device__ __forceinline__ float group_sum(float v) {
+  if constexpr (GS <= 64) {
+#pragma unroll
+    for (int o = GS >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, GS);
+    return v;
+  } else {
+    __shared__ float red[4];
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float r = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return r;
+  }
+}
+
+// Row-group iteration of the row kernels: a group of GS lanes owns a row,
+//   const RowGroup<GS> rg(B, blockDim.x);  for (int64_t b = rg.first; b < rg.rows_pad; b += rg.stride) { live = b < B; ... }
+// The row range is padded to a multiple of the number of groups in the grid, so every group makes the same number of trips
+// and the shuffles and __syncthreads of group_sum stay convergent; a padded row (b >= B, not live) touches no memory, it only
+// takes part in the reduction.  The kernel hands blockDim.x in: read inside a device function it compiles to a second,
+// slower load path, and the loop stays in the kernel: as a function taking the row's work as a lambda it read SLOWER in five
+// of the six kernels (profiles/README.md).
+template <int GS>
+struct RowGroup {
+  int lane;
+  int64_t first, stride, rows_pad;
+  __device__ __forceinline__ RowGroup(int64_t B, unsigned block_dim) {
+    lane = threadIdx.x & (GS - 1);
+    const int64_t gpb = block_dim / GS;
+    first = blockIdx.x * gpb + threadIdx.x / GS;
+    stride = (int64_t)gridDim.x * gpb;
+    rows_pad = ((B + stride - 1) / stride) * stride;
+  }
+};
+
+// norm correction x <- x * norm0/||x|| (sde_scheme.py:85-86): ss is the lane's part of the row's sum of squares; every lane
+// rescales its own writes.  Called by live and padded rows alike (group_sum).
+template <int GS>
+__device__ __forceinline__ void norm_correct(float* out, const float* norm0, int64_t b, int64_t n, int lane, bool live, float ss) {
+  ss = group_sum<GS>(ss);
+  if (live) {
+    const float scale = norm0[b] / sqrtf(ss);
+    for (int64_t i = lane; i < n; i += GS) out[b * n + i] *= scale;   // own writes, same lane
+  }
+}
+
+// x + (k1 + 2k2 + 2k3 + k4)/6                                  sde_scheme.py:250-253
+__device__ __forceinline__ float rk4_value(float x, float k1, float k2, float k3, float k4) {
+  return x + (k1 + 2.0f * k2 + 2.0f * k3 + k4) / 6.0f;
+}
 
 // ============================================================ RNG helpers
 __global__ void k_rng_advance(uint64_t* rng, uint64_t n) { rng[1] += n; }
@@ -14,8 +82,8 @@ __global__ void k_fill(float* __restrict__ out, int64_t n, const uint64_t* __res
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
     f32x4 r = NORMAL ? philox_normal4(rng, 0, stream, q) : philox_uniform4(rng, 0, stream, q);
     int64_t e = q << 2;
-    if (e + 3 < n && ((reinterpret_cast<uintptr_t>(out) & 15) == 0)) {
-      *reinterpret_cast<f32x4*>(out + e) = r;
+    if (e + 3 < n && aligned16(out)) {
+      st4(out + e, r);
     } else {
       for (int k = 0; k < 4 && e + k < n; ++k) out[e + k] = r[k];
     }
@@ -37,52 +105,66 @@ __global__ void k_time_tick(const float* __restrict__ ts, const int64_t* __restr
 }
 
 // ============================================================ K1 perturb_vp
-// t_b = clamp(u_b T) (SDEs.py:688-693), y = eps*sqrt(var(t)) + mean_weight(t)*x0
-// (SDEs.py:139-142).  One thread per element-quad of the flat (B*d) tensor.
+// t_b = clamp(u_b T) (SDEs.py:688-693), y = eps*sqrt(var(t)) + mean_weight(t)*x0 (SDEs.py:139-142).  One thread per
+// element-quad of the flat (B*d) tensor.  k_perturb_vp and k_ssm_prep take a row's time from vp_row and an element's value
+// from vp_value: same streams, same indices, same bits.  The walk over the quad's elements stays written out in both: through
+// one function taking the per-element work as a lambda k_perturb_vp read SLOWER against the parent commit at 4096 x 12288
+// (+0.88 us of 188.8, where the parent differed from itself by 0.74: profiles/README.md); with these lines both kernels
+// are the parent's machine code.
+struct VpSde { float b0, b1, T, t_eps; };
+struct VpRow { float t, mw, sd; };
+
+// Row b's time — as given (SGMsde.sample(t, y0): no clamp, SDEs.py:134-146), or u_b T with u_b injected or drawn from
+// RNG_STREAM_T, clamped by mask arithmetic as upstream — and its mean weight and standard deviation (one Philox block + two exp).
+__device__ __forceinline__ VpRow vp_row(const VpSde& P, int64_t b, const uint64_t* __restrict__ rng, const float* __restrict__ u,
+                                        const float* __restrict__ t_given) {
+  float t;
+  if (t_given) {
+    t = t_given[b];
+  } else {
+    const float ub = u ? u[b] : philox_uniform1(rng, 0, RNG_STREAM_T, (uint64_t)b);
+    t = ub * P.T;
+    const float m = (t <= P.t_eps) ? 1.0f : 0.0f;
+    t = m * P.t_eps + (1.0f - m) * t;
+  }
+  return {t, vp_mean_weight(P.b0, P.b1, t), sqrtf(vp_var(P.b0, P.b1, t))};
+}
+__device__ __forceinline__ float vp_value(const VpRow& r, float eps, float x0) { return eps * r.sd + r.mw * x0; }
+
 __global__ void k_perturb_vp(const float* __restrict__ x0, float* __restrict__ y, float* __restrict__ t_out,
                              float* __restrict__ eps_out, int64_t B, int64_t d, float b0, float b1, float T,
                              float t_eps, const float* __restrict__ u, const float* __restrict__ eps,
                              const uint64_t* __restrict__ rng, const float* __restrict__ t_given) {
+  const VpSde P = {b0, b1, T, t_eps};
   const int64_t n = B * d;
   const int64_t nq = (n + 3) >> 2;
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e0 = q << 2;
     f32x4 ez;
     if (eps == nullptr) ez = philox_normal4(rng, 0, RNG_STREAM_EPS, q);
-    // the row's time (one Philox block + two exp) is evaluated once per row the quad touches, not once per element
+    // the row's time is evaluated once per row the quad touches, not once per element
     int64_t b_prev = -1;
-    float t = 0.f, mw = 0.f, sd = 0.f;
+    VpRow r = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int64_t e = e0 + k;
       if (e >= n) break;
       const int64_t b = e / d;
-      if (b != b_prev) {
-        if (t_given) {                                    // SGMsde.sample(t, y0): t used as given, no clamp (SDEs.py:134-146)
-          t = t_given[b];
-        } else {
-          const float ub = u ? u[b] : philox_uniform1(rng, 0, RNG_STREAM_T, (uint64_t)b);
-          t = ub * T;
-          const float m = (t <= t_eps) ? 1.0f : 0.0f;    // mask arithmetic as upstream
-          t = m * t_eps + (1.0f - m) * t;
-        }
-        mw = vp_mean_weight(b0, b1, t);
-        sd = sqrtf(vp_var(b0, b1, t));
-        b_prev = b;
-      }
-      float ee = eps ? eps[e] : ez[k];
-      y[e] = ee * sd + mw * x0[e];
+      if (b != b_prev) { r = vp_row(P, b, rng, u, t_given); b_prev = b; }
+      const float ee = eps ? eps[e] : ez[k];
+      y[e] = vp_value(r, ee, x0[e]);
       if (eps_out) eps_out[e] = ee;
-      if (t_out && e - b * d == 0) t_out[b] = t;
+      if (t_out && e - b * d == 0) t_out[b] = r.t;
     }
   }
 }
 
-// K1 + probe in one launch for the training step: y,t as k_perturb_vp, v = Rademacher
-// (SDEs.py:514-515,637-638), and (thread 0) the optimizer step counter tick.
+// K1 + probe in one launch for the training step: y,t as k_perturb_vp, v = Rademacher (SDEs.py:514-515,637-638), and
+// (thread 0) the optimizer step counter tick.  A kernel of its own: the training path carries no optional-pointer tests.
 __global__ void k_ssm_prep(const float* __restrict__ x0, float* __restrict__ y, float* __restrict__ t_out,
                            float* __restrict__ v, int64_t B, int64_t d, float b0, float b1, float T, float t_eps,
                            const uint64_t* __restrict__ rng, int64_t* step_ctr) {
+  const VpSde P = {b0, b1, T, t_eps};
   const int64_t n = B * d;
   const int64_t nq = (n + 3) >> 2;
   if (step_ctr && blockIdx.x == 0 && threadIdx.x == 0) step_ctr[0] += 1;
@@ -91,23 +173,16 @@ __global__ void k_ssm_prep(const float* __restrict__ x0, float* __restrict__ y, 
     const f32x4 ez = philox_normal4(rng, 0, RNG_STREAM_EPS, q);
     const f32x4 uv = philox_uniform4(rng, 0, RNG_STREAM_V, q);
     int64_t b_prev = -1;
-    float t = 0.f, mw = 0.f, sd = 0.f;
+    VpRow r = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int64_t e = e0 + k;
       if (e >= n) break;
       const int64_t b = e / d;
-      if (b != b_prev) {                                 // once per row the quad touches
-        t = philox_uniform1(rng, 0, RNG_STREAM_T, (uint64_t)b) * T;
-        const float m = (t <= t_eps) ? 1.0f : 0.0f;
-        t = m * t_eps + (1.0f - m) * t;
-        mw = vp_mean_weight(b0, b1, t);
-        sd = sqrtf(vp_var(b0, b1, t));
-        b_prev = b;
-      }
-      y[e] = ez[k] * sd + mw * x0[e];
+      if (b != b_prev) { r = vp_row(P, b, rng, nullptr, nullptr); b_prev = b; }   // once per row the quad touches
+      y[e] = vp_value(r, ez[k], x0[e]);
       v[e] = (uv[k] >= 0.5f) ? 1.0f : -1.0f;
-      if (e - b * d == 0) t_out[b] = t;
+      if (e - b * d == 0) t_out[b] = r.t;
     }
   }
 }
@@ -137,27 +212,6 @@ __global__ void k_rademacher(float* __restrict__ v, int64_t n, const float* __re
   }
 }
 
-// Sum over the GS lanes that share a row.  GS <= 64: a lane group inside a wave (xor tree).  GS = 256: the whole workgroup
-// owns the row (long rows: n >= 2048 — 12288-element images have too few rows per launch to fill the chip with 64-lane
-// groups: 32 rows were 8 workgroups and 67-82 us per launch); wave sums meet through LDS in a fixed order.  The group size
-// depends on n only, never on the batch: a row's sum is the same bits in every batch size.
-template <int GS>
-__device__ __forceinline__ float group_sum(float v) {
-  if constexpr (GS <= 64) {
-#pragma unroll
-    for (int o = GS >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, GS);
-    return v;
-  } else {
-    __shared__ float red[4];
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-  }
-}
-
 // ============================================================ integrator stage
 struct StageArgs {
   float* out; const float* base; float c_out;
@@ -183,32 +237,77 @@ __device__ __forceinline__ float stage_noise(const StageArgs& A, int64_t e, floa
   return sqrt_delta * zz;                                  // delta**0.5 * randn   sde_scheme.py:84
 }
 
-// SGM (diagonal) flat kernel, no norm correction: 12-16 B/element.
-// Reverse: mu = (1-l/2) sqrt(beta) a + 1/2 beta x (SDEs.py:560-561,183-194 with
-// divSigma = 0); sigma = sqrt(1-l) sqrt(beta).  Forward: mu = -1/2 beta x.
+// Row b's stage coefficients at the stage time tnow (= stage_time(A): host t or t_dev): step length delta_b and its root
+// (per row with delta_rows, then also t_b = tnow + t_frac delta_b), beta at t_b — at T - t_b for the reverse process — and its
+// root.  PER_ROW = false is the kernel-uniform form of k_stage_diag_flat, which msgm_sde_stage never sends delta_rows to.
+struct StageCoef { float delta, sqd, beta, sb; };
+template <bool PER_ROW = true>
+__device__ __forceinline__ StageCoef stage_coef(const StageArgs& A, float tnow, int64_t b) {
+  const float* dr = PER_ROW ? A.delta_rows : nullptr;
+  const float delta = dr ? dr[b] : A.delta;
+  const float sqd = dr ? sqrtf(delta) : A.sqrt_delta;
+  const float tb = dr ? tnow + A.t_frac * delta : tnow;
+  const float s = A.proc == MSGM_PROC_REVERSE ? A.T - tb : tb;
+  const float beta = sde_beta(A.b0, A.b1, s);
+  return {delta, sqd, beta, sqrtf(beta)};
+}
+// sigma's factor besides sqrt(beta): sqrt(1-l) for the reverse process (SDEs.py:587-588)
+__device__ __forceinline__ float stage_sig_scale(const StageArgs& A) {
+  return (A.proc == MSGM_PROC_REVERSE) ? sqrtf(1.0f - A.lmbd) : 1.0f;
+}
+
+// The drift of a stage from ga = G a, f, fs (f of the Stratonovich forward form) and div = divSigma.
+__device__ __forceinline__ float stage_mu(const StageArgs& A, float ga, float f, float fs, float div) {
+  const float l = A.lmbd;
+  float mu;
+  if (A.proc == MSGM_PROC_REVERSE) {
+    mu = (1.0f - 0.5f * l) * ga - f + (1.0f - l) * div;          // SDEs.py:560-561
+    if (A.strato) mu = mu - 0.5f * (1.0f - l) * div;             // SDEs.py:583-584
+  } else {
+    mu = fs;                                                      // SDEs.py:42-43
+    if (!A.strato) mu = mu + 0.5f * div;                          // SDEs.py:38-39
+  }
+  return mu;
+}
+
+// Sparse rotation tensor, element i of G(x) w: entries (I=i,J=i+1,K=i,V=+c) and (I=i,J=i-1,K=i-1,V=-c), c = sqrt(2)/2, circular
+// (SDEs.py:369-399,425-430; sde_scheme.py:27-32): c sb (x_{i+1} w_i - x_{i-1} w_{i-1}).  w is the noise (gw) or the score (ga).
+__device__ __forceinline__ float sparse_g(float sb, float xp, float xm, float w_i, float w_m) {
+  const float cV = 0.5f * sqrtf(2.0f);
+  return (cV * (sb * xp)) * w_i + (-cV * (sb * xm)) * w_m;
+}
+
+// SGM (diagonal), one element: the bare increment.  Reverse: mu = (1-l/2) sqrt(beta) a + 1/2 beta x (SDEs.py:560-561,183-194
+// with divSigma = 0); sigma = sqrt(1-l) sqrt(beta).  Forward: mu = -1/2 beta x.
+// This is NOT stage_mu(sb a, f, f, 0) with f = -1/2 beta x: that form adds (1-l) 0 (reverse) or 1/2 0 (forward, Ito) to mu,
+// which turns a mu of -0 into +0 — x = +-0 with a Wiener increment of -0 (a Box-Muller radius of 0) then gives the other
+// zero.  The flat kernel keeps the parent's spelling and its bits; k_stage_rows (SGM with norm0 / delta_rows) keeps stage_mu's.
+struct DiagCoef { float beta, sb, ca, sig; };
+__device__ __forceinline__ float diag_inc(const StageArgs& A, const DiagCoef& c, float x, float a, float w) {
+  float mu;
+  if (A.proc == MSGM_PROC_REVERSE) mu = c.ca * (c.sb * a) - (-0.5f * c.beta * x);
+  else mu = -0.5f * c.beta * x;
+  return mu * A.delta + c.sig * w;
+}
+
+// SGM (diagonal) flat kernel, no norm correction: 12-16 B/element.  The vector body (B n % 4 == 0, every operand 16-byte
+// aligned) and the scalar body differ in their loads and stores only: the quad's arithmetic is the one loop over diag_inc.
 __global__ void k_stage_diag_flat(StageArgs A) {
   const int64_t n = A.B * A.n;
   const int64_t nq = (n + 3) >> 2;
-  const float tnow = stage_time(A);
-  const float s = A.proc == MSGM_PROC_REVERSE ? A.T - tnow : tnow;
-  const float beta = sde_beta(A.b0, A.b1, s);
-  const float sb = sqrtf(beta);
-  const float ca = (1.0f - 0.5f * A.lmbd);
-  const float sig = (A.proc == MSGM_PROC_REVERSE ? sqrtf(1.0f - A.lmbd) : 1.0f) * sb;
-  const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(A.x) | reinterpret_cast<uintptr_t>(A.out) |
-                                     reinterpret_cast<uintptr_t>(A.a) | reinterpret_cast<uintptr_t>(A.dW) |
-                                     reinterpret_cast<uintptr_t>(A.z) | reinterpret_cast<uintptr_t>(A.base) |
-                                     reinterpret_cast<uintptr_t>(A.dW_out) | reinterpret_cast<uintptr_t>(A.inc_out)) & 15) == 0;
+  const StageCoef sc = stage_coef<false>(A, stage_time(A), 0);          // kernel-uniform: once per thread
+  const DiagCoef c = {sc.beta, sc.sb, (1.0f - 0.5f * A.lmbd), stage_sig_scale(A) * sc.sb};
+  const bool vec = (n & 3) == 0 && aligned16(A.x, A.out, A.a, A.dW, A.z, A.base, A.dW_out, A.inc_out);
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e0 = q << 2;
     f32x4 xv, av = {0, 0, 0, 0}, wv, bv = {0, 0, 0, 0};
     if (vec) {
-      xv = *reinterpret_cast<const f32x4*>(A.x + e0);
-      if (A.proc == MSGM_PROC_REVERSE) av = *reinterpret_cast<const f32x4*>(A.a + e0);
-      if (A.base) bv = (A.base == A.x) ? xv : *reinterpret_cast<const f32x4*>(A.base + e0);
-      if (A.dW) wv = *reinterpret_cast<const f32x4*>(A.dW + e0);
+      xv = ld4(A.x + e0);
+      if (A.proc == MSGM_PROC_REVERSE) av = ld4(A.a + e0);
+      if (A.base) bv = (A.base == A.x) ? xv : ld4(A.base + e0);
+      if (A.dW) wv = ld4(A.dW + e0);
       else {
-        f32x4 zz = A.z ? *reinterpret_cast<const f32x4*>(A.z + e0) : philox_normal4(A.rng, stage_step(A), RNG_STREAM_DW, q);
+        f32x4 zz = A.z ? ld4(A.z + e0) : philox_normal4(A.rng, stage_step(A), RNG_STREAM_DW, q);
         wv = A.sqrt_delta * zz;
       }
     } else {
@@ -225,16 +324,13 @@ __global__ void k_stage_diag_flat(StageArgs A) {
     f32x4 o, iv;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      float mu;
-      if (A.proc == MSGM_PROC_REVERSE) mu = ca * (sb * av[k]) - (-0.5f * beta * xv[k]);
-      else mu = -0.5f * beta * xv[k];
-      iv[k] = mu * A.delta + sig * wv[k];
+      iv[k] = diag_inc(A, c, xv[k], av[k], wv[k]);
       o[k] = bv[k] + A.c_out * iv[k];
     }
     if (vec) {
-      *reinterpret_cast<f32x4*>(A.out + e0) = o;
-      if (A.dW_out) *reinterpret_cast<f32x4*>(A.dW_out + e0) = wv;
-      if (A.inc_out) *reinterpret_cast<f32x4*>(A.inc_out + e0) = iv;
+      st4(A.out + e0, o);
+      if (A.dW_out) st4(A.dW_out + e0, wv);
+      if (A.inc_out) st4(A.inc_out + e0, iv);
     } else {
       for (int k = 0; k < 4; ++k) {
         int64_t e = e0 + k;
@@ -245,67 +341,50 @@ __global__ void k_stage_diag_flat(StageArgs A) {
 }
 
 // Multiplicative SDE, SPARSE rotation tensor, no norm correction (the RK4 stages of the forward perturbation and of the
-// Stratonovich samplers): the update is a 3-point circular stencil along the row,
-//   dx_i = c sqrt(beta) (x_{i+1} w_i - x_{i-1} w_{i-1})        (SDEs.py:369-399,425-430; sde_scheme.py:27-32),
-// so it runs as a FLAT float4 kernel like the additive one — 12-16 B / element — instead of one 64-lane group per row
-// (256 rows of 12288 elements were 309 us per stage = 0.12 TB/s).  n % 4 == 0: a quad never straddles two rows.
-// Same expressions, in the same order, as k_stage_rows (bit-identical results).
+// Stratonovich samplers): the update is the 3-point circular stencil of sparse_g along the row, so it runs as a FLAT float4
+// kernel like the additive one — 12-16 B / element — instead of one 64-lane group per row (256 rows of 12288 elements were
+// 309 us per stage = 0.12 TB/s).  n % 4 == 0: a quad never straddles two rows.  stage_coef, sparse_g and stage_mu are
+// the expressions of k_stage_rows in the same order (bit-identical results; k_stage_rows keeps its own lines, see there).
 __global__ void __launch_bounds__(256) k_stage_sparse_flat(StageArgs A) {
   const int64_t n = A.n, nq = (A.B * n) >> 2;
-  const float l = A.lmbd;
-  const float sig_scale = (A.proc == MSGM_PROC_REVERSE) ? sqrtf(1.0f - l) : 1.0f;
-  const float cV = 0.5f * sqrtf(2.0f);
+  const float sig_scale = stage_sig_scale(A);
   const float tnow = stage_time(A);
   const int lane = threadIdx.x & 63;
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e0 = q << 2, b = e0 / n, i0 = e0 - b * n;
-    const float delta = A.delta_rows ? A.delta_rows[b] : A.delta;
-    const float sqd = A.delta_rows ? sqrtf(delta) : A.sqrt_delta;
-    const float tb = A.delta_rows ? tnow + A.t_frac * delta : tnow;
-    const float s = A.proc == MSGM_PROC_REVERSE ? A.T - tb : tb;
-    const float beta = sde_beta(A.b0, A.b1, s);
-    const float sb = sqrtf(beta);
+    const StageCoef c = stage_coef(A, tnow, b);
     const int64_t row = b * n;
     const int64_t em = row + (i0 == 0 ? n - 1 : i0 - 1), ep = row + (i0 + 4 == n ? 0 : i0 + 4);
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(A.x + e0);
+    const f32x4 xv = ld4(A.x + e0);
     const float xm0 = A.x[em], xp3 = A.x[ep];
     f32x4 av = {0, 0, 0, 0}, bv = {0, 0, 0, 0}, wv;
     float am0 = 0.f, wm0;
-    if (A.a) { av = *reinterpret_cast<const f32x4*>(A.a + e0); am0 = A.a[em]; }
-    if (A.base) bv = (A.base == A.x) ? xv : *reinterpret_cast<const f32x4*>(A.base + e0);
-    if (A.dW) { wv = *reinterpret_cast<const f32x4*>(A.dW + e0); wm0 = A.dW[em]; }
-    else if (A.z) { wv = sqd * *reinterpret_cast<const f32x4*>(A.z + e0); wm0 = sqd * A.z[em]; }
+    if (A.a) { av = ld4(A.a + e0); am0 = A.a[em]; }
+    if (A.base) bv = (A.base == A.x) ? xv : ld4(A.base + e0);
+    if (A.dW) { wv = ld4(A.dW + e0); wm0 = A.dW[em]; }
+    else if (A.z) { wv = c.sqd * ld4(A.z + e0); wm0 = c.sqd * A.z[em]; }
     else {
       const f32x4 zz = philox_normal4(A.rng, stage_step(A), RNG_STREAM_DW, (uint64_t)q);
-      wv = sqd * zz;
+      wv = c.sqd * zz;
       // the previous element's draw sits in the neighbouring lane's quad (same row unless this quad opens the row)
       const float zprev = __shfl_up(zz[3], 1, 64);
-      wm0 = sqd * ((lane == 0 || i0 == 0) ? philox_normal1(A.rng, stage_step(A), RNG_STREAM_DW, (uint64_t)em) : zprev);
+      wm0 = c.sqd * ((lane == 0 || i0 == 0) ? philox_normal1(A.rng, stage_step(A), RNG_STREAM_DW, (uint64_t)em) : zprev);
     }
     f32x4 o, iv;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float xi = xv[k];
       const float xp = k < 3 ? xv[k + 1] : xp3, xm = k > 0 ? xv[k - 1] : xm0;
-      const float w_i = wv[k], w_m = k > 0 ? wv[k - 1] : wm0;
-      const float f = 0.5f * beta * xi, div = 2.0f * f;
-      const float gw = (cV * (sb * xp)) * w_i + (-cV * (sb * xm)) * w_m;
+      const float f = 0.5f * c.beta * xi, div = 2.0f * f;
+      const float gw = sparse_g(c.sb, xp, xm, wv[k], k > 0 ? wv[k - 1] : wm0);
       float ga = 0.f;
-      if (A.a) ga = (cV * (sb * xp)) * av[k] + (-cV * (sb * xm)) * (k > 0 ? av[k - 1] : am0);
-      float mu;
-      if (A.proc == MSGM_PROC_REVERSE) {
-        mu = (1.0f - 0.5f * l) * ga - f + (1.0f - l) * div;
-        if (A.strato) mu = mu - 0.5f * (1.0f - l) * div;
-      } else {
-        mu = 0.f;
-        if (!A.strato) mu = mu + 0.5f * div;
-      }
-      iv[k] = mu * delta + sig_scale * gw;
+      if (A.a) ga = sparse_g(c.sb, xp, xm, av[k], k > 0 ? av[k - 1] : am0);
+      iv[k] = stage_mu(A, ga, f, 0.f, div) * c.delta + sig_scale * gw;
       o[k] = bv[k] + A.c_out * iv[k];
     }
-    *reinterpret_cast<f32x4*>(A.out + e0) = o;
-    if (A.dW_out) *reinterpret_cast<f32x4*>(A.dW_out + e0) = wv;
-    if (A.inc_out) *reinterpret_cast<f32x4*>(A.inc_out + e0) = iv;
+    st4(A.out + e0, o);
+    if (A.dW_out) st4(A.dW_out + e0, wv);
+    if (A.inc_out) st4(A.inc_out + e0, iv);
   }
 }
 
@@ -315,22 +394,22 @@ __global__ void __launch_bounds__(256) k_rk4_combine_flat(float* __restrict__ ou
                                                           const float* __restrict__ k3, const float* __restrict__ k4, int64_t nq) {
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e = q << 2;
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + e), a = *reinterpret_cast<const f32x4*>(k1 + e);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(k2 + e), c = *reinterpret_cast<const f32x4*>(k3 + e);
-    const f32x4 d = *reinterpret_cast<const f32x4*>(k4 + e);
+    const f32x4 xv = ld4(x + e), a = ld4(k1 + e), b = ld4(k2 + e), c = ld4(k3 + e), d = ld4(k4 + e);
     f32x4 o;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = xv[k] + (a[k] + 2.0f * b[k] + 2.0f * c[k] + d[k]) / 6.0f;
-    *reinterpret_cast<f32x4*>(out + e) = o;
+    for (int k = 0; k < 4; ++k) o[k] = rk4_value(xv[k], a[k], b[k], c[k], d[k]);
+    st4(out + e, o);
   }
 }
 
-// Row kernel: a group of GS lanes owns one row; handles all three layouts and
-// the optional norm correction (x <- x * norm0/||x||, sde_scheme.py:85-86).
-//  sparse: dx_i = c sb (x_{i+1} w_i - x_{i-1} w_{i-1}), c = sqrt(2)/2, circular
-//          (SDEs.py:369-399,425-430; sde_scheme.py:27-32).
+// Row kernel: a group of GS lanes owns one row; handles all three layouts and the optional norm correction.
+//  sparse: the stencil of sparse_g.
 //  dense : dx_i = sum_{j,k} G[i,j,k] (sb x_j) w_k (SDEs.py:432; sde_scheme.py:36)
 //          and f = L_G (beta x) (SDEs.py:415) — (B,n,n) is never materialised.
+// k_stage_rows keeps its own lines for every phase: built on RowGroup, stage_coef, stage_mu, sparse_g and norm_correct it read
+// SLOWER at 4096 x 12288 (GS = 256: +0.40 % sgm, +0.22 % sparse with norm0, where the parent differed from itself by 0.2 %;
+// profiles/README.md); with these lines it is the parent's machine code.  Its drift rule and stencil are the expressions of
+// stage_mu and sparse_g in the same order (tests/test_sde_paths_gpu.py::test_stage_sparse_rows_bitwise_equals_flat).
 template <int GS>
 __global__ void k_stage_rows(StageArgs A) {
   const int lane = threadIdx.x & (GS - 1);
@@ -406,7 +485,7 @@ __global__ void k_stage_rows(StageArgs A) {
       }
     }
     if (A.norm0) {
-ss = group_sum<GS>(ss);
+      ss = group_sum<GS>(ss);
       if (live) {
         const float scale = A.norm0[b] / sqrtf(ss);
         for (int64_t i = lane; i < n; i += GS) A.out[b * n + i] *= scale;   // own writes, same lane
@@ -415,32 +494,23 @@ ss = group_sum<GS>(ss);
   }
 }
 
-// x + (k1 + 2k2 + 2k3 + k4)/6 with optional norm correction   sde_scheme.py:250-253
+// rk4_value with optional norm correction
 template <int GS>
 __global__ void k_rk4_combine(float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ k1,
                               const float* __restrict__ k2, const float* __restrict__ k3, const float* __restrict__ k4,
                               int64_t B, int64_t n, const float* __restrict__ norm0) {
-  const int lane = threadIdx.x & (GS - 1);
-  const int64_t gpb = blockDim.x / GS;
-  const int64_t gid = blockIdx.x * gpb + threadIdx.x / GS;
-  const int64_t gstride = (int64_t)gridDim.x * gpb;
-  const int64_t rows_pad = ((B + gstride - 1) / gstride) * gstride;
-  for (int64_t b = gid; b < rows_pad; b += gstride) {
+  const RowGroup<GS> rg(B, blockDim.x);
+  const int lane = rg.lane;
+  for (int64_t b = rg.first; b < rg.rows_pad; b += rg.stride) {
     const bool live = b < B;
     float ss = 0.f;
     if (live)
       for (int64_t i = lane; i < n; i += GS) {
         const int64_t e = b * n + i;
-        float o = x[e] + (k1[e] + 2.0f * k2[e] + 2.0f * k3[e] + k4[e]) / 6.0f;
+        float o = rk4_value(x[e], k1[e], k2[e], k3[e], k4[e]);
         out[e] = o; ss += o * o;
       }
-    if (norm0) {
-ss = group_sum<GS>(ss);
-      if (live) {
-        const float sc = norm0[b] / sqrtf(ss);
-        for (int64_t i = lane; i < n; i += GS) out[b * n + i] *= sc;
-      }
-    }
+    if (norm0) norm_correct<GS>(out, norm0, b, n, lane, live, ss);
   }
 }
 
@@ -452,14 +522,12 @@ template <int GS>
 __global__ void k_ssm_loss_diag(const float* __restrict__ out, const float* __restrict__ v, const float* __restrict__ t,
                                 float* __restrict__ per, float* __restrict__ g, int64_t B, int64_t n, float b0, float b1,
                                 float w) {
-  const int lane = threadIdx.x & (GS - 1);
-  const int64_t gpb = blockDim.x / GS;
-  const int64_t gid = blockIdx.x * gpb + threadIdx.x / GS;
-  const int64_t gstride = (int64_t)gridDim.x * gpb;
-  const int64_t rows_pad = ((B + gstride - 1) / gstride) * gstride;
-  for (int64_t b = gid; b < rows_pad; b += gstride) {
+  const RowGroup<GS> rg(B, blockDim.x);
+  const int lane = rg.lane;
+  for (int64_t b = rg.first; b < rg.rows_pad; b += rg.stride) {
+    const bool live = b < B;
     float acc = 0.f;
-    if (b < B) {
+    if (live) {
       const float beta = sde_beta(b0, b1, t[b]);
       const float sb = sqrtf(beta);
       for (int64_t i = lane; i < n; i += GS) {
@@ -469,8 +537,8 @@ __global__ void k_ssm_loss_diag(const float* __restrict__ out, const float* __re
         g[(B + b) * n + i] = sb * vi * w;
       }
     }
-acc = group_sum<GS>(acc);
-    if (b < B && lane == 0) per[b] = acc;
+    acc = group_sum<GS>(acc);
+    if (live && lane == 0) per[b] = acc;
   }
 }
 
@@ -485,15 +553,13 @@ template <int GS>
 __global__ void k_ssm_terms(const float* __restrict__ y, const float* __restrict__ v, const float* __restrict__ t,
                             float* __restrict__ u, float* __restrict__ cst, int64_t B, int64_t n, int kind, float b0,
                             float b1, const float* __restrict__ G) {
-  const int lane = threadIdx.x & (GS - 1);
-  const int64_t gpb = blockDim.x / GS;
-  const int64_t gid = blockIdx.x * gpb + threadIdx.x / GS;
-  const int64_t gstride = (int64_t)gridDim.x * gpb;
-  const int64_t rows_pad = ((B + gstride - 1) / gstride) * gstride;
   const float cV = 0.5f * sqrtf(2.0f);
-  for (int64_t b = gid; b < rows_pad; b += gstride) {
+  const RowGroup<GS> rg(B, blockDim.x);
+  const int lane = rg.lane;
+  for (int64_t b = rg.first; b < rg.rows_pad; b += rg.stride) {
+    const bool live = b < B;
     float acc = 0.f;
-    if (b < B) {
+    if (live) {
       const float beta = sde_beta(b0, b1, t[b]);
       const float sb = sqrtf(beta);
       const float* yr = y + b * n;
@@ -518,8 +584,8 @@ __global__ void k_ssm_terms(const float* __restrict__ y, const float* __restrict
         u[b * n + k] = uk;
       }
     }
-acc = group_sum<GS>(acc);
-    if (b < B && lane == 0) cst[b] = acc;
+    acc = group_sum<GS>(acc);
+    if (live && lane == 0) cst[b] = acc;
   }
 }
 
@@ -527,22 +593,20 @@ acc = group_sum<GS>(acc);
 template <int GS>
 __global__ void k_ssm_loss_generic(const float* __restrict__ out, const float* __restrict__ u, const float* __restrict__ cst,
                                    float* __restrict__ per, float* __restrict__ g, int64_t B, int64_t n, float w) {
-  const int lane = threadIdx.x & (GS - 1);
-  const int64_t gpb = blockDim.x / GS;
-  const int64_t gid = blockIdx.x * gpb + threadIdx.x / GS;
-  const int64_t gstride = (int64_t)gridDim.x * gpb;
-  const int64_t rows_pad = ((B + gstride - 1) / gstride) * gstride;
-  for (int64_t b = gid; b < rows_pad; b += gstride) {
+  const RowGroup<GS> rg(B, blockDim.x);
+  const int lane = rg.lane;
+  for (int64_t b = rg.first; b < rg.rows_pad; b += rg.stride) {
+    const bool live = b < B;
     float acc = 0.f;
-    if (b < B)
+    if (live)
       for (int64_t i = lane; i < n; i += GS) {
         const float a = out[b * n + i], ad = out[(B + b) * n + i], ui = u[b * n + i];
         acc += ad * ui + 0.5f * a * a;
         g[b * n + i] = a * w;
         g[(B + b) * n + i] = ui * w;
       }
-acc = group_sum<GS>(acc);
-    if (b < B && lane == 0) per[b] = acc + cst[b];
+    acc = group_sum<GS>(acc);
+    if (live && lane == 0) per[b] = acc + cst[b];
   }
 }
 
@@ -559,16 +623,14 @@ __global__ void k_lincomb(float* __restrict__ out, const float* __restrict__ a, 
 
 template <int GS>
 __global__ void k_row_norm(const float* __restrict__ x, float* __restrict__ out, int64_t B, int64_t n) {
-  const int lane = threadIdx.x & (GS - 1);
-  const int64_t gpb = blockDim.x / GS;
-  const int64_t gid = blockIdx.x * gpb + threadIdx.x / GS;
-  const int64_t gstride = (int64_t)gridDim.x * gpb;
-  const int64_t rows_pad = ((B + gstride - 1) / gstride) * gstride;
-  for (int64_t b = gid; b < rows_pad; b += gstride) {
+  const RowGroup<GS> rg(B, blockDim.x);
+  const int lane = rg.lane;
+  for (int64_t b = rg.first; b < rg.rows_pad; b += rg.stride) {
+    const bool live = b < B;
     float ss = 0.f;
-    if (b < B) for (int64_t i = lane; i < n; i += GS) { float v = x[b * n + i]; ss += v * v; }
-ss = group_sum<GS>(ss);
-    if (b < B && lane == 0) out[b] = sqrtf(ss);
+    if (live) for (int64_t i = lane; i < n; i += GS) { float v = x[b * n + i]; ss += v * v; }
+    ss = group_sum<GS>(ss);
+    if (live && lane == 0) out[b] = sqrtf(ss);
   }
 }
 
@@ -585,59 +647,92 @@ __global__ void k_keep_rows(float* __restrict__ kept, const float* __restrict__ 
 // Mirrors torch's single-tensor update: m.lerp_(g, 1-b1); v = v*b2 + (1-b2) g g;
 // denom = sqrt(v)/sqrt(bc2) + eps; p += -(lr/bc1) * (m/denom), with the bias
 // corrections formed in double precision as the Python scalars upstream are.
+struct AdamCoef { float step_size, bc2_sqrt, w1, b2f, w2, epsf, gscale; };
+struct AdamPmv { float p, m, v; };
+__device__ __forceinline__ AdamPmv adam_elem(const AdamCoef& c, float p, float g, float m, float v) {
+  const float gg = g * c.gscale;
+  m = m + c.w1 * (gg - m);
+  v = v * c.b2f + c.w2 * (gg * gg);
+  const float denom = sqrtf(v) / c.bc2_sqrt + c.epsf;
+  return {p - c.step_size * (m / denom), m, v};
+}
+
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                        int64_t n, double lr, double b1, double b2, double eps, float gscale, int64_t step,
                        const int64_t* __restrict__ step_dev) {
   const int64_t st = step_dev ? step_dev[0] : step;
   const double bc1 = 1.0 - pow(b1, (double)st);
   const double bc2 = 1.0 - pow(b2, (double)st);
-  const float step_size = (float)(lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
-  const float w1 = (float)(1.0 - b1), b2f = (float)b2, w2 = (float)(1.0 - b2), epsf = (float)eps;
+  const AdamCoef c = {(float)(lr / bc1), (float)sqrt(bc2), (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, gscale};
   const int64_t nq = (n + 3) >> 2;
-  const bool vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
-                                     reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+  const bool vec = (n & 3) == 0 && aligned16(p, g, m, v);
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e0 = q << 2;
     if (vec) {
-      f32x4 pv = *reinterpret_cast<f32x4*>(p + e0), gv = *reinterpret_cast<const f32x4*>(g + e0);
-      f32x4 mv = *reinterpret_cast<f32x4*>(m + e0), vv = *reinterpret_cast<f32x4*>(v + e0);
+      f32x4 pv = ld4(p + e0), gv = ld4(g + e0), mv = ld4(m + e0), vv = ld4(v + e0);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        float gg = gv[k] * gscale;
-        mv[k] = mv[k] + w1 * (gg - mv[k]);
-        vv[k] = vv[k] * b2f + w2 * (gg * gg);
-        float denom = sqrtf(vv[k]) / bc2_sqrt + epsf;
-        pv[k] = pv[k] - step_size * (mv[k] / denom);
+        const AdamPmv r = adam_elem(c, pv[k], gv[k], mv[k], vv[k]);
+        pv[k] = r.p; mv[k] = r.m; vv[k] = r.v;
       }
-      *reinterpret_cast<f32x4*>(p + e0) = pv; *reinterpret_cast<f32x4*>(m + e0) = mv; *reinterpret_cast<f32x4*>(v + e0) = vv;
+      st4(p + e0, pv); st4(m + e0, mv); st4(v + e0, vv);
     } else {
       for (int k = 0; k < 4; ++k) {
         int64_t e = e0 + k;
         if (e >= n) break;
-        float gg = g[e] * gscale;
-        float mm = m[e] + w1 * (gg - m[e]);
-        float vv = v[e] * b2f + w2 * (gg * gg);
-        float denom = sqrtf(vv) / bc2_sqrt + epsf;
-        p[e] = p[e] - step_size * (mm / denom); m[e] = mm; v[e] = vv;
+        const AdamPmv r = adam_elem(c, p[e], g[e], m[e], v[e]);
+        p[e] = r.p; m[e] = r.m; v[e] = r.v;
       }
     }
   }
 }
 
 // ============================================================ C ABI
+// A row kernel's launch: lanes per row GS = next power of two >= min(n,64), at least 2; long rows (n >= 2048): the whole
+// workgroup owns a row (group_sum<256>) — a function of n only.  launch(GS, grid, block) gets GS as a std::integral_constant
+// and launches KERNEL<decltype(GS)::value>: this is the one GS ladder.
 template <typename F>
-static int launch_rows(int64_t B, int64_t n, F&& f) {
-  // lanes per row: next power of two >= min(n,64), at least 2
+static int launch_rows(int64_t B, int64_t n, F&& launch) {
   int gs = 2;
   while (gs < 64 && gs < n) gs <<= 1;
-  if (n >= 2048) gs = 256;             // long rows: the whole workgroup owns a row (group_sum<256>); a function of n only
+  if (n >= 2048) gs = 256;
   const int block = 256;
   int64_t groups = (int64_t)block / gs;
   int grid = (int)((B + groups - 1) / groups);
   if (grid > 4096) grid = 4096;
   if (grid < 1) grid = 1;
-  f(gs, grid, block);
+  switch (gs) {
+    case 2: launch(std::integral_constant<int, 2>{}, grid, block); break;
+    case 4: launch(std::integral_constant<int, 4>{}, grid, block); break;
+    case 8: launch(std::integral_constant<int, 8>{}, grid, block); break;
+    case 16: launch(std::integral_constant<int, 16>{}, grid, block); break;
+    case 32: launch(std::integral_constant<int, 32>{}, grid, block); break;
+    case 256: launch(std::integral_constant<int, 256>{}, grid, block); break;
+    default: launch(std::integral_constant<int, 64>{}, grid, block); break;
+  }
+  return msgm_check_launch();
+}
+
+static int launch_time_tick(const float* ts, const int64_t* step, int64_t n_ts, float T, float t_add, float* t_dev,
+                            float* s_out, int64_t B, msgm_stream_t stream) {
+  if (!ts || !step || !t_dev || !s_out || n_ts <= 0 || B <= 0) return MSGM_E_BADARG;
+  hipLaunchKernelGGL(k_time_tick, dim3(grid_for(B, 256, 256)), dim3(256), 0, S(stream), ts, step, n_ts, T, t_dev, s_out, B, t_add);
+  return msgm_check_launch();
+}
+
+template <bool NORMAL>
+static int launch_fill(float* out, int64_t n, const uint64_t* rng, uint32_t stream_id, msgm_stream_t stream) {
+  if (!out || !rng || n <= 0) return MSGM_E_BADARG;
+  hipLaunchKernelGGL(k_fill<NORMAL>, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, S(stream), out, n, rng, stream_id);
+  return msgm_check_launch();
+}
+
+// the two perturb entries, after their own argument checks: row times drawn / from u (t_out written) or given (t_given)
+static int launch_perturb_vp(const float* x0, float* y, float* t_out, float* eps_out, int64_t B, int64_t d, const msgm_sde_t* sde,
+                             const float* u, const float* eps, const uint64_t* rng, const float* t_given, msgm_stream_t stream) {
+  if (sde->kind != MSGM_SDE_SGM) return MSGM_E_UNSUPPORTED;   // MSGM has no closed form (SDEs.py:434-436)
+  hipLaunchKernelGGL(k_perturb_vp, dim3(grid_for((B * d + 3) / 4, 256)), dim3(256), 0, S(stream), x0, y, t_out, eps_out, B, d,
+                     sde->beta_min, sde->beta_max, sde->T, sde->t_epsilon, u, eps, rng, t_given);
   return msgm_check_launch();
 }
 
@@ -664,16 +759,12 @@ int msgm_rng_advance(uint64_t* rng, uint64_t n, msgm_stream_t stream) {
 
 int msgm_time_tick(const float* ts, const int64_t* step, int64_t n_ts, float T, float* t_dev, float* s_out, int64_t B,
                    msgm_stream_t stream) {
-  if (!ts || !step || !t_dev || !s_out || n_ts <= 0 || B <= 0) return MSGM_E_BADARG;
-  hipLaunchKernelGGL(k_time_tick, dim3(grid_for(B, 256, 256)), dim3(256), 0, S(stream), ts, step, n_ts, T, t_dev, s_out, B, 0.f);
-  return msgm_check_launch();
+  return launch_time_tick(ts, step, n_ts, T, 0.f, t_dev, s_out, B, stream);
 }
 
 int msgm_time_tick_stage(const float* ts, const int64_t* step, int64_t n_ts, float T, float t_add, float* t_dev, float* s_out,
                          int64_t B, msgm_stream_t stream) {
-  if (!ts || !step || !t_dev || !s_out || n_ts <= 0 || B <= 0) return MSGM_E_BADARG;
-  hipLaunchKernelGGL(k_time_tick, dim3(grid_for(B, 256, 256)), dim3(256), 0, S(stream), ts, step, n_ts, T, t_dev, s_out, B, t_add);
-  return msgm_check_launch();
+  return launch_time_tick(ts, step, n_ts, T, t_add, t_dev, s_out, B, stream);
 }
 
 int msgm_counter_inc(int64_t* ctr, msgm_stream_t stream) {
@@ -683,15 +774,11 @@ int msgm_counter_inc(int64_t* ctr, msgm_stream_t stream) {
 }
 
 int msgm_fill_uniform(float* out, int64_t n, const uint64_t* rng, uint32_t stream_id, msgm_stream_t stream) {
-  if (!out || !rng || n <= 0) return MSGM_E_BADARG;
-  hipLaunchKernelGGL(k_fill<false>, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, S(stream), out, n, rng, stream_id);
-  return msgm_check_launch();
+  return launch_fill<false>(out, n, rng, stream_id, stream);
 }
 
 int msgm_fill_normal(float* out, int64_t n, const uint64_t* rng, uint32_t stream_id, msgm_stream_t stream) {
-  if (!out || !rng || n <= 0) return MSGM_E_BADARG;
-  hipLaunchKernelGGL(k_fill<true>, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, S(stream), out, n, rng, stream_id);
-  return msgm_check_launch();
+  return launch_fill<true>(out, n, rng, stream_id, stream);
 }
 
 int msgm_perturb_vp(const float* x0, float* y, float* t_out, float* eps_out, int64_t B, int64_t d,
@@ -699,19 +786,13 @@ int msgm_perturb_vp(const float* x0, float* y, float* t_out, float* eps_out, int
                     msgm_stream_t stream) {
   if (!x0 || !y || !t_out || !sde || B <= 0 || d <= 0) return MSGM_E_BADARG;
   if ((!u || !eps) && !rng) return MSGM_E_BADARG;
-  if (sde->kind != MSGM_SDE_SGM) return MSGM_E_UNSUPPORTED;   // MSGM has no closed form (SDEs.py:434-436)
-  hipLaunchKernelGGL(k_perturb_vp, dim3(grid_for((B * d + 3) / 4, 256)), dim3(256), 0, S(stream), x0, y, t_out, eps_out,
-                     B, d, sde->beta_min, sde->beta_max, sde->T, sde->t_epsilon, u, eps, rng, (const float*)nullptr);
-  return msgm_check_launch();
+  return launch_perturb_vp(x0, y, t_out, eps_out, B, d, sde, u, eps, rng, nullptr, stream);
 }
 
 int msgm_perturb_vp_at(const float* x0, float* y, float* eps_out, int64_t B, int64_t d, const msgm_sde_t* sde, const float* t,
                        const float* eps, const uint64_t* rng, msgm_stream_t stream) {
   if (!x0 || !y || !t || !sde || B <= 0 || d <= 0 || (!eps && !rng)) return MSGM_E_BADARG;
-  if (sde->kind != MSGM_SDE_SGM) return MSGM_E_UNSUPPORTED;
-  hipLaunchKernelGGL(k_perturb_vp, dim3(grid_for((B * d + 3) / 4, 256)), dim3(256), 0, S(stream), x0, y, (float*)nullptr,
-                     eps_out, B, d, sde->beta_min, sde->beta_max, sde->T, sde->t_epsilon, (const float*)nullptr, eps, rng, t);
-  return msgm_check_launch();
+  return launch_perturb_vp(x0, y, nullptr, eps_out, B, d, sde, nullptr, eps, rng, t, stream);
 }
 
 int msgm_ssm_prep(const float* x0, float* y, float* t_out, float* v, int64_t B, int64_t d, const msgm_sde_t* sde,
@@ -754,49 +835,25 @@ int msgm_sde_stage(float* out, const float* base, float c_out, const float* x, c
     hipLaunchKernelGGL(k_stage_diag_flat, dim3(grid_for((B * n + 3) / 4, 256)), dim3(256), 0, S(stream), A);
     return msgm_check_launch();
   }
-  {
-    const uintptr_t al = reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(a) |
-                         reinterpret_cast<uintptr_t>(dW) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(base) |
-                         reinterpret_cast<uintptr_t>(dW_out) | reinterpret_cast<uintptr_t>(inc_out);
-    if (sde->kind == MSGM_SDE_MSGM_SPARSE && !norm0 && n % 4 == 0 && n >= 8 && (al & 15) == 0 && out != x) {
-      hipLaunchKernelGGL(k_stage_sparse_flat, dim3(grid_for((B * n) / 4, 256)), dim3(256), 0, S(stream), A);
-      return msgm_check_launch();
-    }
+  if (sde->kind == MSGM_SDE_MSGM_SPARSE && !norm0 && n % 4 == 0 && n >= 8 && out != x &&
+      aligned16(out, x, a, dW, z, base, dW_out, inc_out)) {
+    hipLaunchKernelGGL(k_stage_sparse_flat, dim3(grid_for((B * n) / 4, 256)), dim3(256), 0, S(stream), A);
+    return msgm_check_launch();
   }
-  return launch_rows(B, n, [&](int gs, int grid, int block) {
-    switch (gs) {
-      case 2: hipLaunchKernelGGL(k_stage_rows<2>, dim3(grid), dim3(block), 0, S(stream), A); break;
-      case 4: hipLaunchKernelGGL(k_stage_rows<4>, dim3(grid), dim3(block), 0, S(stream), A); break;
-      case 8: hipLaunchKernelGGL(k_stage_rows<8>, dim3(grid), dim3(block), 0, S(stream), A); break;
-      case 16: hipLaunchKernelGGL(k_stage_rows<16>, dim3(grid), dim3(block), 0, S(stream), A); break;
-      case 32: hipLaunchKernelGGL(k_stage_rows<32>, dim3(grid), dim3(block), 0, S(stream), A); break;
-      case 256: hipLaunchKernelGGL(k_stage_rows<256>, dim3(grid), dim3(block), 0, S(stream), A); break;
-      default: hipLaunchKernelGGL(k_stage_rows<64>, dim3(grid), dim3(block), 0, S(stream), A); break;
-    }
+  return launch_rows(B, n, [&](auto GS, int grid, int block) {
+    hipLaunchKernelGGL((k_stage_rows<decltype(GS)::value>), dim3(grid), dim3(block), 0, S(stream), A);
   });
 }
 
 int msgm_rk4_combine(float* out, const float* x, const float* k1, const float* k2, const float* k3, const float* k4,
                      int64_t B, int64_t n, const float* norm0, msgm_stream_t stream) {
   if (!out || !x || !k1 || !k2 || !k3 || !k4 || B <= 0 || n <= 0) return MSGM_E_BADARG;
-  {
-    const uintptr_t al = reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(k1) |
-                         reinterpret_cast<uintptr_t>(k2) | reinterpret_cast<uintptr_t>(k3) | reinterpret_cast<uintptr_t>(k4);
-    if (!norm0 && (B * n) % 4 == 0 && (al & 15) == 0) {
-      hipLaunchKernelGGL(k_rk4_combine_flat, dim3(grid_for((B * n) / 4, 256)), dim3(256), 0, S(stream), out, x, k1, k2, k3, k4, (B * n) / 4);
-      return msgm_check_launch();
-    }
+  if (!norm0 && (B * n) % 4 == 0 && aligned16(out, x, k1, k2, k3, k4)) {
+    hipLaunchKernelGGL(k_rk4_combine_flat, dim3(grid_for((B * n) / 4, 256)), dim3(256), 0, S(stream), out, x, k1, k2, k3, k4, (B * n) / 4);
+    return msgm_check_launch();
   }
-  return launch_rows(B, n, [&](int gs, int grid, int block) {
-    switch (gs) {
-      case 2: hipLaunchKernelGGL(k_rk4_combine<2>, dim3(grid), dim3(block), 0, S(stream), out, x, k1, k2, k3, k4, B, n, norm0); break;
-      case 4: hipLaunchKernelGGL(k_rk4_combine<4>, dim3(grid), dim3(block), 0, S(stream), out, x, k1, k2, k3, k4, B, n, norm0); break;
-      case 8: hipLaunchKernelGGL(k_rk4_combine<8>, dim3(grid), dim3(block), 0, S(stream), out, x, k1, k2, k3, k4, B, n, norm0); break;
-      case 16: hipLaunchKernelGGL(k_rk4_combine<16>, dim3(grid), dim3(block), 0, S(stream), out, x, k1, k2, k3, k4, B, n, norm0); break;
-      case 32: hipLaunchKernelGGL(k_rk4_combine<32>, dim3(grid), dim3(block), 0, S(stream), out, x, k1, k2, k3, k4, B, n, norm0); break;
-      case 256: hipLaunchKernelGGL(k_rk4_combine<256>, dim3(grid), dim3(block), 0, S(stream), out, x, k1, k2, k3, k4, B, n, norm0); break;
-      default: hipLaunchKernelGGL(k_rk4_combine<64>, dim3(grid), dim3(block), 0, S(stream), out, x, k1, k2, k3, k4, B, n, norm0); break;
-    }
+  return launch_rows(B, n, [&](auto GS, int grid, int block) {
+    hipLaunchKernelGGL((k_rk4_combine<decltype(GS)::value>), dim3(grid), dim3(block), 0, S(stream), out, x, k1, k2, k3, k4, B, n, norm0);
   });
 }
 
@@ -804,45 +861,28 @@ int msgm_ssm_loss_diag(const float* out, const float* v, const float* t, float* 
                        const msgm_sde_t* sde, float inv_batch, msgm_stream_t stream) {
   if (!out || !v || !t || !per || !g || !sde || B <= 0 || n <= 0) return MSGM_E_BADARG;
   if (sde->kind != MSGM_SDE_SGM) return MSGM_E_UNSUPPORTED;
-  return launch_rows(B, n, [&](int gs, int grid, int block) {
-    switch (gs) {
-      case 2: hipLaunchKernelGGL(k_ssm_loss_diag<2>, dim3(grid), dim3(block), 0, S(stream), out, v, t, per, g, B, n, sde->beta_min, sde->beta_max, inv_batch); break;
-      case 4: hipLaunchKernelGGL(k_ssm_loss_diag<4>, dim3(grid), dim3(block), 0, S(stream), out, v, t, per, g, B, n, sde->beta_min, sde->beta_max, inv_batch); break;
-      case 8: hipLaunchKernelGGL(k_ssm_loss_diag<8>, dim3(grid), dim3(block), 0, S(stream), out, v, t, per, g, B, n, sde->beta_min, sde->beta_max, inv_batch); break;
-      case 16: hipLaunchKernelGGL(k_ssm_loss_diag<16>, dim3(grid), dim3(block), 0, S(stream), out, v, t, per, g, B, n, sde->beta_min, sde->beta_max, inv_batch); break;
-      case 32: hipLaunchKernelGGL(k_ssm_loss_diag<32>, dim3(grid), dim3(block), 0, S(stream), out, v, t, per, g, B, n, sde->beta_min, sde->beta_max, inv_batch); break;
-      case 256: hipLaunchKernelGGL(k_ssm_loss_diag<256>, dim3(grid), dim3(block), 0, S(stream), out, v, t, per, g, B, n, sde->beta_min, sde->beta_max, inv_batch); break;
-      default: hipLaunchKernelGGL(k_ssm_loss_diag<64>, dim3(grid), dim3(block), 0, S(stream), out, v, t, per, g, B, n, sde->beta_min, sde->beta_max, inv_batch); break;
-    }
+  return launch_rows(B, n, [&](auto GS, int grid, int block) {
+    hipLaunchKernelGGL((k_ssm_loss_diag<decltype(GS)::value>), dim3(grid), dim3(block), 0, S(stream), out, v, t, per, g, B, n,
+                       sde->beta_min, sde->beta_max, inv_batch);
   });
 }
-
-#define ROWS_DISPATCH(KERNEL, ...)                                                                              \
-  switch (gs) {                                                                                                  \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(grid), dim3(block), 0, S(stream), __VA_ARGS__); break;           \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(grid), dim3(block), 0, S(stream), __VA_ARGS__); break;           \
-    case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(grid), dim3(block), 0, S(stream), __VA_ARGS__); break;           \
-    case 16: hipLaunchKernelGGL(KERNEL<16>, dim3(grid), dim3(block), 0, S(stream), __VA_ARGS__); break;         \
-    case 32: hipLaunchKernelGGL(KERNEL<32>, dim3(grid), dim3(block), 0, S(stream), __VA_ARGS__); break;         \
-    case 256: hipLaunchKernelGGL(KERNEL<256>, dim3(grid), dim3(block), 0, S(stream), __VA_ARGS__); break;       \
-    default: hipLaunchKernelGGL(KERNEL<64>, dim3(grid), dim3(block), 0, S(stream), __VA_ARGS__); break;         \
-  }
 
 int msgm_ssm_terms(const float* y, const float* v, const float* t, float* u, float* cst, int64_t B, int64_t n,
                    const msgm_sde_t* sde, msgm_stream_t stream) {
   if (!y || !v || !t || !u || !cst || !sde || B <= 0 || n <= 0) return MSGM_E_BADARG;
   if (sde->kind < 0 || sde->kind > 2) return MSGM_E_BADARG;
   if (sde->kind == MSGM_SDE_MSGM_DENSE && (!sde->G || n > 64)) return sde->G ? MSGM_E_UNSUPPORTED : MSGM_E_BADARG;
-  return launch_rows(B, n, [&](int gs, int grid, int block) {
-    ROWS_DISPATCH(k_ssm_terms, y, v, t, u, cst, B, n, sde->kind, sde->beta_min, sde->beta_max, sde->G)
+  return launch_rows(B, n, [&](auto GS, int grid, int block) {
+    hipLaunchKernelGGL((k_ssm_terms<decltype(GS)::value>), dim3(grid), dim3(block), 0, S(stream), y, v, t, u, cst, B, n, sde->kind,
+                       sde->beta_min, sde->beta_max, sde->G);
   });
 }
 
 int msgm_ssm_loss(const float* out, const float* u, const float* cst, float* per, float* g, int64_t B, int64_t n,
                   float inv_batch, msgm_stream_t stream) {
   if (!out || !u || !cst || !per || !g || B <= 0 || n <= 0) return MSGM_E_BADARG;
-  return launch_rows(B, n, [&](int gs, int grid, int block) {
-    ROWS_DISPATCH(k_ssm_loss_generic, out, u, cst, per, g, B, n, inv_batch)
+  return launch_rows(B, n, [&](auto GS, int grid, int block) {
+    hipLaunchKernelGGL((k_ssm_loss_generic<decltype(GS)::value>), dim3(grid), dim3(block), 0, S(stream), out, u, cst, per, g, B, n, inv_batch);
   });
 }
 
@@ -855,16 +895,8 @@ int msgm_lincomb(float* out, const float* a, float c0, const float* b, float c1,
 
 int msgm_row_norm(const float* x, float* out, int64_t B, int64_t n, msgm_stream_t stream) {
   if (!x || !out || B <= 0 || n <= 0) return MSGM_E_BADARG;
-  return launch_rows(B, n, [&](int gs, int grid, int block) {
-    switch (gs) {
-      case 2: hipLaunchKernelGGL(k_row_norm<2>, dim3(grid), dim3(block), 0, S(stream), x, out, B, n); break;
-      case 4: hipLaunchKernelGGL(k_row_norm<4>, dim3(grid), dim3(block), 0, S(stream), x, out, B, n); break;
-      case 8: hipLaunchKernelGGL(k_row_norm<8>, dim3(grid), dim3(block), 0, S(stream), x, out, B, n); break;
-      case 16: hipLaunchKernelGGL(k_row_norm<16>, dim3(grid), dim3(block), 0, S(stream), x, out, B, n); break;
-      case 32: hipLaunchKernelGGL(k_row_norm<32>, dim3(grid), dim3(block), 0, S(stream), x, out, B, n); break;
-      case 256: hipLaunchKernelGGL(k_row_norm<256>, dim3(grid), dim3(block), 0, S(stream), x, out, B, n); break;
-      default: hipLaunchKernelGGL(k_row_norm<64>, dim3(grid), dim3(block), 0, S(stream), x, out, B, n); break;
-    }
+  return launch_rows(B, n, [&](auto GS, int grid, int block) {
+    hipLaunchKernelGGL((k_row_norm<decltype(GS)::value>), dim3(grid), dim3(block), 0, S(stream), x, out, B, n);
   });
 }
 

@@ -15,7 +15,7 @@ Extra keyword ``noise=`` (steps,B,n) injects the standard-normal draws
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -36,6 +36,66 @@ def EMstep(mu, delta, sigma, dW, sparse=False, I=None, K=None):
     else:
         dx = sigma * dW
     return mu * delta + dx
+
+
+class _Clock(NamedTuple):
+    """The process an integrator step advances and where its stage times, step length and Wiener draw come from.  The
+    three calling styles differ here and nowhere else:
+      eager samplers (``_Run.clock``): host stage times ``t=``, the step's ``z=`` or the Philox step index ``rng_step=i``;
+      ``GraphedStepSampler``: ``t_dev=`` the device clocks ``time_tick`` sets, ``step_dev=`` the device step counter;
+      the short rows of ``msgm_forward_perturb``: ``delta_rows=`` with ``t_frac=`` (times 0, t_b/2, t_b), ``delta = 0``."""
+    struct: object
+    proc: int
+    lmbd: float
+    delta: float
+    at: list            # at[k]: the keywords that place a stage at the step's k-th distinct stage time
+    draw: dict          # the keywords of the stage that draws the step's Wiener increment
+    score: Callable     # (x, k) -> a(x, T - t_k) for the reverse process, None for the forward one
+
+    def stage(self, k, out, base, c_out, x, strato, **kw):
+        """out = base + c_out * (the increment at x and stage time k); the score is evaluated first."""
+        return ops.sde_stage(out, base, c_out, x, self.score(x, k), self.struct, self.proc, strato, delta=self.delta,
+                             lmbd=self.lmbd, **self.at[k], **kw)
+
+
+def _em_step(c, x, other, norm0):
+    """Euler-Maruyama (sde_scheme.py:80-86).  The additive SDE updates x in place; the stencil / contraction of the
+    multiplicative ones reads neighbours, so they write ``other``.  Returns the buffer that holds the new state."""
+    out = x if c.struct.kind == L.SDE_SGM else other
+    return c.stage(0, out, x, 1.0, x, False, norm0=norm0, **c.draw)
+
+
+def _heun_step(c, x, bufs, norm0):
+    """Heun in Stratonovich form, stage times (t, t + delta) (sde_scheme.py:101-172); the new state is in bufs[-1]."""
+    dW, k1, xp, xn = bufs
+    c.stage(0, xp, x, 1.0, x, True, dW_out=dW, inc_out=k1, **c.draw)       # predictor x + K1 (keeps K1 and the Wiener increment)
+    ops.lincomb(xn, x, 1.0, k1, 0.5)                                       # x + K1/2
+    # corrector: (x + K1/2) + K2/2, K2 evaluated at the predictor (out aliases base, not x_eval)
+    return c.stage(1, xn, xn, 0.5, xp, True, dW=dW, norm0=norm0)
+
+
+def _rk4_step(c, x, bufs, norm0):
+    """RK4-Stratonovich, stage times (t, t + delta/2, t + delta), one dW (sde_scheme.py:174-269); the new state is in bufs[-1]."""
+    dW, k1, k2, k3, k4, xm, xn = bufs
+    c.stage(0, xm, x, 0.5, x, True, dW_out=dW, inc_out=k1, **c.draw)       # x + K1/2
+    c.stage(1, xn, x, 0.5, xm, True, dW=dW, inc_out=k2)
+    c.stage(1, xm, x, 1.0, xn, True, dW=dW, inc_out=k3)
+    c.stage(2, k4, None, 1.0, xm, True, dW=dW)
+    return ops.rk4_combine(xn, x, k1, k2, k3, k4, norm0=norm0)
+
+
+def _capture(body, dev):
+    """body() once on a side stream (loads the code objects: nothing of that may happen during capture), then captured."""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        body()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize(dev)
+    graph = ops.new_graph()
+    with torch.cuda.graph(graph):
+        body()
+    return graph
 
 
 class _Run:
@@ -100,6 +160,13 @@ class _Run:
         s = torch.full((self.B,), self.T - t, dtype=torch.float32, device=self.device)
         return self.sde.a(x, s).contiguous()
 
+    def clock(self, i, fracs=()):
+        """Step i on the host: stage times t_i and the fp32 sums t_i + f delta upstream forms (sde_scheme.py:150,233-247)."""
+        t = self.t(i)
+        times = [t] + [float(torch.tensor(t, dtype=torch.float32) + self.delta * f) for f in fracs]
+        return _Clock(self.struct, self.proc, self.lmbd, self.delta, [dict(t=s) for s in times],
+                      dict(z=self.z(i), rng=self.rng, rng_step=i), lambda x, k: self.score(x, times[k]))
+
     def after_step(self, i):
         if self.keep_all:
             self.traj[i + int(self.include_t0)].copy_(self.x)
@@ -135,17 +202,24 @@ def _em(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, 
         return r
     other = torch.empty_like(r.x)
     for i in range(num_steps):
-        t = r.t(i)
         if fused:                     # score net + update in ONE kernel
-            ops.mlp_em_step(P, r.x, r.struct, t, r.delta, r.lmbd, z=r.z(i), rng=r.rng, rng_step=i)
+            ops.mlp_em_step(P, r.x, r.struct, r.t(i), r.delta, r.lmbd, z=r.z(i), rng=r.rng, rng_step=i)
         else:
-            a = r.score(r.x, t)
-            inplace = r.base.kind == L.SDE_SGM
-            out = r.x if inplace else other
-            ops.sde_stage(out, r.x, 1.0, r.x, a, r.struct, r.proc, False, t, r.delta, r.lmbd, z=r.z(i), rng=r.rng,
-                          rng_step=i, norm0=r.norm0)
-            if not inplace:
-                r.x, other = out, r.x
+            new = _em_step(r.clock(i), r.x, other, r.norm0)
+            if new is other:
+                r.x, other = other, r.x
+        r.after_step(i)
+    return r
+
+
+def _integrate(step, fracs, nbuf, sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_, norm_correction,
+               noise):
+    """The eager Heun / RK4 loop: the step's new state (its last buffer) swaps places with the state."""
+    r = _Run(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_, norm_correction, noise)
+    bufs = [torch.empty_like(r.x) for _ in range(nbuf)]
+    for i in range(num_steps):
+        step(r.clock(i, fracs), r.x, bufs, r.norm0)
+        r.x, bufs[-1] = bufs[-1], r.x
         r.after_step(i)
     return r
 
@@ -155,21 +229,8 @@ def heun_sampler(sde, x_0, num_steps=1000, lmbd=0., keep_all_samples=True, sampl
                  include_t0=False, T_=-1, norm_correction=False, noise=None):
     """Heun / RK2 in Stratonovich form (sde_scheme.py:101-172):
     x <- x + 1/2 (K1 + K2), K = mu_Strato*delta + sigma.dW, one shared dW."""
-    r = _Run(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_, norm_correction, noise)
-    dW, k1, xp, xn = (torch.empty_like(r.x) for _ in range(4))
-    for i in range(num_steps):
-        t = r.t(i)
-        # predictor x + K1 (also keeps K1 and the Wiener increment)
-        ops.sde_stage(xp, r.x, 1.0, r.x, r.score(r.x, t), r.struct, r.proc, True, t, r.delta, r.lmbd, z=r.z(i),
-                      rng=r.rng, rng_step=i, dW_out=dW, inc_out=k1)
-        ops.lincomb(xn, r.x, 1.0, k1, 0.5)                                    # x + K1/2
-        t2 = float(torch.tensor(t, dtype=torch.float32) + r.delta)            # fp32 t + delta as upstream
-        # corrector: (x + K1/2) + K2/2, K2 evaluated at the predictor (out aliases base, not x_eval)
-        ops.sde_stage(xn, xn, 0.5, xp, r.score(xp, t2), r.struct, r.proc, True, t2, r.delta, r.lmbd, dW=dW,
-                      norm0=r.norm0)
-        r.x, xn = xn, r.x
-        r.after_step(i)
-    return r.result()
+    return _integrate(_heun_step, (1.0,), 4, sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_,
+                      norm_correction, noise).result()
 
 
 @torch.no_grad()
@@ -180,22 +241,8 @@ def rk4_stratonovich_sampler(sde, x_0, num_steps=1000, lmbd=0., keep_all_samples
                 noise).result()
 
 
-def _rk4(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_, norm_correction, noise):
-    r = _Run(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_, norm_correction, noise)
-    dW, k1, k2, k3, k4, xm, xn = (torch.empty_like(r.x) for _ in range(7))
-    for i in range(num_steps):
-        t = r.t(i)
-        tf = torch.tensor(t, dtype=torch.float32)
-        th, te = float(tf + r.delta / 2), float(tf + r.delta)
-        ops.sde_stage(xm, r.x, 0.5, r.x, r.score(r.x, t), r.struct, r.proc, True, t, r.delta, r.lmbd, z=r.z(i),
-                      rng=r.rng, rng_step=i, dW_out=dW, inc_out=k1)           # x + K1/2
-        ops.sde_stage(xn, r.x, 0.5, xm, r.score(xm, th), r.struct, r.proc, True, th, r.delta, r.lmbd, dW=dW, inc_out=k2)
-        ops.sde_stage(xm, r.x, 1.0, xn, r.score(xn, th), r.struct, r.proc, True, th, r.delta, r.lmbd, dW=dW, inc_out=k3)
-        ops.sde_stage(k4, None, 1.0, xm, r.score(xm, te), r.struct, r.proc, True, te, r.delta, r.lmbd, dW=dW)
-        ops.rk4_combine(xn, r.x, k1, k2, k3, k4, norm0=r.norm0)
-        r.x, xn = xn, r.x
-        r.after_step(i)
-    return r
+def _rk4(*args):
+    return _integrate(_rk4_step, (0.5, 1.0), 7, *args)
 
 
 @torch.no_grad()
@@ -208,27 +255,19 @@ def msgm_forward_perturb(base, t, y0, noise_main=None, noise_short=None):
     loop over rows, no D2H/H2D round trips."""
     from .SDEs import forward_SDE
     dev = y0.device
-    B, n = y0.shape
     nsf = base.num_steps_forward
-    T = base.T_float()
     tt = t.reshape(-1).contiguous().float()
-    k = ops.forward_step_index(tt, nsf, T)
+    k = ops.forward_step_index(tt, nsf, base.T_float())
     fwd = forward_SDE(base, base.T)
     kept = _rk4(fwd, y0, nsf, 0., False, k, True, -1, False, noise_main).kept
     # rows with k == 0: one RK4 step, delta_b = t_b, stage times 0, t_b/2, t_b/2, t_b
-    st = base.struct()
     x = y0.contiguous().float()
-    dW, k1, k2, k3, k4, xm, xn = (torch.empty_like(x) for _ in range(7))
+    bufs = [torch.empty_like(x) for _ in range(7)]
     rng = None if noise_short is not None else base.philox(dev)
     z = None if noise_short is None else noise_short.to(dev).contiguous()
-    kw = dict(delta_rows=tt)
-    ops.sde_stage(xm, x, 0.5, x, None, st, L.PROC_FORWARD, True, 0.0, 0.0, 0.0, z=z, rng=rng, rng_step=nsf + 1,
-                  dW_out=dW, inc_out=k1, t_frac=0.0, **kw)
-    ops.sde_stage(xn, x, 0.5, xm, None, st, L.PROC_FORWARD, True, 0.0, 0.0, 0.0, dW=dW, inc_out=k2, t_frac=0.5, **kw)
-    ops.sde_stage(xm, x, 1.0, xn, None, st, L.PROC_FORWARD, True, 0.0, 0.0, 0.0, dW=dW, inc_out=k3, t_frac=0.5, **kw)
-    ops.sde_stage(k4, None, 1.0, xm, None, st, L.PROC_FORWARD, True, 0.0, 0.0, 0.0, dW=dW, t_frac=1.0, **kw)
-    ops.rk4_combine(xn, x, k1, k2, k3, k4)
-    ops.keep_rows(kept, xn, k, 0)
+    c = _Clock(base.struct(), L.PROC_FORWARD, 0.0, 0.0, [dict(t=0.0, delta_rows=tt, t_frac=f) for f in (0.0, 0.5, 1.0)],
+               dict(z=z, rng=rng, rng_step=nsf + 1), lambda xx, kk: None)
+    ops.keep_rows(kept, _rk4_step(c, x, bufs, None), k, 0)
     base.philox(dev).advance(2 * nsf + 2)
     return kept
 
@@ -267,15 +306,7 @@ class GraphedEMSampler:
                     ops.mlp_em_step(P, self.x, st, ts[i].item(), delta, lmbd, rng=self.rng, rng_step=i)
             self.rng.advance(num_steps)
 
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            body()                                   # warm-up (loads code objects) before capture
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
-        self.graph = ops.new_graph()
-        with torch.cuda.graph(self.graph):
-            body()
+        self.graph = _capture(body, dev)
 
     @torch.no_grad()
     def run(self, x_0):
@@ -293,11 +324,14 @@ class GraphedStepSampler:
     sde_scheme.py:81).  ``method='rk4'`` is what the driver generates with (MSGM_higherDim.py:903).  Only kernel nodes
     are captured (no D2D memcpy / memset nodes — see msgm_zero_async in csrc/common.h)."""
 
+    # method -> (the step, the stage times after t as fractions of delta, stage buffers; em: ``other``, multiplicative SDEs only)
+    METHODS = {"em": (_em_step, (), 1), "heun": (_heun_step, (1.0,), 4), "rk4": (_rk4_step, (0.5, 1.0), 7)}
+
     def __init__(self, sde, B, n, num_steps, lmbd=0.0, norm_correction=False, method="em"):
         from .SDEs import PluginReverseSDE
         if not isinstance(sde, PluginReverseSDE):
             raise MsgmError("GraphedStepSampler integrates a PluginReverseSDE")
-        if method not in ("em", "heun", "rk4"):
+        if method not in self.METHODS:
             raise MsgmError(f"unknown integrator {method}")
         base = sde.base_sde
         dev = sde.T.device
@@ -305,68 +339,34 @@ class GraphedStepSampler:
         T = base.T_float()
         self.ts = (torch.linspace(0, 1, num_steps + 1) * T).to(dev)
         self.step = torch.zeros(1, dtype=torch.int64, device=dev)
-        nstage = {"em": 1, "heun": 2, "rk4": 3}[method]                   # distinct stage times
-        self.t_dev = [torch.zeros(1, device=dev) for _ in range(nstage)]
-        self.s = [torch.zeros(B, device=dev) for _ in range(nstage)]
+        step, fracs, nbuf = self.METHODS[method]
+        self.t_dev = [torch.zeros(1, device=dev) for _ in range(1 + len(fracs))]      # distinct stage times
+        self.s = [torch.zeros(B, device=dev) for _ in self.t_dev]
         self.x = torch.zeros(B, n, device=dev)
         self.norm0 = torch.zeros(B, device=dev) if norm_correction else None
         self.rng = base.philox(dev)
         st, delta = base.struct(), T / num_steps
         self._keep = st
-        inplace = base.kind == L.SDE_SGM
-        buf = lambda: torch.zeros(B, n, device=dev)
         if method == "em":
-            other = None if inplace else buf()
-        elif method == "heun":
-            dW, k1, xp, xn = buf(), buf(), buf(), buf()
+            bufs = None if base.kind == L.SDE_SGM else torch.zeros(B, n, device=dev)
         else:
-            dW, k1, k2, k3, k4, xm, xn = (buf() for _ in range(7))
-        f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))       # the fp32 value upstream adds to the fp32 t
-        R = L.PROC_REVERSE
-
-        def score(xx, k):
-            return sde.a(xx, self.s[k]).contiguous()
+            bufs = [torch.zeros(B, n, device=dev) for _ in range(nbuf)]
+        # the fp32 value upstream adds to the fp32 t; 0.0 (no add) for the step's own time
+        t_add = [0.0] + [float(torch.tensor(delta * f, dtype=torch.float32)) for f in fracs]
+        clock = _Clock(st, L.PROC_REVERSE, lmbd, delta, [dict(t=0.0, t_dev=td) for td in self.t_dev],
+                       dict(rng=self.rng, step_dev=self.step), lambda xx, k: sde.a(xx, self.s[k]).contiguous())
 
         def body():
-            x = self.x
-            ops.time_tick(self.ts, self.step, T, self.t_dev[0], self.s[0])
-            if method == "em":
-                out = x if inplace else other
-                ops.sde_stage(out, x, 1.0, x, score(x, 0), st, R, False, 0.0, delta, lmbd, rng=self.rng, norm0=self.norm0,
-                              t_dev=self.t_dev[0], step_dev=self.step)
-                if not inplace:
-                    ops.lincomb(x, out, 1.0)
-            elif method == "heun":                                        # sde_scheme.py:101-172
-                ops.time_tick(self.ts, self.step, T, self.t_dev[1], self.s[1], t_add=f32(delta))
-                ops.sde_stage(xp, x, 1.0, x, score(x, 0), st, R, True, 0.0, delta, lmbd, rng=self.rng, dW_out=dW, inc_out=k1,
-                              t_dev=self.t_dev[0], step_dev=self.step)
-                ops.lincomb(xn, x, 1.0, k1, 0.5)
-                ops.sde_stage(xn, xn, 0.5, xp, score(xp, 1), st, R, True, 0.0, delta, lmbd, dW=dW, norm0=self.norm0,
-                              t_dev=self.t_dev[1])
-                ops.lincomb(x, xn, 1.0)
-            else:                                                         # sde_scheme.py:174-269
-                ops.time_tick(self.ts, self.step, T, self.t_dev[1], self.s[1], t_add=f32(delta / 2))
-                ops.time_tick(self.ts, self.step, T, self.t_dev[2], self.s[2], t_add=f32(delta))
-                ops.sde_stage(xm, x, 0.5, x, score(x, 0), st, R, True, 0.0, delta, lmbd, rng=self.rng, dW_out=dW, inc_out=k1,
-                              t_dev=self.t_dev[0], step_dev=self.step)
-                ops.sde_stage(xn, x, 0.5, xm, score(xm, 1), st, R, True, 0.0, delta, lmbd, dW=dW, inc_out=k2, t_dev=self.t_dev[1])
-                ops.sde_stage(xm, x, 1.0, xn, score(xn, 1), st, R, True, 0.0, delta, lmbd, dW=dW, inc_out=k3, t_dev=self.t_dev[1])
-                ops.sde_stage(k4, None, 1.0, xm, score(xm, 2), st, R, True, 0.0, delta, lmbd, dW=dW, t_dev=self.t_dev[2])
-                ops.rk4_combine(xn, x, k1, k2, k3, k4, norm0=self.norm0)
-                ops.lincomb(x, xn, 1.0)
+            for td, s, add in zip(self.t_dev, self.s, t_add):
+                ops.time_tick(self.ts, self.step, T, td, s, t_add=add)
+            new = step(clock, self.x, bufs, self.norm0)
+            if new is not self.x:
+                ops.lincomb(self.x, new, 1.0)
             ops.counter_inc(self.step)
 
-        # the captured graph holds raw pointers only: the stage buffers (other, dW, k1, ...) live as long as this closure
+        # the captured graph holds raw pointers only: the stage buffers live as long as this closure
         self._body = body
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            body()                                   # warm-up outside capture
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.graph = ops.new_graph()
-        with torch.cuda.graph(self.graph):
-            body()
+        self.graph = _capture(body, dev)
 
     @torch.no_grad()
     def run(self, x_0):

@@ -38,10 +38,14 @@ Case -> kernel and body, from the dispatch conditions of msgm_sde_stage, msgm_rk
                                                 k_ssm_loss_diag<GS>
   ssm_terms_dense n 2|7|64                      k_ssm_terms<2|8|64>        dense; 65 refused
   perturb_*                                     k_perturb_vp               d 1|2|3|5|1024: quads over 4, 2-3, 2, 1-2 rows
+  ssm_prep (5,3) (3,4) (33,8) (7,1)             k_ssm_prep                 quads over 2, 1, 1, 4 rows, ragged last quad (15, 7
+                                                                           elements); shard base; the step counter; bitwise
+                                                                           k_perturb_vp and k_rademacher (vp_row / vp_value)
   time_tick                                     k_time_tick                B 65541: past the 256-block cap; clamp
   lincomb / keep_rows / adam / fill             k_lincomb, k_keep_rows, k_adam (vector and scalar body), k_fill<>
 """
 import os
+import re
 
 import numpy as np
 import pytest
@@ -120,6 +124,16 @@ def c_perturb_vp_at(L, x0, st, t, eps=None, rng=None):
     _call(L, "msgm_perturb_vp_at", L.ptr(x0), L.ptr(y), L.ptr(eo), B, d, st, L.ptr(t), L.ptr(eps),
           rng.ptr() if rng is not None else None)
     return (y, eo) if rng is not None else y
+
+
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "msgm_hip.h")) as _h:
+    MSGM_E_BADARG = int(re.search(r"MSGM_E_BADARG\s*=\s*(-?\d+)", _h.read()).group(1))      # _lib carries MSGM_E_UNSUPPORTED only
+
+
+def c_ssm_prep(L, x0, st, rng, ctr):
+    (B, d), y, t, v = x0.shape, nan(*x0.shape), nan(x0.shape[0]), nan(*x0.shape)
+    _call(L, "msgm_ssm_prep", L.ptr(x0), L.ptr(y), L.ptr(t), L.ptr(v), B, d, st, rng.ptr(), L.ptr(ctr))
+    return y, t, v
 
 
 def shifted(t):
@@ -443,6 +457,41 @@ def test_perturb_vp_writes_every_row_time(ops, L, d):
     y, t = c_perturb_vp(L, x0, sde(L, "sgm"), u, eps)
     assert torch.equal(t, R.clamp_time(u)), "t_out: every row, bit-exact under the clamp"
     check("perturb", 0, y, R.perturb_vp(x0, t, eps), f"perturb_vp d={d}")
+
+
+SSM_PREP_SHAPES = [(5, 3), (3, 4), (33, 8), (7, 1)]
+
+
+@pytest.mark.parametrize("B,d", SSM_PREP_SHAPES)
+@pytest.mark.parametrize("row_base", [0, 4])
+def test_ssm_prep(ops, L, B, d, row_base):
+    """The kernel that opens every training step: y and t are the bits of msgm_perturb_vp(rng=) and v those of
+    msgm_rademacher(rng=) from an identical Philox state (same streams and indices, shared vp_row / vp_value,
+    contraction off), the step counter ticks once, the Philox state is only read; y also against float64 with the
+    perturb family's constant."""
+    g = torch.Generator(device=DEV).manual_seed(31 * B + d)
+    x0, st = torch.randn(B, d, generator=g, device=DEV), sde(L, "sgm")
+    rng = L.PhiloxState(SEED, DEV, OFFSET, row_base, d)
+    state0 = rng.state.clone()
+    ctr = torch.tensor([41], dtype=torch.int64, device=DEV)
+    y, t, v = c_ssm_prep(L, x0, st, rng, ctr)
+    assert all(bool(torch.isfinite(o).all()) for o in (y, t, v)), "non-finite output (an unwritten NaN pre-fill?)"
+    assert int(ctr) == 42 and torch.equal(rng.state, state0)
+    yp, tp = ops.perturb_vp(x0, st, rng=rng)
+    assert torch.equal(y, yp) and torch.equal(t, tp)
+    # independent of vp_row: the row times are the clamp (bit-exact restatement) of the device fill of RNG_STREAM_T
+    assert torch.equal(t, R.clamp_time(ops.fill_uniform(nan(B), rng, L.RNG_STREAM_T)))
+    assert torch.equal(v, ops.rademacher((B, d), DEV, rng=rng))
+    if row_base:                                             # a shard draws other numbers than the unsharded state
+        assert not torch.equal(t, ops.perturb_vp(x0, st, rng=L.PhiloxState(SEED, DEV, OFFSET))[1])
+    eps = ops.fill_normal(nan(B, d), rng, L.RNG_STREAM_EPS)
+    check("perturb", 0, y, R.perturb_vp(x0, t, eps), f"ssm_prep ({B},{d}) row_base={row_base}")
+    assert all(torch.equal(a, b) for a, b in zip(c_ssm_prep(L, x0, st, rng, None), (y, t, v))), "null step counter"
+    assert int(ctr) == 42
+    args = lambda s, r: (L.ptr(x0), L.ptr(y), L.ptr(t), L.ptr(v), B, d, s, r, L.ptr(ctr), L.stream())   # noqa: E731
+    assert L.lib().msgm_ssm_prep(*args(sde(L, "sparse"), rng.ptr())) == L.MSGM_E_UNSUPPORTED
+    assert L.lib().msgm_ssm_prep(*args(st, None)) == MSGM_E_BADARG
+    assert int(ctr) == 42
 
 
 @pytest.mark.parametrize("B", [1, 255, 257, 65541])
