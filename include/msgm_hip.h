@@ -236,6 +236,35 @@ int msgm_mlp_em_step(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm
 int msgm_mlp_em_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm_sde_t* sde, const float* ts, int32_t n_steps,
                      float delta, float lmbd, const uint64_t* rng, uint64_t rng_step0, msgm_stream_t stream);
 
+/* The WHOLE sampler loop of euler_maruyama_sampler / heun_sampler / rk4_stratonovich_sampler (sde_scheme.py:43-99,
+ * 101-172, 174-269) for the MLP and the reverse process of any of the three SDE families, in ONE launch — what the
+ * driver generates with (rk4_stratonovich_sampler, MSGM_higherDim.py:903).  Per step it replaces 1 / 2 / 4
+ * msgm_mlp_forward launches, as many msgm_sde_stage launches, the Heun msgm_lincomb or the msgm_rk4_combine, the
+ * trajectory copy and msgm_keep_rows.  Rows never interact (SGM is diagonal, the sparse tensor a circular 3-point
+ * stencil inside a row, the dense contraction and the norm correction per-row sums), so a workgroup carries its rows
+ * through every stage of every step; the stage formulas are those of msgm_sde_stage (csrc/sde_stage.h).
+ *   method   MSGM_METHOD_EM (Ito form), MSGM_METHOD_HEUN, MSGM_METHOD_RK4 (Stratonovich form, one dW per step)
+ *   ts       device array of n_steps + 1 times, linspace(0,1,N+1)*T as upstream (sde_scheme.py:59); the later stages
+ *            run at ts[i] + fp32(delta/2) and ts[i] + fp32(delta), added in fp32 (msgm_time_tick_stage)
+ *   z / rng  the step's standard normals: z[i] of an (n_steps, B, d) array, else Philox step rng_step0 + i of
+ *            RNG_STREAM_DW at the global element index — the numbers the composed path draws
+ *   norm0    (B) optional: norm correction where the composed path applies it (EM stage, Heun corrector, RK4 combine)
+ *   traj     optional (n_steps + include_t0, B, d): row i + include_t0 receives the state after step i (row 0 of an
+ *            include_t0 trajectory is the caller's)
+ *   keep_stop, kept   optional: msgm_keep_rows(kept, x, keep_stop, i + include_t0) after every step
+ *   workspace   msgm_mlp_sde_loop_workspace(B, d, method) bytes: evaluation point, Wiener increment and the running
+ *            sum of increments, (3, B, d) floats for Heun / RK4, nothing for Euler-Maruyama
+ * x is updated in place to the final state.  Never allocates or synchronises.  MSGM_E_UNSUPPORTED where
+ * msgm_mlp_sde_loop_supported says no: B <= 32 (a workgroup needs two tiles), the extra-wide class (d > 30 or
+ * d + 1 + premodule > 32), dense tensors with n > 16. */
+enum { MSGM_METHOD_EM = 0, MSGM_METHOD_HEUN = 1, MSGM_METHOD_RK4 = 2 };
+int msgm_mlp_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B);   /* host only */
+size_t msgm_mlp_sde_loop_workspace(int64_t B, int32_t d, int32_t method);                              /* host only */
+int msgm_mlp_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts,
+                      int32_t n_steps, float delta, float sqrt_delta, float lmbd, const float* z, const uint64_t* rng,
+                      uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop,
+                      float* kept, void* workspace, size_t workspace_bytes, msgm_stream_t stream);
+
 /* Fused SSM training pass for SGM + MLP (replaces SDEs.py:607-646 +
  * loss.mean().backward(), MSGM_higherDim.py:807-808):
  *   per sample: a = MLP(y,t), adot = J_a v (forward-mode), loss_b =

@@ -19,6 +19,7 @@ MSGM_OK = 0
 MSGM_E_UNSUPPORTED = -2
 SDE_SGM, SDE_MSGM_SPARSE, SDE_MSGM_DENSE = 0, 1, 2
 PROC_REVERSE, PROC_FORWARD = 0, 1
+METHOD_EM, METHOD_HEUN, METHOD_RK4 = 0, 1, 2          # msgm_mlp_sde_loop
 RNG_STREAM_T, RNG_STREAM_EPS, RNG_STREAM_V, RNG_STREAM_DW, RNG_STREAM_ROWS, RNG_STREAM_USER = 0, 1, 2, 3, 4, 16
 RNG_STREAM_DROPOUT = 64          # + the ResBlock's index: the U-Net's dropout masks (include/msgm_hip.h, msgm_dropout_t)
 
@@ -173,6 +174,10 @@ SIGNATURES = {
     "msgm_mlp_forward": (C.c_int, [C.POINTER(MlpParamsT), _P, _P, _P, _I64, _P]),
     "msgm_mlp_em_step": (C.c_int, [C.POINTER(MlpParamsT), _P, _I64, C.POINTER(SdeT), _F, _F, _F, _P, _P, _U64, _P]),
     "msgm_mlp_em_loop": (C.c_int, [C.POINTER(MlpParamsT), _P, _I64, C.POINTER(SdeT), _P, _I32, _F, _F, _P, _U64, _P]),
+    "msgm_mlp_sde_loop_supported": (C.c_int, [_I32, _I32, _I32, _I64, _I64]),
+    "msgm_mlp_sde_loop_workspace": (_SZ, [_I64, _I32, _I32]),
+    "msgm_mlp_sde_loop": (C.c_int, [C.POINTER(MlpParamsT), _P, _I64, C.POINTER(SdeT), _I32, _P, _I32, _F, _F, _F, _P, _P, _U64, _P, _P,
+                                    _I32, _P, _P, _P, _SZ, _P]),
     "msgm_mlp_ssm_workspace": (_SZ, [_I32, _I32]),
     "msgm_mlp_num_params": (_I64, [_I32, _I32]),
     "msgm_mlp_ssm_partial": (C.c_int, [C.POINTER(MlpParamsT), _P, _P, _P, _P, _P, _I64, C.POINTER(SdeT), _F, _P, _P, _SZ,

@@ -20,6 +20,7 @@
 //   * per-workgroup gradient slabs are written once at the end and reduced by a
 //     second (deterministic) kernel — no float atomics.
 #include "common.h"
+#include "sde_stage.h"
 
 #define HID 128
 
@@ -61,13 +62,16 @@ struct MlpLds {
   static constexpr int DP = WIDE ? 32 : 16;        // padded output width
   static constexpr int DROWS = TINY ? 4 : DP;      // rows of W4 held in LDS
   static constexpr bool TRAIN = MODE == 2;
+  static constexpr bool SDE = MODE == 3;
   static constexpr int SPT = TRAIN ? 16 : 32;      // samples per tile
   static constexpr int DMAX = WIDE ? 32 : (TINY ? 4 : 16);   // raw rows are packed (pitch d), sized for d <= DMAX
-  // one raw input buffer: the tile's y | v | u chunks, t and cst, copied verbatim from global one tile ahead
+  // one raw input buffer: the tile's y | v | u chunks (sampler loop: y | dW), t and cst, copied verbatim from global one
+  // tile ahead
   static constexpr int RY = 0;
   static constexpr int RV = RY + SPT * DMAX;
   static constexpr int RU = RV + (TRAIN ? SPT * DMAX : 0);
-  static constexpr int RT = RU + (TRAIN ? SPT * DMAX : 0);
+  static constexpr int RW = RU + (TRAIN ? SPT * DMAX : 0);
+  static constexpr int RT = RW + (SDE ? SPT * DMAX : 0);
   static constexpr int RC = RT + 32;
   static constexpr int RAWN = RC + 16;
   static constexpr int X = 0;
@@ -111,9 +115,33 @@ struct MlpArgs {
   float inv_batch;
   float* loss_per; float* slabs;   // slabs: [gridDim.x][slab_stride], element n_params = loss sum; stride = 4-aligned
   int64_t n_params;
+  // sampler loop (MODE_SDE): n_stages = 1 (EM), 2 (Heun) or 4 (RK4-Stratonovich) stages per step, SDE family `kind`
+  int n_stages, kind;
+  float t_half, t_full;            // fp32 delta/2 and delta: what the later stages add to ts[i]
+  const float* G; const float* L_G;   // dense tensor (n <= 16), read through L2 by every row
+  const float* norm0;              // (B) optional: rows are rescaled to this norm at the end of a step
+  float* ws;                       // (3, B, d) stage state: evaluation point | Wiener increment | running sum of increments
+  float* traj; int include_t0;     // optional (N[+1], B, d): row i + include_t0 receives the state after step i
+  const int32_t* keep_stop; float* kept;   // optional: row b of kept receives the state after step keep_stop[b] - include_t0
 };
 
-enum { MODE_FWD = 0, MODE_EM = 1, MODE_TRAIN = 2 };
+enum { MODE_FWD = 0, MODE_EM = 1, MODE_TRAIN = 2, MODE_SDE = 3 };
+// the modes whose net is the score of a reverse process: its time argument is T - t
+constexpr bool mode_reverse(int mode) { return mode == MODE_EM || mode == MODE_SDE; }
+
+// Item `item` of the sampler loop = (step i, stage): the stage index runs fastest.
+struct SdeItem { int i, stage; };
+__device__ __forceinline__ SdeItem sde_item(const MlpArgs& A, int item) {
+  const int i = item / A.n_stages;
+  return {i, item - i * A.n_stages};
+}
+// Stage times ts[i], ts[i] + fp32(delta/2) (RK4's two middle stages), ts[i] + fp32(delta): fp32 adds, as k_time_tick.
+__device__ __forceinline__ float sde_item_time(const MlpArgs& A, SdeItem it) {
+  const float add = it.stage == 0 ? 0.f : ((A.n_stages == 4 && it.stage < 3) ? A.t_half : A.t_full);
+  return add != 0.f ? __fadd_rn(A.ts[it.i], add) : A.ts[it.i];
+}
+// A word that this workgroup wrote an item ago: device-scope load, so no stale L1 line is served.
+__device__ __forceinline__ float load_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // Swish and its first two derivatives from z.
 __device__ __forceinline__ void swish012(float z, float& s0, float& s1, float& s2) {
@@ -379,7 +407,7 @@ struct MlpLayout {
 // operand h0 at the end of the previous tile (build_h0) — no global-load latency sits on the tile's critical path.
 // A thread holds NR elements of each chunk (element ev + NT k of the tile, ev = its index in the workgroup), and
 // thread tid < SPT the t / cst of sample tid.  STAGE_U: the u chunk travels the same way (else its reader fetches it).
-template <int NR> struct RawRegs { float y[NR], v[NR], u[NR], t = 0.f, c = 0.f; };
+template <int NR> struct RawRegs { float y[NR], v[NR], u[NR], t = 0.f, c = 0.f, w[NR]; };
 
 template <int MODE, class LO, int NT, bool STAGE_U, int NR>
 __device__ __forceinline__ void raw_issue(const MlpArgs& A, RawRegs<NR>& pf, int ev, int tid, int64_t tl, int step) {
@@ -394,7 +422,13 @@ __device__ __forceinline__ void raw_issue(const MlpArgs& A, RawRegs<NR>& pf, int
     const bool ok = e < cnt && e0 + e < etot;
     // EM loop: x was rewritten by THIS workgroup a sweep ago — device-scope load so no stale L1 line is served
     if (MODE == MODE_EM) pf.y[k] = ok ? __hip_atomic_load(A.y + e0 + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    else pf.y[k] = ok ? A.y[e0 + e] : 0.f;
+    else if (MODE == MODE_SDE) {
+      // sampler loop: the net's input is the state (stage 0) or the evaluation point the previous stage left in the
+      // workspace, which also holds the step's Wiener increment since stage 0
+      const int stage = sde_item(A, step).stage;
+      pf.y[k] = ok ? load_agent((stage == 0 ? A.y : A.ws) + e0 + e) : 0.f;
+      pf.w[k] = (ok && stage > 0) ? load_agent(A.ws + etot + e0 + e) : 0.f;
+    } else pf.y[k] = ok ? A.y[e0 + e] : 0.f;
     if (MODE == MODE_TRAIN) {
       pf.v[k] = ok ? A.v[e0 + e] : 0.f;
       if (STAGE_U) pf.u[k] = (ok && A.u) ? A.u[e0 + e] : 0.f;
@@ -402,7 +436,8 @@ __device__ __forceinline__ void raw_issue(const MlpArgs& A, RawRegs<NR>& pf, int
   }
   if (tid < SPT) {
     const int64_t smp = tl * SPT + tid;
-    pf.t = smp < A.B ? (A.t ? A.t[smp] : ((MODE == MODE_EM && A.ts) ? A.ts[step] : A.t_scalar)) : 0.f;
+    if (MODE == MODE_SDE) pf.t = smp < A.B ? sde_item_time(A, sde_item(A, step)) : 0.f;
+    else pf.t = smp < A.B ? (A.t ? A.t[smp] : ((MODE == MODE_EM && A.ts) ? A.ts[step] : A.t_scalar)) : 0.f;
     if (MODE == MODE_TRAIN) pf.c = (smp < A.B && A.u && A.cst) ? A.cst[smp] : 0.f;
   }
 }
@@ -416,6 +451,7 @@ __device__ __forceinline__ void raw_commit(const RawRegs<NR>& pf, float* R, int 
       R[LO::RY + e] = pf.y[k];
       if (MODE == MODE_TRAIN) R[LO::RV + e] = pf.v[k];
       if constexpr (MODE == MODE_TRAIN && STAGE_U) R[LO::RU + e] = pf.u[k];
+      if constexpr (MODE == MODE_SDE) R[LO::RW + e] = pf.w[k];
     }
   }
   if (tid < SPT) { R[LO::RT + tid] = pf.t; if (MODE == MODE_TRAIN) R[LO::RC + tid] = pf.c; }
@@ -435,7 +471,7 @@ __device__ __forceinline__ void build_h0(const MlpArgs& A, float* H0b, const flo
   float tt = 0.f;
   if (live) {
     tt = R[LO::RT + l];
-    if (MODE == MODE_EM) tt = A.T - tt;                                 // s = T - t  SDEs.py:556-557
+    if (mode_reverse(MODE)) tt = A.T - tt;                              // s = T - t  SDEs.py:556-557
   }
   const float* yr = R + LO::RY + l * d;
   const float* vr = R + LO::RV + l * d;
@@ -516,6 +552,137 @@ __device__ __forceinline__ float em_update(const MlpArgs& A, float ca, float a, 
   const float zz = A.z ? A.z[e] : philox_normal1(A.rng, A.rng_step + (uint64_t)step, RNG_STREAM_DW, (uint64_t)e);
   const float mu = ca * (sb * a) - (-0.5f * beta * x);
   return x + (mu * A.delta + (sqrtf(1.0f - A.lmbd) * sb) * (A.sqrt_delta * zz));
+}
+
+// ---- sampler loop (MODE_SDE): the stage update behind the layer-4 reduce.  Thread (sample c, output o) owns element
+// idx = c d + o of the tile — the element it fetched in raw_issue — and forms the stage's increment with the formulas of
+// msgm_sde_stage (sde_stage.h), in the order of _em_step / _heun_step / _rk4_step (sde_scheme.py):
+//   EM    stage 0: x <- x + K                                   (Ito form, norm correction)
+//   Heun  stage 0: E = x + K1, S = K1;  stage 1 at E: x <- (x + S/2) + K2/2          (norm correction)
+//   RK4   stage 0: E = x + K1/2, S = K1;  1 at E: E = x + K2/2, S += 2 K2;  2 at E: E = x + K3, S += 2 K3;
+//         stage 3 at E: x <- x + (S + K4)/6                                           (norm correction)
+// E (the next stage's evaluation point), the step's Wiener increment and S live in the caller's workspace and only travel
+// to L2 and back.  Neighbours of x, a and dW in the row (sparse stencil, dense contraction) and the row sum of the norm
+// correction are read from LDS: the raw row, the reduced layer-4 outputs (parked in wave 0's partial slice) and the
+// updated row (in wave 1's slice, dead after the reduce).
+template <int NR> struct SdeRegs { float xb[NR], sm[NR]; };
+template <> struct SdeRegs<0> {};   // the other modes carry nothing
+
+// the step's state x and the running sum S of this thread's elements: issued ahead of the layer-3 gemm
+template <class LO, int NT, int NR>
+__device__ __forceinline__ void sde_issue(const MlpArgs& A, SdeRegs<NR>& sr, const float* R, int64_t s_base, int tid, SdeItem it) {
+  const int d = A.P.d;
+  const int64_t etot = A.B * d;
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    const int idx = tid + NT * k;
+    const int64_t e = s_base * d + idx;
+    const bool ok = idx < LO::SPT * d && e < etot;
+    sr.xb[k] = 0.f; sr.sm[k] = 0.f;
+    if (ok && it.stage == 0) sr.xb[k] = R[LO::RY + idx];          // stage 0 is evaluated at x itself
+    if (ok && it.stage > 0) { sr.xb[k] = load_agent(A.y + e); sr.sm[k] = load_agent(A.ws + 2 * etot + e); }
+  }
+}
+
+template <class LO, int NT, int NW, int NR>
+__device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& sr, float* PART, const float* B4s, float* R,
+                                           int64_t s_base, int tid, SdeItem it) {
+  constexpr int PP = LO::PP;
+  const int d = A.P.d, NS = A.n_stages;
+  const int64_t etot = A.B * d;
+  const bool last = it.stage == NS - 1;
+  const bool nc = last && A.norm0;
+  StageArgs S{};
+  S.kind = A.kind; S.proc = MSGM_PROC_REVERSE; S.strato = NS > 1;
+  S.b0 = A.b0; S.b1 = A.b1; S.T = A.T; S.delta = A.delta; S.sqrt_delta = A.sqrt_delta; S.lmbd = A.lmbd;
+  const float sig_scale = stage_sig_scale(S);
+  // a = b4 + the waves' K-slices, parked in wave 0's slice; stage 0 draws the step's Wiener increment
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    const int idx = tid + NT * k, c = idx / d, o = idx - c * d;
+    const int64_t e = s_base * d + idx;
+    if (idx < LO::SPT * d && e < etot) {
+      float a = B4s[o];
+#pragma unroll
+      for (int ww = 0; ww < NW; ++ww) a += PART[(ww * 32 + c) * PP + o];
+      PART[c * PP + o] = a;
+      if (it.stage == 0) {
+        const float zz = A.z ? A.z[(int64_t)it.i * etot + e]
+                             : philox_normal1(A.rng, A.rng_step + (uint64_t)it.i, RNG_STREAM_DW, (uint64_t)e);
+        const float w = A.sqrt_delta * zz;                     // delta**0.5 * randn   sde_scheme.py:84
+        R[LO::RW + idx] = w;
+        if (NS > 1) A.ws[etot + e] = w;
+      }
+    }
+  }
+  lds_barrier();
+  float val[NR];
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    const int idx = tid + NT * k, c = idx / d, o = idx - c * d;
+    const int64_t e = s_base * d + idx;
+    val[k] = 0.f;
+    if (idx < LO::SPT * d && e < etot) {
+      const float* xr = R + LO::RY + c * d;
+      const float* wr = R + LO::RW + c * d;
+      const float* ar = PART + c * PP;
+      const StageCoef sc = stage_coef<false>(S, R[LO::RT + c], 0);
+      const float xi = xr[o];
+      float inc;
+      if (A.kind == MSGM_SDE_SGM && !nc) {       // the flat kernel's spelling; with norm correction the row kernel's
+        inc = diag_inc(S, DiagCoef{sc.beta, sc.sb, 1.0f - 0.5f * A.lmbd, sig_scale * sc.sb}, xi, ar[o], wr[o]);
+      } else {
+        float f, fs = 0.f, div, ga, gw;
+        if (A.kind == MSGM_SDE_SGM) {
+          f = -0.5f * sc.beta * xi; fs = f; div = 0.f;
+          ga = sc.sb * ar[o]; gw = sc.sb * wr[o];
+        } else if (A.kind == MSGM_SDE_MSGM_SPARSE) {
+          const int ip = (o + 1 == d) ? 0 : o + 1, im = (o == 0) ? d - 1 : o - 1;
+          const float xp = xr[ip], xm = xr[im];
+          f = 0.5f * sc.beta * xi; div = 2.0f * f;
+          gw = sparse_g(sc.sb, xp, xm, wr[o], wr[im]);
+          ga = sparse_g(sc.sb, xp, xm, ar[o], ar[im]);
+        } else {
+          const DenseTerms t = dense_g(A.G, A.L_G, d, o, sc.beta, sc.sb, xr, wr, ar);
+          f = t.f; div = 2.0f * f; gw = t.gw; ga = t.ga;
+        }
+        inc = stage_mu(S, ga, f, fs, div) * sc.delta + sig_scale * gw;      // sde_scheme.py:40
+      }
+      const float x = sr.xb[k];
+      if (!last) {
+        const float c_out = (NS == 4 && it.stage < 2) ? 0.5f : 1.0f;
+        A.ws[e] = x + c_out * inc;
+        A.ws[2 * etot + e] = it.stage == 0 ? inc : rk4_add(sr.sm[k], inc);
+      } else {
+        float v;
+        if (NS == 1) v = x + 1.0f * inc;
+        else if (NS == 2) { v = 1.0f * x; v += 0.5f * sr.sm[k]; v = v + 0.5f * inc; }
+        else v = rk4_close(x, sr.sm[k], 0.f + 1.0f * inc);
+        val[k] = v;
+        if (nc) PART[(32 + c) * PP + o] = v;
+      }
+    }
+  }
+  if (!last) return;
+  if (nc) lds_barrier();
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    const int idx = tid + NT * k, c = idx / d;
+    const int64_t e = s_base * d + idx, smp = s_base + c;
+    if (idx < LO::SPT * d && e < etot) {
+      float v = val[k];
+      if (nc) {                                                // x <- x norm0/|x|   sde_scheme.py:85-86
+        const float* row = PART + (32 + c) * PP;
+        float ss = 0.f;
+        for (int j = 0; j < d; ++j) ss += row[j] * row[j];
+        v *= A.norm0[smp] / sqrtf(ss);
+      }
+      A.out[e] = v;
+      const int index = it.i + A.include_t0;
+      if (A.traj) A.traj[(int64_t)index * etot + e] = v;
+      if (A.keep_stop && A.keep_stop[smp] == index) A.kept[e] = v;   // msgm_keep_rows after the step
+    }
+  }
 }
 
 // Sliced-score-matching terms of one output o of one sample: returns its share of the sample's loss and sets the
@@ -614,6 +781,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
   constexpr int NR = (SPT * LO::DMAX + NT - 1) / NT;
   float* RAW0 = lds + LO::RAW;
   RawRegs<NR> pf;
+  [[maybe_unused]] SdeRegs<MODE == MODE_SDE ? NR : 0> sr;   // sampler loop: the stage update's own operands
   auto issue = [&](int64_t tl, int step = 0) { raw_issue<MODE, LO, NT, true>(A, pf, tid, tid, tl, step); };
   auto commit = [&](float* R) { raw_commit<MODE, LO, NT, true>(pf, R, tid, tid); };
   auto h0_row = [&](float* H0b, const float* R, int64_t tl, int l) { build_h0<MODE, LO, 1, SM_P>(A, H0b, R, tl, l, 0); };
@@ -695,7 +863,9 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
   // EM loop (n_steps > 1): rows never interact (sde_scheme.py:82-86), so a workgroup takes its tiles through ALL
   // steps in one launch — weights and biases are staged once, x only travels to L2 and back.  The host guarantees
   // >= 2 tiles per workgroup, so the item prefetched one ahead is always a tile whose previous step is complete.
-  const int n_steps = (MODE == MODE_EM && A.n_steps > 1) ? A.n_steps : 1;
+  // Sampler loop (MODE_SDE): items are (step, stage, tile); `step` counts (step, stage) pairs, see sde_item.  A stage reads
+  // what the tile's previous stage wrote, so the same two-tile guarantee covers it.
+  const int n_steps = MODE == MODE_SDE ? A.n_steps * A.n_stages : ((MODE == MODE_EM && A.n_steps > 1) ? A.n_steps : 1);
   int step = 0;
   for (int64_t tile = blockIdx.x; tile < n_tiles;) {
     const int64_t s_base = tile * SPT;
@@ -722,6 +892,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
     // ---- phase 3: layer 3, then this wave's K-slice of layer 4 -------------
     if (MODE != MODE_TRAIN) { if (tid < SPT) h0_row(H0n, Rn, ntile, tid); }   // next item's layer-1 operand
     else issue(ntile);                                       // train: next tile's inputs, in flight during the gemm
+    if constexpr (MODE == MODE_SDE) sde_issue<LO, NT>(A, sr, Rc, s_base, tid, sde_item(A, step));   // sampler loop: likewise
     fwd_hidden<TRN, TRN, IT>(R3, TRN ? R3 : R2, pre, Yc, B3s, fb, il, q, z3, h);   // then W3^T for dgrad / next tile's layer 2
     if (MODE == MODE_TRAIN) store_act<IT>(Z, fb, il, q, h);   // h3 is the dW4 operand later
     {
@@ -750,6 +921,14 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
     STAMP(3);
 
     // ---- phase 4: reduce layer-4 partials; outputs / loss ------------------
+    if constexpr (MODE == MODE_SDE) {
+      // the update first: its stores drain to L2 under the next item's layer 1
+      sde_update<LO, NT, NW>(A, sr, PART, B4s, const_cast<float*>(Rc), s_base, tid, sde_item(A, step));   // (stage 0 parks dW in it)
+      layer1(H0n, Yc);                                         // next item's h1 (h2 is dead)
+      __syncthreads();   // + vmcnt(0): what this item wrote must have left the CU before a later item re-reads it
+      tile = ntile; step = nstep;
+      continue;
+    }
     if (MODE == MODE_FWD || MODE == MODE_EM) {
       layer1(H0n, Yc);                                         // next tile's h1 (h2 is dead)
       // 32 samples x d outputs
@@ -1367,7 +1546,8 @@ static int64_t mlp_wg_per_cu(const MlpArgs& A) { return mlp_xwide(A) ? 1 : (mlp_
 
 template <int MODE>
 static int launch_mlp(const MlpArgs& A, int grid, hipStream_t st) {
-  if (mlp_xwide(A)) return launch_kernel<k_mlp_xw<MODE>, MlpLdsXW<MODE>::BYTES, 256>(A, grid, st);
+  if constexpr (MODE == MODE_SDE) { if (mlp_xwide(A)) return MSGM_E_UNSUPPORTED; }   // the sampler loop has no extra-wide form
+  else if (mlp_xwide(A)) return launch_kernel<k_mlp_xw<MODE>, MlpLdsXW<MODE>::BYTES, 256>(A, grid, st);
   constexpr int nw_w = MlpCfg<MODE, true>::NW, nw_n = MlpCfg<MODE, false>::NW;
   if (A.in_dim > 16 || A.P.d > 16)
     return launch_kernel<k_mlp<MODE, true, nw_w, false>, MlpLds<MODE, true, nw_w>::BYTES, 64 * nw_w>(A, grid, st);
@@ -1446,6 +1626,51 @@ int msgm_mlp_em_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm
   const int64_t cap = mlp_wg_per_cu(A) * MLP_MAX_GRID;
   const int64_t grid = tiles / 2 < cap ? tiles / 2 : cap;
   return launch_mlp<MODE_EM>(A, (int)grid, S(stream));
+}
+
+static int sde_loop_stages(int32_t method) {
+  return method == MSGM_METHOD_EM ? 1 : (method == MSGM_METHOD_HEUN ? 2 : (method == MSGM_METHOD_RK4 ? 4 : 0));
+}
+
+int msgm_mlp_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B) {
+  if (d < 1 || d > 30 || d + 1 + (premodule ? 1 : 0) > 32 || n != d) return 0;     // the extra-wide class stays composed
+  if (kind != MSGM_SDE_SGM && kind != MSGM_SDE_MSGM_SPARSE && kind != MSGM_SDE_MSGM_DENSE) return 0;
+  if (kind == MSGM_SDE_MSGM_DENSE && n > 16) return 0;
+  return B > 32;                                           // a workgroup needs two tiles to prefetch one ahead
+}
+
+size_t msgm_mlp_sde_loop_workspace(int64_t B, int32_t d, int32_t method) {
+  if (B <= 0 || d <= 0 || sde_loop_stages(method) < 2) return 0;   // Euler-Maruyama keeps no state between stages
+  return (size_t)3 * (size_t)B * (size_t)d * sizeof(float);
+}
+
+int msgm_mlp_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts,
+                      int32_t n_steps, float delta, float sqrt_delta, float lmbd, const float* z, const uint64_t* rng,
+                      uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop, float* kept,
+                      void* workspace, size_t workspace_bytes, msgm_stream_t stream) {
+  MlpArgs A{};
+  int rc = fill_common(A, P, B);
+  if (rc) return rc;
+  const int stages = sde_loop_stages(method);
+  if (!x || !sde || !ts || n_steps < 1 || !stages || (!z && !rng) || (keep_stop && !kept)) return MSGM_E_BADARG;
+  if (sde->kind == MSGM_SDE_MSGM_DENSE && (!sde->G || !sde->L_G)) return MSGM_E_BADARG;
+  if (!msgm_mlp_sde_loop_supported(P->d, P->premodule, sde->kind, P->d, B)) return MSGM_E_UNSUPPORTED;
+  const size_t need = msgm_mlp_sde_loop_workspace(B, P->d, method);
+  if (need && (!workspace || workspace_bytes < need)) return MSGM_E_WORKSPACE;
+  A.y = x; A.out = x; A.t = nullptr;
+  A.b0 = sde->beta_min; A.b1 = sde->beta_max; A.T = sde->T;
+  A.delta = delta; A.sqrt_delta = sqrt_delta; A.lmbd = lmbd;
+  A.z = z; A.rng = rng; A.rng_step = rng_step0;
+  A.n_steps = n_steps; A.ts = ts;
+  A.n_stages = stages; A.kind = sde->kind;
+  A.t_half = 0.5f * delta; A.t_full = delta;
+  A.G = sde->G; A.L_G = sde->L_G;
+  A.norm0 = norm0; A.ws = reinterpret_cast<float*>(workspace);
+  A.traj = traj; A.include_t0 = include_t0 ? 1 : 0; A.keep_stop = keep_stop; A.kept = kept;
+  const int64_t tiles = (B + 31) / 32;
+  const int64_t cap = mlp_wg_per_cu(A) * MLP_MAX_GRID;
+  const int64_t grid = tiles / 2 < cap ? tiles / 2 : cap;   // at least two tiles per workgroup
+  return launch_mlp<MODE_SDE>(A, (int)grid, S(stream));
 }
 
 int msgm_mlp_ssm_partial(const msgm_mlp_params_t* P, const float* y, const float* t, const float* v, const float* u,

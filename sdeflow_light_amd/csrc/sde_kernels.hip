@@ -6,6 +6,7 @@
 // Phases that more than one kernel runs are ONE __device__ function each ("SDE kernels, shared
 // phases"); the build keeps -ffp-contract=off, so two kernels that call the same function give the same bits.
 #include "common.h"
+#include "sde_stage.h"
 #include <type_traits>
 
 // ============================================================ shared pieces
@@ -65,11 +66,6 @@ __device__ __forceinline__ void norm_correct(float* out, const float* norm0, int
     const float scale = norm0[b] / sqrtf(ss);
     for (int64_t i = lane; i < n; i += GS) out[b * n + i] *= scale;   // own writes, same lane
   }
-}
-
-// x + (k1 + 2k2 + 2k3 + k4)/6                                  sde_scheme.py:250-253
-__device__ __forceinline__ float rk4_value(float x, float k1, float k2, float k3, float k4) {
-  return x + (k1 + 2.0f * k2 + 2.0f * k3 + k4) / 6.0f;
 }
 
 // ============================================================ RNG helpers
@@ -213,82 +209,7 @@ __global__ void k_rademacher(float* __restrict__ v, int64_t n, const float* __re
 }
 
 // ============================================================ integrator stage
-struct StageArgs {
-  float* out; const float* base; float c_out;
-  const float* x; const float* a; const float* dW; const float* z; float sqrt_delta;
-  const uint64_t* rng; uint64_t rng_step; float* dW_out;
-  int64_t B; int64_t n;
-  int kind, proc, strato;
-  float b0, b1, T, t, delta, lmbd;
-  const float* G; const float* L_G;
-  const float* norm0;
-  float* inc_out;              // optional: the bare increment
-  const float* delta_rows;     // optional per-row step length (MSGM short-time rows, SDEs.py:112-117)
-  float t_frac;                // with delta_rows: t_b = t + t_frac * delta_b
-  const float* t_dev;          // optional device scalar overriding t   (graph replay: time lives on the device)
-  const int64_t* step_dev;     // optional device scalar overriding rng_step
-};
-
-__device__ __forceinline__ uint64_t stage_step(const StageArgs& A) { return A.step_dev ? (uint64_t)A.step_dev[0] : A.rng_step; }
-__device__ __forceinline__ float stage_time(const StageArgs& A) { return A.t_dev ? A.t_dev[0] : A.t; }
-__device__ __forceinline__ float stage_noise(const StageArgs& A, int64_t e, float sqrt_delta) {
-  if (A.dW) return A.dW[e];
-  float zz = A.z ? A.z[e] : philox_normal1(A.rng, stage_step(A), RNG_STREAM_DW, (uint64_t)e);
-  return sqrt_delta * zz;                                  // delta**0.5 * randn   sde_scheme.py:84
-}
-
-// Row b's stage coefficients at the stage time tnow (= stage_time(A): host t or t_dev): step length delta_b and its root
-// (per row with delta_rows, then also t_b = tnow + t_frac delta_b), beta at t_b — at T - t_b for the reverse process — and its
-// root.  PER_ROW = false is the kernel-uniform form of k_stage_diag_flat, which msgm_sde_stage never sends delta_rows to.
-struct StageCoef { float delta, sqd, beta, sb; };
-template <bool PER_ROW = true>
-__device__ __forceinline__ StageCoef stage_coef(const StageArgs& A, float tnow, int64_t b) {
-  const float* dr = PER_ROW ? A.delta_rows : nullptr;
-  const float delta = dr ? dr[b] : A.delta;
-  const float sqd = dr ? sqrtf(delta) : A.sqrt_delta;
-  const float tb = dr ? tnow + A.t_frac * delta : tnow;
-  const float s = A.proc == MSGM_PROC_REVERSE ? A.T - tb : tb;
-  const float beta = sde_beta(A.b0, A.b1, s);
-  return {delta, sqd, beta, sqrtf(beta)};
-}
-// sigma's factor besides sqrt(beta): sqrt(1-l) for the reverse process (SDEs.py:587-588)
-__device__ __forceinline__ float stage_sig_scale(const StageArgs& A) {
-  return (A.proc == MSGM_PROC_REVERSE) ? sqrtf(1.0f - A.lmbd) : 1.0f;
-}
-
-// The drift of a stage from ga = G a, f, fs (f of the Stratonovich forward form) and div = divSigma.
-__device__ __forceinline__ float stage_mu(const StageArgs& A, float ga, float f, float fs, float div) {
-  const float l = A.lmbd;
-  float mu;
-  if (A.proc == MSGM_PROC_REVERSE) {
-    mu = (1.0f - 0.5f * l) * ga - f + (1.0f - l) * div;          // SDEs.py:560-561
-    if (A.strato) mu = mu - 0.5f * (1.0f - l) * div;             // SDEs.py:583-584
-  } else {
-    mu = fs;                                                      // SDEs.py:42-43
-    if (!A.strato) mu = mu + 0.5f * div;                          // SDEs.py:38-39
-  }
-  return mu;
-}
-
-// Sparse rotation tensor, element i of G(x) w: entries (I=i,J=i+1,K=i,V=+c) and (I=i,J=i-1,K=i-1,V=-c), c = sqrt(2)/2, circular
-// (SDEs.py:369-399,425-430; sde_scheme.py:27-32): c sb (x_{i+1} w_i - x_{i-1} w_{i-1}).  w is the noise (gw) or the score (ga).
-__device__ __forceinline__ float sparse_g(float sb, float xp, float xm, float w_i, float w_m) {
-  const float cV = 0.5f * sqrtf(2.0f);
-  return (cV * (sb * xp)) * w_i + (-cV * (sb * xm)) * w_m;
-}
-
-// SGM (diagonal), one element: the bare increment.  Reverse: mu = (1-l/2) sqrt(beta) a + 1/2 beta x (SDEs.py:560-561,183-194
-// with divSigma = 0); sigma = sqrt(1-l) sqrt(beta).  Forward: mu = -1/2 beta x.
-// This is NOT stage_mu(sb a, f, f, 0) with f = -1/2 beta x: that form adds (1-l) 0 (reverse) or 1/2 0 (forward, Ito) to mu,
-// which turns a mu of -0 into +0 — x = +-0 with a Wiener increment of -0 (a Box-Muller radius of 0) then gives the other
-// zero.  The flat kernel keeps the parent's spelling and its bits; k_stage_rows (SGM with norm0 / delta_rows) keeps stage_mu's.
-struct DiagCoef { float beta, sb, ca, sig; };
-__device__ __forceinline__ float diag_inc(const StageArgs& A, const DiagCoef& c, float x, float a, float w) {
-  float mu;
-  if (A.proc == MSGM_PROC_REVERSE) mu = c.ca * (c.sb * a) - (-0.5f * c.beta * x);
-  else mu = -0.5f * c.beta * x;
-  return mu * A.delta + c.sig * w;
-}
+// StageArgs and the per-element formulas of a stage (stage_coef, stage_mu, sparse_g, dense_g, diag_inc, rk4_value): sde_stage.h
 
 // SGM (diagonal) flat kernel, no norm correction: 12-16 B/element.  The vector body (B n % 4 == 0, every operand 16-byte
 // aligned) and the scalar body differ in their loads and stores only: the quad's arithmetic is the one loop over diag_inc.
@@ -409,7 +330,8 @@ __global__ void __launch_bounds__(256) k_rk4_combine_flat(float* __restrict__ ou
 // k_stage_rows keeps its own lines for every phase: built on RowGroup, stage_coef, stage_mu, sparse_g and norm_correct it read
 // SLOWER at 4096 x 12288 (GS = 256: +0.40 % sgm, +0.22 % sparse with norm0, where the parent differed from itself by 0.2 %;
 // profiles/README.md); with these lines it is the parent's machine code.  Its drift rule and stencil are the expressions of
-// stage_mu and sparse_g in the same order (tests/test_sde_paths_gpu.py::test_stage_sparse_rows_bitwise_equals_flat).
+// stage_mu and sparse_g in the same order (tests/test_sde_paths_gpu.py::test_stage_sparse_rows_bitwise_equals_flat), its dense
+// branch the sums of dense_g (sde_stage.h) in the same order.
 template <int GS>
 __global__ void k_stage_rows(StageArgs A) {
   const int lane = threadIdx.x & (GS - 1);

@@ -234,6 +234,58 @@ def mlp_em_loop(P: L.MlpParamsT, x: torch.Tensor, sde: L.SdeT, ts: torch.Tensor,
     return x
 
 
+SDE_LOOP_METHODS = {"em": L.METHOD_EM, "heun": L.METHOD_HEUN, "rk4": L.METHOD_RK4}
+
+
+def mlp_sde_loop_supported(d: int, premodule: bool, kind: int, n: int, B: int) -> bool:
+    """Whether msgm_mlp_sde_loop takes this shape: 1 <= d = n <= 30 and in_dim <= 32, dense tensors up to n = 16, B > 32."""
+    return bool(lib().msgm_mlp_sde_loop_supported(int(d), int(bool(premodule)), int(kind), int(n), int(B)))
+
+
+def mlp_sde_loop_workspace(B: int, d: int, method: str, device) -> Optional[torch.Tensor]:
+    """The stage state of the loop (evaluation point, Wiener increment, running sum); None for Euler-Maruyama."""
+    nbytes = int(lib().msgm_mlp_sde_loop_workspace(int(B), int(d), SDE_LOOP_METHODS[method]))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def mlp_sde_loop(P: L.MlpParamsT, x: torch.Tensor, sde: L.SdeT, method: str, ts: torch.Tensor, delta: float,
+                 lmbd: float = 0.0, z: Optional[torch.Tensor] = None, rng: Optional[PhiloxState] = None, rng_step0: int = 0,
+                 norm0: Optional[torch.Tensor] = None, traj: Optional[torch.Tensor] = None, include_t0: bool = False,
+                 keep: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """All len(ts)-1 steps of the reverse process — Euler-Maruyama, Heun or RK4-Stratonovich, any SDE family — in ONE
+    launch; x (B,d) becomes the final state.  ts: device fp32 time grid; z: optional (N,B,d) normals, else Philox steps
+    rng_step0 + i; traj: optional (N + include_t0, B, d), rows include_t0.. are written; keep / kept: keep_rows after
+    every step; workspace: mlp_sde_loop_workspace(B, d, method), allocated here when None."""
+    if method not in SDE_LOOP_METHODS:
+        raise MsgmError(f"unknown integrator {method}")
+    if x.dim() != 2 or not x.is_cuda:
+        raise MsgmError("sde loop: the state must be a (B,d) device tensor; there is no CPU fallback")
+    B, d = x.shape
+    if d != P.d:
+        raise MsgmError(f"state has d={d}, the MLP was built for d={P.d}")
+    if ts.device != x.device or ts.dtype != torch.float32 or ts.numel() < 2:
+        raise MsgmError("sde loop: ts must be a device fp32 grid of N+1 values")
+    N = ts.numel() - 1
+    _same_shape(z, (N, B, d), "z")
+    _same_shape(norm0, (B,), "norm0")
+    _same_shape(traj, (N + int(bool(include_t0)), B, d), "traj")
+    _same_shape(kept, (B, d), "kept")
+    if (keep is None) != (kept is None) or (keep is not None and (keep.dtype != torch.int32 or keep.numel() != B)):
+        raise MsgmError("sde loop: keep must be int32 of length B and come with kept (B,d)")
+    for nm, tt in (("z", z), ("norm0", norm0), ("traj", traj), ("kept", kept)):
+        if tt is not None:
+            f32(tt, nm)
+    if workspace is None:
+        workspace = mlp_sde_loop_workspace(B, d, method, x.device)
+    nbytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    check(lib().msgm_mlp_sde_loop(P, ptr(f32(x)), B, sde, SDE_LOOP_METHODS[method], ptr(ts), N, float(delta), float(delta ** 0.5),
+                                  float(lmbd), ptr(z), _rng_ptr(rng), int(rng_step0), ptr(norm0), ptr(traj),
+                                  int(bool(include_t0)), ptr(keep), ptr(kept), ptr(workspace), nbytes, stream()),
+          "msgm_mlp_sde_loop")
+    return x
+
+
 def mlp_ssm_workspace(d: int, premodule: bool, device) -> torch.Tensor:
     nbytes = int(lib().msgm_mlp_ssm_workspace(d, int(bool(premodule))))
     return torch.empty(nbytes // 4, dtype=torch.float32, device=device)

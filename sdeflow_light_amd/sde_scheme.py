@@ -5,7 +5,8 @@ error behaviour: sde_scheme.py:44-46,73-75,94-99).
 Per step the reference launches ~20 eager kernels plus a host ``.item()`` and,
 with ``keep_all_samples``, a blocking D2H copy (sde_scheme.py:80-92).  Here a
 step is ONE fused stage kernel after the score net (or one kernel in total for
-MLP + SGM: ``msgm_mlp_em_step``), the time grid is computed on the host exactly
+MLP + SGM: ``msgm_mlp_em_step``; with the MLP, Heun, RK4-Stratonovich and the multiplicative Euler-Maruyama are one
+kernel for the WHOLE loop, ``msgm_mlp_sde_loop``, when ``_Run.mlp_loop`` finds the shape supported), the time grid is computed on the host exactly
 as upstream (fp32 ``linspace``) and passed by value, trajectories are captured
 into a device buffer and copied once at the end, and the whole fused loop can
 be replayed as a single hipGraph (``GraphedEMSampler``).
@@ -173,6 +174,22 @@ class _Run:
         elif self.keep is not None:
             ops.keep_rows(self.kept, self.x, self.keep, i + int(self.include_t0))
 
+    def mlp_loop(self, method):
+        """The whole loop as ONE launch (``msgm_mlp_sde_loop``) when the shapes allow it: the reverse process of the MLP,
+        Philox noise, and a shape the kernel takes (``ops.mlp_sde_loop_supported``: d <= 30 and in_dim <= 32, dense tensors
+        up to n = 16, B > 32).  Same time grid, stage times and Philox draws as the composed steps; trajectory rows and
+        kept rows are written by the kernel.  Returns whether it ran; everything else keeps the composed route."""
+        from .NN import MLP
+        net = self.sde.a if self.reverse else None
+        if not isinstance(net, MLP) or self.noise is not None or net.input_dim != self.n:
+            return False
+        if not ops.mlp_sde_loop_supported(self.n, net.pre is not None, self.struct.kind, self.n, self.B):
+            return False
+        ops.mlp_sde_loop(net.kernel_params(), self.x, self.struct, method, self.ts.to(self.device), self.delta, self.lmbd,
+                         rng=self.rng, rng_step0=0, norm0=self.norm0, traj=self.traj, include_t0=self.include_t0,
+                         keep=self.keep, kept=self.kept if self.keep is not None else None)
+        return True
+
     def result(self, advance=True):
         if self.rng is not None and advance:
             self.rng.advance(self.N)
@@ -200,6 +217,8 @@ def _em(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, 
         # final state only: the whole loop in ONE launch, same time grid and Philox draws as the per-step kernels
         ops.mlp_em_loop(P, r.x, r.struct, r.ts.to(r.device), r.delta, r.lmbd, r.rng, 0)
         return r
+    if r.base.kind != L.SDE_SGM and r.mlp_loop("em"):     # the multiplicative SDEs: every stage of every step in one launch
+        return r
     other = torch.empty_like(r.x)
     for i in range(num_steps):
         if fused:                     # score net + update in ONE kernel
@@ -213,9 +232,12 @@ def _em(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, 
 
 
 def _integrate(step, fracs, nbuf, sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_, norm_correction,
-               noise):
-    """The eager Heun / RK4 loop: the step's new state (its last buffer) swaps places with the state."""
+               noise, loop=None):
+    """The eager Heun / RK4 loop: the step's new state (its last buffer) swaps places with the state.  ``loop`` names the
+    method of the one-launch MLP route (``_Run.mlp_loop``), tried first; None keeps the composed steps."""
     r = _Run(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_, norm_correction, noise)
+    if loop is not None and r.mlp_loop(loop):
+        return r
     bufs = [torch.empty_like(r.x) for _ in range(nbuf)]
     for i in range(num_steps):
         step(r.clock(i, fracs), r.x, bufs, r.norm0)
@@ -230,6 +252,15 @@ def heun_sampler(sde, x_0, num_steps=1000, lmbd=0., keep_all_samples=True, sampl
     """Heun / RK2 in Stratonovich form (sde_scheme.py:101-172):
     x <- x + 1/2 (K1 + K2), K = mu_Strato*delta + sigma.dW, one shared dW."""
     return _integrate(_heun_step, (1.0,), 4, sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_,
+                      norm_correction, noise, loop="heun").result()
+
+
+@torch.no_grad()
+def heun_composed(sde, x_0, num_steps=1000, lmbd=0., keep_all_samples=True, samplesToKeep=None,
+                  include_t0=False, T_=-1, norm_correction=False, noise=None):
+    """heun_sampler on the composed route (score net, stage kernel and glue as separate launches), whatever the shape:
+    the yardstick of the one-launch loop."""
+    return _integrate(_heun_step, (1.0,), 4, sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_,
                       norm_correction, noise).result()
 
 
@@ -238,11 +269,18 @@ def rk4_stratonovich_sampler(sde, x_0, num_steps=1000, lmbd=0., keep_all_samples
                              include_t0=False, T_=-1, norm_correction=False, noise=None):
     """RK4 for Stratonovich SDEs, one dW per step (sde_scheme.py:174-269)."""
     return _rk4(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_, norm_correction,
-                noise).result()
+                noise, loop="rk4").result()
 
 
-def _rk4(*args):
-    return _integrate(_rk4_step, (0.5, 1.0), 7, *args)
+@torch.no_grad()
+def rk4_stratonovich_composed(sde, x_0, num_steps=1000, lmbd=0., keep_all_samples=True, samplesToKeep=None,
+                              include_t0=False, T_=-1, norm_correction=False, noise=None):
+    """rk4_stratonovich_sampler on the composed route, whatever the shape: the yardstick of the one-launch loop."""
+    return _rk4(sde, x_0, num_steps, lmbd, keep_all_samples, samplesToKeep, include_t0, T_, norm_correction, noise).result()
+
+
+def _rk4(*args, loop=None):
+    return _integrate(_rk4_step, (0.5, 1.0), 7, *args, loop=loop)
 
 
 @torch.no_grad()
