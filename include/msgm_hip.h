@@ -583,8 +583,10 @@ int msgm_bmm(const float* A, const float* B, const float* A2, const float* B2, f
 
 /* The same with a SECOND output that shares the A operand: C3 = alpha A.B3 (B3 with B's strides, C3 with C's).
  * The dual-number attention always needs such a pair — P v next to Pdot v + P vdot, and the three adjoint pairs of
- * the backward alike — so the (T,T) operand is streamed from HBM once instead of twice.  Built for outputs that are
- * contiguous along j (sCj == 1) and K % 16 == 0; MSGM_E_UNSUPPORTED otherwise.  B3 / C3 NULL = msgm_bmm. */
+ * the backward alike — so the (T,T) operand is streamed from HBM once instead of twice.  alpha and accumulate apply to
+ * both outputs; C3 is bitwise what msgm_bmm(A, B3, ...) alone writes, at any batch size, with no atomics.  Built for
+ * outputs that are contiguous along j (sCj == 1, sCi != 1) at any K >= 1 (K % 16 != 0 runs the generic-K kernel with a
+ * second accumulator); any other output layout returns MSGM_E_UNSUPPORTED.  B3 / C3 NULL = msgm_bmm. */
 int msgm_bmm_dual(const float* A, const float* B, const float* A2, const float* B2, const float* B3, float* C, float* C3,
                   int32_t M, int32_t N, int32_t K, int32_t batch,
                   int64_t sAb, int64_t sAi, int64_t sAk, int64_t sBb, int64_t sBk, int64_t sBj,

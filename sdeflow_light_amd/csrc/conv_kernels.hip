@@ -1046,12 +1046,14 @@ __global__ void __launch_bounds__(256) k_conv3x3_cin_small(ConvArgs A, long Mtot
     for (int k = 0; k < 4; ++k) acc[4 * c4 + k] = v[k];
   }
   if (A.cstat) {       // host: P % 64 == 0, so a wave's 64 pixels are one slot of one sample
+    // a wave past the last pixel (N P % 256 != 0: e.g. 5 samples of 24 x 24) computed on a copy of the LAST pixel's
+    // coordinates: it owns no slot and must not write its zeros over the last live wave's
     const int lane = threadIdx.x & 63;
     float* cp = A.cstat + (((size_t)n * A.cs_S + (r >> 6)) * 2) * CO;
 #pragma unroll
     for (int co = 0; co < CO; ++co) {
       const float s = wave64_sum_to_last(acc[co]), ss = wave64_sum_to_last(acc[co] * acc[co]);
-      if (lane == 63) { cp[co] = s; cp[CO + co] = ss; }
+      if (lane == 63 && live) { cp[co] = s; cp[CO + co] = ss; }
     }
   }
 }

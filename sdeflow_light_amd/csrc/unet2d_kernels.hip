@@ -761,38 +761,52 @@ __global__ void __launch_bounds__(256) k_bmm_lds(BmmArgs P) {
   }
 }
 
-// generic-K fallback (K % 16 != 0): scalar, one k per lane quarter
+// generic-K fallback (K % 16 != 0): scalar, one k per lane quarter.  DUAL: the second output C3 = alpha A3.B rides along
+// with the first pair's B element in an accumulator chain of its own (two independent chains also hide the MFMA's
+// dependent latency); k runs in the same order for both outputs, so C3 is bitwise what a launch of its own would give.
+template <bool DUAL>
 __global__ void __launch_bounds__(256) k_bmm_slow(BmmArgs P) {
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const int tiles_n = (P.N + 31) / 32;
   const int tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n;
   const int i0 = tm * 32 + (w >> 1) * 16, j0 = tn * 32 + (w & 1) * 16;
   if (i0 >= P.M || j0 >= P.N) return;
-  f32x4 acc = {0, 0, 0, 0};
+  f32x4 acc = {0, 0, 0, 0}, acc3 = {0, 0, 0, 0};
   const bool vi = i0 + il < P.M, vj = j0 + il < P.N;
   for (int pair = 0; pair < 2; ++pair) {
     const float* Ab = (pair ? P.A2 : P.A);
     const float* Bb = (pair ? P.B2 : P.B);
     if (!Ab) break;
-    Ab += (size_t)blockIdx.y * P.sAb + (size_t)(vi ? i0 + il : 0) * P.sAi;
+    const size_t offA = (size_t)blockIdx.y * P.sAb + (size_t)(vi ? i0 + il : 0) * P.sAi;
+    Ab += offA;
     Bb += (size_t)blockIdx.y * P.sBb + (size_t)(vj ? j0 + il : 0) * P.sBj;
+    const bool third = DUAL && pair == 0;
+    const float* Ab3 = third ? P.A3 + offA : nullptr;
     for (int k0 = 0; k0 < P.K; k0 += 4) {
       const int k = k0 + q;
       const float a = (vi && k < P.K) ? Ab[(size_t)k * P.sAk] : 0.f;
       const float b = (vj && k < P.K) ? Bb[(size_t)k * P.sBk] : 0.f;
       acc = mfma16(a, b, acc);
+      if (third) {
+        const float a3 = (vi && k < P.K) ? Ab3[(size_t)k * P.sAk] : 0.f;
+        acc3 = mfma16(a3, b, acc3);
+      }
     }
   }
-  float* Cb = P.C + (size_t)blockIdx.y * P.sCb;
   const int j = j0 + il;
-  if (j < P.N)
+  if (j >= P.N) return;
+#pragma unroll
+  for (int which = 0; which < (DUAL ? 2 : 1); ++which) {
+    float* Cb = (which ? P.C3 : P.C) + (size_t)blockIdx.y * P.sCb;
+    const f32x4 av = which ? acc3 : acc;
     for (int r = 0; r < 4; ++r) {
       const int i = i0 + 4 * q + r;
       if (i >= P.M) continue;
       float* cp = Cb + (size_t)i * P.sCi + (size_t)j * P.sCj;
-      const float v = P.alpha * acc[r];
+      const float v = P.alpha * av[r];
       *cp = P.accumulate ? *cp + v : v;
     }
+  }
 }
 
 // ------------------------------------------------------------------ dual softmax rows
@@ -1423,8 +1437,8 @@ int msgm_bmm_dual(const float* A, const float* B, const float* A2, const float* 
   if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || ((A2 == nullptr) != (B2 == nullptr))) return MSGM_E_BADARG;
   if ((B3 == nullptr) != (C3 == nullptr)) return MSGM_E_BADARG;
   // the second output shares the A operand: C3 = alpha A.B3 — built for the case where the host swap below turns A
-  // into the kernel's B role (outputs contiguous along j, as every attention product here), K % 16 == 0
-  if (B3 && (!(sCj == 1 && sCi != 1) || K % 16)) return MSGM_E_UNSUPPORTED;
+  // into the kernel's B role (outputs contiguous along j, as every attention product here); any K
+  if (B3 && !(sCj == 1 && sCi != 1)) return MSGM_E_UNSUPPORTED;
   BmmArgs P{A, B, A2, B2, C, M, N, K, batch, sAb, sAi, sAk, sBb, sBk, sBj, sCb, sCi, sCj, alpha, accumulate, B3, C3};
   if (sCj == 1 && sCi != 1) {
     // C^T = B^T A^T: make the output's contiguous dimension the MFMA row index (16-B stores)
@@ -1436,7 +1450,8 @@ int msgm_bmm_dual(const float* A, const float* B, const float* A2, const float* 
   }
   if (K % 16) {
     dim3 grid((unsigned)(((P.M + 31) / 32) * ((P.N + 31) / 32)), (unsigned)batch);
-    hipLaunchKernelGGL(k_bmm_slow, grid, dim3(256), 0, S(stream), P);
+    if (P.A3) hipLaunchKernelGGL(k_bmm_slow<true>, grid, dim3(256), 0, S(stream), P);
+    else hipLaunchKernelGGL(k_bmm_slow<false>, grid, dim3(256), 0, S(stream), P);
     return msgm_check_launch();
   }
   auto al16 = [](const float* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };

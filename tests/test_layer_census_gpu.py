@@ -34,7 +34,7 @@ from sdeflow_light_amd.convnet import ConvOp, ConvOpSet, Stride2PairOp
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 RAGGED = 13                   # samples of the second replay: tile / workgroup / chunk counts that do not divide
-CONFIGS = ("c4_b256", "c4_b32", "c3_b4096", "c5_4096", "c5_1024")
+CONFIGS = ("c4_b256", "c4_b32", "c3_b4096", "c5_4096", "c5_1024", "v24_b3", "v24_fwd5")
 
 # ------------------------------------------------------------------------------------------------ bounds
 # Output families and their bounds on (rel-L2 over the tensor, worst per-row rel-L2, worst element / reference RMS).
@@ -227,6 +227,17 @@ class Recorder:
         wrap_fn("act_dual_forward", lambda A: ("act_fwd", int(A["act"]), A["z"].numel(), bool(A["dual"])))
         wrap_fn("act_dual_backward", lambda A: ("act_bwd", int(A["act"]), A["z"].numel()))
 
+        # the composed attention (no fused kernel for the shape): every operand offset is kept — it decides the alignment
+        def bmm_sig(A):
+            p2, th = A["pair2"], A["third"]
+            assert th is None or th[2] is A["Cm"]                      # both outputs in one tensor, as the replay lays them out
+            return ("bmm", A["M"], A["N"], A["K"], A["batch"], tuple(A["sA"]), tuple(A["sB"]), tuple(A["sC"]), A["a_off"], A["b_off"],
+                    A["c_off"], float(A["alpha"]), bool(A["accumulate"]), (p2[1], p2[3]) if p2 is not None else None,
+                    (th[1], th[3]) if th is not None else None)
+        wrap_fn("bmm", bmm_sig)
+        wrap_fn("softmax_dual_forward", lambda A: ("softmax_fwd", A["S"].numel() // A["T"], A["T"], has(A["Wd"])))
+        wrap_fn("softmax_dual_backward", lambda A: ("softmax_bwd", A["Pm"].numel() // A["T"], A["T"]))
+
 
 def _unet_ops(net):
     """Every ConvOp / Stride2PairOp of a net, each with the ops that may take its place on a path (the decoder twins)."""
@@ -242,17 +253,32 @@ def _unet_ops(net):
     return [(o, alts.get(id(o), ())) for o in x["all"]]
 
 
+def _build_v24():
+    """The 24x24 one-channel net of tests/test_unet2d_sizes_gpu.py (bench.build_unet builds the benchmarked 64x64x3 one only)."""
+    from oracle.det_params import load_det_
+    from sdeflow_light_amd.NNUnet import VorticityUNet
+    from sdeflow_light_amd.SDEs import SGMsde, PluginReverseSDE
+    torch.manual_seed(0)
+    net = VorticityUNet(base_channels=32, channel_mults=(1, 2, 4), num_res_blocks=2, attention_resolutions=(2, 4), in_space=24,
+                        flatten_order="F")
+    load_det_(net)
+    T = torch.nn.Parameter(torch.FloatTensor([1.0]), requires_grad=False)
+    sde = SGMsde(beta_min=0.1, beta_max=20.0, t_epsilon=1e-3, T=T, num_steps_forward=16, device=DEV)
+    return PluginReverseSDE(sde, net.to(DEV), T, vtype="rademacher", deviceReverseSDE=DEV).to(DEV), 576
+
+
 def _record(config):
     import bench
     from sdeflow_light_amd.train import UNetScoreTrainer
     from sdeflow_light_amd.data import signals_1d, random_images
     rec = Recorder()
-    gen, d = bench.build_unet("c3" if config.startswith("c3") else "c4", torch.device(DEV))
+    v24 = config.startswith("v24")
+    gen, d = _build_v24() if v24 else bench.build_unet("c3" if config.startswith("c3") else "c4", torch.device(DEV))
     net = gen.a
     with pytest.MonkeyPatch.context() as mp:
         rec.patches(mp)
-        if config.startswith("c5"):
-            rows = int(config.split("_")[1])
+        if config.startswith("c5") or config == "v24_fwd5":
+            rows = 5 if v24 else int(config.split("_")[1])
             g = torch.Generator(device=DEV).manual_seed(3)
             x = torch.randn(rows, d, device=DEV, generator=g)
             t = torch.rand(rows, device=DEV, generator=g) * 0.9 + 0.05
@@ -263,7 +289,8 @@ def _record(config):
         else:
             B = int(config.split("_b")[1])
             tr = UNetScoreTrainer(gen, B, d, lr=1e-4, world=1, seed=1, use_graph=False)
-            tr.set_data(signals_1d(B, seed=1234, device=DEV) if config.startswith("c3") else random_images(B, seed=1234, device=DEV))
+            tr.set_data(torch.randn(B, d, device=DEV, generator=torch.Generator(device=DEV).manual_seed(1234)) if v24 else
+                        signals_1d(B, seed=1234, device=DEV) if config.startswith("c3") else random_images(B, seed=1234, device=DEV))
             tr.step()
             del tr
     torch.cuda.synchronize()
@@ -272,7 +299,7 @@ def _record(config):
         ids = {id(o)} | {id(a) for a in alts if a is not None}
         if not ids & rec.fwd_ops:
             missing_f.append(_opcfg(o))
-        if not config.startswith("c5") and not ids & rec.bwd_ops:
+        if not config.startswith("c5") and config != "v24_fwd5" and not ids & rec.bwd_ops:
             missing_b.append(_opcfg(o))
     del gen, net
     gc.collect()
@@ -720,7 +747,35 @@ def replay_act(sig, rnd, ragged=False, with_ref=True):
     return {"dz": ("act", cmp(g.view(1, -1), torch.cat([dp, dt]).view(1, -1)).metrics())}, dig
 
 
-REPLAY = {"conv_fwd": replay_conv_fwd, "conv_bwd": replay_conv_bwd,
+def replay_bmm(sig, rnd, ragged=False, with_ref=True):
+    """A recorded ops.bmm call on random operands through the per-element float64 checker of the composed-attention tests
+    (it asserts by itself: the GEMM bound is a-priori, not one of BOUNDS).  Ragged: 13 batches; an offset that is a multiple of
+    the recorded batch extent (the tangent half, a head's tiles) moves with the batch count."""
+    from test_composed_attention_gpu import run_bmm_case
+    _, M, N, K, batch, sA, sB, sC, a_off, b_off, c_off, alpha, acc, p2, th = sig
+    nb = RAGGED if ragged else batch
+    mv = lambda off, s: off % (batch * s[0]) + (off // (batch * s[0])) * nb * s[0]          # noqa: E731
+    case = dict(name=" ".join(str(v) for v in sig[1:]) + (f" ragged({RAGGED})" if ragged else ""), M=M, N=N, K=K, batch=nb, sA=sA,
+                sB=sB, sC=sC, a_off=mv(a_off, sA), b_off=mv(b_off, sB), c_off=mv(c_off, sC), alpha=alpha, acc=acc,
+                pair2=p2 is not None, third=th is not None, a2_off=mv(p2[0], sA) if p2 else 0, b2_off=mv(p2[1], sB) if p2 else 0,
+                b3_off=mv(th[0], sB) if th else 0, c3_off=mv(th[1], sC) if th else 0)
+    label, out = run_bmm_case(ops, case, seed=int(rnd.g.initial_seed()))
+    assert label != "unsupported"
+    return {}, {"C": digest(out)}
+
+
+def replay_softmax(sig, rnd, ragged=False, with_ref=True):
+    """The dual softmax at the recorded row count (forward without and with the tangent, and the backward, whichever of them
+    was recorded) through the per-element float64 checker of the composed-attention tests."""
+    import attn_composed_ref as AR
+    from test_composed_attention_gpu import run_softmax
+    rows, T = sig[1:3]
+    rows = RAGGED * T if ragged else rows
+    outs = run_softmax(ops, *AR.softmax_inputs(T, int(rnd.g.initial_seed()), rows), f"{sig[0]} rows={rows} T={T}")
+    return {}, {k: digest(v) for k, v in outs.items()}
+
+
+REPLAY = {"bmm": replay_bmm, "softmax_fwd": replay_softmax, "softmax_bwd": replay_softmax, "conv_fwd": replay_conv_fwd, "conv_bwd": replay_conv_bwd,
           "conv_bwd_ups": lambda s, r, **k: replay_conv_bwd(s, r, ups_form=True, **k),
           "gn_fwd": replay_gn, "gn_bwd": replay_gn, "gn_fwd2": replay_gn, "gn_bwd2": replay_gn,
           "gn_affine": replay_gn_affine, "gn_affine_cs": replay_gn_affine,
