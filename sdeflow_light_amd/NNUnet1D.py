@@ -27,6 +27,19 @@ from .convnet import ConvOp, ConvOpSet, Stride2PairOp
 GELU = ops.ACT_GELU
 
 
+def level_lengths(input_dim: int, levels: int) -> List[int]:
+    """[L_0 .. L_levels]: the length each encoder level runs at, then the middle block's.  Every downsampling is a k = 4,
+    s = 2, p = 1 convolution, floor(L / 2) positions.  A net whose middle block would have no position cannot run (the
+    reference fails inside its stride-2 convolution there): MsgmError, naming the length and the level count."""
+    lens = [int(input_dim)]
+    for _ in range(levels):
+        lens.append(lens[-1] // 2)
+    if lens[-1] < 1:
+        raise MsgmError(f"UNet1D: input length {input_dim} is too short for {levels} levels (lengths per level {lens}: a "
+                        f"stride-2 convolution would have no output position); the least length is {1 << levels}")
+    return lens
+
+
 class ConvBlock1D(nn.Module):
     """conv k3 -> GELU -> conv k3 -> GELU (NNUnet1D.py:13-24); parameter holder."""
 
@@ -50,6 +63,7 @@ class UNet1D(nn.Module, FlatParamMixin):
             if self.premodule is not None else None
         chs = [base_channels * m for m in channel_mults]
         self.chs = chs
+        level_lengths(input_dim, len(chs))         # a length no forward could serve is refused here, not after some launches
         self.enc_blocks, self.downs = nn.ModuleList(), nn.ModuleList()
         in_ch = 1
         for out_ch in chs:
@@ -67,6 +81,18 @@ class UNet1D(nn.Module, FlatParamMixin):
         self._flat = None
 
     # ------------------------------------------------------------------ ops
+    def _paired(self) -> bool:
+        return self.input_dim % (1 << len(self.chs)) == 0 and all(c % 16 == 0 for c in self.chs)
+
+    def _check_length(self, L: int):
+        """Refuse, before the first launch, a length this net cannot serve: one too short for its levels, or — on a net whose
+        ``input_dim`` chose the paired stride-2 route — one that is odd at some level (Stride2PairOp would refuse it there,
+        after the levels above it had run)."""
+        level_lengths(L, len(self.chs))
+        if self._paired() and L % (1 << len(self.chs)):
+            raise MsgmError(f"UNet1D built with input_dim {self.input_dim} runs its stride-2 convolutions over position pairs "
+                            f"and cannot serve length {L} (no multiple of {1 << len(self.chs)}): build it with input_dim={L}")
+
     def _build(self):
         """(Re)create the ConvOps over the current parameter storage."""
         self.flat_parameters()
@@ -76,7 +102,7 @@ class UNet1D(nn.Module, FlatParamMixin):
         E, chs = self.emb_dim, self.chs
         # Downsample / Upsample (k=4, s=2, p=1) as 3-tap stride-1 convs over position PAIRS (convnet.Stride2PairOp):
         # needs an even length at every level and channel counts that are multiples of 16
-        paired = self.input_dim % (1 << len(chs)) == 0 and all(c % 16 == 0 for c in chs)
+        paired = self._paired()
         o = {"t0": ConvOp(self.time_mlp[0].weight, self.time_mlp[0].bias, "linear", (1,), 1, 0, [1]),
              "t2": ConvOp(self.time_mlp[2].weight, self.time_mlp[2].bias, "linear", (1,), 1, 0, [E])}
         if self.scale_embed is not None:
@@ -184,6 +210,7 @@ class UNet1D(nn.Module, FlatParamMixin):
         if x.ndim == 3:
             x = x.squeeze(1)
         B, L = x.shape
+        self._check_length(L)
         t = t.reshape(-1).float()
         if t.numel() == 1 and B != 1:
             t = t.expand(B)
@@ -198,6 +225,7 @@ class UNet1D(nn.Module, FlatParamMixin):
         ``msgm_ssm_terms``: any SDE family); d(sum_b loss_b * inv_batch)/d(params) is written into ``.grad``.
         ``rng`` (the caller's training stream) is accepted like the 2-D U-Net's; this net draws nothing from it."""
         B, L = y.shape
+        self._check_length(L)
         N = 2 * B
         flat, gflat = self.flat_parameters()
         for p in self.parameters():

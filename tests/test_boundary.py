@@ -109,3 +109,34 @@ def test_shard_rows_cover_everything():
             assert cuts[0][0] == 0 and cuts[-1][1] == n
             assert all(cuts[i][1] == cuts[i + 1][0] for i in range(w - 1))
             assert max(e - b for b, e in cuts) - min(e - b for b, e in cuts) <= 1
+
+
+def test_unet1d_level_lengths_and_lengths_it_cannot_serve():
+    """Lengths per level of the 1-D U-Net (k = 4, s = 2, p = 1 downsampling: floor(L / 2)), against PyTorch's own stride-2
+    convolution; a length whose middle block would have no position is refused by the helper, by the constructor and by
+    forward / ssm_grad before any launch (the CPU tensors here would otherwise reach a kernel wrapper's own refusal), with a
+    message that names the length and the level count."""
+    from sdeflow_light_amd import _lib
+    from sdeflow_light_amd.NNUnet1D import UNet1D, level_lengths
+    assert level_lengths(1024, 3) == [1024, 512, 256, 128]
+    assert level_lengths(37, 3) == [37, 18, 9, 4] and level_lengths(9, 3) == [9, 4, 2, 1] and level_lengths(8, 3) == [8, 4, 2, 1]
+    assert level_lengths(13, 2) == [13, 6, 3] and level_lengths(100, 3) == [100, 50, 25, 12]
+    w = torch.zeros(1, 1, 4)
+    for L in range(2, 41):
+        lens = level_lengths(L, 1)
+        assert lens[1] == torch.nn.functional.conv1d(torch.zeros(1, 1, L), w, stride=2, padding=1).shape[-1]
+    for L, levels in ((7, 3), (1, 1), (3, 2), (0, 3)):
+        with pytest.raises(_lib.MsgmError, match=rf"length {L} .* {levels} levels"):
+            level_lengths(L, levels)
+    with pytest.raises(_lib.MsgmError, match=r"length 7 .* 3 levels"):
+        UNet1D(input_dim=7)
+    net = UNet1D(input_dim=8)
+    with pytest.raises(_lib.MsgmError, match=r"length 5 .* 3 levels"):
+        net(torch.zeros(2, 5), torch.zeros(2))
+    with pytest.raises(_lib.MsgmError, match=r"length 5 .* 3 levels"):
+        net.ssm_grad(torch.zeros(2, 5), torch.zeros(2), torch.zeros(2, 5), torch.zeros(2, 5), torch.zeros(2), 0.5)
+    assert len(level_lengths(8, 3)) == 4 and UNet1D(input_dim=3, channel_mults=(1,)).chs == [32]
+    # a net on the paired stride-2 route (input_dim % 8 == 0) asked for a length that is odd at some level: refused up front too
+    with pytest.raises(_lib.MsgmError, match=r"input_dim 8 .* length 36 .*input_dim=36"):
+        net(torch.zeros(2, 36), torch.zeros(2))
+    assert not UNet1D(input_dim=36)._paired() and net._paired()

@@ -34,7 +34,7 @@ from sdeflow_light_amd.convnet import ConvOp, ConvOpSet, Stride2PairOp
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 RAGGED = 13                   # samples of the second replay: tile / workgroup / chunk counts that do not divide
-CONFIGS = ("c4_b256", "c4_b32", "c3_b4096", "c5_4096", "c5_1024", "v24_b3", "v24_fwd5")
+CONFIGS = ("c4_b256", "c4_b32", "c3_b4096", "c5_4096", "c5_1024", "v24_b3", "v24_fwd5", "u1d37_b3", "u1d37_fwd5")
 
 # ------------------------------------------------------------------------------------------------ bounds
 # Output families and their bounds on (rel-L2 over the tensor, worst per-row rel-L2, worst element / reference RMS).
@@ -267,17 +267,37 @@ def _build_v24():
     return PluginReverseSDE(sde, net.to(DEV), T, vtype="rademacher", deviceReverseSDE=DEV).to(DEV), 576
 
 
+def _build_u1d37():
+    """Case C of tests/test_unet1d_deep_gpu.py: the 1-D U-Net at L = 37 (levels 37 / 18 / 9 / 4: the unpaired k = 4, s = 2
+    convolutions and transposed convolutions, no level on a halo-tile kernel) with NormalizeLogRadius."""
+    import unet1d_deep as U
+    from oracle.det_params import load_init_like_
+    from sdeflow_light_amd.NNUnet1D import UNet1D
+    from sdeflow_light_amd.SDEs import SGMsde, PluginReverseSDE
+    c = U.CASES["C"]
+    torch.manual_seed(0)
+    net = UNet1D(input_dim=c["L"], base_channels=c["base"], channel_mults=c["mults"], num_res_blocks=2, premodule=c["pre"],
+                 emb_dim=c["emb"])
+    load_init_like_(net, gain=U.GAIN)
+    T = torch.nn.Parameter(torch.FloatTensor([1.0]), requires_grad=False)
+    sde = SGMsde(beta_min=0.1, beta_max=20.0, t_epsilon=1e-3, T=T, num_steps_forward=16, device=DEV)
+    return PluginReverseSDE(sde, net.to(DEV), T, vtype="rademacher", deviceReverseSDE=DEV).to(DEV), c["L"]
+
+
 def _record(config):
     import bench
     from sdeflow_light_amd.train import UNetScoreTrainer
     from sdeflow_light_amd.data import signals_1d, random_images
     rec = Recorder()
-    v24 = config.startswith("v24")
-    gen, d = _build_v24() if v24 else bench.build_unet("c3" if config.startswith("c3") else "c4", torch.device(DEV))
+    u37 = config.startswith("u1d37")
+    v24 = config.startswith("v24") or u37                                  # the nets bench.build_unet does not build
+    fwd_only = config.startswith("c5") or config.endswith("_fwd5")
+    gen, d = (_build_u1d37() if u37 else _build_v24() if v24 else
+              bench.build_unet("c3" if config.startswith("c3") else "c4", torch.device(DEV)))
     net = gen.a
     with pytest.MonkeyPatch.context() as mp:
         rec.patches(mp)
-        if config.startswith("c5") or config == "v24_fwd5":
+        if fwd_only:
             rows = 5 if v24 else int(config.split("_")[1])
             g = torch.Generator(device=DEV).manual_seed(3)
             x = torch.randn(rows, d, device=DEV, generator=g)
@@ -299,7 +319,7 @@ def _record(config):
         ids = {id(o)} | {id(a) for a in alts if a is not None}
         if not ids & rec.fwd_ops:
             missing_f.append(_opcfg(o))
-        if not config.startswith("c5") and config != "v24_fwd5" and not ids & rec.bwd_ops:
+        if not fwd_only and not ids & rec.bwd_ops:
             missing_b.append(_opcfg(o))
     del gen, net
     gc.collect()

@@ -835,6 +835,32 @@ def g21_kde():
     save("g21_kde", **out)
 
 
+def g22_unet1d_deep():
+    """The reference's UNet1D where every level counts (load_init_like_(gain=3.0): tests/unet1d_deep.py) at lengths that are
+    no multiple of 8 — cases B (L = 37), C (37 + NormalizeLogRadius), D (9 + NormalizeLogRadius: middle block at one position)
+    and G (13, two levels, 16 | 32 channels, emb 32): forward output, the three forced SSM draws, per-sample loss and the
+    gradient digest.  The weights are the closed form, not stored."""
+    out = {}
+    for tag, L, B, pre, base, mults, emb in (("B", 37, 3, None, 32, (1, 2, 4), 128), ("C", 37, 3, "NormalizeLogRadius", 32, (1, 2, 4), 128),
+                                             ("D", 9, 3, "NormalizeLogRadius", 32, (1, 2, 4), 128),
+                                             ("G", 13, 3, "NormalizeLogRadius", 16, (1, 2), 32)):
+        net = UNet1D(input_dim=L, base_channels=base, channel_mults=mults, num_res_blocks=2, premodule=pre, emb_dim=emb)
+        load_init_like_(net, gain=3.0)
+        rev = PluginReverseSDE(sgm(), net, Tparam())
+        torch.manual_seed(L)
+        x, u_t, eps, u_v = torch.randn(B, L) * 3, torch.rand(B), torch.randn(B, L), torch.rand(B, L)
+        u_t = u_t.reshape(B, 1)
+        res = _ssm_case(rev, x, u_t, eps, u_v, full_grads=False)
+        out.update({f"{tag}_x": x, f"{tag}_u_t": u_t, f"{tag}_eps": eps, f"{tag}_u_v": u_v})
+        out.update({f"{tag}_{k}": v for k, v in res.items()})
+        torch.manual_seed(1000 + L)
+        xf, t = torch.randn(5, L) * 3, torch.rand(5) * 0.9 + 0.05
+        with torch.no_grad():
+            out[f"{tag}_fwd_x"], out[f"{tag}_fwd_t"], out[f"{tag}_fwd"] = xf, t, net(xf, t)
+        print(tag, "loss", float(res["loss"]), "per", res["per"].tolist())
+    save("g22_unet1d_deep", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
