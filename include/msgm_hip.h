@@ -104,6 +104,37 @@ int msgm_ssm_prep(const float* x0, float* y, float* t_out, float* v, int64_t B, 
 int msgm_forward_step_index(const float* t, int32_t* k, int64_t B, int32_t nsf, float T,
                             msgm_stream_t stream);
 
+/* y_t | y_0 of the multiplicative SDE in ONE launch.  Replaces SDE.sample_scheme (SDEs.py:78-122) and MSGMsde.sample
+ * (SDEs.py:434-436), i.e. the composed chain of msgm_forward_step_index, nsf RK4-Stratonovich steps of the forward
+ * process (4 msgm_sde_stage + msgm_rk4_combine + msgm_keep_rows each), the state copy and the short step of the rows
+ * with k = 0 — 6 nsf + 9 launches.  Rows never interact (the sparse tensor is a circular 3-point stencil inside a row,
+ * the dense one a per-row contraction), so row b is carried in registers through exactly the steps it needs and
+ * stops: k_b = trunc((nsf t_b)/T) steps on the nsf-step grid (msgm_forward_step_index's expression), or, for
+ * k_b = 0, one step of length t_b from y_0 with stage times 0, t_b/2, t_b/2, t_b.  The stage arithmetic is that of
+ * msgm_sde_stage (csrc/sde_stage.h; MSGM_PROC_FORWARD, Stratonovich form, lmbd = 0, no norm correction) in the same
+ * order: the result equals the composed chain bit for bit.
+ *   x0, y     (B, n); y receives every row's final state, one store per element; y must not overlap x0
+ *   t         (B) row times, used as passed
+ *   k_out     optional (B) int32: the stop indices
+ *   ts        device array of nsf + 1 times, linspace(0,1,nsf+1)*T formed in fp32 on the host (sde_scheme.py:59)
+ *   delta, sqrt_delta   T/nsf and its root, rounded to fp32 from the host's double values
+ *   t_half, t_full      fp32(delta/2), fp32(delta): the later stages run at ts[i] + t_half and ts[i] + t_full, fp32 adds
+ *   z_main    optional (nsf, B, n) standard normals: step i of row b uses sqrt_delta z_main[i, b, :]; NULL: Philox
+ *             RNG_STREAM_DW, extra offset i, at the global element index — the numbers msgm_sde_stage draws
+ *   z_short   optional (B, n): the short step's normals; NULL: Philox extra offset nsf + 1
+ *   rng       needed when either z is NULL; read only (the caller advances the stream by 2 nsf + 2 as before)
+ * Rows whose index falls outside [0, nsf] (negative times) are written as zeros, which is what the composed chain's
+ * masked capture leaves them as.  MSGM_E_UNSUPPORTED where msgm_forward_perturb_supported says no: the additive SDE
+ * (msgm_perturb_vp is its closed form), dense tensors with n > 64, sparse rows longer than 12288 (768 threads of a
+ * workgroup x 16 elements each in registers) or longer than 4096 with n % 4 != 0.  Up to n = 4096, operands that are
+ * only 4-byte aligned, or n % 4 != 0, take scalar loads and stores; above, x0, y, z_main and z_short must be 16-byte
+ * aligned (MSGM_E_UNSUPPORTED otherwise).  Never allocates or synchronises. */
+int msgm_forward_perturb_supported(int32_t kind, int64_t n);   /* host only */
+int msgm_forward_perturb(const float* x0, const float* t, float* y, int32_t* k_out, int64_t B, int64_t n,
+                         const msgm_sde_t* sde, int32_t nsf, const float* ts, float delta, float sqrt_delta,
+                         float t_half, float t_full, const float* z_main, const float* z_short, const uint64_t* rng,
+                         msgm_stream_t stream);
+
 /* Rademacher probe v = 2[u>=1/2]-1 (SDEs.py:514-515); u NULL => rng stream 2. */
 int msgm_rademacher(float* v, int64_t n, const float* u, const uint64_t* rng, msgm_stream_t stream);
 

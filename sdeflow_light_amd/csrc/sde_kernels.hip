@@ -186,11 +186,7 @@ __global__ void k_ssm_prep(const float* __restrict__ x0, float* __restrict__ y, 
 // bit-exact stop index                                        SDEs.py:89-101
 __global__ void k_forward_step_index(const float* __restrict__ t, int32_t* __restrict__ k, int64_t B, int32_t nsf, float T) {
   for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
-    float tb = t[b];
-    float f = __fdiv_rn(__fmul_rn((float)nsf, tb), T);   // (nsf*t)/T in fp32, no contraction
-    int32_t kk = (int32_t)truncf(f);
-    if (tb >= T) kk = nsf;
-    k[b] = kk;
+    k[b] = forward_step_k(t[b], nsf, T);                 // (nsf*t)/T in fp32, no contraction (sde_stage.h)
   }
 }
 

@@ -103,6 +103,15 @@ __device__ __forceinline__ float diag_inc(const StageArgs& A, const DiagCoef& c,
   return mu * A.delta + c.sig * w;
 }
 
+// Row stop index of the forward perturbation: k = trunc((nsf t)/T) in fp32 without contraction, rows with t >= T forced to
+// nsf (SDEs.py:89-101).  k_forward_step_index and k_forward_perturb_* both call it.
+__device__ __forceinline__ int32_t forward_step_k(float tb, int32_t nsf, float T) {
+  const float f = __fdiv_rn(__fmul_rn((float)nsf, tb), T);
+  int32_t kk = (int32_t)truncf(f);
+  if (tb >= T) kk = nsf;
+  return kk;
+}
+
 // x + (k1 + 2k2 + 2k3 + k4)/6                                  sde_scheme.py:250-253
 // The sum is taken left to right, so it can also be carried one increment at a time: s = k1, s = rk4_add(s, k2),
 // s = rk4_add(s, k3), x_new = rk4_close(x, s, k4) — the same bits as rk4_value with all four at hand.

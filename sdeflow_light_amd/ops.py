@@ -78,6 +78,41 @@ def forward_step_index(t: torch.Tensor, nsf: int, T: float) -> torch.Tensor:
     return k
 
 
+def forward_perturb_supported(kind: int, n: int) -> bool:
+    """Whether msgm_forward_perturb takes this row: the sparse tensor up to n = 4096, and up to n = 12288 when n % 4 == 0;
+    the dense one up to n = 64."""
+    return bool(lib().msgm_forward_perturb_supported(int(kind), int(n)))
+
+
+def forward_perturb(x0: torch.Tensor, t: torch.Tensor, sde: L.SdeT, nsf: int, ts: torch.Tensor, delta: float,
+                    z_main: Optional[torch.Tensor] = None, z_short: Optional[torch.Tensor] = None,
+                    rng: Optional[PhiloxState] = None, k_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y_t | y_0 of the multiplicative SDE in ONE launch: row b takes k_b = trunc(nsf t_b / T) RK4-Stratonovich steps of
+    the forward process on the nsf-step grid ts (device fp32, nsf + 1 values), or one step of length t_b when k_b = 0.
+    z_main (nsf,B,n) / z_short (B,n): injected standard normals, else the Philox draws of the composed route (the stream
+    is NOT advanced here).  k_out: optional int32 (B) receiving k.  Returns y (B,n)."""
+    if x0.dim() != 2 or not x0.is_cuda:
+        raise MsgmError("forward perturb: the state must be a (B,n) device tensor; there is no CPU fallback")
+    B, n = x0.shape
+    t = t.reshape(-1)
+    _same_shape(t, (B,), "t")
+    if ts.device != x0.device or ts.dtype != torch.float32 or ts.numel() != nsf + 1:
+        raise MsgmError("forward perturb: ts must be a device fp32 grid of nsf + 1 values")
+    _same_shape(z_main, (nsf, B, n), "z_main")
+    _same_shape(z_short, (B, n), "z_short")
+    for nm, tt in (("z_main", z_main), ("z_short", z_short)):
+        if tt is not None:
+            f32(tt, nm)
+    if k_out is not None and (k_out.dtype != torch.int32 or k_out.numel() != B):
+        raise MsgmError("k_out must be int32 of length B")
+    y = torch.empty_like(x0)
+    # the stage offsets are rounded to fp32 on the way in, as upstream adds them to an fp32 time (sde_scheme.py:150,233-247)
+    check(lib().msgm_forward_perturb(ptr(f32(x0)), ptr(f32(t)), ptr(y), ptr(k_out), B, n, sde, int(nsf), ptr(ts), float(delta),
+                                     float(delta ** 0.5), float(delta * 0.5), float(delta * 1.0), ptr(z_main), ptr(z_short),
+                                     _rng_ptr(rng), stream()), "msgm_forward_perturb")
+    return y
+
+
 def rademacher(shape, device, u: Optional[torch.Tensor] = None, rng: Optional[PhiloxState] = None) -> torch.Tensor:
     v = torch.empty(shape, dtype=torch.float32, device=device)
     _same_shape(u, v.shape, "u")

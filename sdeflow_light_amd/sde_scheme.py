@@ -44,7 +44,7 @@ class _Clock(NamedTuple):
     three calling styles differ here and nowhere else:
       eager samplers (``_Run.clock``): host stage times ``t=``, the step's ``z=`` or the Philox step index ``rng_step=i``;
       ``GraphedStepSampler``: ``t_dev=`` the device clocks ``time_tick`` sets, ``step_dev=`` the device step counter;
-      the short rows of ``msgm_forward_perturb``: ``delta_rows=`` with ``t_frac=`` (times 0, t_b/2, t_b), ``delta = 0``."""
+      the short rows of ``msgm_forward_perturb_composed``: ``delta_rows=`` with ``t_frac=`` (times 0, t_b/2, t_b), ``delta = 0``."""
     struct: object
     proc: int
     lmbd: float
@@ -283,14 +283,57 @@ def _rk4(*args, loop=None):
     return _integrate(_rk4_step, (0.5, 1.0), 7, *args, loop=loop)
 
 
+def _forward_grid(base, nsf, dev):
+    """The forward time grid linspace(0,1,nsf+1)*T (fp32, formed on the host as ``_Run`` does) on the device, cached on the
+    base SDE per (nsf, T, device): the trainers capture ``msgm_forward_perturb`` into a hipGraph that holds kernel nodes
+    only, so the copy to the device happens on first use — their eager warm-up step — and never during a capture."""
+    cache = getattr(base, "_forward_ts", None)
+    if cache is None:
+        cache = base._forward_ts = {}
+    T_ = base.T_float()
+    key = (int(nsf), T_, dev)
+    if key not in cache:
+        if torch.cuda.is_current_stream_capturing():
+            raise MsgmError("the forward time grid is needed for the first time inside a graph capture; "
+                            "run one eager step first")
+        cache[key] = ((torch.linspace(0, 1, nsf + 1) * T_).to(dev), T_ / nsf)
+    return cache[key]
+
+
 @torch.no_grad()
 def msgm_forward_perturb(base, t, y0, noise_main=None, noise_short=None):
-    """y_t | y_0 for the multiplicative SDE (SDE.sample_scheme, SDEs.py:78-122)
-    kept on the device: all rows are RK4-integrated over the nsf-step grid and
-    row b is captured when the step count reaches k_b = trunc(nsf t_b / T)
-    (bit-exact int32 index kernel); rows with k_b = 0 take one RK4 step of
-    length t_b from y_0 (per-row delta inside the stage kernel) — no Python
-    loop over rows, no D2H/H2D round trips."""
+    """y_t | y_0 for the multiplicative SDE (SDE.sample_scheme, SDEs.py:78-122) in ONE launch
+    (``msgm_forward_perturb``) where ``ops.forward_perturb_supported`` takes the row length: row b takes exactly its
+    k_b = trunc(nsf t_b / T) RK4 steps — or the one step of length t_b when k_b = 0 — with the state in registers, and
+    is stored once.  Same time grid, stage times and noise (``noise_main`` / ``noise_short`` or the Philox draws) as
+    ``msgm_forward_perturb_composed``, which every other shape takes; the result is the same bit for bit.  Both routes
+    advance the stream by 2 nsf + 2."""
+    st = base.struct()
+    if y0.dim() != 2 or not y0.is_cuda or not ops.forward_perturb_supported(st.kind, y0.shape[1]):
+        return msgm_forward_perturb_composed(base, t, y0, noise_main, noise_short)
+    dev = y0.device
+    nsf = base.num_steps_forward
+    x = y0.detach().contiguous().float()
+    zm = None if noise_main is None else noise_main.to(dev).contiguous()
+    zs = None if noise_short is None else noise_short.to(dev).contiguous()
+    if any(v is not None and v.data_ptr() % 16 for v in (x, zm, zs)):
+        # views that are only 4-byte aligned: the long-row form of the kernel does not take them
+        return msgm_forward_perturb_composed(base, t, y0, noise_main, noise_short)
+    ts, delta = _forward_grid(base, nsf, dev)
+    rng = base.philox(dev)
+    y = ops.forward_perturb(x, t.reshape(-1).contiguous().float(), st, nsf, ts, delta,
+                            z_main=zm, z_short=zs, rng=None if (zm is not None and zs is not None) else rng)
+    rng.advance(2 * nsf + 2)
+    return y
+
+
+@torch.no_grad()
+def msgm_forward_perturb_composed(base, t, y0, noise_main=None, noise_short=None):
+    """msgm_forward_perturb on the composed route (index kernel, nsf RK4 steps of stage, combine and masked-capture
+    launches, then the short step), whatever the shape: the yardstick of the one-launch kernel.  All rows are
+    RK4-integrated over the nsf-step grid and row b is captured when the step count reaches k_b = trunc(nsf t_b / T)
+    (bit-exact int32 index kernel); rows with k_b = 0 take one RK4 step of length t_b from y_0 (per-row delta inside
+    the stage kernel) — no Python loop over rows, no D2H/H2D round trips."""
     from .SDEs import forward_SDE
     dev = y0.device
     nsf = base.num_steps_forward
