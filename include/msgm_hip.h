@@ -201,6 +201,15 @@ int msgm_ssm_terms(const float* y, const float* v, const float* t, float* u, flo
  * `out` the (primal | tangent) stacked net output [2B][n]. */
 int msgm_ssm_loss(const float* out, const float* u, const float* cst, float* per, float* g, int64_t B, int64_t n,
                   float inv_batch, msgm_stream_t stream);
+/* The two K12 seeds with per-row weights (SDEs.py:607-646: upstream's per-sample losses are an autograd tensor, so any
+ * weighting of the rows back-propagates): g = [a ; .] * (inv_batch * row_w[b]), per[b] stays unweighted.  row_w: B
+ * contiguous floats of any sign; NULL is the unweighted entry to the bit.  Zero-weight rows still flow through the
+ * arithmetic (0 * NaN poisons everything downstream of g): the caller keeps every row finite. */
+int msgm_ssm_loss_diag_w(const float* out, const float* v, const float* t, float* per, float* g,
+                         int64_t B, int64_t n, const msgm_sde_t* sde, float inv_batch, const float* row_w,
+                         msgm_stream_t stream);
+int msgm_ssm_loss_w(const float* out, const float* u, const float* cst, float* per, float* g, int64_t B, int64_t n,
+                    float inv_batch, const float* row_w, msgm_stream_t stream);
 
 /* out = c0*a + c1*b + c2*c (b, c may be NULL): stage points of Heun / RK4
  * (x + K/2, sde_scheme.py:148,234,240,246). */
@@ -328,6 +337,29 @@ int msgm_mlp_ssm_partial(const msgm_mlp_params_t* P, const float* y, const float
                          msgm_stream_t stream);
 int msgm_mlp_ssm_reduce(int32_t d, int32_t premodule, const void* workspace, int32_t n_slabs,
                         float inv_batch, float* grads, float* loss_sum, msgm_stream_t stream);
+
+/* Per-row weights in the SSM loss (SDEs.py:607-646 returns the per-sample
+ * losses as an autograd tensor, so upstream back-propagates any weighting of
+ * the rows; here the gradient is formed inside the kernel, so the weights go
+ * in with the call).  row_w: B contiguous floats of any sign, or NULL, which
+ * is the unweighted entry to the bit.  With s = inv_batch:
+ *   grads = s sum_b w_b dL_b/dtheta;  loss_per[b] = L_b (unweighted);
+ *   loss_sum = s sum_b w_b L_b.
+ * The seed of a row is (s * w_b), so w = 1 is bitwise the unweighted call,
+ * w = c (a power of two) bitwise the unweighted call with s * c, and w = -1
+ * its exact negation.  Zero-weight rows still flow through the arithmetic
+ * (0 * NaN would poison the sums): the caller keeps every row finite.
+ * msgm_mlp_ssm_reduce / _reduce_adam serve both forms unchanged. */
+int msgm_mlp_ssm_grad_w(const msgm_mlp_params_t* P, const float* y, const float* t, const float* v,
+                        const float* u, const float* cst,
+                        int64_t B, const msgm_sde_t* sde, float inv_batch, const float* row_w,
+                        float* grads, float* loss_per, float* loss_sum,
+                        void* workspace, size_t workspace_bytes, msgm_stream_t stream);
+int msgm_mlp_ssm_partial_w(const msgm_mlp_params_t* P, const float* y, const float* t, const float* v,
+                           const float* u, const float* cst,
+                           int64_t B, const msgm_sde_t* sde, float inv_batch, const float* row_w,
+                           float* loss_per, void* workspace, size_t workspace_bytes, int32_t* n_slabs_host,
+                           msgm_stream_t stream);
 
 /* ---- K6/K11: convolutions as implicit GEMMs (U-Net score nets) ------------- */
 /* Activations are channels-last [N][H][W][C] (1-D: H = 1).  The forward-mode

@@ -632,14 +632,18 @@ class VorticityUNet(nn.Module, FlatParamMixin):
 
     # ------------------------------------------------------------------ training
     @torch.no_grad()
-    def ssm_grad(self, y, t, v, u, cst, inv_batch, rng: Optional[PhiloxState] = None):
+    def ssm_grad(self, y, t, v, u, cst, inv_batch, rng: Optional[PhiloxState] = None, *,
+                 row_weight: Optional[torch.Tensor] = None):
         """Per-sample SSM loss (B,) in the general form loss_b = adot.u + cst + |a|^2/2 (u, cst from
         ``msgm_ssm_terms``: any SDE family); gradients of sum_b loss_b*inv_batch into .grad.
         With dropout active the masks are drawn from ``rng`` (the caller's training stream, shard base included; the net's
         own stream when None) at its current offset — the forward and the backward use the same masks, primal and tangent
-        share them — and the stream is advanced by 1 afterwards."""
+        share them — and the stream is advanced by 1 afterwards.
+        ``row_weight`` (B,) float32 on the device: gradients of sum_b w_b loss_b*inv_batch — the weight enters at the loss
+        seed, everything after it is linear in the seed; the returned losses stay unweighted."""
         B, d = y.shape
         N = 2 * B
+        ops._row_weight(row_weight, B)   # refused before any launch
         S_, Cc = self.in_space, self.channels
         self.flat_parameters()
         for p in self.parameters():
@@ -663,7 +667,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         drop = (rng if rng is not None else self.dropout_stream(y.device)) if self.dropout_active() else None
         out = self._run(img, tt, N, B, tape, drop, logr=logr)
         a_flat = ops.image_to_flat(out, N, Cc, S_, S_, forder, float(scale_image))      # [2B][d]: a | adot
-        per, g = ops.ssm_loss(a_flat.view(-1), u, cst, inv_batch)
+        per, g = ops.ssm_loss(a_flat.view(-1), u, cst, inv_batch, row_weight=row_weight)
         gimg = ops.flat_to_image(g.view(N, d), N, Cc, S_, S_, forder, float(scale_image))   # adjoint of (x5, unflatten)
         with ops.DeferredReduces.on(y.device):           # the ~140 slot reductions of the weight / bias gradients: one launch
             self._backward(tape, gimg, N, B)

@@ -220,12 +220,15 @@ class UNet1D(nn.Module, FlatParamMixin):
     # ------------------------------------------------------------------ training
     @torch.no_grad()
     def ssm_grad(self, y: torch.Tensor, t: torch.Tensor, v: torch.Tensor, u: torch.Tensor, cst: torch.Tensor,
-                 inv_batch: float, rng=None):
+                 inv_batch: float, rng=None, *, row_weight: Optional[torch.Tensor] = None):
         """Per-sample SSM loss (B,) in the general form loss_b = adot.u + cst + |a|^2/2 (u, cst from
         ``msgm_ssm_terms``: any SDE family); d(sum_b loss_b * inv_batch)/d(params) is written into ``.grad``.
-        ``rng`` (the caller's training stream) is accepted like the 2-D U-Net's; this net draws nothing from it."""
+        ``rng`` (the caller's training stream) is accepted like the 2-D U-Net's; this net draws nothing from it.
+        ``row_weight`` (B,) float32 on the device: the gradient becomes d(sum_b w_b loss_b * inv_batch)/d(params) — the
+        weight enters at the loss seed, everything after it is linear in the seed; the returned losses stay unweighted."""
         B, L = y.shape
         self._check_length(L)
+        ops._row_weight(row_weight, B)             # refused before any launch
         N = 2 * B
         flat, gflat = self.flat_parameters()
         for p in self.parameters():
@@ -238,7 +241,7 @@ class UNet1D(nn.Module, FlatParamMixin):
         tape = []
         h0 = torch.cat([y.contiguous().float(), v.contiguous().float()], 0).reshape(-1)
         out = self._run(h0, t.reshape(-1).contiguous().float(), N, B, L, True, tape)
-        per, g = ops.ssm_loss(out, u, cst, inv_batch)
+        per, g = ops.ssm_loss(out, u, cst, inv_batch, row_weight=row_weight)
         with ops.DeferredReduces.on(y.device):           # all slot reductions of the weight / bias gradients in one launch
             self._backward(tape, g, N, B)
         self._opset.unpack_grads()

@@ -561,9 +561,13 @@ class PluginReverseSDE(nn.Module):
         y, t = ops.perturb_vp(x.contiguous(), base.struct(), u=u, eps=eps, rng=rng)
         return t.reshape(-1, 1), x, y
 
-    def ssm(self, x, u=None, eps=None, u_v=None, y=None, t_given=None, v=None):
+    def ssm(self, x, u=None, eps=None, u_v=None, y=None, t_given=None, v=None, row_weight=None):
         """Per-sample SSM loss (B,), gradients of its mean accumulated into the
-        score net's ``.grad`` (see class docstring).  ``u``/``eps``/``u_v``
+        score net's ``.grad`` (see class docstring).  ``row_weight`` (B,) float32 on the device, any sign: the returned
+        tensor is w (.) L and its ``.mean()`` / ``.sum()`` differentiate as upstream's do; the weights go into the fused
+        pass of this call (with a dropout net: the live stream's masks).  Zero-weight rows still flow through the
+        arithmetic, so keep them finite.  Any other weighting of the rows of the result (a non-uniform cotangent) costs
+        one more fused pass in ``backward``.  ``u``/``eps``/``u_v``
         inject the three draws of SDEs.py:688,141,515 (parity tests); ``v`` injects
         the probe itself (any ``vtype``).  ``vtype`` 'gaussian' / 'uniform' (sphere)
         probes (SDEs.py:517-536) are drawn from the Philox stream and go through the
@@ -578,6 +582,7 @@ class PluginReverseSDE(nn.Module):
         x = x.contiguous().float()
         B, d = x.shape
         dev = x.device
+        ops._row_weight(row_weight, B)               # CPU / wrong length / wrong dtype: refused before any launch or draw
         rng = base.philox(dev)
         if y is None:
             t, _, y = self.sample_txy(x, u=u, eps=eps)
@@ -599,13 +604,27 @@ class PluginReverseSDE(nn.Module):
         if base.kind != L.SDE_SGM or not isinstance(net, MLP) or not pm1:
             # general form of the loss: loss_b = adot.u + cst + |a|^2/2 (u = G(y)^T v for the multiplicative SDE)
             uu, cst = ops.ssm_terms(y, v, t.reshape(-1).contiguous(), st)
+        per, gtmp, gflat = self._ssm_pass(y, t.reshape(-1), v, uu, cst, 1.0 / B, row_weight, rng)
+        if row_weight is not None:
+            per = per * row_weight                   # the returned tensor is w (.) L; gtmp = (1/B) sum_b w_b dL_b
+        return _SSMGradBridge.apply(per, gtmp, gflat, net, B, next(net.parameters()), self,
+                                    (y, t, v, uu, cst), row_weight)
+
+    def _ssm_pass(self, y, t, v, uu, cst, inv_batch, row_weight, rng):
+        """One fused pass: (per-sample losses, d(inv_batch sum_b w_b L_b)/d(params) as a flat tensor of its own, the
+        net's flat gradient bucket, left as it was)."""
+        from .NN import MLP
+        net = self.a
+        B, d = y.shape
+        dev = y.device
         flat, gflat = net.flat_parameters()
         if isinstance(net, MLP):
             if self._ws is None or self._ws.device != dev:
                 self._ws = ops.mlp_ssm_workspace(d, net.pre is not None, dev)
             per = torch.empty(B, dtype=torch.float32, device=dev)
             gtmp = torch.empty_like(gflat)
-            ops.mlp_ssm_grad(net.kernel_params(), y, t.reshape(-1), v, st, 1.0 / B, gtmp, self._ws, loss_per=per, u=uu, cst=cst)
+            ops.mlp_ssm_grad(net.kernel_params(), y, t, v, self.base_sde.struct(), inv_batch, gtmp, self._ws, loss_per=per, u=uu,
+                             cst=cst, row_weight=row_weight)
         else:
             # U-Nets: dual-number forward + hand-written backward; the net writes its flat .grad bucket
             # (what was accumulated so far is put back afterwards; a parameter whose .grad is None — zero_grad() —
@@ -617,15 +636,15 @@ class PluginReverseSDE(nn.Module):
                     keep[off:off + p_.numel()].zero_()
                 off += p_.numel()
             # a 2-D U-Net with active dropout draws its masks from the SDE's stream (shard base, checkpoint, graph replay)
-            per = net.ssm_grad(y, t.reshape(-1), v, uu, cst, 1.0 / B, rng=rng)
+            per = net.ssm_grad(y, t, v, uu, cst, inv_batch, rng=rng, row_weight=row_weight)
             flat, gflat = net.flat_parameters()
             gtmp = gflat.clone()
             gflat.copy_(keep)
-        return _SSMGradBridge.apply(per, gtmp, gflat, net, B, next(net.parameters()))
+        return per, gtmp, gflat
 
-    def ssm_loss(self, t_, x, y, u_v=None):
+    def ssm_loss(self, t_, x, y, u_v=None, row_weight=None):
         """Reference entry point (SDEs.py:616-646) with (t, y) given: same fused forward-mode kernels as ``ssm``."""
-        return self.ssm(x, u_v=u_v, y=y, t_given=t_)
+        return self.ssm(x, u_v=u_v, y=y, t_given=t_, row_weight=row_weight)
 
     def latent_sample(self, num_samples, n):
         return self.base_sde.latent_sample(num_samples, n)
@@ -655,20 +674,52 @@ class PluginReverseSDE(nn.Module):
 
 
 class _SSMGradBridge(torch.autograd.Function):
-    """Lets ``ssm(x).mean().backward()`` deliver the kernel-computed parameter
-    gradients: backward adds ``sum(grad_output) * grad_of_mean`` to the flat
-    gradient bucket (exact for uniform reductions: sum_b c dL_b = c B grad_of_mean)."""
+    """Lets ``ssm(x).mean().backward()`` deliver the kernel-computed parameter gradients.  Upstream's ``ssm`` returns an
+    ordinary autograd tensor (SDEs.py:607-646), so any weighting of its rows back-propagates; here the gradient of the
+    mean, ``gmean = (1/B) sum_b w_b dL_b`` (w = ``row_weight`` or ones), was formed inside the fused pass of the forward
+    call, and ``backward`` has two paths:
+
+    * uniform cotangent (every entry bit-equal: ``.mean()``, ``.sum()``, a scalar factor): adds
+      ``sum(grad_output) * gmean`` to the flat gradient bucket (sum_b c w_b dL_b = c B gmean).  One element and a
+      stride-0 expansion are recognised without a device synchronisation; anything else costs one device comparison,
+      whose host read is confined to this eager surface (the trainers never pass through the bridge).
+    * non-uniform cotangent: one more fused pass over the saved ``(y, t, v, u, cst)`` with the row weights
+      ``grad_output`` (times ``row_weight`` where one was given) and ``inv_batch = 1``.  A 2-D U-Net whose dropout was
+      active in the forward call cannot be re-run with the same masks from here and raises ``MsgmError``."""
 
     @staticmethod
-    def forward(ctx, per, gmean, gflat, net, B, anchor):
+    def forward(ctx, per, gmean, gflat, net, B, anchor, sde=None, saved=None, row_weight=None):
         # `anchor` (a parameter that requires grad) only makes autograd record this node
         ctx.gmean, ctx.gflat, ctx.net, ctx.B = gmean, gflat, net, B
+        # by reference, no copies: the operands of a second fused pass
+        ctx.sde, ctx.saved, ctx.row_weight = sde, saved, row_weight
+        ctx.dropout = bool(getattr(net, "dropout_active", lambda: False)())
         return per.clone()
 
     @staticmethod
+    def _uniform(g) -> bool:
+        if g.numel() == 1 or all(st == 0 for st in g.stride()):
+            return True
+        bits = g.contiguous().view(torch.int32).reshape(-1)
+        return bool((bits == bits[0]).all())
+
+    @staticmethod
     def backward(ctx, grad_out):
-        scale = grad_out.sum()          # = c*B for a uniform weight c; gmean already carries 1/B
         net = ctx.net
+        gadd = None
+        if ctx.saved is not None and not _SSMGradBridge._uniform(grad_out):
+            if ctx.dropout:
+                raise MsgmError("ssm(): a non-uniform weighting of the rows needs a second pass, and a 2-D U-Net with active "
+                                "dropout cannot be re-run with the forward call's masks; pass the weights as "
+                                "ssm(x, row_weight=w), which applies them inside the forward call")
+            w = grad_out.detach().reshape(-1).contiguous().float()
+            if ctx.row_weight is not None:
+                w = w * ctx.row_weight
+            y, t, v, uu, cst = ctx.saved
+            with torch.no_grad():
+                _, gadd, _ = ctx.sde._ssm_pass(y, t.reshape(-1), v, uu, cst, 1.0, w, None)
+        else:
+            scale = grad_out.sum()          # = c*B for a uniform weight c; gmean already carries 1/B
         flat, gflat = net.flat_parameters()
         off = 0
         for p in net.parameters():
@@ -677,5 +728,5 @@ class _SSMGradBridge(torch.autograd.Function):
                 gflat[off:off + k].zero_()
                 p.grad = gflat[off:off + k].view(p.shape)
             off += k
-        gflat.add_(ctx.gmean * scale)
-        return None, None, None, None, None, None
+        gflat.add_(ctx.gmean * scale if gadd is None else gadd)
+        return None, None, None, None, None, None, None, None, None

@@ -189,6 +189,13 @@ SIGNATURES = {
     "msgm_mlp_ssm_grad": (C.c_int, [C.POINTER(MlpParamsT), _P, _P, _P, _P, _P, _I64, C.POINTER(SdeT), _F, _P, _P, _P, _P, _SZ, _P]),
     "msgm_ssm_terms": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, C.POINTER(SdeT), _P]),
     "msgm_ssm_loss": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _F, _P]),
+    # per-row weights in the SSM loss: row_w follows inv_batch, NULL is the unweighted entry
+    "msgm_mlp_ssm_partial_w": (C.c_int, [C.POINTER(MlpParamsT), _P, _P, _P, _P, _P, _I64, C.POINTER(SdeT), _F, _P, _P, _P, _SZ,
+                                         C.POINTER(C.c_int32), _P]),
+    "msgm_mlp_ssm_grad_w": (C.c_int, [C.POINTER(MlpParamsT), _P, _P, _P, _P, _P, _I64, C.POINTER(SdeT), _F, _P, _P, _P, _P, _P, _SZ,
+                                      _P]),
+    "msgm_ssm_loss_diag_w": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, C.POINTER(SdeT), _F, _P, _P]),
+    "msgm_ssm_loss_w": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _F, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

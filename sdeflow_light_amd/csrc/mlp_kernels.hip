@@ -72,6 +72,7 @@ struct MlpLds {
   static constexpr int RU = RV + (TRAIN ? SPT * DMAX : 0);
   static constexpr int RW = RU + (TRAIN ? SPT * DMAX : 0);
   static constexpr int RT = RW + (SDE ? SPT * DMAX : 0);
+  static constexpr int RWT = RT + 16;              // train (16 rows a tile): the optional row weights, in RT's upper half
   static constexpr int RC = RT + 32;
   static constexpr int RAWN = RC + 16;
   static constexpr int X = 0;
@@ -113,6 +114,7 @@ struct MlpArgs {
   int n_steps; const float* ts;   // EM loop: n_steps > 1 steps in ONE launch, time of step i = ts[i] (device array)
   // train
   float inv_batch;
+  const float* row_w;    // (B) optional per-row weights of the loss: the row's seed is inv_batch * row_w[b]; null => inv_batch
   float* loss_per; float* slabs;   // slabs: [gridDim.x][slab_stride], element n_params = loss sum; stride = 4-aligned
   int64_t n_params;
   // sampler loop (MODE_SDE): n_stages = 1 (EM), 2 (Heun) or 4 (RK4-Stratonovich) stages per step, SDE family `kind`
@@ -407,7 +409,7 @@ struct MlpLayout {
 // operand h0 at the end of the previous tile (build_h0) — no global-load latency sits on the tile's critical path.
 // A thread holds NR elements of each chunk (element ev + NT k of the tile, ev = its index in the workgroup), and
 // thread tid < SPT the t / cst of sample tid.  STAGE_U: the u chunk travels the same way (else its reader fetches it).
-template <int NR> struct RawRegs { float y[NR], v[NR], u[NR], t = 0.f, c = 0.f, w[NR]; };
+template <int NR> struct RawRegs { float y[NR], v[NR], u[NR], t = 0.f, c = 0.f, rw = 0.f, w[NR]; };
 
 template <int MODE, class LO, int NT, bool STAGE_U, int NR>
 __device__ __forceinline__ void raw_issue(const MlpArgs& A, RawRegs<NR>& pf, int ev, int tid, int64_t tl, int step) {
@@ -438,11 +440,16 @@ __device__ __forceinline__ void raw_issue(const MlpArgs& A, RawRegs<NR>& pf, int
     const int64_t smp = tl * SPT + tid;
     if (MODE == MODE_SDE) pf.t = smp < A.B ? sde_item_time(A, sde_item(A, step)) : 0.f;
     else pf.t = smp < A.B ? (A.t ? A.t[smp] : ((MODE == MODE_EM && A.ts) ? A.ts[step] : A.t_scalar)) : 0.f;
-    if (MODE == MODE_TRAIN) pf.c = (smp < A.B && A.u && A.cst) ? A.cst[smp] : 0.f;
+    if (MODE == MODE_TRAIN) {
+      pf.c = (smp < A.B && A.u && A.cst) ? A.cst[smp] : 0.f;
+      // the ONLY test of the weight pointer (workgroup-uniform); in flight with t and cst.  Unweighted: 1, and x * 1 is x
+      // to the bit, so everything after this line is one instruction sequence for both forms
+      pf.rw = A.row_w ? (smp < A.B ? A.row_w[smp] : 0.f) : 1.f;
+    }
   }
 }
 template <int MODE, class LO, int NT, bool STAGE_U, int NR>
-__device__ __forceinline__ void raw_commit(const RawRegs<NR>& pf, float* R, int ev, int tid) {
+__device__ __forceinline__ void raw_commit(const MlpArgs& A, const RawRegs<NR>& pf, float* R, int ev, int tid) {
   constexpr int SPT = LO::SPT, CHUNK = SPT * LO::DMAX;
 #pragma unroll
   for (int k = 0; k < NR; ++k) {
@@ -454,7 +461,13 @@ __device__ __forceinline__ void raw_commit(const RawRegs<NR>& pf, float* R, int 
       if constexpr (MODE == MODE_SDE) R[LO::RW + e] = pf.w[k];
     }
   }
-  if (tid < SPT) { R[LO::RT + tid] = pf.t; if (MODE == MODE_TRAIN) R[LO::RC + tid] = pf.c; }
+  if (tid < SPT) {
+    R[LO::RT + tid] = pf.t;
+    if (MODE == MODE_TRAIN) {
+      R[LO::RC + tid] = pf.c;
+      R[LO::RWT + tid] = pf.rw;
+    }
+  }
 }
 // h0 (and its tangent) of tile tl from its raw buffer, GS threads per sample row: thread (l, sub) takes the elements
 // sub, sub + GS, .. of row l, and the norm of NormalizeLogRadius meets by shuffle within the group.
@@ -686,7 +699,7 @@ __device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& 
 }
 
 // Sliced-score-matching terms of one output o of one sample: returns its share of the sample's loss and sets the
-// cotangents of a and adot (wgt = 1/batch, 0 for a dead row).  p = u_o in the general form, v_o in the SGM closed form:
+// cotangents of a and adot (wgt = ssm_seed: 1/batch, 0 for a dead row).  p = u_o in the general form, v_o in the SGM closed form:
 //   general (MSGM): loss_b = sum_o adot_o u_o + cst_b + 1/2 a_o^2, u = (d mu/d a)^T v = G(y)^T v
 //   SGM: loss_b = sum_o v_o (sqrt(beta) adot_o + 1/2 beta v_o) + 1/2 a_o^2     SDEs.py:631-646
 __device__ __forceinline__ float ssm_terms(bool general, float a, float ad, float p, float beta, float sb, float wgt,
@@ -696,14 +709,21 @@ __device__ __forceinline__ float ssm_terms(bool general, float a, float ad, floa
   adb = sb * p * wgt;
   return p * (sb * ad + 0.5f * beta * p) + 0.5f * a * a;
 }
+// The seed of one sample row: inv_batch times the row's weight rw (its slot in the tile's raw buffer, read by the sample's
+// 16 lanes as one LDS broadcast; exactly 1 without weights: inv_batch * 1 is inv_batch to the bit); 0 for a dead row.
+// Zero-weight rows still go through the arithmetic: the caller keeps them finite.
+__device__ __forceinline__ float ssm_seed(const MlpArgs& A, bool live, float rw) {
+  return live ? A.inv_batch * rw : 0.f;
+}
 // The 16 threads (ol = 0..15) of a sample add up their terms; thread ol == 0 adds cst, counts the sample and stores it.
+// The workgroup's sum takes rw * loss_b (rw: the row's weight, 1 without weights); the stored loss_per stays unweighted.
 __device__ __forceinline__ void ssm_sample_loss(const MlpArgs& A, float lj, int ol, bool live, int64_t smp, const float* cst_lds,
-                                                float& loss_acc) {
+                                                float rw, float& loss_acc) {
 #pragma unroll
   for (int m = 8; m > 0; m >>= 1) lj += __shfl_xor(lj, m, 64);
   if (ol == 0 && live) {
     if (A.u && A.cst) lj += *cst_lds;
-    loss_acc += lj;
+    loss_acc += rw * lj;
     if (A.loss_per) A.loss_per[smp] = lj;
   }
 }
@@ -783,7 +803,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
   RawRegs<NR> pf;
   [[maybe_unused]] SdeRegs<MODE == MODE_SDE ? NR : 0> sr;   // sampler loop: the stage update's own operands
   auto issue = [&](int64_t tl, int step = 0) { raw_issue<MODE, LO, NT, true>(A, pf, tid, tid, tl, step); };
-  auto commit = [&](float* R) { raw_commit<MODE, LO, NT, true>(pf, R, tid, tid); };
+  auto commit = [&](float* R) { raw_commit<MODE, LO, NT, true>(A, pf, R, tid, tid); };
   auto h0_row = [&](float* H0b, const float* R, int64_t tl, int l) { build_h0<MODE, LO, 1, SM_P>(A, H0b, R, tl, l, 0); };
 
   // ---- prologue.  The first tile's inputs and the first weight fragments go out first; the one-time staging of
@@ -956,7 +976,8 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
         const int c = tid >> 4, ol = tid & 15;
         const int64_t smp = s_base + c;
         const bool live = smp < A.B;
-        const float wgt = live ? A.inv_batch : 0.f;
+        const float rw = Rc[LO::RWT + c];
+        const float wgt = ssm_seed(A, live, rw);
         float beta = 0.f, sb = 0.f;
         if (!A.u) { beta = sde_beta(A.b0, A.b1, Rc[LO::RT + c]); sb = sqrtf(beta); }
         float lj = 0.f;
@@ -974,7 +995,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
           ABAR[(16 + c) * SM_P + o] = adb;
           DB4[c * DPAD + o] += ab;
         }
-        ssm_sample_loss(A, lj, ol, live, smp, Rc + LO::RC + c, loss_acc);
+        ssm_sample_loss(A, lj, ol, live, smp, Rc + LO::RC + c, rw, loss_acc);
       }
       // next tile's layer-1 operand, by a wave that has no part in the loss when there are eight
       if (tid >= NT - 64 && tid < NT - 64 + 16) h0_row(H0n, Rn, ntile, tid - (NT - 64));
@@ -1080,6 +1101,7 @@ struct MlpLdsXW {
   static constexpr int RY = 0;
   static constexpr int RV = RY + SPT * DMAX;
   static constexpr int RT = RV + (TRAIN ? SPT * DMAX : 0);
+  static constexpr int RWT = RT + 16;              // train (16 rows a tile): the optional row weights, in RT's upper half
   static constexpr int RC = RT + 32;
   static constexpr int RAWN = RC + 16;
   static constexpr int X = 0;
@@ -1186,7 +1208,7 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
   constexpr int NR = SPT * LO::DMAX / NT, GS = NT / SPT;
   RawRegs<NR> pf;
   auto issue = [&](int64_t tl, int step = 0) { raw_issue<MODE, LO, NT, false>(A, pf, (w << 6) + lane_v, tid, tl, step); };
-  auto commit = [&](float* R) { raw_commit<MODE, LO, NT, false>(pf, R, (w << 6) + lane_v, tid); };
+  auto commit = [&](float* R) { raw_commit<MODE, LO, NT, false>(A, pf, R, (w << 6) + lane_v, tid); };
   auto h0_rows = [&](float* H0b, const float* R, int64_t tl) {
     const int tv = (w << 6) + lane_v;
     build_h0<MODE, LO, GS, XP>(A, H0b, R, tl, tv / GS, tv % GS);
@@ -1351,7 +1373,8 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
         const int c = tv >> 4, ol = tv & 15;
         const int64_t smp = s_base + c;
         const bool live = smp < A.B;
-        const float wgt = live ? A.inv_batch : 0.f;
+        const float rw = Rc[LO::RWT + c];
+        const float wgt = ssm_seed(A, live, rw);
         float beta = 0.f, sb = 0.f;
         if (!A.u) { beta = sde_beta(A.b0, A.b1, Rc[LO::RT + c]); sb = sqrtf(beta); }
         float uo[8];
@@ -1374,7 +1397,7 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
           ABAR[(16 + c) * ACT_P + o] = adb;
           db4[ot] += ab;
         }
-        ssm_sample_loss(A, lj, ol, live, smp, Rc + LO::RC + c, loss_acc);
+        ssm_sample_loss(A, lj, ol, live, smp, Rc + LO::RC + c, rw, loss_acc);
       }
       h0_rows(H0n, Rn, ntile);                           // next tile's layer-1 operand
       lds_barrier();
@@ -1676,6 +1699,13 @@ int msgm_mlp_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msg
 int msgm_mlp_ssm_partial(const msgm_mlp_params_t* P, const float* y, const float* t, const float* v, const float* u,
                          const float* cst, int64_t B, const msgm_sde_t* sde, float inv_batch, float* loss_per,
                          void* workspace, size_t workspace_bytes, int32_t* n_slabs, msgm_stream_t stream) {
+  return msgm_mlp_ssm_partial_w(P, y, t, v, u, cst, B, sde, inv_batch, nullptr, loss_per, workspace, workspace_bytes, n_slabs, stream);
+}
+
+int msgm_mlp_ssm_partial_w(const msgm_mlp_params_t* P, const float* y, const float* t, const float* v, const float* u,
+                           const float* cst, int64_t B, const msgm_sde_t* sde, float inv_batch, const float* row_w,
+                           float* loss_per, void* workspace, size_t workspace_bytes, int32_t* n_slabs,
+                           msgm_stream_t stream) {
   MlpArgs A{};
   int rc = fill_common(A, P, B);
   if (rc) return rc;
@@ -1684,7 +1714,7 @@ int msgm_mlp_ssm_partial(const msgm_mlp_params_t* P, const float* y, const float
   if (workspace_bytes < msgm_mlp_ssm_workspace(P->d, P->premodule)) return MSGM_E_WORKSPACE;
   A.y = y; A.t = t; A.v = v; A.u = u; A.cst = cst;
   A.b0 = sde->beta_min; A.b1 = sde->beta_max; A.T = sde->T;
-  A.inv_batch = inv_batch; A.loss_per = loss_per; A.slabs = reinterpret_cast<float*>(workspace);
+  A.inv_batch = inv_batch; A.row_w = row_w; A.loss_per = loss_per; A.slabs = reinterpret_cast<float*>(workspace);
   A.n_params = msgm_mlp_num_params(P->d, P->premodule);
   const int64_t tiles = (B + 15) / 16;
   const int grid = (int)(tiles < MLP_MAX_GRID ? tiles : MLP_MAX_GRID);
@@ -1718,9 +1748,16 @@ int msgm_mlp_ssm_reduce_adam(int32_t d, int32_t premodule, const void* workspace
 int msgm_mlp_ssm_grad(const msgm_mlp_params_t* P, const float* y, const float* t, const float* v, const float* u,
                       const float* cst, int64_t B, const msgm_sde_t* sde, float inv_batch, float* grads, float* loss_per,
                       float* loss_sum, void* workspace, size_t workspace_bytes, msgm_stream_t stream) {
+  return msgm_mlp_ssm_grad_w(P, y, t, v, u, cst, B, sde, inv_batch, nullptr, grads, loss_per, loss_sum, workspace, workspace_bytes, stream);
+}
+
+int msgm_mlp_ssm_grad_w(const msgm_mlp_params_t* P, const float* y, const float* t, const float* v, const float* u,
+                        const float* cst, int64_t B, const msgm_sde_t* sde, float inv_batch, const float* row_w,
+                        float* grads, float* loss_per, float* loss_sum, void* workspace, size_t workspace_bytes,
+                        msgm_stream_t stream) {
   if (!grads) return MSGM_E_BADARG;
   int32_t n_slabs = 0;
-  int rc = msgm_mlp_ssm_partial(P, y, t, v, u, cst, B, sde, inv_batch, loss_per, workspace, workspace_bytes, &n_slabs, stream);
+  int rc = msgm_mlp_ssm_partial_w(P, y, t, v, u, cst, B, sde, inv_batch, row_w, loss_per, workspace, workspace_bytes, &n_slabs, stream);
   if (rc) return rc;
   return msgm_mlp_ssm_reduce(P->d, P->premodule, workspace, n_slabs, inv_batch, grads, loss_sum, stream);
 }

@@ -436,16 +436,18 @@ __global__ void k_rk4_combine(float* __restrict__ out, const float* __restrict__
 // out is the score net's (primal | tangent) output [2B][n]: a = out[:B], adot = J_a v = out[B:].
 //   loss_b = sum_i v_i (sqrt(beta) adot_i + 1/2 beta v_i) + 1/2 a_i^2        SDEs.py:631-646
 //   g[:B] = a * w, g[B:] = sqrt(beta) v * w   (w = 1/global batch: gradient of the mean)
+// row_w (optional, B floats): the row's seed is (inv_batch * row_w[b]); per[b] stays unweighted.
 template <int GS>
 __global__ void k_ssm_loss_diag(const float* __restrict__ out, const float* __restrict__ v, const float* __restrict__ t,
                                 float* __restrict__ per, float* __restrict__ g, int64_t B, int64_t n, float b0, float b1,
-                                float w) {
+                                float inv_batch, const float* __restrict__ row_w) {
   const RowGroup<GS> rg(B, blockDim.x);
   const int lane = rg.lane;
   for (int64_t b = rg.first; b < rg.rows_pad; b += rg.stride) {
     const bool live = b < B;
     float acc = 0.f;
     if (live) {
+      const float w = row_w ? inv_batch * row_w[b] : inv_batch;
       const float beta = sde_beta(b0, b1, t[b]);
       const float sb = sqrtf(beta);
       for (int64_t i = lane; i < n; i += GS) {
@@ -508,21 +510,25 @@ __global__ void k_ssm_terms(const float* __restrict__ y, const float* __restrict
 }
 
 // generic K12: per[b] = adot.u + cst + 1/2|a|^2 ; g[:B] = a w ; g[B:] = u w      (out = [a ; adot] stacked)
+// w = inv_batch, or (inv_batch * row_w[b]) with the optional per-row weights; per[b] stays unweighted.
 template <int GS>
 __global__ void k_ssm_loss_generic(const float* __restrict__ out, const float* __restrict__ u, const float* __restrict__ cst,
-                                   float* __restrict__ per, float* __restrict__ g, int64_t B, int64_t n, float w) {
+                                   float* __restrict__ per, float* __restrict__ g, int64_t B, int64_t n, float inv_batch,
+                                   const float* __restrict__ row_w) {
   const RowGroup<GS> rg(B, blockDim.x);
   const int lane = rg.lane;
   for (int64_t b = rg.first; b < rg.rows_pad; b += rg.stride) {
     const bool live = b < B;
     float acc = 0.f;
-    if (live)
+    if (live) {
+      const float w = row_w ? inv_batch * row_w[b] : inv_batch;
       for (int64_t i = lane; i < n; i += GS) {
         const float a = out[b * n + i], ad = out[(B + b) * n + i], ui = u[b * n + i];
         acc += ad * ui + 0.5f * a * a;
         g[b * n + i] = a * w;
         g[(B + b) * n + i] = ui * w;
       }
+    }
     acc = group_sum<GS>(acc);
     if (live && lane == 0) per[b] = acc + cst[b];
   }
@@ -777,11 +783,16 @@ int msgm_rk4_combine(float* out, const float* x, const float* k1, const float* k
 
 int msgm_ssm_loss_diag(const float* out, const float* v, const float* t, float* per, float* g, int64_t B, int64_t n,
                        const msgm_sde_t* sde, float inv_batch, msgm_stream_t stream) {
+  return msgm_ssm_loss_diag_w(out, v, t, per, g, B, n, sde, inv_batch, nullptr, stream);
+}
+
+int msgm_ssm_loss_diag_w(const float* out, const float* v, const float* t, float* per, float* g, int64_t B, int64_t n,
+                         const msgm_sde_t* sde, float inv_batch, const float* row_w, msgm_stream_t stream) {
   if (!out || !v || !t || !per || !g || !sde || B <= 0 || n <= 0) return MSGM_E_BADARG;
   if (sde->kind != MSGM_SDE_SGM) return MSGM_E_UNSUPPORTED;
   return launch_rows(B, n, [&](auto GS, int grid, int block) {
     hipLaunchKernelGGL((k_ssm_loss_diag<decltype(GS)::value>), dim3(grid), dim3(block), 0, S(stream), out, v, t, per, g, B, n,
-                       sde->beta_min, sde->beta_max, inv_batch);
+                       sde->beta_min, sde->beta_max, inv_batch, row_w);
   });
 }
 
@@ -798,9 +809,14 @@ int msgm_ssm_terms(const float* y, const float* v, const float* t, float* u, flo
 
 int msgm_ssm_loss(const float* out, const float* u, const float* cst, float* per, float* g, int64_t B, int64_t n,
                   float inv_batch, msgm_stream_t stream) {
+  return msgm_ssm_loss_w(out, u, cst, per, g, B, n, inv_batch, nullptr, stream);
+}
+
+int msgm_ssm_loss_w(const float* out, const float* u, const float* cst, float* per, float* g, int64_t B, int64_t n,
+                    float inv_batch, const float* row_w, msgm_stream_t stream) {
   if (!out || !u || !cst || !per || !g || B <= 0 || n <= 0) return MSGM_E_BADARG;
   return launch_rows(B, n, [&](auto GS, int grid, int block) {
-    hipLaunchKernelGGL((k_ssm_loss_generic<decltype(GS)::value>), dim3(grid), dim3(block), 0, S(stream), out, u, cst, per, g, B, n, inv_batch);
+    hipLaunchKernelGGL((k_ssm_loss_generic<decltype(GS)::value>), dim3(grid), dim3(block), 0, S(stream), out, u, cst, per, g, B, n, inv_batch, row_w);
   });
 }
 

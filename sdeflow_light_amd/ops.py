@@ -26,6 +26,20 @@ def _same_shape(a: Optional[torch.Tensor], shape, name: str):
         raise MsgmError(f"{name} has shape {tuple(a.shape)}, expected {tuple(shape)}")
 
 
+def _row_weight(w: Optional[torch.Tensor], B: int):
+    """Pointer of the optional per-row loss weights: a contiguous float32 device tensor of B entries (any sign), checked
+    before any launch; None is the unweighted call."""
+    if w is None:
+        return None
+    if not torch.is_tensor(w) or not w.is_cuda:
+        raise MsgmError("row_weight must be a device tensor (got a CPU tensor or a non-tensor); there is no CPU fallback")
+    if w.dtype != torch.float32:
+        raise MsgmError(f"row_weight must be float32 (got {w.dtype})")
+    if w.dim() != 1 or w.numel() != B:
+        raise MsgmError(f"row_weight has shape {tuple(w.shape)}, expected ({B},): one weight per row")
+    return ptr(w)
+
+
 def fill_uniform(out: torch.Tensor, rng: PhiloxState, stream_id: int = L.RNG_STREAM_USER) -> torch.Tensor:
     check(lib().msgm_fill_uniform(ptr(f32(out)), out.numel(), rng.ptr(), stream_id, stream()), "msgm_fill_uniform")
     return out
@@ -143,15 +157,18 @@ def sde_stage(out: torch.Tensor, base: Optional[torch.Tensor], c_out: float, x: 
     return out
 
 
-def ssm_loss_diag(out: torch.Tensor, v: torch.Tensor, t: torch.Tensor, sde: L.SdeT, inv_batch: float):
-    """(per[B], g[2B][n]) from the stacked (primal | tangent) net output — K12."""
+def ssm_loss_diag(out: torch.Tensor, v: torch.Tensor, t: torch.Tensor, sde: L.SdeT, inv_batch: float, *,
+                  row_weight: Optional[torch.Tensor] = None):
+    """(per[B], g[2B][n]) from the stacked (primal | tangent) net output — K12.  row_weight (B,): row b is seeded with
+    inv_batch * row_weight[b]; per stays unweighted."""
     B, n = v.shape
     if out.numel() != 2 * B * n or t.numel() != B:
         raise MsgmError("ssm_loss_diag: out must be [2B][n], t [B]")
+    pw = _row_weight(row_weight, B)
     per = torch.empty(B, dtype=torch.float32, device=v.device)
     g = torch.empty(2 * B * n, dtype=torch.float32, device=v.device)
-    check(lib().msgm_ssm_loss_diag(ptr(f32(out)), ptr(f32(v)), ptr(f32(t)), ptr(per), ptr(g), B, n, sde, float(inv_batch),
-                                   stream()), "msgm_ssm_loss_diag")
+    check(lib().msgm_ssm_loss_diag_w(ptr(f32(out)), ptr(f32(v)), ptr(f32(t)), ptr(per), ptr(g), B, n, sde, float(inv_batch),
+                                     pw, stream()), "msgm_ssm_loss_diag_w")
     return per, g
 
 
@@ -336,21 +353,26 @@ def ssm_terms(y: torch.Tensor, v: torch.Tensor, t: torch.Tensor, sde: L.SdeT):
     return u, cst
 
 
-def ssm_loss(out: torch.Tensor, u: torch.Tensor, cst: torch.Tensor, inv_batch: float):
+def ssm_loss(out: torch.Tensor, u: torch.Tensor, cst: torch.Tensor, inv_batch: float, *,
+             row_weight: Optional[torch.Tensor] = None):
+    """(per[B], g[2B][n]) in the general form; row_weight (B,): row b is seeded with inv_batch * row_weight[b]."""
     B, n = u.shape
     if out.numel() != 2 * B * n or cst.numel() != B:
         raise MsgmError("ssm_loss: out must be [2B][n]")
+    pw = _row_weight(row_weight, B)
     per = torch.empty(B, dtype=torch.float32, device=u.device)
     g = torch.empty(2 * B * n, dtype=torch.float32, device=u.device)
-    check(lib().msgm_ssm_loss(ptr(f32(out)), ptr(f32(u)), ptr(f32(cst)), ptr(per), ptr(g), B, n, float(inv_batch), stream()),
-          "msgm_ssm_loss")
+    check(lib().msgm_ssm_loss_w(ptr(f32(out)), ptr(f32(u)), ptr(f32(cst)), ptr(per), ptr(g), B, n, float(inv_batch), pw, stream()),
+          "msgm_ssm_loss_w")
     return per, g
 
 
 def mlp_ssm_grad(P: L.MlpParamsT, y: torch.Tensor, t: torch.Tensor, v: torch.Tensor, sde: L.SdeT, inv_batch: float,
                  grads: torch.Tensor, workspace: torch.Tensor, loss_per: Optional[torch.Tensor] = None,
                  loss_sum: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
-                 cst: Optional[torch.Tensor] = None):
+                 cst: Optional[torch.Tensor] = None, *, row_weight: Optional[torch.Tensor] = None):
+    """grads = inv_batch sum_b w_b dL_b/dtheta, loss_per[b] = L_b, loss_sum = inv_batch sum_b w_b L_b, with
+    w = row_weight (B,), or all ones when it is None (the unweighted entry, to the bit)."""
     B, d = y.shape
     if d != P.d:
         raise MsgmError(f"input has d={d}, the MLP was built for d={P.d}")
@@ -362,9 +384,10 @@ def mlp_ssm_grad(P: L.MlpParamsT, y: torch.Tensor, t: torch.Tensor, v: torch.Ten
         raise MsgmError("grads bucket has the wrong size")
     _same_shape(u, (B, d), "u")
     _same_shape(cst, (B,), "cst")
-    check(lib().msgm_mlp_ssm_grad(P, ptr(f32(y)), ptr(f32(t)), ptr(f32(v)), ptr(u), ptr(cst), B, sde, float(inv_batch), ptr(f32(grads)),
-                                  ptr(loss_per), ptr(loss_sum), ptr(workspace), workspace.numel() * 4, stream()),
-          "msgm_mlp_ssm_grad")
+    pw = _row_weight(row_weight, B)
+    check(lib().msgm_mlp_ssm_grad_w(P, ptr(f32(y)), ptr(f32(t)), ptr(f32(v)), ptr(u), ptr(cst), B, sde, float(inv_batch), pw,
+                                    ptr(f32(grads)), ptr(loss_per), ptr(loss_sum), ptr(workspace), workspace.numel() * 4, stream()),
+          "msgm_mlp_ssm_grad_w")
 
 
 # ---------------------------------------------------------------- convolutions (implicit GEMM)

@@ -104,6 +104,25 @@ def _msgm_draws(tr):
     return y, tr.t, v, uu, cst
 
 
+def _init_row_weights(tr, row_weights: bool):
+    """``row_weights=True``: a resident (B_local,) buffer of per-row loss weights, ones until ``set_data(x, weight=w)``
+    copies others in.  Its POINTER goes into the captured step, so later replays read the new values without a
+    re-capture.  Weights are per local row; ``inv_batch`` stays 1/(B_local * world), the reported loss is
+    inv_batch * sum_b w_b L_b.  A ragged last batch: pad it, weight the valid rows B/n_valid and the padding 0 (the
+    padding rows still flow through the arithmetic: keep them finite)."""
+    tr.w = torch.ones(tr.B, dtype=torch.float32, device=tr.dev) if row_weights else None
+
+
+def _set_data(tr, x, weight):
+    if weight is not None:
+        if tr.w is None:
+            raise MsgmError("set_data(weight=...) needs a trainer built with row_weights=True")
+        ops._row_weight(weight, tr.B)
+    tr.x.copy_(x)
+    if weight is not None:
+        tr.w.copy_(weight)
+
+
 def _adopt_stream(tr):
     """The multiplicative SDE's forward perturbation draws through ``base.philox()``: hand it the trainer's stream."""
     tr.msgm = tr.base.kind != L.SDE_SGM
@@ -119,7 +138,7 @@ class MLPScoreTrainer(_TrainerState):
     fresh (t, eps | forward-SDE noise, v) on the device."""
 
     def __init__(self, gen_sde, batch_local: int, lr: float = 1e-3, world: int = 1, use_graph: bool = True,
-                 seed: int = 0, row_base: int = 0):
+                 seed: int = 0, row_base: int = 0, row_weights: bool = False):
         from .NN import MLP
         net, base = gen_sde.a, gen_sde.base_sde
         if not isinstance(net, MLP):
@@ -148,6 +167,7 @@ class MLPScoreTrainer(_TrainerState):
         self.inv_batch = 1.0 / (batch_local * world)        # mean over the GLOBAL batch
         self.graph = None
         self.use_graph = use_graph and not parallel.multi(world)
+        _init_row_weights(self, row_weights)
         _adopt_stream(self)
 
     def _body(self):
@@ -167,9 +187,9 @@ class MLPScoreTrainer(_TrainerState):
                                         self.d, self.st, self.rng.ptr(), self.step_dev.data_ptr(), s), "msgm_ssm_prep")
             y, t, vp, pu, pc, adv = self.y, self.t, self.vp, None, None, self.rng.ptr()
         nsl = C.c_int32(0)
-        ops.check(lib.msgm_mlp_ssm_partial(self.P, y.data_ptr(), t.data_ptr(), vp.data_ptr(), pu, pc, self.B,
-                                           self.st, self.inv_batch, None, self.ws.data_ptr(), self.ws.numel() * 4,
-                                           C.byref(nsl), s), "msgm_mlp_ssm_partial")
+        ops.check(lib.msgm_mlp_ssm_partial_w(self.P, y.data_ptr(), t.data_ptr(), vp.data_ptr(), pu, pc, self.B,
+                                             self.st, self.inv_batch, ops.ptr(self.w), None, self.ws.data_ptr(),
+                                             self.ws.numel() * 4, C.byref(nsl), s), "msgm_mlp_ssm_partial_w")
         pre = int(self.net.pre is not None)
         if not parallel.multi(self.world):
             ops.check(lib.msgm_mlp_ssm_reduce_adam(self.d, pre, self.ws.data_ptr(), nsl.value, self.inv_batch,
@@ -197,8 +217,8 @@ class MLPScoreTrainer(_TrainerState):
         with torch.cuda.graph(self.graph):
             self._body()
 
-    def set_data(self, x: torch.Tensor):
-        self.x.copy_(x)
+    def set_data(self, x: torch.Tensor, weight: Optional[torch.Tensor] = None):
+        _set_data(self, x, weight)
 
     def step(self):
         if self.use_graph:
@@ -223,7 +243,7 @@ class UNetScoreTrainer(_TrainerState):
     with one rank the Adam update and the Philox advance are inside the graph too."""
 
     def __init__(self, gen_sde, batch_local: int, dim: int, lr: float = 1e-4, world: int = 1, seed: int = 0,
-                 use_graph: Optional[bool] = None, row_base: int = 0):
+                 use_graph: Optional[bool] = None, row_base: int = 0, row_weights: bool = False):
         net, base = gen_sde.a, gen_sde.base_sde
         if not hasattr(net, "ssm_grad"):
             raise MsgmError("UNetScoreTrainer needs a HIP U-Net score net (SGMsde or MSGMsde)")
@@ -247,10 +267,11 @@ class UNetScoreTrainer(_TrainerState):
         # all-reduce and Adam follow eagerly on the same stream
         self.use_graph = True if use_graph is None else bool(use_graph)
         self.graph = None
+        _init_row_weights(self, row_weights)
         _adopt_stream(self)
 
-    def set_data(self, x):
-        self.x.copy_(x)
+    def set_data(self, x, weight: Optional[torch.Tensor] = None):
+        _set_data(self, x, weight)
 
     def _fwd_bwd(self):
         """Everything before the collective; leaves [grads | loss] (already x 1/global_batch) in ``gbuf``."""
@@ -263,11 +284,14 @@ class UNetScoreTrainer(_TrainerState):
                                         self.d, self.st, self.rng.ptr(), self.step_dev.data_ptr(), s), "msgm_ssm_prep")
             y, t, vp = self.y, self.t, self.vp
             u, cst = ops.ssm_terms(y, vp, t, self.st)
-        per = self.net.ssm_grad(y, t, vp, u, cst, self.inv_batch, rng=self.rng)     # 2-D U-Net dropout masks: the trainer's stream
+        per = self.net.ssm_grad(y, t, vp, u, cst, self.inv_batch, rng=self.rng,     # 2-D U-Net dropout masks: the trainer's stream
+                                row_weight=self.w)
         flat, gflat = self.net.flat_parameters()
         if flat.data_ptr() != self.flat.data_ptr() or gflat.data_ptr() != self.gbuf.data_ptr():
             raise MsgmError("the flat parameter bucket moved; rebuild the trainer")
         # kernel nodes only inside the captured step (no D2D memcpy / memset nodes: see msgm_zero_async in csrc/common.h)
+        if self.w is not None:
+            per = per * self.w                   # the reported loss is inv_batch * sum_b w_b L_b (an elementwise kernel)
         torch.sum(per.view(1, -1), dim=1, out=self.loss)
         self.loss.mul_(self.inv_batch)
 
