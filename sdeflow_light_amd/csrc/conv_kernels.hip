@@ -1578,15 +1578,27 @@ __global__ void __launch_bounds__(256, 1) k_conv_wino_p32(ConvArgs A, int tiles_
 //     21 pieces of 1 KB, lane-linear in LDS.  Lane l of piece m fills 16-B slot s = 64 m + l with channel quad
 //     (s & 3) ^ ((P >> 1) & 3) of halo pixel P = s >> 2 — the swizzle is chosen by the per-lane SOURCE address, so the patch
 //     reads cost what the padded CT_P image did (384 LDS cycles per wave and group, counted from the ds_read_b128 lane groups);
-//     the zero border, the folded 2x upsample (iy >> 1) and the second source are per-lane source addresses too;
+//     the folded 2x upsample (iy >> 1) and the second source are per-lane source offsets too, the zero border is an offset
+//     the buffer load's range check refuses; these offsets are worked out per ITEM (and at the switch of source), not per
+//     group: a group's fills, halo and weights, are buffer loads whose group-dependent part is a scalar offset (hsetup /
+//     hfill / wfill below) and cost no vector instruction;
 //   * a workgroup walks a list of (tile, output-channel block) items — the XCD-aware order of k_conv_wino, blockIdx.x & 7
 //     picks the XCD, so the n_cob blocks of a tile stay on one XCD — and the stream of channel groups runs on across item
 //     boundaries: group k + 1's halo (the next item's group 0 at the end of an item) is requested while group k computes;
-//   * per half-group (8 positions, 64 MFMAs per wave) one raw barrier.  Issue order per group: weights of half 1, then the
-//     next group's halo; half 1 waits vmcnt(5) (every wave issues 5 or 6 halo pieces, all younger), half 0 vmcnt(0);
+//   * per half-group (8 positions, 64 MFMAs per wave) one raw barrier.  Order behind the barrier of half 0: the patch reads
+//     and the first weight fragments are requested from LDS, then the fills are issued (weights of half 1, then the next
+//     group's halo), then the patch is completed and transformed — rows 0 and 1 of V in front of the MFMAs of half 0, rows
+//     2 and 3 among them.  Half 1 waits vmcnt(5) (every wave issues 5 or 6 halo pieces, all younger), half 0 vmcnt(0);
+//   * the (tile, output-channel block) of an item is decoded where the stream enters it and in its epilogue, behind branches
+//     taken once per item: no division in a group's path (profiles/wino_diet/asm_counts.txt);
 //   * LDS: 2 x 16 KB weight halves + 2 x 21 KB halo stages = 74 KB: two workgroups per CU.
 // The arithmetic is that of k_conv_wino: the same transforms, channel groups in ascending order and r = 0..3 per position,
 // the same epilogue (wino_epilogue) — equal outputs, bit for bit (tests/test_wino_pipe_gpu.py).
+// one row of wino_input_transform's second loop (x B), in place: k_conv_wino_pipe transforms its patch in two parts
+__device__ __forceinline__ void wino_row_transform(f32x4 (&x)[4]) {
+  const f32x4 c0_ = x[0] - x[2], c1_ = x[1] + x[2], c2_ = x[2] - x[1], c3_ = x[1] - x[3];
+  x[0] = c0_; x[1] = c1_; x[2] = c2_; x[3] = c3_;
+}
 constexpr int WP_HPIECES = 21;                                // ceil(18 * 18 pixels * 4 quads / 64 lanes)
 constexpr int WP_HSTAGE = WP_HPIECES * 64 * 4;                // floats per halo stage
 constexpr int WP_LDS_BYTES = (2 * 4096 + 2 * WP_HSTAGE) * (int)sizeof(float);
@@ -1610,41 +1622,59 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
   const int tt = 16 * w + il, ty = tt >> 3, tx = tt & 7;
   const int P0 = 2 * ty * HW + 2 * tx, h0 = (P0 >> 1) & 3;
 
-  // half `half` of channel group grp_'s weights for output-channel block cob_: as k_conv_wino's WL form
+  // half `half` of channel group grp_'s weights for output-channel block cob_: the pieces and the sources of wino_wfill
+  // (k_conv_wino's WL form), as buffer loads to LDS.  A lane's part of the address, U[.][il][4 q], never changes; the
+  // output-channel block, the group, the position and the co tile of a piece are wave-uniform and travel in the scalar offset:
+  // a fill costs no vector instruction (byte offsets: the packed image is below 2^31 bytes, msgm_conv_forward_wino)
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)A.Wp, 0, 16 * (int)pos_stride * 4, 0x00020000);
+  const int wlane = (il * A.Ktot + 4 * q) * 4;
   auto wfill = [&](int cob_, int grp_, int half) __attribute__((always_inline)) {
-    wino_wfill(A.Wp + (size_t)(cob_ * (NCO * 16) + il) * A.Ktot + 16 * grp_ + 4 * q + (size_t)(8 * half) * pos_stride,
-               wbuf + half * 4096, w, pos_stride, a_co_stride);
-  };
-  // channel group grp_'s halo of tile tile_ into stage b: wave w copies pieces w, w + 4, ... (6 for wave 0, 5 for the others)
-  // (branch-free: the source of each lane is a select between its pixel and the zero row)
-  // The decode of a piece's slot does not change during the kernel: halo pixel (hy, hx) and channel quad c of lane l in piece
-  // m = w + 4 j, packed in ONE register per piece (hy << 16 | hx << 2 | c; a slot past the 18 x 18 pixels gets a row outside
-  // every image) and unpacked per group behind an asm the optimiser cannot hoist — kept apart, the decoded values of the six
-  // pieces occupy registers the MFMA loop has no room for.
-  const int Hu = g.Hi << up, Wu = g.Wi << up;
-  int hpk[(WP_HPIECES + 3) / 4];
+    const int so = ((cob_ * (NCO * 16)) * A.Ktot + 16 * grp_ + (8 * half + 2 * w) * (int)pos_stride) * 4;
 #pragma unroll
-  for (int j = 0; j < (WP_HPIECES + 3) / 4; ++j) {
-    const int sl = 64 * (w + 4 * j) + lane, P = sl >> 2, c = (sl & 3) ^ ((P >> 1) & 3), hy = P / HW, hx = P - hy * HW;
-    hpk[j] = P < HW * HW ? (hy << 16) | (hx << 2) | c : 0x7fff << 16;
-  }
-  auto hfill = [&](int tile_, int grp_, int b) __attribute__((always_inline)) {
+    for (int j = 0; j < 4; ++j) {
+      const int pw = 4 * w + j;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)(wbuf + half * 4096 + pw * 256), 16, wlane,
+                                               so + ((j >> 1) * (int)pos_stride + (j & 1) * (int)a_co_stride) * 4, 0, 0);
+    }
+  };
+  // The halo of one channel group: wave w copies pieces w, w + 4, ... (6 for wave 0, 5 for the others) with buffer loads to
+  // LDS.  What a lane fetches for piece m = w + 4 j (halo pixel (hy, hx) and channel quad c of slot 64 m + lane) is a BYTE
+  // OFFSET INSIDE THE SAMPLE, hoff[j] = (((iy >> up) Wi + (ix >> up)) C + 4 c) * 4: it depends on the item (y0, x0) and on the
+  // source's channel count C, not on the channel group, so hsetup works it out when the stream of groups enters an item or
+  // changes source — once or twice per item — and a group's fill is five or six loads with no vector arithmetic: the
+  // sample's base travels in the (wave-uniform) buffer descriptor and the group's channel offset in the scalar offset.
+  // A slot outside the image (the zero border; slots past the 18 x 18 pixels) has the offset 2^31, past the descriptor's
+  // num_records = the sample's bytes (< 2^31, msgm_conv_forward_wino), and the range check of the load delivers zeros.
+  const int Hu = g.Hi << up, Wu = g.Wi << up;
+  int hoff[(WP_HPIECES + 3) / 4];
+  const float* hbase;                                       // sample n of the source the next fill reads
+  int hnum, hsub;                                           // that sample's bytes; 4 C0 from the second source on, else 0
+  auto hsetup = [&](int tile_, int s1) __attribute__((always_inline)) {
     const int n = tile_ / tpi, r = tile_ - n * tpi, ty_i = r / tiles_x, y0 = ty_i * 16, x0 = (r - ty_i * tiles_x) * 16;
-    const bool s1 = 16 * grp_ >= A.C[0];                    // channel groups of the second source follow the first's (C0 % 16 == 0)
     const int C = s1 ? A.C[1] : A.C[0];
-    const float* base = (s1 ? A.src[1] : A.src[0]) + (size_t)n * g.Hi * g.Wi * C + (16 * grp_ - (s1 ? A.C[0] : 0));
+    hbase = (s1 ? A.src[1] : A.src[0]) + (size_t)n * g.Hi * g.Wi * C;
+    hnum = g.Hi * g.Wi * C * 4;
+    hsub = s1 ? 4 * A.C[0] : 0;
+    int l = lane;
+    asm volatile("" : "+v"(l));                             // (the slot decode stays here: hoisted, it occupies registers of the MFMA loop)
+#pragma unroll
+    for (int j = 0; j < (WP_HPIECES + 3) / 4; ++j) {
+      const int sl = 64 * (w + 4 * j) + l, P = sl >> 2, c = (sl & 3) ^ ((P >> 1) & 3), hy = P / HW, hx = P - hy * HW;
+      const int iy = y0 + hy - 1, ix = x0 + hx - 1;
+      const bool in = P < HW * HW && (unsigned)iy < (unsigned)Hu && (unsigned)ix < (unsigned)Wu;
+      hoff[j] = in ? (((iy >> up) * g.Wi + (ix >> up)) * C + 4 * c) * 4 : (int)0x80000000;
+    }
+  };
+  // channel group grp_ (of the item and source hsetup last saw) into stage b
+  auto hfill = [&](int grp_, int b) __attribute__((always_inline)) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)hbase, 0, hnum, 0x00020000);
+    const int soff = 64 * grp_ - hsub;
 #pragma unroll
     for (int j = 0; j < (WP_HPIECES + 3) / 4; ++j) {
       const int m = w + 4 * j;
-      if (m < WP_HPIECES) {
-        int pk = hpk[j];
-        asm volatile("" : "+v"(pk));
-        const int c = pk & 3, iy = y0 + (pk >> 16) - 1, ix = x0 + ((pk >> 2) & 31) - 1;
-        const bool in = (unsigned)iy < (unsigned)Hu && (unsigned)ix < (unsigned)Wu;
-        const float* p = in ? base + (((iy >> up) * g.Wi + (ix >> up)) * C + 4 * c) : g_wino_zero;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p,
-                                         (__attribute__((address_space(3))) void*)(hbuf + b * WP_HSTAGE + m * 256), 16, 0, 0);
-      }
+      if (j < WP_HPIECES / 4 || m < WP_HPIECES)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(hbuf + b * WP_HSTAGE + m * 256), 16,
+                                                 hoff[j], soff, 0, 0);
     }
   };
 
@@ -1655,30 +1685,33 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
     for (int c = 0; c < NCO; ++c) acc[p][c] = f32x4{0, 0, 0, 0};
   int grp = 0, hb = 0;
   wfill(cob, 0, 0);
-  hfill(tile, 0, 0);
+  hsetup(tile, 0);
+  hfill(0, 0);
   for (;;) {
-    // the group that follows this one: the next channel group of this item, or group 0 of the workgroup's next item
+    // the group that follows this one: the next channel group of this item, or group 0 of the workgroup's next item (the
+    // divisions of an item's decode run behind a branch of their own, once per item: the asm keeps them there)
     int nloc = loc, ntile = tile, ncob = cob, ngrp_ = grp + 1;
-    if (ngrp_ == ngrp) {
+    const bool last = ngrp_ == ngrp;
+    if (last) {
       ngrp_ = 0; nloc = loc + loc_stride;
-      ntile = (nloc / n_cob) * 8 + xcd; ncob = nloc % n_cob;
+      asm volatile("" : "+s"(nloc));
+      const int nq = nloc / n_cob;
+      ntile = nq * 8 + xcd; ncob = nloc - nq * n_cob;
     }
     const bool more = ntile < n_tiles;
-    f32x4 d[4][4];
+    f32x4 d[4][4], t1[4];
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       // this half-group's weights (and at half 0 this group's halo) have landed — every wave waits for its own pieces, then
       // all meet; the reads of the buffers refilled below are behind the same barrier
       if (half == 1 && more) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)\n\ts_barrier" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      const float* wb = wbuf + half * 4096 + lane * 4;
+      f32x4 a0, a1;
       if (half == 0) {
-        wfill(cob, grp, 1);
-        if (more) hfill(ntile, ngrp_, hb ^ 1);
-      } else if (more) {
-        wfill(ncob, ngrp_, 0);
-      }
-      if (half == 0) {
-        // ---- the lane's 4x4 patch (4 channels) and its transform V = B^T d B, in place (as k_conv_wino)
+        // ---- the lane's 4x4 patch (4 channels), columns 0 and 1, and the first weight fragments are requested from LDS
+        // BEFORE the fills are issued: their latency passes under the fills' scalar work (the fills' targets, the other
+        // halo stage and the other weight half, are free behind the same barrier either way)
         const float* hs = hbuf + hb * WP_HSTAGE;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1686,6 +1719,16 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
           d[i][0] = *reinterpret_cast<const f32x4*>(rp);
           d[i][1] = *reinterpret_cast<const f32x4*>(rp + 16);
         }
+        a0 = *reinterpret_cast<const f32x4*>(wb); a1 = *reinterpret_cast<const f32x4*>(wb + 256);
+        __builtin_amdgcn_sched_barrier(0);
+        wfill(cob, grp, 1);
+        if (more) {
+          if (last) hsetup(ntile, 0);
+          else if (16 * ngrp_ == A.C[0]) hsetup(tile, 1);
+          hfill(ngrp_, hb ^ 1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- the rest of the patch and its transform V = B^T d B, in place (as k_conv_wino)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1700,13 +1743,23 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
             d[i][3] = *reinterpret_cast<const f32x4*>(rp + 16);
           }
         }
-        wino_input_transform(d);
+        // wino_input_transform's operations in two parts.  Positions 0 .. 7 need rows 0 and 1 of the column transform only
+        // (d0 - d2 in place, d1 + d2 in t1) and their row transforms; rows 2 and 3 (positions 8 .. 15) follow among the
+        // MFMAs of half 0, below.  The same subtractions and additions on the same values: the same V, bit for bit.
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          t1[j] = d[1][j] + d[2][j];
+          d[0][j] = d[0][j] - d[2][j];
+        }
+        wino_row_transform(d[0]);
+        wino_row_transform(t1);
+      } else {
+        a0 = *reinterpret_cast<const f32x4*>(wb); a1 = *reinterpret_cast<const f32x4*>(wb + 256);
+        if (more) wfill(ncob, ngrp_, 0);
       }
       // (wino_mfma_lds<8>'s loop, kept written out: through the function this kernel measured up to 0.5 % slower at the 1024-row
       // shapes, outside the parent's own spread on two of six; the rows of build "pipe_shared_mfma_loop" in
       // profiles/conv_shared/bench_conv_shared.json)
-      const float* wb = wbuf + half * 4096 + lane * 4;
-      f32x4 a0 = *reinterpret_cast<const f32x4*>(wb), a1 = *reinterpret_cast<const f32x4*>(wb + 256);
 #pragma unroll
       for (int pl = 0; pl < 8; ++pl) {
         const f32x4 x0_ = a0, x1_ = a1;
@@ -1715,11 +1768,25 @@ __global__ void __launch_bounds__(256, 2) k_conv_wino_pipe(ConvArgs A, int tiles
           a1 = *reinterpret_cast<const f32x4*>(wb + (2 * pl + 3) * 256);
         }
         const int pos = 8 * half + pl;
-        const f32x4 b = d[pos >> 2][pos & 3];
+        const f32x4 b = half ? d[pos >> 2][pos & 3] : pl < 4 ? d[0][pl] : t1[pl - 4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           acc[pos][0] = mfma16(x0_[r], b[r], acc[pos][0]);
           acc[pos][1] = mfma16(x1_[r], b[r], acc[pos][1]);
+        }
+        if (half == 0) {
+          // rows 2 and 3 of V: one column per position 0 .. 3 (d1 - d3, then d2 - d1: d1 is read last), a row transform
+          // with positions 4 and 5; the fence below keeps each part beside its position's eight MFMAs
+          // (the empty asm makes the results exist HERE: left alone, hipcc sinks these operations to their first use, behind
+          // the barrier of half 1, where the parent's second half of the transform already stood)
+          if (pl < 4) {
+            d[3][pl] = d[1][pl] - d[3][pl];
+            d[2][pl] = d[2][pl] - d[1][pl];
+            asm volatile("" : "+v"(d[3][pl]), "+v"(d[2][pl]));
+          } else if (pl < 6) {
+            wino_row_transform(d[pl - 2]);
+            asm volatile("" : "+v"(d[pl - 2][0]), "+v"(d[pl - 2][1]), "+v"(d[pl - 2][2]), "+v"(d[pl - 2][3]));
+          }
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -3033,6 +3100,9 @@ int msgm_conv_forward_wino(const msgm_conv_geom_t* geom, const float* src0, int3
   if (!A.in_scale) {
     // no folded input transform (every training forward and dgrad): the pipelined stream of channel groups, two
     // workgroups per CU, each walking (tile, output-channel block) items of one XCD
+    // (its fills address a sample of a source and the packed weights by 32-bit byte offsets)
+    const int64_t lim = (int64_t)1 << 31;
+    if ((int64_t)geom->Hi * geom->Wi * std::max(C0, A.C[1]) * 4 >= lim || (int64_t)16 * CoutP * Ktot * 4 >= lim) return MSGM_E_UNSUPPORTED;
     conv_raise_lds_limit<&k_conv_wino_pipe, WP_LDS_BYTES>();
     const int items_per_xcd = gy * ((n_tiles + 7) / 8);
     const int wg_per_xcd = std::min(items_per_xcd, std::max(1, 2 * conv_n_cu() / 8));
