@@ -240,6 +240,49 @@ int msgm_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
                    double lr, double beta1, double beta2, double eps, float gscale,
                    int64_t step, const int64_t* step_dev, msgm_stream_t stream);
 
+/* ---- optimizer stage: device hyper-parameters, global-norm clipping, EMA --- */
+/* Six float64 values ON THE DEVICE, read by msgm_adam_step_ex at every launch:
+ * a replayed graph sees whatever the host last wrote (a learning-rate
+ * schedule needs no re-capture).  Doubles for the reason given above: the
+ * bias corrections are formed in double, then rounded. */
+typedef struct { double lr, beta1, beta2, eps, max_grad_norm, ema_rate; } msgm_opt_t;
+
+/* Number of slices msgm_grad_sqnorm cuts n elements into (host query): a
+ * function of n only — 8192 elements per slice up to 1024 slices, beyond
+ * that 1024 slices of ceil(n / 1024) rounded up to a multiple of 1024. */
+int32_t msgm_grad_sqnorm_partials(int64_t n);
+
+/* Deterministic squared norm for torch.nn.utils.clip_grad_norm_ (norm_type 2):
+ * partials[s] = sum over slice s of (g[e] * gscale)^2, one workgroup per slice,
+ * no atomics, float64 accumulation in a fixed order (csrc/optim_kernels.hip).
+ * partials: msgm_grad_sqnorm_partials(n) doubles on the device; the count is
+ * also written to *n_partials_out (HOST, may be NULL). */
+int msgm_grad_sqnorm(const float* g, int64_t n, float gscale, double* partials,
+                     int32_t* n_partials_out, msgm_stream_t stream);
+
+/* msgm_adam_step (torch.optim.Adam, MSGM_higherDim.py:792) with the
+ * hyper-parameters read from *opt_dev and the step count from *step_dev, plus
+ *  - partials != NULL: clip_grad_norm_ — every workgroup sums the n_partials
+ *    doubles in one fixed order (they may be the concatenation of several
+ *    msgm_grad_sqnorm outputs: one global norm over several buffers),
+ *    norm = sqrt(sum), coef = (float)min(1, max_grad_norm / (norm + 1e-6)),
+ *    g' = (g * gscale) * coef; (float)norm goes to *grad_norm_out when non-NULL.
+ *    A non-finite norm propagates as with error_if_nonfinite=False.
+ *  - ema != NULL: update_ema (model/nn_utils.py:117-127) on the new parameter,
+ *    ema = ema * (float)rate + p_new * (float)(1 - rate).
+ * Which work is done is fixed by the pointers (so by a capture), how large the
+ * effect is by the device values.  coef == 1 and ema == NULL: bitwise
+ * msgm_adam_step with the same lr. */
+int msgm_adam_step_ex(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                      const msgm_opt_t* opt_dev, float gscale, const int64_t* step_dev,
+                      const double* partials, int32_t n_partials, float* grad_norm_out,
+                      msgm_stream_t stream);
+
+/* a <-> b in place (n floats each, not overlapping): the parameters and their
+ * average change places for sampling from the EMA (the copy_ of
+ * model/nn_utils.py:117-127's users, without a third buffer). */
+int msgm_swap(float* a, float* b, int64_t n, msgm_stream_t stream);
+
 /* *ctr += 1 (one thread) — device-side step counter for graph replays. */
 int msgm_counter_inc(int64_t* ctr, msgm_stream_t stream);
 

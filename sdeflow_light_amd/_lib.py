@@ -196,6 +196,11 @@ SIGNATURES = {
                                       _P]),
     "msgm_ssm_loss_diag_w": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, C.POINTER(SdeT), _F, _P, _P]),
     "msgm_ssm_loss_w": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _F, _P, _P]),
+    # optimizer stage: msgm_opt_t is six float64 on the device, passed as a pointer
+    "msgm_grad_sqnorm_partials": (_I32, [_I64]),
+    "msgm_grad_sqnorm": (C.c_int, [_P, _I64, _F, _P, C.POINTER(C.c_int32), _P]),
+    "msgm_adam_step_ex": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _F, _P, _P, _I32, _P, _P]),
+    "msgm_swap": (C.c_int, [_P, _P, _I64, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

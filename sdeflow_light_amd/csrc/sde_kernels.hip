@@ -7,15 +7,11 @@
 // phases"); the build keeps -ffp-contract=off, so two kernels that call the same function give the same bits.
 #include "common.h"
 #include "sde_stage.h"
+#include "optim_elem.h"
 #include <type_traits>
 
 // ============================================================ shared pieces
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-// every pointer 16-byte aligned (a null pointer counts as aligned: optional operands)
-template <typename... P>
-__host__ __device__ __forceinline__ bool aligned16(P... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }
-
+// ld4 / st4 / aligned16 (16-byte access to flat buffers): optim_elem.h
 // Sum over the GS lanes that share a row.  GS <= 64: a lane group inside a wave (xor tree).  GS = 256: the whole workgroup
 // owns the row (long rows: n >= 2048 — 12288-element images have too few rows per launch to fill the chip with 64-lane
 // groups: 32 rows were 8 workgroups and 67-82 us per launch); wave sums meet through LDS in a fixed order.  The group size
@@ -567,27 +563,13 @@ __global__ void k_keep_rows(float* __restrict__ kept, const float* __restrict__ 
 }
 
 // ============================================================ K13 Adam
-// torch.optim.Adam (defaults, no weight decay / amsgrad): MSGM_higherDim.py:792.
-// Mirrors torch's single-tensor update: m.lerp_(g, 1-b1); v = v*b2 + (1-b2) g g;
-// denom = sqrt(v)/sqrt(bc2) + eps; p += -(lr/bc1) * (m/denom), with the bias
-// corrections formed in double precision as the Python scalars upstream are.
-struct AdamCoef { float step_size, bc2_sqrt, w1, b2f, w2, epsf, gscale; };
-struct AdamPmv { float p, m, v; };
-__device__ __forceinline__ AdamPmv adam_elem(const AdamCoef& c, float p, float g, float m, float v) {
-  const float gg = g * c.gscale;
-  m = m + c.w1 * (gg - m);
-  v = v * c.b2f + c.w2 * (gg * gg);
-  const float denom = sqrtf(v) / c.bc2_sqrt + c.epsf;
-  return {p - c.step_size * (m / denom), m, v};
-}
-
+// torch.optim.Adam (defaults, no weight decay / amsgrad): MSGM_higherDim.py:792.  The element update (adam_elem) and its
+// coefficients (adam_coef) live in optim_elem.h: msgm_adam_step_ex (optim_kernels.hip) runs the same copy.
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                        int64_t n, double lr, double b1, double b2, double eps, float gscale, int64_t step,
                        const int64_t* __restrict__ step_dev) {
   const int64_t st = step_dev ? step_dev[0] : step;
-  const double bc1 = 1.0 - pow(b1, (double)st);
-  const double bc2 = 1.0 - pow(b2, (double)st);
-  const AdamCoef c = {(float)(lr / bc1), (float)sqrt(bc2), (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, gscale};
+  const AdamCoef c = adam_coef(lr, b1, b2, eps, gscale, st);
   const int64_t nq = (n + 3) >> 2;
   const bool vec = (n & 3) == 0 && aligned16(p, g, m, v);
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {

@@ -220,6 +220,90 @@ def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor
                                float(gscale), int(step), ptr(step_dev), stream()), "msgm_adam_step")
 
 
+# ---------------------------------------------------------------- optimizer stage (csrc/optim_kernels.hip)
+OPT_LR, OPT_BETA1, OPT_BETA2, OPT_EPS, OPT_MAX_GRAD_NORM, OPT_EMA_RATE = range(6)      # fields of msgm_opt_t
+
+
+def opt_hyper(device, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None,
+              ema_rate: Optional[float] = None) -> torch.Tensor:
+    """The six float64 values behind ``msgm_opt_t`` on ``device``: (lr, beta1, beta2, eps, max_grad_norm, ema_rate).
+    ``adam_step_ex`` reads them at every launch, so writing one (``hyper[OPT_LR:OPT_LR + 1].fill_(lr)``) changes the
+    next replay of a captured step.  ``max_grad_norm=None`` is stored as inf (never clips), ``ema_rate=None`` as 0; a
+    launch without partials / without an EMA buffer does not read them."""
+    vals = [lr, betas[0], betas[1], eps, math.inf if max_grad_norm is None else max_grad_norm,
+            0.0 if ema_rate is None else ema_rate]
+    return torch.tensor([float(x) for x in vals], dtype=torch.float64).to(device)
+
+
+def _flat_dev(t: torch.Tensor, name: str, dtype=torch.float32, numel: Optional[int] = None) -> torch.Tensor:
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise MsgmError(f"{name} must be a device tensor (got a CPU tensor or a non-tensor); there is no CPU fallback")
+    if t.dtype != dtype:
+        raise MsgmError(f"{name} must be {dtype} (got {t.dtype})")
+    if numel is not None and t.numel() != numel:
+        raise MsgmError(f"{name} has {t.numel()} elements, expected {numel}")
+    return t
+
+
+def grad_sqnorm_partials(n: int) -> int:
+    """Number of slices (= float64 partial sums) ``grad_sqnorm`` writes for n elements: a function of n only."""
+    return int(lib().msgm_grad_sqnorm_partials(int(n)))
+
+
+def grad_sqnorm(g: torch.Tensor, gscale: float = 1.0, partials: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """partials[s] = sum over slice s of (g * gscale)^2, float64, deterministic.  ``partials``: a float64 device buffer of
+    ``grad_sqnorm_partials(g.numel())`` entries (e.g. this buffer's slice of a larger one), allocated when None."""
+    _flat_dev(g, "g")
+    n = g.numel()
+    if n < 1:
+        raise MsgmError("grad_sqnorm: empty gradient")
+    need = grad_sqnorm_partials(n)
+    if partials is None:
+        partials = torch.empty(need, dtype=torch.float64, device=g.device)
+    _flat_dev(partials, "partials", torch.float64, need)
+    if partials.device != g.device:
+        raise MsgmError("grad_sqnorm: partials live on another device than g")
+    check(lib().msgm_grad_sqnorm(ptr(g), n, float(gscale), ptr(partials), None, stream()), "msgm_grad_sqnorm")
+    return partials
+
+
+def adam_step_ex(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, hyper: torch.Tensor,
+                 step_dev: torch.Tensor, ema: Optional[torch.Tensor] = None, gscale: float = 1.0,
+                 partials: Optional[torch.Tensor] = None, grad_norm_out: Optional[torch.Tensor] = None):
+    """Adam with the hyper-parameters of ``hyper`` (``opt_hyper``) and the 1-based step count of ``step_dev`` read on the
+    device; ``partials`` (all of it: the concatenated ``grad_sqnorm`` outputs of every buffer in the norm) switches on
+    clip_grad_norm_ by hyper[OPT_MAX_GRAD_NORM] and the pre-clip norm goes to ``grad_norm_out``; ``ema`` switches on
+    ema = ema * rate + p_new * (1 - rate)."""
+    n = _flat_dev(p, "p").numel()
+    if n < 1:
+        raise MsgmError("adam_step_ex: empty parameter buffer")
+    for nm, tt in (("g", g), ("m", m), ("v", v), ("ema", ema)):
+        if tt is not None:
+            _flat_dev(tt, nm, numel=n)
+    _flat_dev(hyper, "hyper", torch.float64, 6)
+    _flat_dev(step_dev, "step_dev", torch.int64, 1)
+    if partials is not None and _flat_dev(partials, "partials", torch.float64).numel() < 1:
+        raise MsgmError("adam_step_ex: empty partials")
+    if grad_norm_out is not None:
+        _flat_dev(grad_norm_out, "grad_norm_out", numel=1)
+    for nm, tt in (("g", g), ("m", m), ("v", v), ("ema", ema), ("hyper", hyper), ("step_dev", step_dev),
+                   ("partials", partials), ("grad_norm_out", grad_norm_out)):
+        if tt is not None and tt.device != p.device:
+            raise MsgmError(f"adam_step_ex: {nm} lives on another device than p")
+    check(lib().msgm_adam_step_ex(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), n, ptr(hyper), float(gscale), ptr(step_dev),
+                                  ptr(partials), 0 if partials is None else partials.numel(), ptr(grad_norm_out),
+                                  stream()), "msgm_adam_step_ex")
+
+
+def swap_(a: torch.Tensor, b: torch.Tensor):
+    """Exchanges the contents of two float32 device buffers of equal size in place (one launch, no third buffer)."""
+    n = _flat_dev(a, "a").numel()
+    _flat_dev(b, "b", numel=n)
+    if n < 1 or a.device != b.device:
+        raise MsgmError("swap_: empty buffers or buffers on two devices")
+    check(lib().msgm_swap(ptr(a), ptr(b), n, stream()), "msgm_swap")
+
+
 def time_tick(ts: torch.Tensor, step: torch.Tensor, T: float, t_dev: torch.Tensor, s_out: torch.Tensor, t_add: float = 0.0):
     """Device clock of a replayed sampler step: t_dev = ts[step] (+ t_add in fp32 for the later Heun / RK4 stages),
     s_out[:] = T - t_dev."""

@@ -7,6 +7,15 @@ state is exposed per parameter as ``step / exp_avg / exp_avg_sq`` so
 ``state_dict()`` is wire-compatible with ``torch.optim.Adam`` checkpoints
 (NN.py:13-42).  The step counter lives on the device so a captured hipGraph can
 replay the update.
+
+``lr`` (like betas and eps) is read from the param group on EVERY eager step, so torch's ``lr_scheduler`` classes work
+with this optimizer as they do with ``torch.optim.Adam``.
+
+``max_grad_norm`` / ``ema_rate`` (csrc/optim_kernels.hip) fold ``torch.nn.utils.clip_grad_norm_`` and the reference's
+``update_ema`` (model/nn_utils.py:117-127) into the update: the norm is GLOBAL over all runs (each run writes its float64
+partial sums into its slice of one buffer, every run's update reads the whole buffer), ``opt.grad_norm`` is a device
+scalar holding the pre-clip norm of the last step, ``opt.ema_state_dict()`` maps a parameter's index to its average.
+Both need every run's gradients in one contiguous buffer (what ``FlatParamMixin`` nets have): MsgmError otherwise.
 """
 from __future__ import annotations
 
@@ -15,10 +24,11 @@ from typing import List
 import torch
 
 from . import ops
+from ._lib import MsgmError
 
 
 class _Run:
-    __slots__ = ("params", "numel", "m", "v", "group")
+    __slots__ = ("params", "numel", "m", "v", "group", "hyper", "hyper_host", "ema", "poff", "pnum")
 
     def __init__(self, params, group):
         self.params: List[torch.nn.Parameter] = params
@@ -27,6 +37,8 @@ class _Run:
         dev = params[0].device
         self.m = torch.zeros(self.numel, dtype=torch.float32, device=dev)
         self.v = torch.zeros(self.numel, dtype=torch.float32, device=dev)
+        self.hyper = self.hyper_host = self.ema = None     # the option route: device hyper-parameters, their host copy, EMA
+        self.poff = self.pnum = 0                          # this run's slice of the shared partials buffer
 
 
 def _flat_view(first: torch.Tensor, numel: int) -> torch.Tensor:
@@ -34,9 +46,13 @@ def _flat_view(first: torch.Tensor, numel: int) -> torch.Tensor:
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale: float = 1.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale: float = 1.0, max_grad_norm=None,
+                 ema_rate=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self.grad_scale = grad_scale          # 1/world_size after a sum all-reduce
+        self.max_grad_norm, self.ema_rate = max_grad_norm, ema_rate
+        self.grad_norm = None                 # device scalar: pre-clip global norm of the last step (max_grad_norm set)
+        self._partials = None
         self._runs = None
         self._step_dev = None
         self._step_host = 0
@@ -61,6 +77,19 @@ class FusedAdam(torch.optim.Optimizer):
         self._runs = runs
         dev = runs[0].params[0].device
         self._step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        if self._options():
+            if any(r.params[0].device != dev for r in runs):
+                raise MsgmError("FusedAdam(max_grad_norm / ema_rate): all parameters must live on one device")
+            if self.max_grad_norm is not None:
+                off = 0
+                for r in runs:
+                    r.poff, r.pnum = off, ops.grad_sqnorm_partials(r.numel)
+                    off += r.pnum
+                self._partials = torch.zeros(off, dtype=torch.float64, device=dev)
+                self.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+            if self.ema_rate is not None:
+                for r in runs:
+                    r.ema = _flat_view(r.params[0].data, r.numel).detach().clone()      # seeded from the parameters
         for r in runs:
             off = 0
             for p in r.params:
@@ -70,25 +99,83 @@ class FusedAdam(torch.optim.Optimizer):
                                  "exp_avg_sq": r.v[off:off + k].view(p.shape)}
                 off += k
 
+    def _options(self) -> bool:
+        return self.max_grad_norm is not None or self.ema_rate is not None
+
+    @staticmethod
+    def _contiguous_grads(r) -> bool:
+        p0 = r.params[0]
+        if p0.grad is None:
+            return False
+        ptr = p0.grad.data_ptr()
+        for p in r.params:
+            if p.grad is None or p.grad.data_ptr() != ptr or not p.grad.is_contiguous():
+                return False
+            ptr += p.numel() * 4
+        return True
+
+    def _prepare_options(self):
+        """Before anything is launched: refuse scattered gradients, write the groups' hyper-parameters where they changed."""
+        for r in self._runs:
+            if not self._contiguous_grads(r):
+                raise MsgmError("FusedAdam(max_grad_norm / ema_rate) needs each run's gradients in one contiguous buffer "
+                                "(a FlatParamMixin net); this run's .grad tensors are scattered or missing")
+            g = r.group
+            vals = (g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.max_grad_norm, self.ema_rate)
+            if vals != r.hyper_host:           # read from the group on every step; written when it changed (a scheduler)
+                h = ops.opt_hyper("cpu", vals[0], vals[1:3], vals[3], vals[4], vals[5])
+                if r.hyper is None:
+                    r.hyper = h.to(r.m.device)
+                else:
+                    r.hyper.copy_(h)
+                r.hyper_host = vals
+
+    def _step_options(self):
+        """[grad_sqnorm per run into its slice of the partials] -> adam_step_ex per run, reading ALL partials."""
+        if self._partials is not None:
+            for r in self._runs:
+                ops.grad_sqnorm(_flat_view(r.params[0].grad, r.numel), self.grad_scale,
+                                self._partials[r.poff:r.poff + r.pnum])
+        for r in self._runs:
+            p0 = r.params[0]
+            ops.adam_step_ex(_flat_view(p0.data, r.numel), _flat_view(p0.grad, r.numel), r.m, r.v, r.hyper, self._step_dev,
+                             ema=r.ema, gscale=self.grad_scale, partials=self._partials, grad_norm_out=self.grad_norm)
+
+    def ema_state_dict(self) -> dict:
+        """{index of the parameter in state_dict()'s numbering: its averaged tensor} (ema_rate set, after the first step
+        or load_state_dict)."""
+        if self.ema_rate is None:
+            raise MsgmError("ema_state_dict() needs FusedAdam(ema_rate=...)")
+        if self._runs is None:
+            self._build_runs()
+        index = {id(p): i for i, p in enumerate(q for g in self.param_groups for q in g["params"])}
+        out = {}
+        for r in self._runs:
+            off = 0
+            for p in r.params:
+                out[index[id(p)]] = r.ema[off:off + p.numel()].view(p.shape).clone()
+                off += p.numel()
+        return out
+
     @torch.no_grad()
     def step(self, closure=None):
         if self._runs is None:
             self._build_runs()
+        if self._options():
+            self._prepare_options()
         ops.counter_inc(self._step_dev)
         self._step_host += 1
+        if self._options():
+            self._step_options()
+            for r in self._runs:
+                for p in r.params:
+                    self.state[p]["step"] = torch.tensor(float(self._step_host))
+            return None
         for r in self._runs:
             g = r.group
             lr, (b1, b2), eps = g["lr"], g["betas"], g["eps"]
             p0 = r.params[0]
-            contiguous = p0.grad is not None
-            if contiguous:
-                ptr = p0.grad.data_ptr()
-                for p in r.params:
-                    if p.grad is None or p.grad.data_ptr() != ptr or not p.grad.is_contiguous():
-                        contiguous = False
-                        break
-                    ptr += p.numel() * 4
-            if contiguous:
+            if self._contiguous_grads(r):
                 ops.adam_step(_flat_view(p0.data, r.numel), _flat_view(p0.grad, r.numel), r.m, r.v, step=0, lr=lr,
                               beta1=b1, beta2=b2, eps=eps, gscale=self.grad_scale, step_dev=self._step_dev)
             else:
@@ -121,3 +208,10 @@ class FusedAdam(torch.optim.Optimizer):
             st["exp_avg"], st["exp_avg_sq"] = m, v
         self._step_host = step
         self._step_dev.fill_(step)
+        if self.ema_rate is not None and "ema" in state_dict:      # a trainer's checkpoint carries its average under "ema"
+            index = {id(p): i for i, p in enumerate(q for g in self.param_groups for q in g["params"])}
+            for r in self._runs:
+                off = 0
+                for p in r.params:
+                    r.ema[off:off + p.numel()].copy_(state_dict["ema"][index[id(p)]].reshape(-1))
+                    off += p.numel()

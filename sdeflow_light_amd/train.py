@@ -9,10 +9,18 @@ Both trainers expose ``state_dict()`` / ``load_state_dict()`` in the layout of `
 {index: step / exp_avg / exp_avg_sq}, ``param_groups``) plus a ``philox`` entry, so the fast path goes through
 ``NN.save_checkpoint`` / ``load_checkpoint`` like the reference loop does (MSGM_higherDim.py:794-826, NN.py:13-42)
 and a resumed run continues the SAME noise stream.
+
+Optimizer stage (keyword-only, all off by default; csrc/optim_kernels.hip): ``max_grad_norm`` (global-norm
+clipping on a deterministic device norm, ``tr.grad_norm``), ``ema_rate`` (``tr.ema``, ``ema_state_dict()``,
+``with tr.ema_weights():``, an ``"ema"`` entry in the checkpoint), ``lr_schedule`` (k -> lr, e.g. ``warmup_cosine``) and
+``device_lr`` (``set_lr`` between replays); any of the first three implies the last.  A trainer built without them runs
+the launches it always ran, with the learning rate baked into the captured step.
 """
 from __future__ import annotations
 
-from typing import Optional
+import contextlib
+import math
+from typing import Callable, Optional
 
 import torch
 
@@ -55,7 +63,10 @@ class _TrainerState:
         group = {"lr": self.lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "decoupled_weight_decay": False, "params": list(range(len(allp)))}
-        return {"state": st, "param_groups": [group], "philox": self.rng.state_dict()}
+        sd = {"state": st, "param_groups": [group], "philox": self.rng.state_dict()}
+        if self.ema is not None:                  # laid out like "state"; torch.optim.Adam's loader ignores the key
+            sd["ema"] = {i: self.ema[off:off + p.numel()].view(p.shape).clone() for i, off, p in mine}
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         allp, mine = self._param_index()
@@ -76,13 +87,118 @@ class _TrainerState:
                 self.m[off:off + k].copy_(e["exp_avg"].reshape(-1)); self.v[off:off + k].copy_(e["exp_avg_sq"].reshape(-1))
                 step = int(float(e["step"]))
         self.step_dev.fill_(step)
+        self._k = step                          # lr_schedule(k) continues at the update after the loaded one
         if sd.get("param_groups"):
-            lr = float(sd["param_groups"][0]["lr"])
-            if lr != self.lr and self.graph is not None:
-                raise MsgmError("the captured step has the learning rate baked in; build a new trainer for another lr")
-            self.lr = lr
+            self.set_lr(float(sd["param_groups"][0]["lr"]))
+        if self.ema is not None:
+            if "ema" in sd:
+                for i, off, p in mine:
+                    self.ema[off:off + p.numel()].copy_(sd["ema"][i - shift].reshape(-1))
+            else:                               # a checkpoint without an average: seed it from the loaded parameters
+                self.ema.copy_(self.flat)
         if "philox" in sd:                      # absent in checkpoints written by torch.optim.Adam: keep the stream
             self.rng.load_state_dict(sd["philox"])      # stream position only; the shard base stays this rank's
+
+    # ------------------------------------------------------------------ optimizer stage (csrc/optim_kernels.hip)
+    def _init_optim(self, lr, max_grad_norm, ema_rate, lr_schedule, device_lr):
+        """``device_lr``: lr, betas, eps, max_grad_norm and ema_rate live in six float64 values on the device
+        (``ops.opt_hyper``) that ``msgm_adam_step_ex`` reads at every launch, so a captured step takes a new learning
+        rate without a re-capture.  Clipping, EMA or a schedule imply it.  All off: today's launches, lr baked in."""
+        self.max_grad_norm, self.ema_rate, self.lr_schedule = max_grad_norm, ema_rate, lr_schedule
+        self.device_lr = bool(device_lr) or any(o is not None for o in (max_grad_norm, ema_rate, lr_schedule))
+        self.lr = float(lr)
+        self.hyper = self.partials = self.grad_norm = self.ema = None
+        self._k, self._in_ema = 0, False          # host count of the updates made; inside ema_weights()
+        if not self.device_lr:
+            return
+        self.hyper = ops.opt_hyper(self.dev, lr, (0.9, 0.999), 1e-8, max_grad_norm, ema_rate)
+        if max_grad_norm is not None:
+            self.partials = torch.zeros(ops.grad_sqnorm_partials(self.n), dtype=torch.float64, device=self.dev)
+            self.grad_norm = torch.zeros((), dtype=torch.float32, device=self.dev)      # the pre-clip global norm
+        if ema_rate is not None:
+            self.ema = self.flat.detach().clone()                                       # seeded from the parameters
+
+    def _optim_update(self, g):
+        """[grad_sqnorm if clipping] -> adam_step_ex: kernel nodes only.  With N ranks ``g`` is the all-reduced bucket,
+        so every rank forms the same norm and the same coefficient and the replicas stay bitwise identical."""
+        if self.partials is not None:
+            ops.grad_sqnorm(g, 1.0, self.partials)
+        ops.adam_step_ex(self.flat, g, self.m, self.v, self.hyper, self.step_dev, ema=self.ema, partials=self.partials,
+                         grad_norm_out=self.grad_norm)
+
+    def set_lr(self, lr: float) -> None:
+        """A device-lr trainer: one ordinary fill kernel on the current stream (outside any capture), legal between
+        replays.  A default trainer has the learning rate baked into the captured step: only before the capture."""
+        lr = float(lr)
+        if self.device_lr:
+            self.hyper[ops.OPT_LR:ops.OPT_LR + 1].fill_(lr)
+        elif lr != self.lr and self.graph is not None:
+            raise MsgmError("the captured step has the learning rate baked in; build a new trainer for another lr")
+        self.lr = lr
+
+    def _pre_step(self):
+        """Host side of ``step()``: refuse inside ``ema_weights()``, apply ``lr_schedule(k)`` for the 1-based number k of
+        the update about to be made."""
+        if self._in_ema:
+            raise MsgmError("step() inside ema_weights(): the parameter bucket holds the average; leave the context first")
+        self._k += 1
+        if self.lr_schedule is not None:
+            self.set_lr(self.lr_schedule(self._k))
+
+    def _pre_capture(self):
+        if self._in_ema:
+            raise MsgmError("capture() inside ema_weights(): the parameter bucket holds the average")
+
+    def ema_state_dict(self) -> dict:
+        """The averaged weights under ``net.state_dict()``'s own keys and shapes (buffers, if any, as they are): loads
+        into this net's class and into the reference's modules alike."""
+        if self.ema is None:
+            raise MsgmError("ema_state_dict() needs a trainer built with ema_rate=...")
+        offs, off = {}, 0
+        for name, p in self.net.named_parameters():
+            offs[name] = (off, p.numel())
+            off += p.numel()
+        out = type(self.net.state_dict())()
+        for k, t in self.net.state_dict().items():
+            out[k] = (self.ema[offs[k][0]:offs[k][0] + offs[k][1]].view(t.shape) if k in offs else t).detach().clone()
+        return out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with tr.ema_weights():`` — the contents of the parameter bucket and of the average change places
+        (msgm_swap, in place: no address changes), so forward, ``ssm`` and the samplers run on the average; the exit
+        swaps back bitwise.  The convolution sets repack their images from the live weights on every pass
+        (ConvOpSet.pack / pack_wino run inside each forward), and so does a ``GraphedStepSampler`` graph built BEFORE
+        entering: its pack launches are kernel nodes of the captured forward, so it needs no rebuild and samples from
+        the average inside the context.  ``step()``, ``capture()`` and nesting raise MsgmError here; write checkpoints
+        outside the context (inside it ``gen_sde.state_dict()`` holds the average)."""
+        if self.ema is None:
+            raise MsgmError("ema_weights() needs a trainer built with ema_rate=...")
+        if self._in_ema:
+            raise MsgmError("ema_weights() does not nest")
+        if torch.cuda.is_current_stream_capturing():
+            raise MsgmError("ema_weights() inside a graph capture")
+        ops.swap_(self.flat, self.ema)
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            ops.swap_(self.flat, self.ema)
+            self._in_ema = False
+
+
+def warmup_cosine(base_lr: float, warmup: int, total: int, min_lr: float = 0.0) -> Callable[[int], float]:
+    """A ready-made ``lr_schedule``: k -> lr for the 1-based update number k.  Linear warm-up base_lr * k / warmup over
+    the first ``warmup`` updates, then half a cosine from base_lr (k = warmup) down to min_lr (k >= total)."""
+    if warmup < 0 or total <= warmup:
+        raise ValueError("warmup_cosine needs 0 <= warmup < total")
+
+    def lr(k: int) -> float:
+        if k <= warmup:
+            return base_lr * k / warmup
+        q = min(1.0, (k - warmup) / (total - warmup))
+        return min_lr + 0.5 * (base_lr - min_lr) * (1.0 + math.cos(math.pi * q))
+    return lr
 
 
 def _msgm_draws(tr):
@@ -138,7 +254,9 @@ class MLPScoreTrainer(_TrainerState):
     fresh (t, eps | forward-SDE noise, v) on the device."""
 
     def __init__(self, gen_sde, batch_local: int, lr: float = 1e-3, world: int = 1, use_graph: bool = True,
-                 seed: int = 0, row_base: int = 0, row_weights: bool = False):
+                 seed: int = 0, row_base: int = 0, row_weights: bool = False, *, max_grad_norm: Optional[float] = None,
+                 ema_rate: Optional[float] = None, lr_schedule: Optional[Callable[[int], float]] = None,
+                 device_lr: bool = False):
         from .NN import MLP
         net, base = gen_sde.a, gen_sde.base_sde
         if not isinstance(net, MLP):
@@ -161,7 +279,7 @@ class MLPScoreTrainer(_TrainerState):
         self.y = torch.empty_like(self.x)
         self.t = torch.empty(batch_local, dtype=torch.float32, device=self.dev)
         self.vp = torch.empty_like(self.x)
-        self.lr = lr
+        self._init_optim(lr, max_grad_norm, ema_rate, lr_schedule, device_lr)
         self.P = net.kernel_params()
         self.st = base.struct()
         self.inv_batch = 1.0 / (batch_local * world)        # mean over the GLOBAL batch
@@ -191,7 +309,16 @@ class MLPScoreTrainer(_TrainerState):
                                              self.st, self.inv_batch, ops.ptr(self.w), None, self.ws.data_ptr(),
                                              self.ws.numel() * 4, C.byref(nsl), s), "msgm_mlp_ssm_partial_w")
         pre = int(self.net.pre is not None)
-        if not parallel.multi(self.world):
+        if self.device_lr:
+            # option route: slab reduction -> [all-reduce] -> [grad_sqnorm] -> adam_step_ex -> Philox advance
+            ops.check(lib.msgm_mlp_ssm_reduce(self.d, pre, self.ws.data_ptr(), nsl.value, self.inv_batch,
+                                              self.gflat.data_ptr(), self.loss.data_ptr(), s), "msgm_mlp_ssm_reduce")
+            if parallel.multi(self.world):
+                parallel.allreduce_sum_(self.gbuf)
+            self._optim_update(self.gflat)
+            if not self.msgm:
+                self.rng.advance(1)
+        elif not parallel.multi(self.world):
             ops.check(lib.msgm_mlp_ssm_reduce_adam(self.d, pre, self.ws.data_ptr(), nsl.value, self.inv_batch,
                                                    self.gflat.data_ptr(), self.loss.data_ptr(), self.flat.data_ptr(),
                                                    self.m.data_ptr(), self.v.data_ptr(), self.lr, 0.9, 0.999, 1e-8,
@@ -207,6 +334,7 @@ class MLPScoreTrainer(_TrainerState):
     def capture(self):
         """One ordinary step on a side stream (loads code objects; it is a REAL training step: parameters, Adam state,
         Philox offset and step counter all live on the device), then the capture — which records and executes nothing."""
+        self._pre_capture()
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(s):
@@ -221,6 +349,7 @@ class MLPScoreTrainer(_TrainerState):
         _set_data(self, x, weight)
 
     def step(self):
+        self._pre_step()
         if self.use_graph:
             if self.graph is None:
                 self.capture()           # its warm-up IS this call's training step (one update per call)
@@ -243,15 +372,18 @@ class UNetScoreTrainer(_TrainerState):
     with one rank the Adam update and the Philox advance are inside the graph too."""
 
     def __init__(self, gen_sde, batch_local: int, dim: int, lr: float = 1e-4, world: int = 1, seed: int = 0,
-                 use_graph: Optional[bool] = None, row_base: int = 0, row_weights: bool = False):
+                 use_graph: Optional[bool] = None, row_base: int = 0, row_weights: bool = False, *,
+                 max_grad_norm: Optional[float] = None, ema_rate: Optional[float] = None,
+                 lr_schedule: Optional[Callable[[int], float]] = None, device_lr: bool = False):
         net, base = gen_sde.a, gen_sde.base_sde
         if not hasattr(net, "ssm_grad"):
             raise MsgmError("UNetScoreTrainer needs a HIP U-Net score net (SGMsde or MSGMsde)")
         self.gen_sde, self.net, self.base = gen_sde, net, base
         self.dev = next(net.parameters()).device
-        self.B, self.d, self.world, self.lr = batch_local, dim, world, lr
+        self.B, self.d, self.world = batch_local, dim, world
         self.flat, self.gflat = net.flat_parameters()
         self.n = self.flat.numel()
+        self._init_optim(lr, max_grad_norm, ema_rate, lr_schedule, device_lr)
         self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
         self.gbuf = net.grad_bucket()            # ONE bucket [grads | mean loss]: the net's gradient bucket IS the
         self.loss = self.gbuf[self.n:]           # collective buffer (no 16 MB staging copy per step)
@@ -296,7 +428,10 @@ class UNetScoreTrainer(_TrainerState):
         self.loss.mul_(self.inv_batch)
 
     def _update(self):
-        ops.adam_step(self.flat, self.gbuf[: self.n], self.m, self.v, step=0, lr=self.lr, step_dev=self.step_dev)
+        if self.device_lr:
+            self._optim_update(self.gbuf[: self.n])
+        else:
+            ops.adam_step(self.flat, self.gbuf[: self.n], self.m, self.v, step=0, lr=self.lr, step_dev=self.step_dev)
         if not self.msgm:                        # the multiplicative SDE's draws advance the stream as they go
             self.rng.advance(1)
 
@@ -310,6 +445,7 @@ class UNetScoreTrainer(_TrainerState):
         images, one-time kernel attributes), then the capture.  Parameters, Adam state, Philox offset and step
         counter all live on the device, so the warm-up is a real training step and every replay is the next one.
         With one rank the graph holds the whole step; with N ranks it ends before the RCCL all-reduce."""
+        self._pre_capture()
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(side):
@@ -327,6 +463,7 @@ class UNetScoreTrainer(_TrainerState):
         self.graph = graph
 
     def step(self):
+        self._pre_step()
         if not self.use_graph:
             self._fwd_bwd()
             self._collective_update()
