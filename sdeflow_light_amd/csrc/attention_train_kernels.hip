@@ -251,6 +251,21 @@ __global__ void __launch_bounds__(256) k_attn_dual_delta(const float* __restrict
 // loop over the key blocks of a group was tried first: it needs ~37 more registers than the 246 the kernel has, spilled, and
 // ran the whole step 1 ms SLOWER at kseq = 1; it also exposed a hipcc hazard bug — no wait states between an MFMA and a global
 // store of its result when a branch sits in between — which a compile-time ACC cannot hit.)
+
+// the PF fragment reads (see the kernel): four tiles STRIDE floats apart behind ONE address register `off`
+template <int STRIDE>
+__device__ __forceinline__ void attn_rd_rows(const float* lds, int off, f32x4* f) {          // rows: one b128 per tile
+#pragma unroll
+  for (int m = 0; m < 4; ++m) f[m] = *reinterpret_cast<const f32x4*>(lds + off + m * STRIDE);
+}
+template <int STRIDE, int KP>
+__device__ __forceinline__ void attn_rd_cols(const float* lds, int off, float (*f)[4]) {     // columns: rows r = 0..3, one b32 each
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int m = 0; m < 4; ++m) f[m][r] = lds[off + m * STRIDE + r * KP];
+}
+
 template <int CT, int KG, bool ACC = false, bool MH = false>
 __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restrict__ qkv, const float* __restrict__ datt,
                                                         const float* __restrict__ stats /* [2][NP*T]: lse | rbar */,
@@ -308,6 +323,35 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) dk[ct] = dkd[ct] = dv[ct] = dvd[ct] = f32x4{0, 0, 0, 0};
 
+  // PF (C = 64: CT = KG, every wave owns exactly ONE channel tile in phase 2): the fragments of channel group g + 1 are
+  // requested under the MFMAs of group g (two register sets), what does not depend on a barrier is requested in front of it,
+  // and the phase-2 column fragments of the resident K / Kd tiles — the same for every query block — are read once.  The
+  // three fragment offsets are made opaque so that each family of reads is ONE address register plus the ds_read's immediate
+  // offset (the staged tiles start 69 632 B into the LDS, past the 16-bit immediate: left alone, hipcc keeps one register per
+  // address, 88 of them).  No MFMA moves: every accumulator receives the same products in the same order.  The other channel
+  // counts keep the text they had: two register sets would cost C = 16 / 32 an occupancy class, and C = 128 has no room.
+  constexpr bool PF = CT == KG;
+  int fa = 0, fb = 0, fc = 0;
+  if constexpr (PF) {
+    int fa4 = KB * KP + (16 * qs + il) * (KP / 4) + q;    // in float4: the b128 reads must stay visibly 16-byte aligned
+    int fb4 = (16 * kg + il) * (KP / 4) + q;
+    fc = 4 * KB * KP + (16 * qs + 4 * q) * KP + il;       // Q | Qd | G | Gd columns (b32): query r at + r KP, tile ct at + 16 ct
+    asm volatile("" : "+v"(fa4), "+v"(fb4), "+v"(fc));
+    fa = 4 * fa4;                                         // Q | Qd | G | Gd rows of this lane (b128): group g at + 16 g
+    fb = 4 * fb4;                                         // K | Kd | V | Vd rows (b128)
+  }
+  float k1[PF ? KG : 1][4], k2[PF ? KG : 1][4];            // PF: K / Kd columns of this wave's phase-2 tile ct = kg
+  if constexpr (PF) {
+    __syncthreads();                                       // the resident tiles are visible
+#pragma unroll
+    for (int kt = 0; kt < KG; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        k1[kt][r] = Ks[(16 * kt + 4 * q + r) * KP + 16 * kg + il];
+        k2[kt][r] = Kd[(16 * kt + 4 * q + r) * KP + 16 * kg + il];
+      }
+  }
+
   f32x4 pq[NQ], pqd[NQ], pg[NQ], pgd[NQ];
   float pst = 0.f;
   auto gload = [&](int qb) __attribute__((always_inline)) {
@@ -344,18 +388,28 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
       *reinterpret_cast<f32x4*>(Gd + qr * KP + 4 * c4) = pgd[i];
     }
     if (tid < 4 * QB) St[tid] = pst;
+    f32x4 A[PF ? 2 : 1][4], B[PF ? 2 : 1][4];              // fragment sets of phase 1a
+    float cf[PF ? 2 : 1][4][4];                            // and of phase 1c
+    if constexpr (PF) attn_rd_rows<KB * KP>(atb_lds, fb, B[0]);                    // resident tiles: requested in front of [B]
     __syncthreads();                                       // [B] staged block visible
+    if constexpr (PF) attn_rd_rows<QB * KP>(atb_lds, fa, A[0]);
     if (qb + 1 < nqb) gload(qb + 1);
 
     // ---- phase 1a: S, Sd, Pbar, D for (queries 16qs.., keys 16kg..); D layout: lane (key il, queries 4q+r)
     f32x4 s = {0, 0, 0, 0}, sd = {0, 0, 0, 0}, pb = {0, 0, 0, 0}, dd = {0, 0, 0, 0};
 #pragma unroll
     for (int g = 0; g < CT; ++g) {
+      const int c = PF ? g & 1 : 0;
+      if constexpr (PF) {
+        if (g + 1 < CT) { attn_rd_rows<QB * KP>(atb_lds + 16 * (g + 1), fa, A[c ^ 1]); attn_rd_rows<KB * KP>(atb_lds + 16 * (g + 1), fb, B[c ^ 1]); }
+        else attn_rd_cols<QB * KP, KP>(atb_lds, fc, cf[0]);                             // the last group covers phase 1c's first tile
+        __builtin_amdgcn_sched_barrier(0);                 // the requests go out first: hipcc sinks them behind the MFMAs
+      }
       const int ao = (16 * qs + il) * KP + 16 * g + 4 * q, bo = (16 * kg + il) * KP + 16 * g + 4 * q;
-      const f32x4 aQ = *reinterpret_cast<const f32x4*>(Qs + ao), aQd = *reinterpret_cast<const f32x4*>(Qd + ao);
-      const f32x4 aG = *reinterpret_cast<const f32x4*>(Gs + ao), aGd = *reinterpret_cast<const f32x4*>(Gd + ao);
-      const f32x4 bK = *reinterpret_cast<const f32x4*>(Ks + bo), bKd = *reinterpret_cast<const f32x4*>(Kd + bo);
-      const f32x4 bV = *reinterpret_cast<const f32x4*>(Vs + bo), bVd = *reinterpret_cast<const f32x4*>(Vd + bo);
+      const f32x4 aQ = PF ? A[c][0] : *reinterpret_cast<const f32x4*>(Qs + ao), aQd = PF ? A[c][1] : *reinterpret_cast<const f32x4*>(Qd + ao);
+      const f32x4 aG = PF ? A[c][2] : *reinterpret_cast<const f32x4*>(Gs + ao), aGd = PF ? A[c][3] : *reinterpret_cast<const f32x4*>(Gd + ao);
+      const f32x4 bK = PF ? B[c][0] : *reinterpret_cast<const f32x4*>(Ks + bo), bKd = PF ? B[c][1] : *reinterpret_cast<const f32x4*>(Kd + bo);
+      const f32x4 bV = PF ? B[c][2] : *reinterpret_cast<const f32x4*>(Vs + bo), bVd = PF ? B[c][3] : *reinterpret_cast<const f32x4*>(Vd + bo);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         s = mfma16(aQ[r], bK[r], s);
@@ -365,7 +419,7 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
         sd = mfma16(aQ[r], bKd[r], sd);
         pb = mfma16(aGd[r], bVd[r], pb);
       }
-      __builtin_amdgcn_sched_barrier(0);                   // keep one channel group of fragments in flight, not all
+      __builtin_amdgcn_sched_barrier(0);                   // keep one (PF: two) channel groups of fragments in flight, not all
     }
     // ---- phase 1b: elementwise adjoints (row scalars of queries 16qs + 4q + r)
     const f32x4 L4 = *reinterpret_cast<const f32x4*>(St + 16 * qs + 4 * q);
@@ -387,11 +441,17 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
     // ---- phase 1c: key-side products, contraction over the 16 queries of the sub-tile (B operand = tile registers)
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
+      const int c = PF ? ct & 1 : 0;
+      if constexpr (PF) {
+        if (ct + 1 < CT) attn_rd_cols<QB * KP, KP>(atb_lds + 16 * (ct + 1), fc, cf[c ^ 1]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       float aG[4], aGd[4], aQ[4], aQd[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int o = (16 * qs + 4 * q + r) * KP + 16 * ct + il;
-        aG[r] = Gs[o]; aGd[r] = Gd[o]; aQ[r] = Qs[o]; aQd[r] = Qd[o];
+        aG[r] = PF ? cf[c][2][r] : Gs[o]; aGd[r] = PF ? cf[c][3][r] : Gd[o];
+        aQ[r] = PF ? cf[c][0][r] : Qs[o]; aQd[r] = PF ? cf[c][1][r] : Qd[o];
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -416,15 +476,24 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
         pdq = *reinterpret_cast<const f32x4*>(sp);
         pdqd = *reinterpret_cast<const f32x4*>(sdp);
       }
+      f32x4 t1[PF ? KG : 1], t2[PF ? KG : 1];
+      if constexpr (PF) {                                  // all parked rows of this lane at once: the MFMAs wait for them in turn
+#pragma unroll
+        for (int kt = 0; kt < KG; ++kt) {
+          t1[kt] = *reinterpret_cast<const f32x4*>(dS + (16 * qs + il) * DP + 16 * kt + 4 * q);
+          t2[kt] = *reinterpret_cast<const f32x4*>(dSd + (16 * qs + il) * DP + 16 * kt + 4 * q);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
 #pragma unroll
       for (int kt = 0; kt < KG; ++kt) {
-        const f32x4 b1 = *reinterpret_cast<const f32x4*>(dS + (16 * qs + il) * DP + 16 * kt + 4 * q);
-        const f32x4 b2 = *reinterpret_cast<const f32x4*>(dSd + (16 * qs + il) * DP + 16 * kt + 4 * q);
+        const f32x4 b1 = PF ? t1[PF ? kt : 0] : *reinterpret_cast<const f32x4*>(dS + (16 * qs + il) * DP + 16 * kt + 4 * q);
+        const f32x4 b2 = PF ? t2[PF ? kt : 0] : *reinterpret_cast<const f32x4*>(dSd + (16 * qs + il) * DP + 16 * kt + 4 * q);
         float a1[4], a2[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          a1[r] = Ks[(16 * kt + 4 * q + r) * KP + 16 * ct + il];
-          a2[r] = Kd[(16 * kt + 4 * q + r) * KP + 16 * ct + il];
+          a1[r] = PF ? k1[PF ? kt : 0][r] : Ks[(16 * kt + 4 * q + r) * KP + 16 * ct + il];
+          a2[r] = PF ? k2[PF ? kt : 0][r] : Kd[(16 * kt + 4 * q + r) * KP + 16 * ct + il];
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {

@@ -2,7 +2,7 @@
 """GPU box: the GroupNorm and attention kernels of this tree's library against another build of it (the parent commit's
 libmsgm_hip.so, built into a scratch path), both loaded into one process, as conv_vs_parent.py / wgrad_vs_parent.py do for the
 convolutions (the shared parts: tools/parent_compare.py):
-    python tools/unet_vs_parent.py <parent.so>                      bitwise: every output, workspace slab and job descriptor
+    python tools/unet_vs_parent.py <parent.so> [--only NAME]        bitwise: every output, workspace slab and job descriptor
     python tools/unet_vs_parent.py <parent.so> [--only NAME] --time [out.json] [name=variant.so ...]
                                                                     timing: parent / parent again / this tree (/ further builds,
                                                                     e.g. one phase routed through its shared function),
@@ -237,7 +237,9 @@ SAMPLER = [(3, 64, 1, 32, 0), (2, 128, 1, 32, 0), (3, 64, 1, 64, 0), (2, 128, 1,
           [(2, T, 2, D, 1) for D in (16, 32, 64) for T in (64, 128)] + [(2, 128, 2, 128, 1)]
 DUAL = [(3, 64, 1, 32, 0), (3, 64, 1, 64, 0), (9, 96, 1, 128, 0), (1, 32, 1, 128, 0), (512, 64, 1, 128, 0), (1024, 128, 1, 32, 0),
         (1024, 64, 1, 128, 0), (3, 64, 2, 16, 1), (3, 64, 2, 32, 1), (2, 64, 2, 64, 1), (5, 96, 2, 128, 1), (256, 64, 2, 128, 1),
-        (256, 128, 4, 32, 1), (3, 64, 1, 64, 1), (3, 64, 1, 16, 1)]      # the last two: one head through the multi-head entries
+        (256, 128, 4, 32, 1), (3, 64, 1, 64, 1), (3, 64, 1, 16, 1),      # these two: one head through the multi-head entries
+        # tests/test_attn_dual_paths_gpu.py: one key block, an odd count, the decode's tail, C = 64 with kseq = 2, D = 64 at two heads
+        (1, 64, 1, 64, 0), (3, 192, 1, 64, 0), (9, 128, 1, 64, 0), (1024, 128, 1, 64, 0), (5, 128, 2, 64, 1)]
 
 
 def attn_cases():
@@ -253,6 +255,8 @@ def bitwise():
     t0, n, bad = time.time(), 0, 0
     for gen in (gn_cases, attn_cases):
         for desc, run in gen():
+            if ONLY not in desc:
+                continue
             a, b = run(PARENT), run(NEW)
             ok = len(a) == len(b) and all(same(x, y) for x, y in zip(a, b)) and bool(torch.isfinite(b[0]).all())
             n += 1; bad += not ok
