@@ -138,6 +138,40 @@ int msgm_forward_perturb(const float* x0, const float* t, float* y, int32_t* k_o
 /* Rademacher probe v = 2[u>=1/2]-1 (SDEs.py:514-515); u NULL => rng stream 2. */
 int msgm_rademacher(float* v, int64_t n, const float* u, const uint64_t* rng, msgm_stream_t stream);
 
+/* ---- The data stage: a fresh minibatch per training step, drawn on the device (csrc/data_kernels.hip) ----
+ * Replaces the host-side `x = sampler.sample(batch_size).to(device)` of the reference loop (MSGM_higherDim.py:806).
+ * Philox streams (csrc/common.h): RNG_STREAM_DATA = 5 indexed by the GLOBAL row (base rng[2], like the time draw),
+ * RNG_STREAM_DATA_ELEM = 6 by the global element (base rng[3]), RNG_STREAM_DATA_CALL = 7 read at element 0 with no base.
+ * None of these calls advances the stream, allocates or synchronises; each is one kernel launch.
+ *
+ * msgm_data_gather: x[b,:] = data[idx_b,:] for a resident float32 (N, d) table, 1 <= N < 2^31 (MSGM_E_UNSUPPORTED above), the
+ * with-replacement draw of data.py:691-697.  idx_b = (uint64(word_b) * N) >> 32, word_b = word e & 3 of block e >> 2 of
+ * RNG_STREAM_DATA at the state's current offset, e = row_base + b.  idx_in (B int32, optional): use these rows instead
+ * (values are clamped into [0, N)); idx_out (B int32, optional): receives the rows used.  d % 4 == 0 with 16-byte aligned
+ * data and x moves 16 bytes per lane, anything else a dword per lane; x must not overlap data. */
+int msgm_data_gather(const float* data, int64_t N, float* x, int64_t B, int64_t d, const int32_t* idx_in, int32_t* idx_out,
+                     const uint64_t* rng, msgm_stream_t stream);
+
+/* msgm_data_gather followed by msgm_ssm_prep, in ONE launch and with the bits of the two from the same stream state:
+ * x receives the gathered batch, y / t_out / v what msgm_ssm_prep writes for it, *step_ctr += 1 (may be NULL). */
+int msgm_ssm_prep_gather(const float* data, int64_t N, float* x, float* y, float* t_out, float* v, int64_t B, int64_t d,
+                         const msgm_sde_t* sde, const uint64_t* rng, int64_t* step_ctr, msgm_stream_t stream);
+
+/* The reference's synthetic samplers (data.py:702-802), x (B, d).  Injected draws follow the library's parity idiom: a
+ * NULL pointer means Philox (rng needed then).
+ *   MSGM_DATA_SWISS            d = 2, A NULL: t = 1.5 pi (1 + 2 u_b), x_b = ((t cos t + noise n0) / 5, (t sin t + noise n1) / 5)
+ *                              (sklearn make_swiss_roll, columns [0, 2]);  u (B) | RNG_STREAM_DATA, z (B, 2) | RNG_STREAM_DATA_ELEM
+ *   MSGM_DATA_GAUSSIAN         x = z A^T;  z (B, d) | normals of RNG_STREAM_DATA_ELEM
+ *   MSGM_DATA_CAUCHY           x = c A^T, c = cauchy(u) / 50;  u (B, d) uniforms in [0, 1) | words of RNG_STREAM_DATA_ELEM
+ *   MSGM_DATA_GAUSSIAN_CAUCHY  x = ((1/50) (z A^T)) s, s = cauchy(u[0]): ONE scalar per call;  z (B, d), u (1) | word 0 of
+ *                              RNG_STREAM_DATA_CALL (no shard base: the same s on every rank)
+ * cauchy(.): k = word >> 8 (or (int)(u 2^24)), m = min(k, 2^24 - 1 - k), w = (m + 1/2) 2^-24, cos(pi w) / sin(pi w), negative
+ * for k < 2^23 — finite for every word, k and 2^24 - 1 - k exact negatives.
+ * A (d, d) row-major, NULL = identity (any d); a dense A needs d <= 128 (MSGM_E_UNSUPPORTED above).  noise: swiss only. */
+enum { MSGM_DATA_SWISS = 0, MSGM_DATA_GAUSSIAN = 1, MSGM_DATA_CAUCHY = 2, MSGM_DATA_GAUSSIAN_CAUCHY = 3 };
+int msgm_data_synth(int32_t kind, float* x, int64_t B, int64_t d, const float* A, float noise, const float* u, const float* z,
+                    const uint64_t* rng, msgm_stream_t stream);
+
 /* ---- K2/K3/K4: one integrator stage -------------------------------------- */
 /* inc = drift(t, x) * delta + sigma(t, x) . dW   (sde_scheme.py:18-40 EMstep
  * applied to sde.mu / sde.mu_Strato and sde.sigma, SDEs.py:30-47,556-588),

@@ -21,6 +21,8 @@ SDE_SGM, SDE_MSGM_SPARSE, SDE_MSGM_DENSE = 0, 1, 2
 PROC_REVERSE, PROC_FORWARD = 0, 1
 METHOD_EM, METHOD_HEUN, METHOD_RK4 = 0, 1, 2          # msgm_mlp_sde_loop
 RNG_STREAM_T, RNG_STREAM_EPS, RNG_STREAM_V, RNG_STREAM_DW, RNG_STREAM_ROWS, RNG_STREAM_USER = 0, 1, 2, 3, 4, 16
+RNG_STREAM_DATA, RNG_STREAM_DATA_ELEM, RNG_STREAM_DATA_CALL = 5, 6, 7     # the data stage: by row, by element, one scalar per call
+DATA_SWISS, DATA_GAUSSIAN, DATA_CAUCHY, DATA_GAUSSIAN_CAUCHY = 0, 1, 2, 3   # msgm_data_synth
 RNG_STREAM_DROPOUT = 64          # + the ResBlock's index: the U-Net's dropout masks (include/msgm_hip.h, msgm_dropout_t)
 
 
@@ -201,6 +203,10 @@ SIGNATURES = {
     "msgm_grad_sqnorm": (C.c_int, [_P, _I64, _F, _P, C.POINTER(C.c_int32), _P]),
     "msgm_adam_step_ex": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _F, _P, _P, _I32, _P, _P]),
     "msgm_swap": (C.c_int, [_P, _P, _I64, _P]),
+    # data stage: a fresh minibatch per step, drawn on the device
+    "msgm_data_gather": (C.c_int, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _P]),
+    "msgm_ssm_prep_gather": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I64, C.POINTER(SdeT), _P, _P, _P]),
+    "msgm_data_synth": (C.c_int, [_I32, _P, _I64, _I64, _P, _F, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -103,25 +103,7 @@ __global__ void k_time_tick(const float* __restrict__ ts, const int64_t* __restr
 // one function taking the per-element work as a lambda k_perturb_vp read SLOWER against the parent commit at 4096 x 12288
 // (+0.88 us of 188.8, where the parent differed from itself by 0.74: profiles/README.md); with these lines both kernels
 // are the parent's machine code.
-struct VpSde { float b0, b1, T, t_eps; };
-struct VpRow { float t, mw, sd; };
-
-// Row b's time — as given (SGMsde.sample(t, y0): no clamp, SDEs.py:134-146), or u_b T with u_b injected or drawn from
-// RNG_STREAM_T, clamped by mask arithmetic as upstream — and its mean weight and standard deviation (one Philox block + two exp).
-__device__ __forceinline__ VpRow vp_row(const VpSde& P, int64_t b, const uint64_t* __restrict__ rng, const float* __restrict__ u,
-                                        const float* __restrict__ t_given) {
-  float t;
-  if (t_given) {
-    t = t_given[b];
-  } else {
-    const float ub = u ? u[b] : philox_uniform1(rng, 0, RNG_STREAM_T, (uint64_t)b);
-    t = ub * P.T;
-    const float m = (t <= P.t_eps) ? 1.0f : 0.0f;
-    t = m * P.t_eps + (1.0f - m) * t;
-  }
-  return {t, vp_mean_weight(P.b0, P.b1, t), sqrtf(vp_var(P.b0, P.b1, t))};
-}
-__device__ __forceinline__ float vp_value(const VpRow& r, float eps, float x0) { return eps * r.sd + r.mw * x0; }
+// VpSde / VpRow / vp_row / vp_value: sde_stage.h (the fused gather prologue of data_kernels.hip calls them too)
 
 __global__ void k_perturb_vp(const float* __restrict__ x0, float* __restrict__ y, float* __restrict__ t_out,
                              float* __restrict__ eps_out, int64_t B, int64_t d, float b0, float b1, float T,

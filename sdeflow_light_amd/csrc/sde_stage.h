@@ -120,3 +120,26 @@ __device__ __forceinline__ float rk4_close(float x, float s, float k4) { return 
 __device__ __forceinline__ float rk4_value(float x, float k1, float k2, float k3, float k4) {
   return rk4_close(x, rk4_add(rk4_add(k1, k2), k3), k4);
 }
+
+// ------------------------------------------------------------ K1: the additive SDE's closed-form perturbation
+// k_perturb_vp, k_ssm_prep (sde_kernels.hip) and k_ssm_prep_gather (data_kernels.hip) take a row's time from vp_row and an
+// element's value from vp_value: same streams, same indices, same bits.
+struct VpSde { float b0, b1, T, t_eps; };
+struct VpRow { float t, mw, sd; };
+
+// Row b's time — as given (SGMsde.sample(t, y0): no clamp, SDEs.py:134-146), or u_b T with u_b injected or drawn from
+// RNG_STREAM_T, clamped by mask arithmetic as upstream — and its mean weight and standard deviation (one Philox block + two exp).
+__device__ __forceinline__ VpRow vp_row(const VpSde& P, int64_t b, const uint64_t* __restrict__ rng, const float* __restrict__ u,
+                                        const float* __restrict__ t_given) {
+  float t;
+  if (t_given) {
+    t = t_given[b];
+  } else {
+    const float ub = u ? u[b] : philox_uniform1(rng, 0, RNG_STREAM_T, (uint64_t)b);
+    t = ub * P.T;
+    const float m = (t <= P.t_eps) ? 1.0f : 0.0f;
+    t = m * P.t_eps + (1.0f - m) * t;
+  }
+  return {t, vp_mean_weight(P.b0, P.b1, t), sqrtf(vp_var(P.b0, P.b1, t))};
+}
+__device__ __forceinline__ float vp_value(const VpRow& r, float eps, float x0) { return eps * r.sd + r.mw * x0; }

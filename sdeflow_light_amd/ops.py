@@ -134,6 +134,94 @@ def rademacher(shape, device, u: Optional[torch.Tensor] = None, rng: Optional[Ph
     return v
 
 
+def _data_table(data: torch.Tensor, d: int, what: str = "data") -> int:
+    """Row count of a resident (N, d) float32 device table, checked before any launch."""
+    if not torch.is_tensor(data) or not data.is_cuda:
+        raise MsgmError(f"{what} must be a device tensor (got a CPU tensor or a non-tensor); there is no CPU fallback")
+    if data.dim() != 2 or data.shape[1] != d or data.shape[0] < 1:
+        raise MsgmError(f"{what} has shape {tuple(data.shape)}, expected (N >= 1, {d})")
+    if data.shape[0] >= 2 ** 31:
+        raise MsgmError(f"{what} has {data.shape[0]} rows; the gather indexes fewer than 2^31")
+    f32(data, what)
+    return int(data.shape[0])
+
+
+def _batch_out(x: torch.Tensor) -> tuple:
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise MsgmError("the batch must be a device tensor (got a CPU tensor or a non-tensor); there is no CPU fallback")
+    if x.dim() != 2 or x.numel() == 0:
+        raise MsgmError(f"the batch must be a non-empty (B, d) tensor (got {tuple(x.shape)})")
+    f32(x, "x")
+    return int(x.shape[0]), int(x.shape[1])
+
+
+def data_gather(data: torch.Tensor, x: torch.Tensor, rng: Optional[PhiloxState] = None, idx: Optional[torch.Tensor] = None,
+                idx_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x[b, :] = data[idx_b, :] in one launch: idx_b drawn with replacement from ``rng``'s current offset (stream
+    RNG_STREAM_DATA by global row; the stream is NOT advanced), or taken from ``idx`` (B int32, clamped into [0, N)).
+    ``idx_out`` (B int32) receives the rows used.  Returns x."""
+    B, d = _batch_out(x)
+    N = _data_table(data, d)
+    if data.device != x.device:
+        raise MsgmError("data and x live on different devices")
+    for nm, t in (("idx", idx), ("idx_out", idx_out)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B):
+            raise MsgmError(f"{nm} must be a device int32 tensor of {B} entries")
+    if idx is None and rng is None:
+        raise MsgmError("data_gather needs rng or idx")
+    check(lib().msgm_data_gather(ptr(data), N, ptr(x), B, d, ptr(idx), ptr(idx_out), _rng_ptr(rng), stream()),
+          "msgm_data_gather")
+    return x
+
+
+def ssm_prep_gather(data: torch.Tensor, x: torch.Tensor, y: torch.Tensor, t: torch.Tensor, v: torch.Tensor, sde: L.SdeT,
+                    rng: PhiloxState, step_dev: Optional[torch.Tensor] = None) -> None:
+    """data_gather(data, x, rng) + msgm_ssm_prep(x -> y, t, v) in one launch, the bits of the two (additive SDE only)."""
+    B, d = _batch_out(x)
+    N = _data_table(data, d)
+    _same_shape(y, (B, d), "y"); _same_shape(v, (B, d), "v"); _same_shape(t, (B,), "t")
+    for nm, tt in (("y", y), ("t", t), ("v", v)):
+        f32(tt, nm)
+    check(lib().msgm_ssm_prep_gather(ptr(data), N, ptr(x), ptr(y), ptr(t), ptr(v), B, d, sde, rng.ptr(), ptr(step_dev),
+                                     stream()), "msgm_ssm_prep_gather")
+
+
+DATA_KINDS = {"swiss": L.DATA_SWISS, "gaussian": L.DATA_GAUSSIAN, "cauchy": L.DATA_CAUCHY,
+              "gaussian_cauchy": L.DATA_GAUSSIAN_CAUCHY}
+
+
+def data_synth(kind: str, x: torch.Tensor, A: Optional[torch.Tensor] = None, noise: float = 0.5,
+               u: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None,
+               rng: Optional[PhiloxState] = None) -> torch.Tensor:
+    """Fill x (B, d) from one of the reference's synthetic samplers (include/msgm_hip.h, msgm_data_synth).  Injected draws:
+    swiss u (B) and z (B, 2); gaussian z (B, d); cauchy u (B, d); gaussian_cauchy z (B, d) and u (1).  A missing one is drawn
+    from ``rng`` at its current offset (not advanced).  A (d, d) or None = identity; a dense A needs d <= 128."""
+    if kind not in DATA_KINDS:
+        raise MsgmError(f"unknown synthetic sampler {kind!r}; one of {sorted(DATA_KINDS)}")
+    B, d = _batch_out(x)
+    if kind == "swiss" and (d != 2 or A is not None):
+        raise MsgmError("the swiss roll is 2-dimensional and takes no A")
+    if A is not None:
+        _same_shape(A, (d, d), "A")
+        f32(A, "A")
+        if A.device != x.device:
+            raise MsgmError("A and x live on different devices")
+        if d > 128:
+            raise MsgmError(f"a dense A is supported up to d = 128 (got {d}); pass A=None for the identity")
+    shapes = {"swiss": ((B,), (B, 2)), "gaussian": (None, (B, d)), "cauchy": ((B, d), None), "gaussian_cauchy": ((1,), (B, d))}[kind]
+    for nm, t, shp in (("u", u, shapes[0]), ("z", z, shapes[1])):
+        if t is not None:
+            if shp is None:
+                raise MsgmError(f"the {kind} sampler takes no {nm}")
+            _same_shape(t, shp, nm)
+            f32(t, nm)
+    if rng is None and any(t is None and shp is not None for t, shp in ((u, shapes[0]), (z, shapes[1]))):
+        raise MsgmError("data_synth needs rng unless every draw is injected")
+    check(lib().msgm_data_synth(DATA_KINDS[kind], ptr(x), B, d, ptr(A), float(noise), ptr(u), ptr(z), _rng_ptr(rng), stream()),
+          "msgm_data_synth")
+    return x
+
+
 def sde_stage(out: torch.Tensor, base: Optional[torch.Tensor], c_out: float, x: torch.Tensor,
               a: Optional[torch.Tensor], sde: L.SdeT, proc: int, strato: bool, t: float, delta: float, lmbd: float = 0.0,
               dW: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None, rng: Optional[PhiloxState] = None,

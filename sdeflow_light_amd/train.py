@@ -15,6 +15,14 @@ clipping on a deterministic device norm, ``tr.grad_norm``), ``ema_rate`` (``tr.e
 ``with tr.ema_weights():``, an ``"ema"`` entry in the checkpoint), ``lr_schedule`` (k -> lr, e.g. ``warmup_cosine``) and
 ``device_lr`` (``set_lr`` between replays); any of the first three implies the last.  A trainer built without them runs
 the launches it always ran, with the learning rate baked into the captured step.
+
+Data stage (keyword-only ``data=sampler``, off by default; csrc/data_kernels.hip): every step begins by
+drawing ``x`` on the device from the trainer's own Philox stream — a fresh minibatch per replay, no host work.  An
+``ArrayData`` under the additive SDE rides in the prep launch (msgm_ssm_prep_gather: the launch count of a fixed-batch
+step); every other combination is ``sampler.sample_into(tr.x, tr.rng)`` ahead of the existing path.  ``tr.x`` shows the
+batch that was trained on.  The stream advances per step as before, so checkpoints keep their keys and a resumed run
+draws the batches of the uninterrupted one; indices and draws are keyed by global row / element, so an N-rank run
+(every rank holding the whole table) trains on the rows of the 1-rank run.
 """
 from __future__ import annotations
 
@@ -230,6 +238,8 @@ def _init_row_weights(tr, row_weights: bool):
 
 
 def _set_data(tr, x, weight):
+    if tr.data is not None:
+        raise MsgmError("set_data() on a trainer built with data=...: the next step draws its own batch over it")
     if weight is not None:
         if tr.w is None:
             raise MsgmError("set_data(weight=...) needs a trainer built with row_weights=True")
@@ -237,6 +247,37 @@ def _set_data(tr, x, weight):
     tr.x.copy_(x)
     if weight is not None:
         tr.w.copy_(weight)
+
+
+def _init_data(tr, data):
+    """``data=sampler``: a device sampler of sdeflow_light_amd.data whose ``sample_into(x, rng)`` heads every step.  An
+    ArrayData under the additive SDE is read by the fused prep launch instead (same bits, one launch fewer)."""
+    from .data import ArrayData
+    tr.data, tr._table = data, None
+    if data is None:
+        return
+    if not hasattr(data, "sample_into") or not hasattr(data, "dim"):
+        raise MsgmError("data= takes a device sampler of sdeflow_light_amd.data (sample_into, dim)")
+    if data.dim != tr.d:
+        raise MsgmError(f"the {getattr(data, 'name', 'data')} sampler has dim {data.dim}, the score net takes {tr.d}")
+    data.to(tr.dev)
+    if isinstance(data, ArrayData) and tr.base.kind == L.SDE_SGM:
+        tr._table = data.table()
+
+
+def _draw_data(tr):
+    """Head of a step on the trainer's stream: the sampler's launches, unless the prep launch gathers (tr._table)."""
+    if tr.data is not None and tr._table is None:
+        tr.data.sample_into(tr.x, tr.rng)
+
+
+def _ssm_prep(tr):
+    """The additive SDE's prep launch: perturbation + probe + step tick, on the resident batch or through the gather."""
+    if tr._table is not None:
+        ops.ssm_prep_gather(tr._table, tr.x, tr.y, tr.t, tr.vp, tr.st, tr.rng, tr.step_dev)
+        return
+    ops.check(ops.lib().msgm_ssm_prep(tr.x.data_ptr(), tr.y.data_ptr(), tr.t.data_ptr(), tr.vp.data_ptr(), tr.B, tr.d, tr.st,
+                                      tr.rng.ptr(), tr.step_dev.data_ptr(), ops.stream()), "msgm_ssm_prep")
 
 
 def _adopt_stream(tr):
@@ -251,12 +292,12 @@ def _adopt_stream(tr):
 class MLPScoreTrainer(_TrainerState):
     """MLP score net (configs C1/C2) under the additive (SGMsde) or the multiplicative SDE (MSGMsde, dense or sparse
     tensor: MSGM_higherDim.py:733-746).  ``x`` is this rank's shard (B_local, d) and stays resident; each ``step()`` draws
-    fresh (t, eps | forward-SDE noise, v) on the device."""
+    fresh (t, eps | forward-SDE noise, v) on the device — and, with ``data=sampler``, a fresh ``x`` as well."""
 
     def __init__(self, gen_sde, batch_local: int, lr: float = 1e-3, world: int = 1, use_graph: bool = True,
                  seed: int = 0, row_base: int = 0, row_weights: bool = False, *, max_grad_norm: Optional[float] = None,
                  ema_rate: Optional[float] = None, lr_schedule: Optional[Callable[[int], float]] = None,
-                 device_lr: bool = False):
+                 device_lr: bool = False, data=None):
         from .NN import MLP
         net, base = gen_sde.a, gen_sde.base_sde
         if not isinstance(net, MLP):
@@ -287,6 +328,7 @@ class MLPScoreTrainer(_TrainerState):
         self.use_graph = use_graph and not parallel.multi(world)
         _init_row_weights(self, row_weights)
         _adopt_stream(self)
+        _init_data(self, data)
 
     def _body(self):
         """3 launches on one GPU: prep (K1 + probe + step tick) -> fused SSM kernel ->
@@ -294,6 +336,7 @@ class MLPScoreTrainer(_TrainerState):
         reduction and Adam are split around the RCCL all-reduce of the flat bucket."""
         import ctypes as C
         lib, s = ops.lib(), ops.stream()
+        _draw_data(self)
         if self.msgm:
             # multiplicative SDE: no closed-form perturbation — masked RK4 on the device, then the general loss form
             y, t, vp, uu, cst = _msgm_draws(self)
@@ -301,8 +344,7 @@ class MLPScoreTrainer(_TrainerState):
             pu, pc, adv = uu.data_ptr(), cst.data_ptr(), None       # the draws advanced the stream themselves
             self._live = (y, vp, uu, cst)
         else:
-            ops.check(lib.msgm_ssm_prep(self.x.data_ptr(), self.y.data_ptr(), self.t.data_ptr(), self.vp.data_ptr(), self.B,
-                                        self.d, self.st, self.rng.ptr(), self.step_dev.data_ptr(), s), "msgm_ssm_prep")
+            _ssm_prep(self)
             y, t, vp, pu, pc, adv = self.y, self.t, self.vp, None, None, self.rng.ptr()
         nsl = C.c_int32(0)
         ops.check(lib.msgm_mlp_ssm_partial_w(self.P, y.data_ptr(), t.data_ptr(), vp.data_ptr(), pu, pc, self.B,
@@ -374,7 +416,7 @@ class UNetScoreTrainer(_TrainerState):
     def __init__(self, gen_sde, batch_local: int, dim: int, lr: float = 1e-4, world: int = 1, seed: int = 0,
                  use_graph: Optional[bool] = None, row_base: int = 0, row_weights: bool = False, *,
                  max_grad_norm: Optional[float] = None, ema_rate: Optional[float] = None,
-                 lr_schedule: Optional[Callable[[int], float]] = None, device_lr: bool = False):
+                 lr_schedule: Optional[Callable[[int], float]] = None, device_lr: bool = False, data=None):
         net, base = gen_sde.a, gen_sde.base_sde
         if not hasattr(net, "ssm_grad"):
             raise MsgmError("UNetScoreTrainer needs a HIP U-Net score net (SGMsde or MSGMsde)")
@@ -401,19 +443,19 @@ class UNetScoreTrainer(_TrainerState):
         self.graph = None
         _init_row_weights(self, row_weights)
         _adopt_stream(self)
+        _init_data(self, data)
 
     def set_data(self, x, weight: Optional[torch.Tensor] = None):
         _set_data(self, x, weight)
 
     def _fwd_bwd(self):
         """Everything before the collective; leaves [grads | loss] (already x 1/global_batch) in ``gbuf``."""
-        lib, s = ops.lib(), ops.stream()
+        _draw_data(self)
         if self.msgm:
             y, t, vp, u, cst = _msgm_draws(self)
             ops.counter_inc(self.step_dev)
         else:
-            ops.check(lib.msgm_ssm_prep(self.x.data_ptr(), self.y.data_ptr(), self.t.data_ptr(), self.vp.data_ptr(), self.B,
-                                        self.d, self.st, self.rng.ptr(), self.step_dev.data_ptr(), s), "msgm_ssm_prep")
+            _ssm_prep(self)
             y, t, vp = self.y, self.t, self.vp
             u, cst = ops.ssm_terms(y, vp, t, self.st)
         per = self.net.ssm_grad(y, t, vp, u, cst, self.inv_batch, rng=self.rng,     # 2-D U-Net dropout masks: the trainer's stream
