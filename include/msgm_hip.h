@@ -382,6 +382,25 @@ int msgm_mlp_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msg
                       uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop,
                       float* kept, void* workspace, size_t workspace_bytes, msgm_stream_t stream);
 
+/* The same loop for the extra-wide MLP class (d > 30 or d + 1 + premodule > 32, d <= 128: the widths of the reference's
+ * real data sets), k_mlp_xw's sampler-loop mode: what the driver's rk4_stratonovich_sampler call (MSGM_higherDim.py:702,
+ * 903; sde_scheme.py:174-269), heun_sampler (sde_scheme.py:101-172) and the multiplicative euler_maruyama_sampler
+ * (sde_scheme.py:43-99) run there.  Arguments, draws, stage times, trajectory and kept rows, workspace layout and the
+ * BADARG / UNSUPPORTED / WORKSPACE checks are those of msgm_mlp_sde_loop; the grid is min(tiles / 2, 256) workgroups of
+ * 32-row tiles, one per CU.  msgm_mlp_xw_sde_loop_supported: n == d <= 128, the shape is in the extra-wide class, the
+ * family is SGM or the sparse tensor (a dense tensor stops at n = 16) and B > 32; it answers 0 for every shape that
+ * msgm_mlp_sde_loop_supported takes, so at most one of the two entries accepts a shape.
+ * msgm_mlp_xw_sde_loop_preferred: the supported shapes that the public samplers send here — those measured faster than
+ * the composed route at the driver's B = 10 000, N = 128 (SGM up to d = 64, the sparse tensor up to d = 40); the rest of
+ * the class stays composed, though the entry takes it. */
+int msgm_mlp_xw_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B);   /* host only */
+int msgm_mlp_xw_sde_loop_preferred(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B);   /* host only */
+size_t msgm_mlp_xw_sde_loop_workspace(int64_t B, int32_t d, int32_t method);                              /* host only */
+int msgm_mlp_xw_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts,
+                         int32_t n_steps, float delta, float sqrt_delta, float lmbd, const float* z, const uint64_t* rng,
+                         uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop,
+                         float* kept, void* workspace, size_t workspace_bytes, msgm_stream_t stream);
+
 /* Fused SSM training pass for SGM + MLP (replaces SDEs.py:607-646 +
  * loss.mean().backward(), MSGM_higherDim.py:807-808):
  *   per sample: a = MLP(y,t), adot = J_a v (forward-mode), loss_b =

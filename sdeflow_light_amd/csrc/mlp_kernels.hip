@@ -597,10 +597,15 @@ __device__ __forceinline__ void sde_issue(const MlpArgs& A, SdeRegs<NR>& sr, con
   }
 }
 
-template <class LO, int NT, int NW, int NR>
-__device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& sr, float* PART, const float* B4s, float* R,
-                                           int64_t s_base, int tid, SdeItem it) {
-  constexpr int PP = LO::PP;
+// What the two kernels do differently is handed in: AIMG, the LDS image [sample][o] (pitch AP) of the net's output a, which
+// `gather(c, o)` completes for element (c, o) before the first barrier (k_mlp: the bias plus the waves' K-slices; k_mlp_xw:
+// nothing, layer 4 left it there); VIMG, a free image of the same pitch that takes the updated row under norm correction;
+// `row_of(idx)` = idx / d.  ROWSUM: the row's sum of squares is formed once per row by the NT / SPT threads of a group
+// (contiguous elements each, partial sums met by shuffle in a fixed order) and passed through RED, instead of every
+// thread summing the whole row (at d = 128 that would be 128 LDS reads per element).
+template <class LO, int NT, int AP, bool ROWSUM, int NR, class ROW, class GATHER>
+__device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& sr, const float* AIMG, float* VIMG, float* RED,
+                                           ROW row_of, GATHER gather, float* R, int64_t s_base, int tid, SdeItem it) {
   const int d = A.P.d, NS = A.n_stages;
   const int64_t etot = A.B * d;
   const bool last = it.stage == NS - 1;
@@ -609,16 +614,13 @@ __device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& 
   S.kind = A.kind; S.proc = MSGM_PROC_REVERSE; S.strato = NS > 1;
   S.b0 = A.b0; S.b1 = A.b1; S.T = A.T; S.delta = A.delta; S.sqrt_delta = A.sqrt_delta; S.lmbd = A.lmbd;
   const float sig_scale = stage_sig_scale(S);
-  // a = b4 + the waves' K-slices, parked in wave 0's slice; stage 0 draws the step's Wiener increment
+  // a into its image; stage 0 draws the step's Wiener increment
 #pragma unroll
   for (int k = 0; k < NR; ++k) {
-    const int idx = tid + NT * k, c = idx / d, o = idx - c * d;
+    const int idx = tid + NT * k, c = row_of(idx), o = idx - c * d;
     const int64_t e = s_base * d + idx;
     if (idx < LO::SPT * d && e < etot) {
-      float a = B4s[o];
-#pragma unroll
-      for (int ww = 0; ww < NW; ++ww) a += PART[(ww * 32 + c) * PP + o];
-      PART[c * PP + o] = a;
+      gather(c, o);
       if (it.stage == 0) {
         const float zz = A.z ? A.z[(int64_t)it.i * etot + e]
                              : philox_normal1(A.rng, A.rng_step + (uint64_t)it.i, RNG_STREAM_DW, (uint64_t)e);
@@ -632,13 +634,13 @@ __device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& 
   float val[NR];
 #pragma unroll
   for (int k = 0; k < NR; ++k) {
-    const int idx = tid + NT * k, c = idx / d, o = idx - c * d;
+    const int idx = tid + NT * k, c = row_of(idx), o = idx - c * d;
     const int64_t e = s_base * d + idx;
     val[k] = 0.f;
     if (idx < LO::SPT * d && e < etot) {
       const float* xr = R + LO::RY + c * d;
       const float* wr = R + LO::RW + c * d;
-      const float* ar = PART + c * PP;
+      const float* ar = AIMG + c * AP;
       const StageCoef sc = stage_coef<false>(S, R[LO::RT + c], 0);
       const float xi = xr[o];
       float inc;
@@ -672,22 +674,38 @@ __device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& 
         else if (NS == 2) { v = 1.0f * x; v += 0.5f * sr.sm[k]; v = v + 0.5f * inc; }
         else v = rk4_close(x, sr.sm[k], 0.f + 1.0f * inc);
         val[k] = v;
-        if (nc) PART[(32 + c) * PP + o] = v;
+        if (nc) VIMG[c * AP + o] = v;
       }
     }
   }
   if (!last) return;
   if (nc) lds_barrier();
+  if constexpr (ROWSUM) {
+    if (nc) {
+      constexpr int GS = NT / LO::SPT;                         // threads per row: elements [sub per, sub per + per) each
+      const int c = tid / GS, sub = tid % GS, per = (d + GS - 1) / GS;
+      const float* row = VIMG + c * AP;
+      float ss = 0.f;
+      for (int j = sub * per; j < (sub + 1) * per && j < d; ++j) ss += row[j] * row[j];
+#pragma unroll
+      for (int m = 1; m < GS; m <<= 1) ss += __shfl_xor(ss, m, 64);
+      if (sub == 0) RED[c] = ss;
+      lds_barrier();
+    }
+  }
 #pragma unroll
   for (int k = 0; k < NR; ++k) {
-    const int idx = tid + NT * k, c = idx / d;
+    const int idx = tid + NT * k, c = row_of(idx);
     const int64_t e = s_base * d + idx, smp = s_base + c;
     if (idx < LO::SPT * d && e < etot) {
       float v = val[k];
       if (nc) {                                                // x <- x norm0/|x|   sde_scheme.py:85-86
-        const float* row = PART + (32 + c) * PP;
         float ss = 0.f;
-        for (int j = 0; j < d; ++j) ss += row[j] * row[j];
+        if constexpr (ROWSUM) ss = RED[c];
+        else {
+          const float* row = VIMG + c * AP;
+          for (int j = 0; j < d; ++j) ss += row[j] * row[j];
+        }
         v *= A.norm0[smp] / sqrtf(ss);
       }
       A.out[e] = v;
@@ -943,7 +961,15 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
     // ---- phase 4: reduce layer-4 partials; outputs / loss ------------------
     if constexpr (MODE == MODE_SDE) {
       // the update first: its stores drain to L2 under the next item's layer 1
-      sde_update<LO, NT, NW>(A, sr, PART, B4s, const_cast<float*>(Rc), s_base, tid, sde_item(A, step));   // (stage 0 parks dW in it)
+      // a = b4 + the waves' K-slices, parked in wave 0's slice; the updated row goes to wave 1's (dead after the reduce)
+      sde_update<LO, NT, PP, false>(A, sr, PART, PART + 32 * PP, nullptr, [=](int idx) { return idx / d; },
+                                    [=](int c, int o) {
+                                      float a = B4s[o];
+#pragma unroll
+                                      for (int ww = 0; ww < NW; ++ww) a += PART[(ww * 32 + c) * PP + o];
+                                      PART[c * PP + o] = a;
+                                    },
+                                    const_cast<float*>(Rc), s_base, tid, sde_item(A, step));   // (stage 0 parks dW in it)
       layer1(H0n, Yc);                                         // next item's h1 (h2 is dead)
       __syncthreads();   // + vmcnt(0): what this item wrote must have left the CU before a later item re-reads it
       tile = ntile; step = nstep;
@@ -1095,12 +1121,14 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
 template <int MODE>
 struct MlpLdsXW {
   static constexpr bool TRAIN = MODE == 2;
+  static constexpr bool SDE = MODE == 3;
   static constexpr int SPT = TRAIN ? 16 : 32;      // samples per tile
-  // raw input buffer: y | v (pitch d), t, cst; u is read straight from global memory by the loss phase
+  // raw input buffer: y | v (pitch d; sampler loop: y | dW), t, cst; u is read straight from global memory by the loss phase
   static constexpr int DMAX = HID;                 // raw rows are packed (pitch d), sized for d <= DMAX
   static constexpr int RY = 0;
   static constexpr int RV = RY + SPT * DMAX;
-  static constexpr int RT = RV + (TRAIN ? SPT * DMAX : 0);
+  static constexpr int RW = RV + (TRAIN ? SPT * DMAX : 0);
+  static constexpr int RT = RW + (SDE ? SPT * DMAX : 0);
   static constexpr int RWT = RT + 16;              // train (16 rows a tile): the optional row weights, in RT's upper half
   static constexpr int RC = RT + 32;
   static constexpr int RAWN = RC + 16;
@@ -1108,7 +1136,7 @@ struct MlpLdsXW {
   static constexpr int Y = X + 32 * ACT_P;
   static constexpr int Z = Y + 32 * ACT_P;                     // train: h3, then zbar2 (inference: h3 goes to X|Y)
   static constexpr int U = Z + (TRAIN ? 32 * ACT_P : 0);       // train: layer-4 output image, then zbar3, then zbar1
-  static constexpr int ABAR = U + (TRAIN ? 32 * ACT_P : 0);    // train: cotangent of layer 4's output [sample][o]
+  static constexpr int ABAR = U + ((TRAIN || SDE) ? 32 * ACT_P : 0);   // (sampler loop: the image is all U holds); train: cotangent of layer 4's output [sample][o]
   static constexpr int H0 = ABAR + (TRAIN ? 32 * ACT_P : 0);   // double-buffered (built one tile ahead)
   static constexpr int B1 = H0 + 2 * 32 * XP;
   static constexpr int B2 = B1 + HID;
@@ -1207,6 +1235,7 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
   // h0, GS = NT / SPT per sample row.
   constexpr int NR = SPT * LO::DMAX / NT, GS = NT / SPT;
   RawRegs<NR> pf;
+  [[maybe_unused]] SdeRegs<MODE == MODE_SDE ? NR : 0> sr;   // sampler loop: the stage update's own operands
   auto issue = [&](int64_t tl, int step = 0) { raw_issue<MODE, LO, NT, false>(A, pf, (w << 6) + lane_v, tid, tl, step); };
   auto commit = [&](float* R) { raw_commit<MODE, LO, NT, false>(A, pf, R, (w << 6) + lane_v, tid); };
   auto h0_rows = [&](float* H0b, const float* R, int64_t tl) {
@@ -1285,7 +1314,10 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
   // dW1[fb + 4q][il] (+ r rows, + (it, kt) scalar) and dW4[o = il][fb + 4q] (+ (it, kt) scalar)
   auto vo1 = [&] { return (((fb + 4 * (lane_v >> 4)) * in_dim + (lane_v & 15)) * 4); };
   auto vo4 = [&] { return (int)((L.oW4 + (int64_t)(lane_v & 15) * HID + fb + 4 * (lane_v >> 4)) * 4); };
-  const int n_steps = (MODE == MODE_EM && A.n_steps > 1) ? A.n_steps : 1;
+  // Items as in k_mlp: (step, tile), or (step, stage, tile) in the sampler loop, the tile fastest, >= 2 tiles per workgroup.
+  const int n_steps = MODE == MODE_SDE ? A.n_steps * A.n_stages : ((MODE == MODE_EM && A.n_steps > 1) ? A.n_steps : 1);
+  // sampler loop: idx / d for idx < 32 d <= 4096 by one multiply (idx r < 2^20 for the r <= d that mdiv d exceeds 2^20 by)
+  const unsigned mdiv = (1u << 20) / (unsigned)d + 1u;
   int step = 0;
   for (int64_t tile = blockIdx.x; tile < n_tiles;) {
     asm volatile("" : "+v"(lane_v));
@@ -1312,6 +1344,7 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
     // ---- layer 3; h3 -> Z (train) / Xc (inference: h1 is dead)
     if (!TRN) h0_rows(H0n, Rn, ntile);
     else issue(ntile);
+    if constexpr (MODE == MODE_SDE) sde_issue<LO, NT>(A, sr, Rc, s_base, (w << 6) + lane_v, sde_item(A, step));   // x and S, in flight during the gemm
     fwd_hidden<TRN, TRN, IT>(R3, TRN ? R3 : R2, pre, Yc, B3s, fb, il, q, z3, h);   // then W3^T for dgrad / next tile's layer 2
     float* H3 = TRN ? Z : Xc;
     store_act<IT>(H3, fb, il, q, h);
@@ -1330,7 +1363,27 @@ __global__ void __launch_bounds__(256, 1) k_mlp_xw(MlpArgs A) {
       if (!TRN) z4[it][1] += bb;
     }
 
-    if (!TRN) {
+    if constexpr (MODE == MODE_SDE) {
+      // the stage update: thread tv owns elements tv + 256 k of the tile; a is read from the image, the updated row of the
+      // norm correction goes to Yc (h2 is dead, the next item's h1 is not written yet), its row sums to RED.  Its stores
+      // drain to L2 under the next item's layer 1.
+      // layer-4 output image [sample][o], as the training mode's
+#pragma unroll
+      for (int it = 0; it < IT; ++it) {
+        if (it >= nit4) continue;
+        const int o0 = 16 * (w + NW * it);
+#pragma unroll
+        for (int ck = 0; ck < 2; ++ck) *reinterpret_cast<f32x4*>(U + (ck * 16 + il) * ACT_P + o0 + 4 * q) = z4[it][ck];
+      }
+      lds_barrier();
+      sde_update<LO, NT, ACT_P, true>(A, sr, U, Yc, RED, [&](int idx) { return (int)(((unsigned)idx * mdiv) >> 20); },
+                                      [](int, int) {}, const_cast<float*>(Rc), s_base, (w << 6) + lane_v,
+                                      sde_item(A, step));   // (stage 0 parks dW in Rc)
+      layer1(H0n, Yc);                                   // next item's h1
+      __syncthreads();   // + vmcnt(0): what this item wrote must have left the CU before a later item re-reads it
+      tile = ntile; step = nstep;
+      continue;
+    } else if (!TRN) {
       // outputs straight from the accumulators: lane (sample 16ck + il), register r -> output o0 + 4q + r
 #pragma unroll
       for (int it = 0; it < IT; ++it) {
@@ -1569,8 +1622,7 @@ static int64_t mlp_wg_per_cu(const MlpArgs& A) { return mlp_xwide(A) ? 1 : (mlp_
 
 template <int MODE>
 static int launch_mlp(const MlpArgs& A, int grid, hipStream_t st) {
-  if constexpr (MODE == MODE_SDE) { if (mlp_xwide(A)) return MSGM_E_UNSUPPORTED; }   // the sampler loop has no extra-wide form
-  else if (mlp_xwide(A)) return launch_kernel<k_mlp_xw<MODE>, MlpLdsXW<MODE>::BYTES, 256>(A, grid, st);
+  if (mlp_xwide(A)) return launch_kernel<k_mlp_xw<MODE>, MlpLdsXW<MODE>::BYTES, 256>(A, grid, st);
   constexpr int nw_w = MlpCfg<MODE, true>::NW, nw_n = MlpCfg<MODE, false>::NW;
   if (A.in_dim > 16 || A.P.d > 16)
     return launch_kernel<k_mlp<MODE, true, nw_w, false>, MlpLds<MODE, true, nw_w>::BYTES, 64 * nw_w>(A, grid, st);
@@ -1656,7 +1708,7 @@ static int sde_loop_stages(int32_t method) {
 }
 
 int msgm_mlp_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B) {
-  if (d < 1 || d > 30 || d + 1 + (premodule ? 1 : 0) > 32 || n != d) return 0;     // the extra-wide class stays composed
+  if (d < 1 || d > 30 || d + 1 + (premodule ? 1 : 0) > 32 || n != d) return 0;     // the extra-wide class: msgm_mlp_xw_sde_loop
   if (kind != MSGM_SDE_SGM && kind != MSGM_SDE_MSGM_SPARSE && kind != MSGM_SDE_MSGM_DENSE) return 0;
   if (kind == MSGM_SDE_MSGM_DENSE && n > 16) return 0;
   return B > 32;                                           // a workgroup needs two tiles to prefetch one ahead
@@ -1667,17 +1719,36 @@ size_t msgm_mlp_sde_loop_workspace(int64_t B, int32_t d, int32_t method) {
   return (size_t)3 * (size_t)B * (size_t)d * sizeof(float);
 }
 
-int msgm_mlp_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts,
-                      int32_t n_steps, float delta, float sqrt_delta, float lmbd, const float* z, const uint64_t* rng,
-                      uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop, float* kept,
-                      void* workspace, size_t workspace_bytes, msgm_stream_t stream) {
+int msgm_mlp_xw_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B) {
+  if (d < 1 || d > HID || n != d) return 0;
+  if (d <= 30 && d + 1 + (premodule ? 1 : 0) <= 32) return 0;                       // the narrower classes: msgm_mlp_sde_loop
+  if (kind != MSGM_SDE_SGM && kind != MSGM_SDE_MSGM_SPARSE) return 0;              // a dense tensor stops at n = 16
+  return B > 32;                                           // a workgroup needs two tiles to prefetch one ahead
+}
+
+size_t msgm_mlp_xw_sde_loop_workspace(int64_t B, int32_t d, int32_t method) { return msgm_mlp_sde_loop_workspace(B, d, method); }
+
+// Where the public samplers route to the loop: the supported shapes whose Heun and RK4 calls beat the composed route at the
+// driver's size (B = 10 000, N = 128; DESIGN §4 has the table) — SGM up to d = 64, the sparse tensor up to d = 40.  Wider
+// rows make an item longer than the composed route's launches, and the workgroup that carries a third tile sets the time.
+int msgm_mlp_xw_sde_loop_preferred(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B) {
+  if (!msgm_mlp_xw_sde_loop_supported(d, premodule, kind, n, B)) return 0;
+  return kind == MSGM_SDE_SGM ? d <= 64 : d <= 40;
+}
+
+// The two sampler-loop entries: every check and argument in one place, `supported` is the entry's own shape rule.
+static int sde_loop_launch(int (*supported)(int32_t, int32_t, int32_t, int64_t, int64_t), const msgm_mlp_params_t* P, float* x,
+                           int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts, int32_t n_steps, float delta,
+                           float sqrt_delta, float lmbd, const float* z, const uint64_t* rng, uint64_t rng_step0,
+                           const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop, float* kept,
+                           void* workspace, size_t workspace_bytes, msgm_stream_t stream) {
   MlpArgs A{};
   int rc = fill_common(A, P, B);
   if (rc) return rc;
   const int stages = sde_loop_stages(method);
   if (!x || !sde || !ts || n_steps < 1 || !stages || (!z && !rng) || (keep_stop && !kept)) return MSGM_E_BADARG;
   if (sde->kind == MSGM_SDE_MSGM_DENSE && (!sde->G || !sde->L_G)) return MSGM_E_BADARG;
-  if (!msgm_mlp_sde_loop_supported(P->d, P->premodule, sde->kind, P->d, B)) return MSGM_E_UNSUPPORTED;
+  if (!supported(P->d, P->premodule, sde->kind, P->d, B)) return MSGM_E_UNSUPPORTED;
   const size_t need = msgm_mlp_sde_loop_workspace(B, P->d, method);
   if (need && (!workspace || workspace_bytes < need)) return MSGM_E_WORKSPACE;
   A.y = x; A.out = x; A.t = nullptr;
@@ -1694,6 +1765,23 @@ int msgm_mlp_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msg
   const int64_t cap = mlp_wg_per_cu(A) * MLP_MAX_GRID;
   const int64_t grid = tiles / 2 < cap ? tiles / 2 : cap;   // at least two tiles per workgroup
   return launch_mlp<MODE_SDE>(A, (int)grid, S(stream));
+}
+
+int msgm_mlp_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts,
+                      int32_t n_steps, float delta, float sqrt_delta, float lmbd, const float* z, const uint64_t* rng,
+                      uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop, float* kept,
+                      void* workspace, size_t workspace_bytes, msgm_stream_t stream) {
+  return sde_loop_launch(msgm_mlp_sde_loop_supported, P, x, B, sde, method, ts, n_steps, delta, sqrt_delta, lmbd, z, rng, rng_step0,
+                         norm0, traj, include_t0, keep_stop, kept, workspace, workspace_bytes, stream);
+}
+
+// k_mlp_xw<MODE_SDE>: one workgroup per CU, so the grid is min(tiles / 2, 256)
+int msgm_mlp_xw_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts,
+                         int32_t n_steps, float delta, float sqrt_delta, float lmbd, const float* z, const uint64_t* rng,
+                         uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop,
+                         float* kept, void* workspace, size_t workspace_bytes, msgm_stream_t stream) {
+  return sde_loop_launch(msgm_mlp_xw_sde_loop_supported, P, x, B, sde, method, ts, n_steps, delta, sqrt_delta, lmbd, z, rng,
+                         rng_step0, norm0, traj, include_t0, keep_stop, kept, workspace, workspace_bytes, stream);
 }
 
 int msgm_mlp_ssm_partial(const msgm_mlp_params_t* P, const float* y, const float* t, const float* v, const float* u,

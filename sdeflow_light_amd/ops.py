@@ -481,6 +481,42 @@ def mlp_sde_loop(P: L.MlpParamsT, x: torch.Tensor, sde: L.SdeT, method: str, ts:
     launch; x (B,d) becomes the final state.  ts: device fp32 time grid; z: optional (N,B,d) normals, else Philox steps
     rng_step0 + i; traj: optional (N + include_t0, B, d), rows include_t0.. are written; keep / kept: keep_rows after
     every step; workspace: mlp_sde_loop_workspace(B, d, method), allocated here when None."""
+    return _sde_loop("msgm_mlp_sde_loop", mlp_sde_loop_workspace, P, x, sde, method, ts, delta, lmbd, z, rng, rng_step0, norm0,
+                     traj, include_t0, keep, kept, workspace)
+
+
+def mlp_xw_sde_loop_supported(d: int, premodule: bool, kind: int, n: int, B: int) -> bool:
+    """Whether msgm_mlp_xw_sde_loop takes this shape: the extra-wide class (d > 30 or in_dim > 32) up to d = n = 128, SGM or
+    the sparse tensor, B > 32.  Never true where mlp_sde_loop_supported is."""
+    return bool(lib().msgm_mlp_xw_sde_loop_supported(int(d), int(bool(premodule)), int(kind), int(n), int(B)))
+
+
+def mlp_xw_sde_loop_preferred(d: int, premodule: bool, kind: int, n: int, B: int) -> bool:
+    """Whether the public samplers send this shape to msgm_mlp_xw_sde_loop: supported and measured faster than the composed
+    route (SGM up to d = 64, the sparse tensor up to d = 40)."""
+    return bool(lib().msgm_mlp_xw_sde_loop_preferred(int(d), int(bool(premodule)), int(kind), int(n), int(B)))
+
+
+def mlp_xw_sde_loop_workspace(B: int, d: int, method: str, device) -> Optional[torch.Tensor]:
+    """The stage state of the extra-wide loop, as mlp_sde_loop_workspace; None for Euler-Maruyama."""
+    nbytes = int(lib().msgm_mlp_xw_sde_loop_workspace(int(B), int(d), SDE_LOOP_METHODS[method]))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def mlp_xw_sde_loop(P: L.MlpParamsT, x: torch.Tensor, sde: L.SdeT, method: str, ts: torch.Tensor, delta: float,
+                    lmbd: float = 0.0, z: Optional[torch.Tensor] = None, rng: Optional[PhiloxState] = None, rng_step0: int = 0,
+                    norm0: Optional[torch.Tensor] = None, traj: Optional[torch.Tensor] = None, include_t0: bool = False,
+                    keep: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mlp_sde_loop for the extra-wide MLP class (31 <= d <= 128, or in_dim > 32): same arguments, draws and outputs, in
+    ONE launch of k_mlp_xw's sampler-loop mode; workspace: mlp_xw_sde_loop_workspace(B, d, method), allocated here when None."""
+    return _sde_loop("msgm_mlp_xw_sde_loop", mlp_xw_sde_loop_workspace, P, x, sde, method, ts, delta, lmbd, z, rng, rng_step0,
+                     norm0, traj, include_t0, keep, kept, workspace)
+
+
+def _sde_loop(entry, workspace_of, P, x, sde, method, ts, delta, lmbd, z, rng, rng_step0, norm0, traj, include_t0, keep, kept,
+              workspace):
+    """The checks and the call that the two sampler-loop entries share."""
     if method not in SDE_LOOP_METHODS:
         raise MsgmError(f"unknown integrator {method}")
     if x.dim() != 2 or not x.is_cuda:
@@ -501,12 +537,12 @@ def mlp_sde_loop(P: L.MlpParamsT, x: torch.Tensor, sde: L.SdeT, method: str, ts:
         if tt is not None:
             f32(tt, nm)
     if workspace is None:
-        workspace = mlp_sde_loop_workspace(B, d, method, x.device)
+        workspace = workspace_of(B, d, method, x.device)
     nbytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
-    check(lib().msgm_mlp_sde_loop(P, ptr(f32(x)), B, sde, SDE_LOOP_METHODS[method], ptr(ts), N, float(delta), float(delta ** 0.5),
-                                  float(lmbd), ptr(z), _rng_ptr(rng), int(rng_step0), ptr(norm0), ptr(traj),
-                                  int(bool(include_t0)), ptr(keep), ptr(kept), ptr(workspace), nbytes, stream()),
-          "msgm_mlp_sde_loop")
+    check(getattr(lib(), entry)(P, ptr(f32(x)), B, sde, SDE_LOOP_METHODS[method], ptr(ts), N, float(delta), float(delta ** 0.5),
+                                float(lmbd), ptr(z), _rng_ptr(rng), int(rng_step0), ptr(norm0), ptr(traj),
+                                int(bool(include_t0)), ptr(keep), ptr(kept), ptr(workspace), nbytes, stream()),
+          entry)
     return x
 
 

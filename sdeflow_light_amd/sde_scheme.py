@@ -6,7 +6,8 @@ Per step the reference launches ~20 eager kernels plus a host ``.item()`` and,
 with ``keep_all_samples``, a blocking D2H copy (sde_scheme.py:80-92).  Here a
 step is ONE fused stage kernel after the score net (or one kernel in total for
 MLP + SGM: ``msgm_mlp_em_step``; with the MLP, Heun, RK4-Stratonovich and the multiplicative Euler-Maruyama are one
-kernel for the WHOLE loop, ``msgm_mlp_sde_loop``, when ``_Run.mlp_loop`` finds the shape supported), the time grid is computed on the host exactly
+kernel for the WHOLE loop, ``msgm_mlp_sde_loop`` or ``msgm_mlp_xw_sde_loop``, when ``_Run.mlp_loop`` finds the shape
+routed there), the time grid is computed on the host exactly
 as upstream (fp32 ``linspace``) and passed by value, trajectories are captured
 into a device buffer and copied once at the end, and the whole fused loop can
 be replayed as a single hipGraph (``GraphedEMSampler``).
@@ -175,19 +176,27 @@ class _Run:
             ops.keep_rows(self.kept, self.x, self.keep, i + int(self.include_t0))
 
     def mlp_loop(self, method):
-        """The whole loop as ONE launch (``msgm_mlp_sde_loop``) when the shapes allow it: the reverse process of the MLP,
-        Philox noise, and a shape the kernel takes (``ops.mlp_sde_loop_supported``: d <= 30 and in_dim <= 32, dense tensors
-        up to n = 16, B > 32).  Same time grid, stage times and Philox draws as the composed steps; trajectory rows and
-        kept rows are written by the kernel.  Returns whether it ran; everything else keeps the composed route."""
+        """The whole loop as ONE launch when the shapes allow it: the reverse process of the MLP, Philox noise, and a shape
+        one of the two kernels takes — ``msgm_mlp_sde_loop`` (``ops.mlp_sde_loop_supported``: d <= 30 and in_dim <= 32, dense
+        tensors up to n = 16, B > 32), tried first, or ``msgm_mlp_xw_sde_loop`` (``ops.mlp_xw_sde_loop_preferred``: the part
+        of the extra-wide class where the loop was measured faster than the composed steps — SGM up to d = 64, the sparse
+        tensor up to d = 40, B > 32).  Same time grid, stage times and Philox draws as
+        the composed steps; trajectory rows and kept rows are written by the kernel.  Returns whether it ran; everything
+        else keeps the composed route."""
         from .NN import MLP
         net = self.sde.a if self.reverse else None
         if not isinstance(net, MLP) or self.noise is not None or net.input_dim != self.n:
             return False
-        if not ops.mlp_sde_loop_supported(self.n, net.pre is not None, self.struct.kind, self.n, self.B):
+        shape = (self.n, net.pre is not None, self.struct.kind, self.n, self.B)
+        if ops.mlp_sde_loop_supported(*shape):
+            loop = ops.mlp_sde_loop
+        elif ops.mlp_xw_sde_loop_preferred(*shape):
+            loop = ops.mlp_xw_sde_loop
+        else:
             return False
-        ops.mlp_sde_loop(net.kernel_params(), self.x, self.struct, method, self.ts.to(self.device), self.delta, self.lmbd,
-                         rng=self.rng, rng_step0=0, norm0=self.norm0, traj=self.traj, include_t0=self.include_t0,
-                         keep=self.keep, kept=self.kept if self.keep is not None else None)
+        loop(net.kernel_params(), self.x, self.struct, method, self.ts.to(self.device), self.delta, self.lmbd,
+             rng=self.rng, rng_step0=0, norm0=self.norm0, traj=self.traj, include_t0=self.include_t0,
+             keep=self.keep, kept=self.kept if self.keep is not None else None)
         return True
 
     def result(self, advance=True):

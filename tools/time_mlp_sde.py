@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Wall time of the MLP samplers at the driver's sizes (MSGM_higherDim.py:903: B = 10 000, N = 128, keep_all_samples=True):
-the one-launch loop (msgm_mlp_sde_loop, what the public samplers route to) against the composed path (score net, stage
-kernels and glue as separate launches), alternated round by round in ONE process, device-synchronised, after a warm-up.
+the one-launch loop (msgm_mlp_sde_loop / msgm_mlp_xw_sde_loop, what the public samplers route to) against the composed
+path (score net, stage kernels and glue as separate launches), alternated round by round in ONE process, device-synchronised, after a warm-up.
 The composed path is also timed against itself (a second call in every round): the difference of the two medians is the
 spread a routing decision has to beat.
 
-    python tools/time_mlp_sde.py [--rounds 7] [--B 10000] [--steps 128] [--out FILE]
+    python tools/time_mlp_sde.py [--rounds 7] [--B 10000] [--steps 128] [--only TEXT] [--out FILE]
 
 Times cover the sampler up to the device synchronisation (set-up, every launch, trajectory capture), not the copy of
 the trajectory to the host, which both routes share.  One JSON line per (configuration, method)."""
@@ -26,7 +26,8 @@ CONFIGS = [  # (name, SDE family, d, premodule, norm correction)
     ("dense d=2 NLR nc", "dense", 2, NLR, True),
     ("sparse d=6 NLR nc", "sparse", 6, NLR, True),
     ("sparse d=20 nc", "sparse", 20, None, True),
-]
+] + [c for d in (40, 64, 90, 128) for c in (   # the extra-wide class (msgm_mlp_xw_sde_loop): the widths of the real data sets
+    (f"sgm d={d}", "sgm", d, None, False), (f"sparse d={d} NLR nc", "sparse", d, NLR, True))]
 
 
 def make_gen(kind, d, pre, dev):
@@ -49,9 +50,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--B", type=int, default=10000)
     ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--only", default="", help="time the configurations whose name contains this text")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    from sdeflow_light_amd import sde_scheme as SS
+    from sdeflow_light_amd import ops, sde_scheme as SS
+    ops.mlp_xw_sde_loop_preferred = ops.mlp_xw_sde_loop_supported   # time the loop wherever the kernel takes the shape
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     out = open(a.out, "w") if a.out else None
@@ -80,6 +83,8 @@ def main():
         return dt * 1e3
 
     for name, kind, d, pre, nc in CONFIGS:
+        if a.only not in name:
+            continue
         gen = make_gen(kind, d, pre, dev)
         x0 = torch.randn(a.B, d, device=dev)
         for method in ("rk4", "heun") + (("em",) if kind != "sgm" else ()):
