@@ -373,7 +373,7 @@ int msgm_mlp_em_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm
  *            sum of increments, (3, B, d) floats for Heun / RK4, nothing for Euler-Maruyama
  * x is updated in place to the final state.  Never allocates or synchronises.  MSGM_E_UNSUPPORTED where
  * msgm_mlp_sde_loop_supported says no: B <= 32 (a workgroup needs two tiles), the extra-wide class (d > 30 or
- * d + 1 + premodule > 32), dense tensors with n > 16. */
+ * d + 1 + premodule > 32), dense tensors with n > 16 (17 <= n <= 30: msgm_mlp_dense_sde_loop below). */
 enum { MSGM_METHOD_EM = 0, MSGM_METHOD_HEUN = 1, MSGM_METHOD_RK4 = 2 };
 int msgm_mlp_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B);   /* host only */
 size_t msgm_mlp_sde_loop_workspace(int64_t B, int32_t d, int32_t method);                              /* host only */
@@ -388,7 +388,7 @@ int msgm_mlp_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msg
  * (sde_scheme.py:43-99) run there.  Arguments, draws, stage times, trajectory and kept rows, workspace layout and the
  * BADARG / UNSUPPORTED / WORKSPACE checks are those of msgm_mlp_sde_loop; the grid is min(tiles / 2, 256) workgroups of
  * 32-row tiles, one per CU.  msgm_mlp_xw_sde_loop_supported: n == d <= 128, the shape is in the extra-wide class, the
- * family is SGM or the sparse tensor (a dense tensor stops at n = 16) and B > 32; it answers 0 for every shape that
+ * family is SGM or the sparse tensor (a dense tensor stops at n = 30, msgm_mlp_dense_sde_loop) and B > 32; it answers 0 for every shape that
  * msgm_mlp_sde_loop_supported takes, so at most one of the two entries accepts a shape.
  * msgm_mlp_xw_sde_loop_preferred: the supported shapes that the public samplers send here — those measured faster than
  * the composed route at the driver's B = 10 000, N = 128 (SGM up to d = 64, the sparse tensor up to d = 40); the rest of
@@ -400,6 +400,29 @@ int msgm_mlp_xw_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const 
                          int32_t n_steps, float delta, float sqrt_delta, float lmbd, const float* z, const uint64_t* rng,
                          uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop,
                          float* kept, void* workspace, size_t workspace_bytes, msgm_stream_t stream);
+
+/* The same loop for a dense rotation tensor with 17 <= n <= 30 (the driver's default multiplicative model at its real-data
+ * widths: MSGM_higherDim.py:61,702 denseTensor = True, ERA5 dims 18 and 30), a third instantiation of k_mlp's sampler-loop
+ * mode at the wide width: the contraction T[r,(i,k)] = sum_j x_rj G[i,j,k] of a 32-row tile runs on the matrix cores
+ * between the layer-4 reduce and the stage update, and gw = sb sum_k T w_k, ga = sb sum_k T a_k, f = beta L_G x come out
+ * of one pass (SDEs.py:415,432; sde_scheme.py:36).  An fp32 MFMA is a k-ordered fma chain, so the result is deterministic
+ * but not the bits of msgm_sde_stage's dense branch: parity of this entry is to float64.
+ *   g_packed   G and L_G in fragment order, msgm_dense_g_packed_floats(n) floats: block k < n holds G[:, :, k], block n
+ *              holds L_G; a block is [ib 2][sg 2][lane 64][r 4] with i = 16 ib + (lane & 15), j = 4 (4 sg + r) + (lane >> 4),
+ *              +0 where i or j >= n.  The host packs it (ops.pack_dense_g); the kernel streams it from L2.
+ * The other arguments, draws, stage times, trajectory and kept rows, workspace layout and checks are those of
+ * msgm_mlp_sde_loop; a missing G, L_G or g_packed is MSGM_E_BADARG.  The grid is min(tiles / 2, 256) workgroups, one per CU.
+ * msgm_mlp_dense_sde_loop_supported: the family is the dense tensor, 17 <= d == n <= 30, d + 1 + premodule <= 32 and
+ * B > 64 (B <= 64 would be one workgroup on one CU; it stays composed).  Neither of the other two entries takes such a shape.
+ * msgm_mlp_dense_sde_loop_preferred: the supported shapes that the public samplers send here (measured). */
+int msgm_mlp_dense_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B);   /* host only */
+int msgm_mlp_dense_sde_loop_preferred(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B);   /* host only */
+size_t msgm_mlp_dense_sde_loop_workspace(int64_t B, int32_t d, int32_t method);                              /* host only */
+size_t msgm_dense_g_packed_floats(int64_t n);                                                                /* host only */
+int msgm_mlp_dense_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts,
+                            int32_t n_steps, float delta, float sqrt_delta, float lmbd, const float* z, const uint64_t* rng,
+                            uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop,
+                            float* kept, void* workspace, size_t workspace_bytes, const float* g_packed, msgm_stream_t stream);
 
 /* Fused SSM training pass for SGM + MLP (replaces SDEs.py:607-646 +
  * loss.mean().backward(), MSGM_higherDim.py:807-808):

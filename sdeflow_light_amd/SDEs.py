@@ -275,6 +275,7 @@ class MSGMsde(SDE):
             self.name_SDE += "logNorm"
         self.estim_cst_norm_dens_r_T = bool(estim_cst_norm_dens_r_T or plot_validate)       # SDEs.py:256-257
         self._cst_log_dens = None
+        self._G_packed = None        # G and L_G in the dense sampler loop's fragment order: built on first use (packed_G)
 
     def to(self, device):
         new = super().to(device)
@@ -287,7 +288,17 @@ class MSGMsde(SDE):
         else:
             new.G = self.G.to(device).contiguous()
         new.L_G = self.L_G.to(device).contiguous()
+        new._G_packed = None         # rebuilt from the moved tensors when next needed
         return new
+
+    def packed_G(self):
+        """ops.pack_dense_g(G, L_G) for msgm_mlp_dense_sde_loop, built once per tensor on G's device.  A plain attribute:
+        not in state_dict() or checkpoints, and dropped by to()."""
+        if self.sparseTensor:
+            raise MsgmError("packed_G: the sparse tensor has no dense image")
+        if self._G_packed is None or self._G_packed.device != self.G.device:
+            self._G_packed = ops.pack_dense_g(self.G, self.L_G)
+        return self._G_packed
 
     @staticmethod
     def new_G(n):

@@ -187,6 +187,12 @@ SIGNATURES = {
     "msgm_mlp_xw_sde_loop_workspace": (_SZ, [_I64, _I32, _I32]),
     "msgm_mlp_xw_sde_loop": (C.c_int, [C.POINTER(MlpParamsT), _P, _I64, C.POINTER(SdeT), _I32, _P, _I32, _F, _F, _F, _P, _P, _U64, _P,
                                        _P, _I32, _P, _P, _P, _SZ, _P]),
+    "msgm_mlp_dense_sde_loop_supported": (C.c_int, [_I32, _I32, _I32, _I64, _I64]),
+    "msgm_mlp_dense_sde_loop_preferred": (C.c_int, [_I32, _I32, _I32, _I64, _I64]),
+    "msgm_mlp_dense_sde_loop_workspace": (_SZ, [_I64, _I32, _I32]),
+    "msgm_dense_g_packed_floats": (_SZ, [_I64]),
+    "msgm_mlp_dense_sde_loop": (C.c_int, [C.POINTER(MlpParamsT), _P, _I64, C.POINTER(SdeT), _I32, _P, _I32, _F, _F, _F, _P, _P, _U64,
+                                          _P, _P, _I32, _P, _P, _P, _SZ, _P, _P]),
     "msgm_mlp_ssm_workspace": (_SZ, [_I32, _I32]),
     "msgm_mlp_num_params": (_I64, [_I32, _I32]),
     "msgm_mlp_ssm_partial": (C.c_int, [C.POINTER(MlpParamsT), _P, _P, _P, _P, _P, _I64, C.POINTER(SdeT), _F, _P, _P, _SZ,

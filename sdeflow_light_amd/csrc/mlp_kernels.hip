@@ -125,6 +125,7 @@ struct MlpArgs {
   float* ws;                       // (3, B, d) stage state: evaluation point | Wiener increment | running sum of increments
   float* traj; int include_t0;     // optional (N[+1], B, d): row i + include_t0 receives the state after step i
   const int32_t* keep_stop; float* kept;   // optional: row b of kept receives the state after step keep_stop[b] - include_t0
+  const float* Gp;                 // dense tensor, 17 <= n <= 30 (k_mlp<MODE_SDE, wide, DENSE_MM>): G and L_G in fragment order
 };
 
 enum { MODE_FWD = 0, MODE_EM = 1, MODE_TRAIN = 2, MODE_SDE = 3 };
@@ -567,6 +568,135 @@ __device__ __forceinline__ float em_update(const MlpArgs& A, float ca, float a, 
   return x + (mu * A.delta + (sqrtf(1.0f - A.lmbd) * sb) * (A.sqrt_delta * zz));
 }
 
+// ---- dense tensor with 17 <= n <= 30 (DENSE_MM): the contraction as a GEMM on the matrix cores, between the layer-4 reduce
+// and the stage update.  With T[r,(i,k)] = sum_j x_rj G[i,j,k] both products come from one pass: gw_ri = sb sum_k T[r,i,k] w_rk
+// and ga_ri likewise with a; one more block of the same shape, L_G in G's place, gives f_ri = beta sum_j L_G[i,j] x_rj.
+//   M = the tile's 32 rows (A operand: the evaluation point in the raw row, j >= n masked to +0), K = j padded to 32,
+//   N-block = 16 values of i at a FIXED k, so D holds T[row 4q + r][i = il] in register r and the lane multiplies it by
+//   its rows' w_k / a_k (LDS broadcasts) and sums in registers: no cross-lane reduction.
+// Wave (ib, kh) takes the i-half ib of the blocks k = kh, kh + 2, ..; the waves kh = 1 also take the L_G block.  A block is
+// 2 x 8 MFMAs, the two row tiles being independent accumulator chains, and its B fragments (two b128 buffer loads a lane
+// from the packed image, ops.pack_dense_g's layout: include/msgm_hip.h) are requested one block ahead.  The two k-halves of gw and ga land in
+// two images each and are added by the reader, always in the order kh = 0, 1.
+constexpr int DMM_P = 36;            // pitch of an image row [sample][o]: q's four rows fall into four different bank groups
+constexpr int DMM_BLOCK = 2 * 2 * 64 * 4;   // floats of one block (k or L_G): [ib][sg][lane][r]
+template <int NW>
+struct MlpDenseLds : MlpLds<MODE_SDE, true, NW> {
+  using Base = MlpLds<MODE_SDE, true, NW>;
+  static constexpr int FI = Base::FLOATS;                 // L_G x
+  static constexpr int GWI = FI + 32 * DMM_P;             // sum_k T w, k-half 0 | 1
+  static constexpr int GAI = GWI + 2 * 32 * DMM_P;        // sum_k T a, k-half 0 | 1
+  static constexpr int FLOATS = GAI + 2 * 32 * DMM_P;
+  static constexpr int BYTES = FLOATS * 4;
+  static_assert(NW == 4, "one wave per (i-half, k-half)");
+  static_assert(Base::BYTES == 115456 && BYTES == 138496 && BYTES <= 160 * 1024, "the wide sampler carve plus five images must fit a CU");
+};
+
+struct NoDenseMM {
+  static constexpr bool ON = false;
+  struct Pre {};
+  __device__ __forceinline__ Pre issue() const { return {}; }
+  __device__ __forceinline__ void run(const Pre&) const {}
+};
+template <class LO, int AP>
+struct DenseMM {
+  static constexpr bool ON = true;
+  const MlpArgs& A; const float* R; const float* AIMG; float* lds; int tid;
+  struct Pre { f32x4 g0, g1; float xa[2][8]; };
+  __device__ __forceinline__ wrsrc_t rsrc() const {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.Gp), 0, (A.P.d + 1) * DMM_BLOCK * 4, 0x00020000);
+  }
+  // fragment sg of block kk for i-half ib (all three scalar: the block's place is the buffer load's scalar offset)
+  __device__ __forceinline__ f32x4 frag(wrsrc_t GR, int kk, int ib, int sg) const {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(GR, (tid & 63) * 16, ((kk * 2 + ib) * 2 + sg) * 1024, 0));
+  }
+  // at the head of the stage update: the wave's first block is requested and the A operand read while a and dW are formed
+  __device__ __forceinline__ Pre issue() const {
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int il = tid & 15, q = (tid & 63) >> 4, n = A.P.d;
+    const wrsrc_t GR = rsrc();
+    Pre p;
+    p.g0 = frag(GR, w >> 1, w & 1, 0); p.g1 = frag(GR, w >> 1, w & 1, 1);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int j = 4 * s + q;
+        p.xa[mt][s] = j < n ? R[LO::RY + (16 * mt + il) * n + j] : 0.f;
+      }
+    return p;
+  }
+  // after the barrier behind `gather` (a and the Wiener increment are complete); ends with the barrier its readers need
+  __device__ __forceinline__ void run(const Pre& p) const {
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63, il = lane & 15, q = lane >> 4;
+    const int ib = w & 1, kh = w >> 1, n = A.P.d;
+    const wrsrc_t GR = rsrc();
+    f32x4 g0 = p.g0, g1 = p.g1;
+    const float (&xa)[2][8] = p.xa;
+    // one block: acc[mt] = x (row tile mt) . the block whose fragments are c0 | c1
+    auto block = [&](const f32x4& c0, const f32x4& c1, f32x4 (&acc)[2]) {
+      acc[0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const float b = s < 4 ? c0[s & 3] : c1[s & 3];
+        acc[0] = mfma16(xa[0][s], b, acc[0]);
+        acc[1] = mfma16(xa[1][s], b, acc[1]);
+      }
+    };
+    f32x4 gw[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, ga[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    for (int kk = kh; kk < n; kk += 2) {
+      const int nk = kk + 2 < n ? kk + 2 : n;         // behind the wave's last k: the L_G block (used by the waves kh = 1)
+      const f32x4 c0 = g0, c1 = g1;
+      g0 = frag(GR, nk, ib, 0); g1 = frag(GR, nk, ib, 1);
+      float wv[2][4], av[2][4];
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * mt + 4 * q + r;
+          wv[mt][r] = R[LO::RW + row * n + kk];
+          av[mt][r] = AIMG[row * AP + kk];
+        }
+      __builtin_amdgcn_sched_barrier(0);             // loads and LDS reads go out ahead of the MFMAs that hide them
+      f32x4 acc[2];
+      block(c0, c1, acc);
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          gw[mt][r] = __builtin_fmaf(acc[mt][r], wv[mt][r], gw[mt][r]);
+          ga[mt][r] = __builtin_fmaf(acc[mt][r], av[mt][r], ga[mt][r]);
+        }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (kh == 1) {
+      f32x4 acc[2];
+      block(g0, g1, acc);
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) lds[LO::FI + (16 * mt + 4 * q + r) * DMM_P + 16 * ib + il] = acc[mt][r];
+    }
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int at = (kh * 32 + 16 * mt + 4 * q + r) * DMM_P + 16 * ib + il;
+        lds[LO::GWI + at] = gw[mt][r];
+        lds[LO::GAI + at] = ga[mt][r];
+      }
+    lds_barrier();
+  }
+  // element (c, o) of the row's f, gw, ga: dense_g's results
+  __device__ __forceinline__ DenseTerms terms(int c, int o, float beta, float sb) const {
+    const int at = c * DMM_P + o;
+    const float tw = lds[LO::GWI + at] + lds[LO::GWI + 32 * DMM_P + at];
+    const float ta = lds[LO::GAI + at] + lds[LO::GAI + 32 * DMM_P + at];
+    return {beta * lds[LO::FI + at], sb * tw, sb * ta};
+  }
+};
+
 // ---- sampler loop (MODE_SDE): the stage update behind the layer-4 reduce.  Thread (sample c, output o) owns element
 // idx = c d + o of the tile — the element it fetched in raw_issue — and forms the stage's increment with the formulas of
 // msgm_sde_stage (sde_stage.h), in the order of _em_step / _heun_step / _rk4_step (sde_scheme.py):
@@ -602,14 +732,18 @@ __device__ __forceinline__ void sde_issue(const MlpArgs& A, SdeRegs<NR>& sr, con
 // nothing, layer 4 left it there); VIMG, a free image of the same pitch that takes the updated row under norm correction;
 // `row_of(idx)` = idx / d.  ROWSUM: the row's sum of squares is formed once per row by the NT / SPT threads of a group
 // (contiguous elements each, partial sums met by shuffle in a fixed order) and passed through RED, instead of every
-// thread summing the whole row (at d = 128 that would be 128 LDS reads per element).
-template <class LO, int NT, int AP, bool ROWSUM, int NR, class ROW, class GATHER>
+// thread summing the whole row (at d = 128 that would be 128 LDS reads per element).  `dense` (DenseMM, else nothing): the
+// phase that forms the dense tensor's f, gw and ga of the whole tile on the matrix cores once a and dW are complete (its
+// first loads go out at the head); the dense branch then takes its terms from that phase's images instead of dense_g.
+template <class LO, int NT, int AP, bool ROWSUM, int NR, class ROW, class GATHER, class DENSE = NoDenseMM>
 __device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& sr, const float* AIMG, float* VIMG, float* RED,
-                                           ROW row_of, GATHER gather, float* R, int64_t s_base, int tid, SdeItem it) {
+                                           ROW row_of, GATHER gather, float* R, int64_t s_base, int tid, SdeItem it,
+                                           const DENSE dense = DENSE{}) {
   const int d = A.P.d, NS = A.n_stages;
   const int64_t etot = A.B * d;
   const bool last = it.stage == NS - 1;
   const bool nc = last && A.norm0;
+  [[maybe_unused]] const typename DENSE::Pre dense_pre = dense.issue();
   StageArgs S{};
   S.kind = A.kind; S.proc = MSGM_PROC_REVERSE; S.strato = NS > 1;
   S.b0 = A.b0; S.b1 = A.b1; S.T = A.T; S.delta = A.delta; S.sqrt_delta = A.sqrt_delta; S.lmbd = A.lmbd;
@@ -631,6 +765,7 @@ __device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& 
     }
   }
   lds_barrier();
+  if constexpr (DENSE::ON) dense.run(dense_pre);
   float val[NR];
 #pragma unroll
   for (int k = 0; k < NR; ++k) {
@@ -658,7 +793,9 @@ __device__ __forceinline__ void sde_update(const MlpArgs& A, const SdeRegs<NR>& 
           gw = sparse_g(sc.sb, xp, xm, wr[o], wr[im]);
           ga = sparse_g(sc.sb, xp, xm, ar[o], ar[im]);
         } else {
-          const DenseTerms t = dense_g(A.G, A.L_G, d, o, sc.beta, sc.sb, xr, wr, ar);
+          DenseTerms t;
+          if constexpr (DENSE::ON) t = dense.terms(c, o, sc.beta, sc.sb);
+          else t = dense_g(A.G, A.L_G, d, o, sc.beta, sc.sb, xr, wr, ar);
           f = t.f; div = 2.0f * f; gw = t.gw; ga = t.ga;
         }
         inc = stage_mu(S, ga, f, fs, div) * sc.delta + sig_scale * gw;      // sde_scheme.py:40
@@ -786,8 +923,9 @@ __device__ __forceinline__ void store_loss_sum(float* RED, int tid, float loss_a
   }
 }
 
-template <int MODE, bool WIDE, int NW, bool TINY = false>
+template <int MODE, bool WIDE, int NW, bool TINY = false, bool DENSE_MM = false>
 __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
+  static_assert(!DENSE_MM || (MODE == MODE_SDE && WIDE && !TINY), "the dense contraction phase belongs to the wide sampler loop");
   constexpr int NT = 64 * NW;         // threads
   constexpr int IT = 8 / NW;          // 16-feature row tiles per wave: 4 waves x 2 or 8 waves x 1
   constexpr int FW = 16 * IT;         // features owned by a wave
@@ -799,7 +937,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
   const int w = tid >> 6, lane = tid & 63, il = lane & 15, q = lane >> 4;
   const int d = A.P.d;
   const int fb = FW * w;              // this wave's first feature
-  using LO = MlpLds<MODE, WIDE, NW, TINY>;
+  using LO = std::conditional_t<DENSE_MM, MlpDenseLds<NW>, MlpLds<MODE, WIDE, NW, TINY>>;
   constexpr int SM_P = LO::SMP, DPAD = LO::DP, PP = LO::PP, DROWS = LO::DROWS;
   float* X = lds + LO::X; float* Y = lds + LO::Y; float* Z = lds + LO::Z; float* U = lds + LO::U;
   float* H0 = lds + LO::H0; float* ABAR = lds + LO::ABAR; float* PART = lds + LO::PART;
@@ -962,14 +1100,20 @@ __global__ void __launch_bounds__(64 * NW, 1) k_mlp(MlpArgs A) {
     if constexpr (MODE == MODE_SDE) {
       // the update first: its stores drain to L2 under the next item's layer 1
       // a = b4 + the waves' K-slices, parked in wave 0's slice; the updated row goes to wave 1's (dead after the reduce)
-      sde_update<LO, NT, PP, false>(A, sr, PART, PART + 32 * PP, nullptr, [=](int idx) { return idx / d; },
-                                    [=](int c, int o) {
-                                      float a = B4s[o];
+      auto row_of = [=](int idx) { return idx / d; };
+      auto gather = [=](int c, int o) {
+        float a = B4s[o];
 #pragma unroll
-                                      for (int ww = 0; ww < NW; ++ww) a += PART[(ww * 32 + c) * PP + o];
-                                      PART[c * PP + o] = a;
-                                    },
-                                    const_cast<float*>(Rc), s_base, tid, sde_item(A, step));   // (stage 0 parks dW in it)
+        for (int ww = 0; ww < NW; ++ww) a += PART[(ww * 32 + c) * PP + o];
+        PART[c * PP + o] = a;
+      };
+      // (stage 0 parks dW in the raw row)
+      if constexpr (DENSE_MM)
+        sde_update<LO, NT, PP, false>(A, sr, PART, PART + 32 * PP, nullptr, row_of, gather, const_cast<float*>(Rc), s_base, tid,
+                                      sde_item(A, step), DenseMM<LO, PP>{A, Rc, PART, lds, tid});
+      else
+        sde_update<LO, NT, PP, false>(A, sr, PART, PART + 32 * PP, nullptr, row_of, gather, const_cast<float*>(Rc), s_base, tid,
+                                      sde_item(A, step));
       layer1(H0n, Yc);                                         // next item's h1 (h2 is dead)
       __syncthreads();   // + vmcnt(0): what this item wrote must have left the CU before a later item re-reads it
       tile = ntile; step = nstep;
@@ -1710,7 +1854,7 @@ static int sde_loop_stages(int32_t method) {
 int msgm_mlp_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B) {
   if (d < 1 || d > 30 || d + 1 + (premodule ? 1 : 0) > 32 || n != d) return 0;     // the extra-wide class: msgm_mlp_xw_sde_loop
   if (kind != MSGM_SDE_SGM && kind != MSGM_SDE_MSGM_SPARSE && kind != MSGM_SDE_MSGM_DENSE) return 0;
-  if (kind == MSGM_SDE_MSGM_DENSE && n > 16) return 0;
+  if (kind == MSGM_SDE_MSGM_DENSE && n > 16) return 0;   // dense_g is n^2 terms per element: 17 <= n <= 30 is msgm_mlp_dense_sde_loop's
   return B > 32;                                           // a workgroup needs two tiles to prefetch one ahead
 }
 
@@ -1722,7 +1866,7 @@ size_t msgm_mlp_sde_loop_workspace(int64_t B, int32_t d, int32_t method) {
 int msgm_mlp_xw_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B) {
   if (d < 1 || d > HID || n != d) return 0;
   if (d <= 30 && d + 1 + (premodule ? 1 : 0) <= 32) return 0;                       // the narrower classes: msgm_mlp_sde_loop
-  if (kind != MSGM_SDE_SGM && kind != MSGM_SDE_MSGM_SPARSE) return 0;              // a dense tensor stops at n = 16
+  if (kind != MSGM_SDE_SGM && kind != MSGM_SDE_MSGM_SPARSE) return 0;              // a dense tensor stops at n = 30 (msgm_mlp_dense_sde_loop)
   return B > 32;                                           // a workgroup needs two tiles to prefetch one ahead
 }
 
@@ -1736,18 +1880,36 @@ int msgm_mlp_xw_sde_loop_preferred(int32_t d, int32_t premodule, int32_t kind, i
   return kind == MSGM_SDE_SGM ? d <= 64 : d <= 40;
 }
 
-// The two sampler-loop entries: every check and argument in one place, `supported` is the entry's own shape rule.
+int msgm_mlp_dense_sde_loop_supported(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B) {
+  if (kind != MSGM_SDE_MSGM_DENSE || n != d || d < 17 || d > 30 || d + 1 + (premodule ? 1 : 0) > 32) return 0;
+  return B > 64;                                           // 32-row tiles, two a workgroup: B <= 64 is one workgroup on one CU
+}
+
+size_t msgm_mlp_dense_sde_loop_workspace(int64_t B, int32_t d, int32_t method) { return msgm_mlp_sde_loop_workspace(B, d, method); }
+
+// Where the public samplers route to the dense loop: the supported shapes measured faster than the composed route of the
+// same build by more than that route's own spread (tools/time_mlp_sde.py; DESIGN §4 has the table).
+int msgm_mlp_dense_sde_loop_preferred(int32_t d, int32_t premodule, int32_t kind, int64_t n, int64_t B) {
+  return msgm_mlp_dense_sde_loop_supported(d, premodule, kind, n, B);
+}
+
+size_t msgm_dense_g_packed_floats(int64_t n) { return n >= 1 && n <= 32 ? (size_t)(n + 1) * DMM_BLOCK : 0; }
+
+// The sampler-loop entries: every check and argument in one place, `supported` is the entry's own shape rule.  `packed`
+// and `dense_mm` belong to msgm_mlp_dense_sde_loop alone.
 static int sde_loop_launch(int (*supported)(int32_t, int32_t, int32_t, int64_t, int64_t), const msgm_mlp_params_t* P, float* x,
                            int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts, int32_t n_steps, float delta,
                            float sqrt_delta, float lmbd, const float* z, const uint64_t* rng, uint64_t rng_step0,
                            const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop, float* kept,
-                           void* workspace, size_t workspace_bytes, msgm_stream_t stream) {
+                           void* workspace, size_t workspace_bytes, msgm_stream_t stream, bool dense_mm = false,
+                           const float* packed = nullptr) {
   MlpArgs A{};
   int rc = fill_common(A, P, B);
   if (rc) return rc;
   const int stages = sde_loop_stages(method);
   if (!x || !sde || !ts || n_steps < 1 || !stages || (!z && !rng) || (keep_stop && !kept)) return MSGM_E_BADARG;
   if (sde->kind == MSGM_SDE_MSGM_DENSE && (!sde->G || !sde->L_G)) return MSGM_E_BADARG;
+  if (dense_mm && !packed) return MSGM_E_BADARG;
   if (!supported(P->d, P->premodule, sde->kind, P->d, B)) return MSGM_E_UNSUPPORTED;
   const size_t need = msgm_mlp_sde_loop_workspace(B, P->d, method);
   if (need && (!workspace || workspace_bytes < need)) return MSGM_E_WORKSPACE;
@@ -1764,6 +1926,12 @@ static int sde_loop_launch(int (*supported)(int32_t, int32_t, int32_t, int64_t, 
   const int64_t tiles = (B + 31) / 32;
   const int64_t cap = mlp_wg_per_cu(A) * MLP_MAX_GRID;
   const int64_t grid = tiles / 2 < cap ? tiles / 2 : cap;   // at least two tiles per workgroup
+  if (dense_mm) {                                           // one workgroup per CU (138 496 B of LDS)
+    A.Gp = packed;
+    constexpr int nw = MlpCfg<MODE_SDE, true>::NW;
+    return launch_kernel<k_mlp<MODE_SDE, true, nw, false, true>, MlpDenseLds<nw>::BYTES, 64 * nw>(
+        A, (int)(grid < MLP_MAX_GRID ? grid : MLP_MAX_GRID), S(stream));
+  }
   return launch_mlp<MODE_SDE>(A, (int)grid, S(stream));
 }
 
@@ -1782,6 +1950,15 @@ int msgm_mlp_xw_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const 
                          float* kept, void* workspace, size_t workspace_bytes, msgm_stream_t stream) {
   return sde_loop_launch(msgm_mlp_xw_sde_loop_supported, P, x, B, sde, method, ts, n_steps, delta, sqrt_delta, lmbd, z, rng,
                          rng_step0, norm0, traj, include_t0, keep_stop, kept, workspace, workspace_bytes, stream);
+}
+
+// k_mlp<MODE_SDE, wide, DENSE_MM>: the dense tensor with 17 <= n <= 30, its contraction on the matrix cores
+int msgm_mlp_dense_sde_loop(const msgm_mlp_params_t* P, float* x, int64_t B, const msgm_sde_t* sde, int32_t method, const float* ts,
+                            int32_t n_steps, float delta, float sqrt_delta, float lmbd, const float* z, const uint64_t* rng,
+                            uint64_t rng_step0, const float* norm0, float* traj, int32_t include_t0, const int32_t* keep_stop,
+                            float* kept, void* workspace, size_t workspace_bytes, const float* g_packed, msgm_stream_t stream) {
+  return sde_loop_launch(msgm_mlp_dense_sde_loop_supported, P, x, B, sde, method, ts, n_steps, delta, sqrt_delta, lmbd, z, rng,
+                         rng_step0, norm0, traj, include_t0, keep_stop, kept, workspace, workspace_bytes, stream, true, g_packed);
 }
 
 int msgm_mlp_ssm_partial(const msgm_mlp_params_t* P, const float* y, const float* t, const float* v, const float* u,

@@ -514,9 +514,67 @@ def mlp_xw_sde_loop(P: L.MlpParamsT, x: torch.Tensor, sde: L.SdeT, method: str, 
                      norm0, traj, include_t0, keep, kept, workspace)
 
 
+def mlp_dense_sde_loop_supported(d: int, premodule: bool, kind: int, n: int, B: int) -> bool:
+    """Whether msgm_mlp_dense_sde_loop takes this shape: the dense tensor with 17 <= d = n <= 30, in_dim <= 32 and B > 64.
+    Never true where one of the other two entries' predicates is."""
+    return bool(lib().msgm_mlp_dense_sde_loop_supported(int(d), int(bool(premodule)), int(kind), int(n), int(B)))
+
+
+def mlp_dense_sde_loop_preferred(d: int, premodule: bool, kind: int, n: int, B: int) -> bool:
+    """Whether the public samplers send this shape to msgm_mlp_dense_sde_loop: supported and measured faster than the
+    composed route of the same build by more than that route's own spread."""
+    return bool(lib().msgm_mlp_dense_sde_loop_preferred(int(d), int(bool(premodule)), int(kind), int(n), int(B)))
+
+
+def mlp_dense_sde_loop_workspace(B: int, d: int, method: str, device) -> Optional[torch.Tensor]:
+    """The stage state of the dense loop, as mlp_sde_loop_workspace; None for Euler-Maruyama."""
+    nbytes = int(lib().msgm_mlp_dense_sde_loop_workspace(int(B), int(d), SDE_LOOP_METHODS[method]))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def pack_dense_g(G: torch.Tensor, L_G: torch.Tensor) -> torch.Tensor:
+    """G (n,n,n) and L_G (n,n), n <= 32, in the fragment order msgm_mlp_dense_sde_loop streams: (n + 1, 2, 2, 64, 4) fp32 on
+    G's device.  Block k < n is G[:, :, k], block n is L_G; element [ib, sg, lane, r] of a block is its entry
+    (i, j) = (16 ib + (lane & 15), 4 (4 sg + r) + (lane >> 4)): the lane's B operand of MFMA step 4 sg + r for the 16
+    outputs i of half ib.  Entries with i >= n or j >= n are +0.  Plain indexing: works on CPU tensors too."""
+    n = G.shape[0]
+    if G.dim() != 3 or tuple(G.shape) != (n, n, n) or tuple(L_G.shape) != (n, n) or not 1 <= n <= 32:
+        raise MsgmError("pack_dense_g: G (n,n,n) and L_G (n,n) with n <= 32")
+    dev = G.device
+    lane = torch.arange(64, device=dev).view(1, 1, 64, 1)
+    ib, sg, r = (torch.arange(m, device=dev) for m in (2, 2, 4))
+    i = (16 * ib.view(2, 1, 1, 1) + (lane & 15)).expand(2, 2, 64, 4)
+    j = (4 * (4 * sg.view(1, 2, 1, 1) + r.view(1, 1, 1, 4)) + (lane >> 4)).expand(2, 2, 64, 4)
+    live = (i < n) & (j < n)
+    blocks = torch.cat([G.permute(2, 0, 1), L_G.to(dev).unsqueeze(0)], 0).to(torch.float32)          # [k][i][j]
+    out = blocks[:, i.clamp(max=n - 1), j.clamp(max=n - 1)]
+    return torch.where(live.unsqueeze(0), out, torch.zeros((), dtype=torch.float32, device=dev)).contiguous()
+
+
+def mlp_dense_sde_loop(P: L.MlpParamsT, x: torch.Tensor, sde: L.SdeT, method: str, ts: torch.Tensor, delta: float,
+                       lmbd: float = 0.0, z: Optional[torch.Tensor] = None, rng: Optional[PhiloxState] = None, rng_step0: int = 0,
+                       norm0: Optional[torch.Tensor] = None, traj: Optional[torch.Tensor] = None, include_t0: bool = False,
+                       keep: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None, packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mlp_sde_loop for a dense tensor with 17 <= n <= 30: same arguments, draws and outputs, in ONE launch whose dense
+    contraction runs on the matrix cores; packed: pack_dense_g(G, L_G) of the tensor in `sde`, on x's device (MSGMsde.packed_G
+    keeps one).  Deterministic, but not the composed path's bits: its parity is to float64."""
+    if x.dim() != 2 or not x.is_cuda:
+        raise MsgmError("sde loop: the state must be a (B,d) device tensor; there is no CPU fallback")
+    if packed is not None:
+        if packed.device != x.device:
+            raise MsgmError("dense sde loop: the packed tensor must be on the state's device")
+        n = x.shape[-1]
+        if packed.dtype != torch.float32 or not packed.is_contiguous() or \
+                packed.numel() != int(lib().msgm_dense_g_packed_floats(int(n))):
+            raise MsgmError(f"dense sde loop: packed must be pack_dense_g's contiguous fp32 image for n = {n}")
+    return _sde_loop("msgm_mlp_dense_sde_loop", mlp_dense_sde_loop_workspace, P, x, sde, method, ts, delta, lmbd, z, rng, rng_step0,
+                     norm0, traj, include_t0, keep, kept, workspace, (ptr(packed),))
+
+
 def _sde_loop(entry, workspace_of, P, x, sde, method, ts, delta, lmbd, z, rng, rng_step0, norm0, traj, include_t0, keep, kept,
-              workspace):
-    """The checks and the call that the two sampler-loop entries share."""
+              workspace, extra=()):
+    """The checks and the call that the sampler-loop entries share; `extra`: the entry's own arguments ahead of the stream."""
     if method not in SDE_LOOP_METHODS:
         raise MsgmError(f"unknown integrator {method}")
     if x.dim() != 2 or not x.is_cuda:
@@ -541,7 +599,7 @@ def _sde_loop(entry, workspace_of, P, x, sde, method, ts, delta, lmbd, z, rng, r
     nbytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
     check(getattr(lib(), entry)(P, ptr(f32(x)), B, sde, SDE_LOOP_METHODS[method], ptr(ts), N, float(delta), float(delta ** 0.5),
                                 float(lmbd), ptr(z), _rng_ptr(rng), int(rng_step0), ptr(norm0), ptr(traj),
-                                int(bool(include_t0)), ptr(keep), ptr(kept), ptr(workspace), nbytes, stream()),
+                                int(bool(include_t0)), ptr(keep), ptr(kept), ptr(workspace), nbytes, *extra, stream()),
           entry)
     return x
 

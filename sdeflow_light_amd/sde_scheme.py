@@ -6,7 +6,7 @@ Per step the reference launches ~20 eager kernels plus a host ``.item()`` and,
 with ``keep_all_samples``, a blocking D2H copy (sde_scheme.py:80-92).  Here a
 step is ONE fused stage kernel after the score net (or one kernel in total for
 MLP + SGM: ``msgm_mlp_em_step``; with the MLP, Heun, RK4-Stratonovich and the multiplicative Euler-Maruyama are one
-kernel for the WHOLE loop, ``msgm_mlp_sde_loop`` or ``msgm_mlp_xw_sde_loop``, when ``_Run.mlp_loop`` finds the shape
+kernel for the WHOLE loop, ``msgm_mlp_sde_loop``, ``msgm_mlp_xw_sde_loop`` or ``msgm_mlp_dense_sde_loop``, when ``_Run.mlp_loop`` finds the shape
 routed there), the time grid is computed on the host exactly
 as upstream (fp32 ``linspace``) and passed by value, trajectories are captured
 into a device buffer and copied once at the end, and the whole fused loop can
@@ -177,12 +177,14 @@ class _Run:
 
     def mlp_loop(self, method):
         """The whole loop as ONE launch when the shapes allow it: the reverse process of the MLP, Philox noise, and a shape
-        one of the two kernels takes — ``msgm_mlp_sde_loop`` (``ops.mlp_sde_loop_supported``: d <= 30 and in_dim <= 32, dense
-        tensors up to n = 16, B > 32), tried first, or ``msgm_mlp_xw_sde_loop`` (``ops.mlp_xw_sde_loop_preferred``: the part
+        one of the three kernels takes — ``msgm_mlp_sde_loop`` (``ops.mlp_sde_loop_supported``: d <= 30 and in_dim <= 32, dense
+        tensors up to n = 16, B > 32), tried first, then ``msgm_mlp_xw_sde_loop`` (``ops.mlp_xw_sde_loop_preferred``: the part
         of the extra-wide class where the loop was measured faster than the composed steps — SGM up to d = 64, the sparse
-        tensor up to d = 40, B > 32).  Same time grid, stage times and Philox draws as
+        tensor up to d = 40, B > 32), then ``msgm_mlp_dense_sde_loop`` (``ops.mlp_dense_sde_loop_preferred``: dense tensors
+        with 17 <= n <= 30, in_dim <= 32 and B > 64, where measured faster; its contraction runs on the matrix cores, so it
+        agrees with the composed steps to float64 parity, not to the bit).  Same time grid, stage times and Philox draws as
         the composed steps; trajectory rows and kept rows are written by the kernel.  Returns whether it ran; everything
-        else keeps the composed route."""
+        else — dense n >= 31, dense B <= 64, ``noise=`` — keeps the composed route."""
         from .NN import MLP
         net = self.sde.a if self.reverse else None
         if not isinstance(net, MLP) or self.noise is not None or net.input_dim != self.n:
@@ -192,6 +194,9 @@ class _Run:
             loop = ops.mlp_sde_loop
         elif ops.mlp_xw_sde_loop_preferred(*shape):
             loop = ops.mlp_xw_sde_loop
+        elif ops.mlp_dense_sde_loop_preferred(*shape):
+            def loop(*a, **k):
+                return ops.mlp_dense_sde_loop(*a, packed=self.base.packed_G(), **k)
         else:
             return False
         loop(net.kernel_params(), self.x, self.struct, method, self.ts.to(self.device), self.delta, self.lmbd,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Wall time of the MLP samplers at the driver's sizes (MSGM_higherDim.py:903: B = 10 000, N = 128, keep_all_samples=True):
-the one-launch loop (msgm_mlp_sde_loop / msgm_mlp_xw_sde_loop, what the public samplers route to) against the composed
+the one-launch loop (msgm_mlp_sde_loop / msgm_mlp_xw_sde_loop / msgm_mlp_dense_sde_loop, what the public samplers route to) against the composed
 path (score net, stage kernels and glue as separate launches), alternated round by round in ONE process, device-synchronised, after a warm-up.
 The composed path is also timed against itself (a second call in every round): the difference of the two medians is the
 spread a routing decision has to beat.
@@ -27,7 +27,9 @@ CONFIGS = [  # (name, SDE family, d, premodule, norm correction)
     ("sparse d=6 NLR nc", "sparse", 6, NLR, True),
     ("sparse d=20 nc", "sparse", 20, None, True),
 ] + [c for d in (40, 64, 90, 128) for c in (   # the extra-wide class (msgm_mlp_xw_sde_loop): the widths of the real data sets
-    (f"sgm d={d}", "sgm", d, None, False), (f"sparse d={d} NLR nc", "sparse", d, NLR, True))]
+    (f"sgm d={d}", "sgm", d, None, False), (f"sparse d={d} NLR nc", "sparse", d, NLR, True))] + [
+    # dense tensors above n = 16 (msgm_mlp_dense_sde_loop): the driver's default model at its real-data widths
+    (f"dense d={d} NLR nc", "dense", d, NLR, True) for d in (17, 24, 30)]
 
 
 def make_gen(kind, d, pre, dev):
@@ -55,6 +57,7 @@ def main():
     a = ap.parse_args()
     from sdeflow_light_amd import ops, sde_scheme as SS
     ops.mlp_xw_sde_loop_preferred = ops.mlp_xw_sde_loop_supported   # time the loop wherever the kernel takes the shape
+    ops.mlp_dense_sde_loop_preferred = ops.mlp_dense_sde_loop_supported
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     out = open(a.out, "w") if a.out else None
