@@ -658,8 +658,9 @@ int msgm_add_row(float* x, const float* E, int32_t N, int32_t P, int32_t C, int3
  * pixel-chunk) workgroups into per-chunk SLOTS of `workspace`, summed in chunk
  * order by a finalise kernel, then an elementwise apply pass), so 32 samples/GPU
  * still fill the chip and the result is bitwise reproducible (no atomics).
- * stats [Bp][G][4] = {mean, 1/sigma, mean(xdot), mean(xhat xdot)} is written by
- * forward (may be NULL when no backward follows) and read by backward, which
+ * stats [Bp][G][4] = {mean - pivot, 1/sigma, mean(xdot), mean(xhat xdot)} (pivot: the sample's first pixel of the group's
+ * first channel, so that a mean that is large against sigma keeps its low bits) is written by
+ * forward (may be NULL when no backward follows) and read by backward with the SAME x, which
  * recomputes xhat / SiLU from x, adds to dgamma / dbeta (slot-ordered sums) and
  * writes the input cotangents (primal | tangent) to gx (may alias gout);
  * `residual` (may be NULL, same shape as gx, may alias gx) is added to them — the

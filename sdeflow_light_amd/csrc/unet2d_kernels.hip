@@ -18,11 +18,15 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 //   1. k_gn_*_reduce: grid (sample, pixel chunk); threads run along channels (coalesced,
 //      256/C pixel lanes), fp32 partials -> LDS -> ONE double per (sample, chunk, group, moment)
 //      stored in that chunk's own slot — no atomics: the slots of a sample are added in chunk
-//      order by the finalise kernels, so the result is bitwise reproducible.  Moments are raw
-//      (sum x, sum x^2, sum xdot, sum x xdot) but combined in double, so the variance does not
-//      suffer from E[x^2]-mu^2 cancellation.
-//   2. k_gn_*_apply: grid-stride elementwise pass that rebuilds {mean, inv_std,
-//      mean(xdot), a = mean(xhat xdot)} from the moments.
+//      order by the finalise kernels, so the result is bitwise reproducible.  The fp32 partials
+//      are SHIFTED moments: sums of u = x - k, u^2, xdot, u xdot with the pivot k = the sample's own
+//      first pixel of that channel (the tangent keeps raw sums: its mean is of the size of its spread), so a group whose mean is large against its spread loses nothing in the fp32
+//      squares (raw x^2 rounds by 2^-24 x^2 per element, which no later double arithmetic removes: the error of
+//      xhat grew like (mean/std)^2).  Every thread puts its pivots back in double before the group sums, so the
+//      slots hold the raw moments (sum x, sum x^2, sum xdot, sum x xdot) and E[x^2] - mu^2 is formed in double
+//      only: exact 0 for a constant group, 2^-53 mean^2 otherwise.
+//   2. k_gn_*_apply: grid-stride elementwise pass that rebuilds {mean - pivot, inv_std,
+//      mean(xdot), a = mean(xhat xdot)} from the moments (gn_pivot: why the mean is kept relative to a pivot).
 // acc[b][chunk < GN_SLOTS][g][8] doubles: forward uses moments 0..3, backward 0..4; the per-channel
 // parameter gradients of the backward go to per-(sample, chunk) slots too and are summed in a fixed order.
 #define GN_SLOTS 32
@@ -88,6 +92,15 @@ __device__ __forceinline__ GnSrc gn_src(const GnArgs& A, int c) {
   return GnSrc{(second ? A.x1 : A.x) + (second ? c - C0 : c), (long)A.Bp * A.P * pitch, pitch};
 }
 
+// gn_pivot: the pivot of (sample b, group g) — the sample's own first pixel of the group's first channel.  The saved mean is
+// kept RELATIVE to it (stats[0] = mean - pivot, rounded to fp32 from double) and xhat = ((x - pivot) - stats[0]) inv: a mean
+// that is large against the spread would lose the group's position to the fp32 rounding of the mean itself
+// (2^-25 |mean| / sigma in xhat), while x - pivot is (nearly) exact and what is left to round is of the size of sigma.
+__device__ __forceinline__ float gn_pivot(const GnArgs& A, int b, int g, int cpg) {
+  const GnSrc s = gn_src(A, g * cpg);
+  return s.base[(long)b * A.P * s.pitch];
+}
+
 // gn_load_x: the thread's V primal elements at source offset ex and, when dual, their tangents (xd is left untouched
 // otherwise).  VEC: one 16-byte load each.
 template <bool VEC>
@@ -123,6 +136,9 @@ __device__ __forceinline__ void gn_group_tail(const double* red, double* dst, in
 
 // Reduce kernels: every thread holds V double partials per moment (per-thread fp32 sums over one sub-chunk are widened and
 // from there on everything is added in double).  ALL moments go to LDS at once and gn_group_tail finishes the chunk.
+// The forward's fp32 sums run over u = x - k (k: pixel 0 of this sample, the same for every workgroup and batch size) and
+// u xdot; with n the pixels this thread summed, sum x = s0 + n k, sum x^2 = s1 + 2 k s0 + n k^2, sum x xdot = s3 + k s2,
+// in double.
 template <bool VEC>
 __global__ void __launch_bounds__(256) k_gn_fwd_reduce(GnArgs A) {
   constexpr int V = VEC ? 4 : 1;
@@ -135,6 +151,11 @@ __global__ void __launch_bounds__(256) k_gn_fwd_reduce(GnArgs A) {
   double d0[V], d1[V], d2[V], d3[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) { d0[k] = 0.0; d1[k] = 0.0; d2[k] = 0.0; d3[k] = 0.0; }
+  float kx[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) kx[k] = 0.f;
+  if (L.live) { float kz[V]; gn_load_x<VEC>(sx, (long)b * P * sx.pitch, false, kx, kz); }
+  int n = 0;
   if (L.live)
    for (int ps = p0; ps < p1; ps += max(A.sub, 1)) {
     const int pe = min(ps + max(A.sub, 1), p1);
@@ -144,10 +165,12 @@ __global__ void __launch_bounds__(256) k_gn_fwd_reduce(GnArgs A) {
     for (int p = ps + L.pl; p < pe; p += L.PL) {
       float xv[V], dv[V];
       gn_load_x<VEC>(sx, ((long)b * P + p) * sx.pitch, A.dual, xv, dv);
+      ++n;
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        s0[k] += xv[k]; s1[k] += xv[k] * xv[k];
-        if (A.dual) { s2[k] += dv[k]; s3[k] += xv[k] * dv[k]; }
+        const float u = xv[k] - kx[k];
+        s0[k] += u; s1[k] += u * u;
+        if (A.dual) { s2[k] += dv[k]; s3[k] += u * dv[k]; }
       }
     }
 #pragma unroll
@@ -156,6 +179,9 @@ __global__ void __launch_bounds__(256) k_gn_fwd_reduce(GnArgs A) {
   if (L.live) {
 #pragma unroll
     for (int k = 0; k < V; ++k) {
+      const double kk = (double)kx[k], nn = (double)n, u0 = d0[k];
+      d0[k] = u0 + nn * kk; d1[k] = d1[k] + 2.0 * kk * u0 + nn * kk * kk;
+      d3[k] = d3[k] + kk * d2[k];
       const int e = L.pl * C + V * L.cv + k;
       red[e] = d0[k]; red[1024 + e] = d1[k];
       if (A.dual) { red[2048 + e] = d2[k]; red[3072 + e] = d3[k]; }
@@ -191,13 +217,14 @@ __device__ __forceinline__ void gn_sum_slots(const GnArgs& A, int b, int g, int 
   }
 }
 
-__device__ __forceinline__ void gn_stats(const double* a8, double cnt, float eps, float& mu, float& inv, float& md, float& a) {
+// kg: the group's pivot (0: mu is the mean itself)
+__device__ __forceinline__ void gn_stats(const double* a8, double cnt, float eps, double kg, float& mu, float& inv, float& md, float& a) {
   const double m = a8[0] / cnt;
   double var = a8[1] / cnt - m * m;
   if (var < 0) var = 0;
   const double iv = 1.0 / sqrt(var + (double)eps);
   const double d = a8[2] / cnt;
-  mu = (float)m; inv = (float)iv; md = (float)d;
+  mu = (float)(m - kg); inv = (float)iv; md = (float)d;
   a = (float)(iv * (a8[3] / cnt - m * d));
 }
 
@@ -210,18 +237,19 @@ __global__ void __launch_bounds__(256) k_gn_affine(GnArgs A, float* __restrict__
     float mu, inv, md, a;
     double a8[8];
     gn_sum_slots(A, b, c / cpg, 2, a8);
-    gn_stats(a8, cnt, A.eps, mu, inv, md, a);
+    gn_stats(a8, cnt, A.eps, 0.0, mu, inv, md, a);
     const float sc = inv * A.gamma[c];
     scale[(size_t)b * A.C + c] = sc;
     shift[(size_t)b * A.C + c] = A.beta[c] - mu * sc;
   }
 }
 
-// gn_consts: the constants of the thread's V channels c0 ..: {mean, inv_std, mean(xdot), a} of each one's group from the f32x4
-// table[row + group] (k_gn_fwd_apply: this sample's LDS copy, row 0; backward: A.stats, row b G) and the affine parameters.
-template <int V> struct GnConsts { float mu[V], inv[V], md[V], a[V], ga[V], be[V]; };
+// gn_consts: the constants of the thread's V channels c0 ..: {mean - pivot, inv_std, mean(xdot), a} of each one's group from the
+// f32x4 table[row + group] (k_gn_fwd_apply: this sample's LDS copy, row 0; backward: A.stats, row b G), the group's pivot kg
+// of sample b and the affine parameters.
+template <int V> struct GnConsts { float mu[V], inv[V], md[V], a[V], ga[V], be[V], kg[V]; };
 template <int V>
-__device__ __forceinline__ GnConsts<V> gn_consts(const GnArgs& A, const f32x4* table, size_t row, int c0, int cpg) {
+__device__ __forceinline__ GnConsts<V> gn_consts(const GnArgs& A, const f32x4* table, size_t row, int b, int c0, int cpg) {
   GnConsts<V> K;
 #pragma unroll
   for (int k = 0; k < V; ++k) {
@@ -229,6 +257,7 @@ __device__ __forceinline__ GnConsts<V> gn_consts(const GnArgs& A, const f32x4* t
     const f32x4 st = table[row + c / cpg];
     K.mu[k] = st[0]; K.inv[k] = st[1]; K.md[k] = st[2]; K.a[k] = st[3];
     K.ga[k] = A.gamma[c]; K.be[k] = A.beta[c];
+    K.kg[k] = gn_pivot(A, b, c / cpg, cpg);
   }
   return K;
 }
@@ -244,15 +273,16 @@ __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
   __shared__ f32x4 sst[64];
   const int C = A.C, P = A.P, G = A.G, cpg = C / G;
   const int tid = threadIdx.x, b = blockIdx.y;
-  // {mean, inv_std, mean(xdot), a} of this sample's groups, rebuilt by every workgroup from the chunk slots the reduce
+  // {mean - pivot, inv_std, mean(xdot), a} of this sample's groups, rebuilt by every workgroup from the chunk slots the reduce
   // kernel left (thread g: the slots of group g in chunk order, in double — the arithmetic of the former one-thread-per-
   // (sample, group) finalise launch, which cost 5-10 us per GroupNorm at the 32-row shard for a few KB of work).
   // The sample's first workgroup keeps them for the backward.
   if (tid < G) {
     float mu, inv, md, a;
     double a8[8];
+    const float kg = gn_pivot(A, b, tid, cpg);               // issued ahead of the slot loads, not after their sums
     gn_sum_slots(A, b, tid, A.dual ? 4 : 2, a8);
-    gn_stats(a8, (double)P * cpg, A.eps, mu, inv, md, a);
+    gn_stats(a8, (double)P * cpg, A.eps, (double)kg, mu, inv, md, a);
     sst[tid] = f32x4{mu, inv, md, a};
     if (A.stats && blockIdx.x == 0) *reinterpret_cast<f32x4*>(A.stats + ((size_t)b * G + tid) * 4) = f32x4{mu, inv, md, a};
   }
@@ -261,7 +291,7 @@ __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
   if (!L.live) return;
   const int cv = L.cv;
   const long tot = (long)A.Bp * P * C;
-  const GnConsts<V> K = gn_consts<V>(A, sst, 0, V * cv, cpg);
+  const GnConsts<V> K = gn_consts<V>(A, sst, 0, b, V * cv, cpg);
   const int p0 = blockIdx.x * A.chunk, p1 = min(p0 + A.chunk, P);
   const GnSrc sx = gn_src(A, V * cv);
   DropKey dk;
@@ -272,7 +302,7 @@ __global__ void __launch_bounds__(256) k_gn_fwd_apply(GnArgs A) {
     gn_load_x<VEC>(sx, ((long)b * P + p) * sx.pitch, A.dual, x, xd);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const float xh = (x[k] - K.mu[k]) * K.inv[k];
+      const float xh = ((x[k] - K.kg[k]) - K.mu[k]) * K.inv[k];
       y[k] = K.ga[k] * xh + K.be[k];
       yd[k] = A.dual ? K.ga[k] * (K.inv[k] * ((xd[k] - K.md[k]) - xh * K.a[k])) : 0.f;
       if (A.silu) {
@@ -332,7 +362,7 @@ struct GnElem { float xh, wh, zbk, zdbk, X, W; };
 template <int V>
 __device__ __forceinline__ GnElem gn_bwd_elem(float x, float xd, const GnConsts<V>& K, int k, int silu, float zb, float zdb) {
   GnElem E;
-  E.xh = (x - K.mu[k]) * K.inv[k];
+  E.xh = ((x - K.kg[k]) - K.mu[k]) * K.inv[k];
   E.wh = K.inv[k] * ((xd - K.md[k]) - E.xh * K.a[k]);
   E.zbk = zb; E.zdbk = zdb;
   if (silu) {
@@ -358,7 +388,7 @@ __global__ void __launch_bounds__(256) k_gn_bwd_reduce(GnArgs A) {
   const GnLane L = gn_lane<VEC>(tid, C);
   const int cv = L.cv, pl = L.pl;
   const long tot = (long)A.Bp * P * C;
-  const GnConsts<V> K = gn_consts<V>(A, reinterpret_cast<const f32x4*>(A.stats), (size_t)b * G, V * cv, cpg);
+  const GnConsts<V> K = gn_consts<V>(A, reinterpret_cast<const f32x4*>(A.stats), (size_t)b * G, b, V * cv, cpg);
   const int p0 = blockIdx.y * A.chunk, p1 = min(p0 + A.chunk, P);
   const GnSrc sx = gn_src(A, V * cv);
   double dX[V], dXx[V], dW[V], dWx[V], dWw[V];
@@ -454,7 +484,7 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(GnArgs A) {
   const int cv = L.cv;
   const long tot = (long)A.Bp * P * C;
   const float rc = 1.0f / ((float)P * (float)cpg);
-  const GnConsts<V> K = gn_consts<V>(A, reinterpret_cast<const f32x4*>(A.stats), (size_t)b * G, V * cv, cpg);
+  const GnConsts<V> K = gn_consts<V>(A, reinterpret_cast<const f32x4*>(A.stats), (size_t)b * G, b, V * cv, cpg);
   float mX[V], mXx[V], mW[V], pp[V], cc[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) {
@@ -1307,7 +1337,7 @@ __global__ void __launch_bounds__(256) k_gn_affine_cs(const float* __restrict__ 
     double a8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int k = 0; k < cpg; ++k) { a8[0] += red[0][g0 + k]; a8[1] += red[1][g0 + k]; }
     float mu, inv, md, a;
-    gn_stats(a8, (double)P * cpg, eps, mu, inv, md, a);
+    gn_stats(a8, (double)P * cpg, eps, 0.0, mu, inv, md, a);
     const float sc = inv * gamma[c];
     scale[(size_t)b * C + c] = sc;
     shift[(size_t)b * C + c] = beta[c] - mu * sc;
