@@ -837,6 +837,28 @@ int msgm_attention_dual_mh_backward(const float* qkv, const float* att, const fl
                                     int64_t Bp, int32_t T, int32_t heads, int32_t D, float scale, void* workspace,
                                     size_t workspace_bytes, msgm_stream_t stream);
 
+/* Self-attention at T = 16 tokens exactly — the 4x4 level of the 16x16 U-Net (AttentionBlock / QKVAttention with
+ * num_heads = heads, model/unet.py:220-250) — which none of the entries above takes.  Same layouts as the multi-head entries:
+ * qkv / dqkv [N][T][3C] channels-last, C = heads * D, head h's q | k | v at columns 3Dh, 3Dh + D, 3Dh + 2D; out / att / datt
+ * [N][T][C] with head h at columns [Dh, D(h+1)); on the dual entries N = 2Bp, rows [0,Bp) primal and [Bp,2Bp) tangent;
+ * scale = D^-1/2.  A (sample, head) pair's logits are ONE 16x16 MFMA tile, so each entry is one kernel launch that keeps every
+ * (T,T) quantity in registers: no online softmax, no statistics handed from the forward to the backward (the backward
+ * recomputes P, Sd and rbar from q, k and takes c and delta from the tile, so it reads neither att nor any statistics), no
+ * workspace, no atomics, no memset; every element of out / att / dqkv is written exactly once.  A pair's result does not
+ * depend on N / Bp or on its place in the launch: bitwise repeatable and batch-invariant.
+ * Built for T = 16, D in {16, 32, 64, 128}, heads in [1, 64] (msgm_attention_small_supported); other shapes return
+ * MSGM_E_UNSUPPORTED.  Null or not 16-byte-aligned pointers return MSGM_E_BADARG. */
+int msgm_attention_small_supported(int32_t T, int32_t heads, int32_t D);
+/* sampler forward, no tangent (model/unet.py:220-250): out = softmax(scale q k^T) v */
+int msgm_attention_small_forward(const float* qkv, float* out, int64_t N, int32_t T, int32_t heads, int32_t D, float scale,
+                                 msgm_stream_t stream);
+/* dual forward (model/unet.py:220-250 under the forward-mode SSM step): att = [o ; od], od = Pd v + P vd */
+int msgm_attention_small_dual_forward(const float* qkv, float* att, int64_t Bp, int32_t T, int32_t heads, int32_t D, float scale,
+                                      msgm_stream_t stream);
+/* dual backward (model/unet.py:220-250): dqkv = [qbar|kbar|vbar ; qdbar|kdbar|vdbar] from datt = [obar ; odbar] */
+int msgm_attention_small_dual_backward(const float* qkv, const float* datt, float* dqkv, int64_t Bp, int32_t T, int32_t heads,
+                                       int32_t D, float scale, msgm_stream_t stream);
+
 /* ---- reporting metric next to the hot path -------------------- */
 /* RBF kernel of compute_kernel / compute_mmd (quantitative_comparison.py:22-46):
  * k(x_i, y_j) = exp(-sum_d (x_i - y_j)^2 / d^2) for x [Nx][d], y [Ny][d].  K (may be NULL) receives the

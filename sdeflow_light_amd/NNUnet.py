@@ -222,6 +222,12 @@ def _attn_kernel(a: _Attn, dual: bool):
     return fns + ((a.c,) if a.nh == 1 else (a.nh, a.d),)
 
 
+def _attn_small(a: _Attn, T: int) -> bool:
+    """True when the one-launch T = 16 kernels (ops.attention_small_*) take the block: decided by shape alone, at any head
+    count.  Looked up on ``ops`` at every call."""
+    return T == 16 and ops.attention_small_supported(T, a.nh, a.d)
+
+
 class _Pass:
     """What one pass through the network shares.  There are two modes: the sampler (``tape`` None: no tangent, nothing
     kept) and training (``tape`` a list: dual numbers, the tangent being the second half of the N = 2 Bp rows, and every
@@ -422,7 +428,8 @@ class VorticityUNet(nn.Module, FlatParamMixin):
 
     class AttnRec(NamedTuple):
         """Tape record of one attention block.  The fused kernel keeps its per-query statistics (``row_stats``), the composed
-        form its (T, T) tensors (``P``, ``Wd``, ``Pd``, every head's); the other group is None."""
+        form its (T, T) tensors (``P``, ``Wd``, ``Pd``, every head's); the other group is None.  The fused T = 16 kernels keep
+        neither (``small``): their backward recomputes the one 16x16 tile."""
         a: _Attn
         x: torch.Tensor
         H: int
@@ -435,6 +442,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         P: Optional[torch.Tensor] = None             # composed: softmax, the logits' tangent, the softmax's tangent
         Wd: Optional[torch.Tensor] = None
         Pd: Optional[torch.Tensor] = None
+        small: bool = False                          # fused at T = 16: nothing kept
 
     def _attn_fwd(self, ctx: _Pass, a: _Attn, x, H, W):
         N, Bp, dual = ctx.N, ctx.Bp, ctx.train
@@ -442,18 +450,28 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         nh, D = a.nh, a.d                                                # heads, channels per head
         dev = x.device
         s2 = 1.0 / math.sqrt(D)                                          # (ch^-1/4)^2, ch = D   model/unet.py:245-248
+        small = _attn_small(a, T)                                        # T = 16: the one-launch kernels, any head count
         supported, forward, _, hd = _attn_kernel(a, False)
-        if supported(T, *hd) and not dual:                               # sampler: nothing to keep, no tangent
+        if (small or supported(T, *hd)) and not dual:                    # sampler: nothing to keep, no tangent
             if a.qkv.can_transform_input(N, 1, T):
                 qkv, _, _ = a.qkv.forward([x], N, 1, T, Bp, in_affine=self._gn_fold(a.m.norm, x, Bp, T, C))   # GN folded in
             else:
                 hn, _ = self._gn(ctx, a.m.norm, x, T, C, False)
                 qkv, _, _ = a.qkv.forward([hn], N, 1, T, Bp)
-            att = forward(qkv, torch.empty(N * T * C, device=dev), N, T, *hd, s2)
+            if small:
+                att = ops.attention_small_forward(qkv, torch.empty(N * T * C, device=dev), N, T, nh, D, s2)
+            else:
+                att = forward(qkv, torch.empty(N * T * C, device=dev), N, T, *hd, s2)
             out, _, _ = a.proj.forward([att], N, 1, T, Bp, residual=x, stats=True)    # x + proj(.) in the epilogue (unet.py:232)
             return out
         hn, st = self._gn(ctx, a.m.norm, x, T, C, False)
         qkv, _, _ = a.qkv.forward([hn], N, 1, T, Bp)                     # [N][T][3C]: per head q | k | v channel slices
+        if small and dual:
+            # training at T = 16: the pair's logits are one MFMA tile; nothing is kept, the backward recomputes the tile
+            att = ops.attention_small_dual_forward(qkv, Bp, T, nh, D, s2)
+            out, _, _ = a.proj.forward([att], N, 1, T, Bp, residual=x)
+            ctx.tape.append(self.AttnRec(a, x, H, W, hn, st, qkv, att, small=True))
+            return out
         supported, forward, _, hd = _attn_kernel(a, True)
         if supported(T, *hd) and dual:
             # training: ONE kernel for the six products of the dual forward, nothing of size (T,T) written; the
@@ -766,7 +784,9 @@ class VorticityUNet(nn.Module, FlatParamMixin):
     def _attn_bwd(self, r: "VorticityUNet.AttnRec", dout, N, Bp):
         a, T = r.a, r.H * r.W
         (datt,) = a.proj.backward(dout, [r.att], N, 1, T, Bp)           # [N][T][C]: abar | adotbar
-        if r.row_stats is not None:                                     # fused dual attention
+        if r.small:                                                     # fused dual attention at T = 16
+            dqkv = ops.attention_small_dual_backward(r.qkv, datt, Bp, T, a.nh, a.d, 1.0 / math.sqrt(a.d))
+        elif r.row_stats is not None:                                   # fused dual attention
             _, _, backward, hd = _attn_kernel(a, True)
             dqkv = backward(r.qkv, r.att, datt, r.row_stats, Bp, T, *hd, 1.0 / math.sqrt(a.d))
         else:

@@ -1412,6 +1412,44 @@ def attention_dual_mh_backward(qkv, att, datt, stats, Bp, T, heads, D, scale):
     return dqkv
 
 
+def attention_small_supported(T, heads, D) -> bool:
+    """T = 16 exactly (the 4x4 level of the 16x16 U-Net), D in {16, 32, 64, 128}, 1 <= heads <= 64."""
+    return bool(lib().msgm_attention_small_supported(int(T), int(heads), int(D)))
+
+
+def attention_small_forward(qkv, out, N, T, heads, D, scale):
+    """attention_mh_forward's layouts at T = 16: one launch, the pair's logits one MFMA tile (model/unet.py:220-250)."""
+    C = heads * D
+    if qkv.numel() < N * T * 3 * C or out.numel() < N * T * C:
+        raise MsgmError("attention_small: buffer too small")
+    check(lib().msgm_attention_small_forward(ptr(f32(qkv)), ptr(f32(out)), N, T, heads, D, float(scale), stream()),
+          "msgm_attention_small_forward")
+    return out
+
+
+def attention_small_dual_forward(qkv, Bp, T, heads, D, scale):
+    """Dual-number attention at T = 16: qkv [2Bp][T][3C] -> att [2Bp][T][C] = o | odot.  No statistics: the backward
+    recomputes the 16x16 tile."""
+    C = heads * D
+    if qkv.numel() < 2 * Bp * T * 3 * C:
+        raise MsgmError("attention_small_dual: qkv too small")
+    att = torch.empty(2 * Bp * T * C, dtype=torch.float32, device=qkv.device)
+    check(lib().msgm_attention_small_dual_forward(ptr(f32(qkv)), ptr(att), Bp, T, heads, D, float(scale), stream()),
+          "msgm_attention_small_dual_forward")
+    return att
+
+
+def attention_small_dual_backward(qkv, datt, Bp, T, heads, D, scale):
+    """dqkv [2Bp][T][3C] from datt = [obar ; odbar] at T = 16: one launch, no workspace, nothing read but qkv and datt."""
+    C = heads * D
+    if min(qkv.numel() // 3, datt.numel()) < 2 * Bp * T * C:
+        raise MsgmError("attention_small_dual backward: buffer too small")
+    dqkv = torch.empty(2 * Bp * T * 3 * C, dtype=torch.float32, device=qkv.device)
+    check(lib().msgm_attention_small_dual_backward(ptr(f32(qkv)), ptr(f32(datt)), ptr(dqkv), Bp, T, heads, D, float(scale),
+                                                   stream()), "msgm_attention_small_dual_backward")
+    return dqkv
+
+
 def softmax_dual_backward(Pm, Wd, Pb, Pdb, T):
     rows = Pm.numel() // T
     if not (Wd.numel() == Pb.numel() == Pdb.numel() == Pm.numel()):
