@@ -666,8 +666,14 @@ int msgm_add_row(float* x, const float* E, int32_t N, int32_t P, int32_t C, int3
  * `residual` (may be NULL, same shape as gx, may alias gx) is added to them — the
  * skip branch of a ResBlock / attention block (`h + x`, model/unet.py:187,232)
  * without a separate axpy pass.
- * The workspace needs no initialisation: every slot that is read was written by the same call. */
-size_t msgm_groupnorm_workspace(int32_t Bp, int32_t G);   /* bytes: double moment accumulators + float statistics */
+ * The workspace needs no initialisation: every slot that is read was written by the same call.
+ * Widths: C % G == 0, G <= 64; C <= 1024 when C % 4 == 0 (the 16-byte builds), C <= 256 otherwise; the two-source forms
+ * need C0 % 4 == 0 and C1 % 4 == 0.  Anything else is MSGM_E_UNSUPPORTED before any launch.
+ * msgm_groupnorm_workspace_c(Bp, G, C): bytes every entry below needs for a tensor of C channels (moment slots, statistics,
+ * dgamma / dbeta slots of pitch max(C, 256)); msgm_groupnorm_workspace(Bp, G) is its value for C <= 256.  Each entry checks
+ * workspace_bytes against its own C -> MSGM_E_WORKSPACE. */
+size_t msgm_groupnorm_workspace(int32_t Bp, int32_t G);
+size_t msgm_groupnorm_workspace_c(int32_t Bp, int32_t G, int32_t C);
 int msgm_groupnorm_dual_forward(const float* x, const float* gamma, const float* beta, float* out, float* stats,
                                 int32_t Bp, int32_t P, int32_t C, int32_t G, int32_t dual, int32_t silu, float eps,
                                 void* workspace, size_t workspace_bytes, msgm_stream_t stream);

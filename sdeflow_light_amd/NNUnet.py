@@ -32,6 +32,8 @@ from .convnet import ConvOp, ConvOpSet
 
 SILU = ops.ACT_SILU
 scale_image = 5          # NNUnet.py:19
+# the kernels' width limits (csrc/unet2d_kernels.hip: GN_MAX_C, gn_max_c; k_emb_bank's K), checked by VorticityUNet._build
+GN_MAX_C, GN_MAX_C_SCALAR, EMB_MAX_K = 1024, 256, 512
 
 
 def flat_to_img(x: torch.Tensor, H: int, W: int, order: Literal["C", "F"] = "C") -> torch.Tensor:
@@ -282,7 +284,28 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         return self.dropout_rng
 
     # ------------------------------------------------------------------ build
+    def _check_widths(self):
+        """What the kernels cannot run, found on the plan before the first launch of the first pass (inside a capture too):
+        the GroupNorm kernels take C <= GN_MAX_C channels when C % 4 == 0 and C <= GN_MAX_C_SCALAR otherwise (a decoder
+        ResBlock's in-norm sees cat([h, skip])), the embedding bank K = 4 model_channels <= EMB_MAX_K."""
+        core = self.core
+        if self._x is not None:          # a built plan passed
+            return
+        if 4 * core.model_channels > EMB_MAX_K:
+            raise MsgmError(f"core.time_embed: 4 * model_channels = {4 * core.model_channels} is wider than the embedding bank's "
+                            f"K <= {EMB_MAX_K} (base_channels <= {EMB_MAX_K // 4})")
+        for name, m in core.named_modules():
+            if not isinstance(m, nn.GroupNorm):
+                continue
+            C = m.num_channels
+            if C > GN_MAX_C:
+                raise MsgmError(f"core.{name}: GroupNorm over {C} channels; the GroupNorm kernels take C <= {GN_MAX_C}")
+            if C > GN_MAX_C_SCALAR and C % 4:
+                raise MsgmError(f"core.{name}: GroupNorm over {C} channels; above {GN_MAX_C_SCALAR} channels the GroupNorm "
+                                f"kernels take only C % 4 == 0")
+
     def _build(self):
+        self._check_widths()
         self.flat_parameters()
         core = self.core
         first = core.time_embed[0].weight
@@ -620,6 +643,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
     @torch.no_grad()
     def forward(self, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         """x: (B, channels*H*W) flat or (B,channels,H,W); t: (B,) or (B,1) (NNUnet.py:195-245)."""
+        self._check_widths()             # refused before any launch
         t = t.reshape(-1).float().contiguous()
         S_, Cc = self.in_space, self.channels
         need_flat = x.dim() == 2
@@ -662,6 +686,7 @@ class VorticityUNet(nn.Module, FlatParamMixin):
         B, d = y.shape
         N = 2 * B
         ops._row_weight(row_weight, B)   # refused before any launch
+        self._check_widths()
         S_, Cc = self.in_space, self.channels
         self.flat_parameters()
         for p in self.parameters():

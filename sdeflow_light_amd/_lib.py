@@ -132,6 +132,7 @@ SIGNATURES = {
     "msgm_gather_row": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
     "msgm_add_row": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _P]),
     "msgm_groupnorm_workspace": (_SZ, [_I32, _I32]),
+    "msgm_groupnorm_workspace_c": (_SZ, [_I32, _I32, _I32]),
     "msgm_groupnorm_dual_forward": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _SZ, _P]),
     "msgm_groupnorm_dual_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _SZ, _P]),
     "msgm_groupnorm_dual_forward2": (C.c_int, [_P, _I32, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _SZ, _P]),

@@ -30,6 +30,10 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 // acc[b][chunk < GN_SLOTS][g][8] doubles: forward uses moments 0..3, backward 0..4; the per-channel
 // parameter gradients of the backward go to per-(sample, chunk) slots too and are summed in a fixed order.
 #define GN_SLOTS 32
+// widest tensor: the VEC builds (C % 4 == 0) take C <= GN_MAX_C (C/4 <= 256 channel vectors, one per thread), the scalar
+// builds one channel per thread (C <= 256); gn_max_c() is the ONE place the entries ask
+#define GN_MAX_C 1024
+static inline int gn_max_c(int C) { return C % 4 == 0 ? GN_MAX_C : 256; }
 struct GnArgs {
   const float* x; const float* gamma; const float* beta;
   float* out; double* acc; float* stats;
@@ -72,7 +76,8 @@ __device__ __forceinline__ f32x4 drop_mul4(const DropKey& k, int b, int P, int C
 
 // ---- the phases the four GroupNorm kernels share
 // gn_lane: a thread's place in the 256-thread workgroup: channel vector cv (channels V*cv .. V*cv+V-1; V = 4 with VEC, else 1)
-// of pixel lane pl, CV vectors per pixel, PL = 256 / CV pixel lanes.  Threads beyond CV*PL (C = 96: 240) are not live: (0, 0).
+// of pixel lane pl, CV <= 256 vectors per pixel (VEC: C <= 1024), PL = 256 / CV pixel lanes, so PL C <= 1024 elements per LDS
+// image.  Threads beyond CV*PL (C = 96: 240; C = 640: 160, one pixel lane) are not live: (0, 0).
 struct GnLane { int cv, pl, CV, PL; bool live; };
 template <bool VEC>
 __device__ __forceinline__ GnLane gn_lane(int tid, int C) {
@@ -231,9 +236,9 @@ __device__ __forceinline__ void gn_stats(const double* a8, double cnt, float eps
 // GroupNorm as a per-(sample, channel) affine map y = a x + b (a = gamma/sigma, b = beta - mean a) for a consumer that
 // applies it while reading x (msgm_conv_forward_fused).  One block per sample.
 __global__ void __launch_bounds__(256) k_gn_affine(GnArgs A, float* __restrict__ scale, float* __restrict__ shift) {
-  const int b = blockIdx.x, c = threadIdx.x, cpg = A.C / A.G;
+  const int b = blockIdx.x, cpg = A.C / A.G;
   const double cnt = (double)A.P * cpg;
-  if (c < A.C) {
+  for (int c = threadIdx.x; c < A.C; c += 256) {
     float mu, inv, md, a;
     double a8[8];
     gn_sum_slots(A, b, c / cpg, 2, a8);
@@ -1209,14 +1214,17 @@ static int gn_chunks_apply(int Bp, int P, int* chunk) {
 }
 
 // workspace: acc[Bp][GN_SLOTS][G][8] doubles (per-chunk moment slots) | accf[Bp][G][8] doubles (backward moments summed)
-// | [Bp][G][4] floats (finalised forward statistics) | [2][Bp*GN_SLOTS][256] floats (dgamma / dbeta slots, C <= 256).
+// | [Bp][G][4] floats (finalised forward statistics) | [2][Bp*GN_SLOTS][max(C, 256)] floats (dgamma / dbeta slots; the
+// kernels use pitch C inside it).  msgm_groupnorm_workspace is the C <= 256 value; every entry checks its own C's.
 // Nothing in it has to be zero on entry: every slot that is read was written by the same call.
 static inline size_t gn_acc_bytes(int32_t Bp, int32_t G) { return (size_t)Bp * GN_SLOTS * (size_t)G * 8 * sizeof(double); }
 static inline size_t gn_accf_bytes(int32_t Bp, int32_t G) { return (size_t)Bp * (size_t)G * 8 * sizeof(double); }
 static inline size_t gn_stats_bytes(int32_t Bp, int32_t G) { return (size_t)Bp * (size_t)G * 4 * sizeof(float); }
-size_t msgm_groupnorm_workspace(int32_t Bp, int32_t G) {
-  return gn_acc_bytes(Bp, G) + gn_accf_bytes(Bp, G) + gn_stats_bytes(Bp, G) + (size_t)2 * Bp * GN_SLOTS * 256 * sizeof(float);
+size_t msgm_groupnorm_workspace_c(int32_t Bp, int32_t G, int32_t C) {
+  return gn_acc_bytes(Bp, G) + gn_accf_bytes(Bp, G) + gn_stats_bytes(Bp, G) +
+         (size_t)2 * Bp * GN_SLOTS * (size_t)(C > 256 ? C : 256) * sizeof(float);
 }
+size_t msgm_groupnorm_workspace(int32_t Bp, int32_t G) { return msgm_groupnorm_workspace_c(Bp, G, 256); }
 
 // dropout descriptor -> the DROP kernels' arguments (single-source input, C % 4 == 0: one Philox block per channel quad)
 static int gn_set_dropout(GnArgs& A, const msgm_dropout_t* drop) {
@@ -1230,8 +1238,8 @@ static int gn_set_dropout(GnArgs& A, const msgm_dropout_t* drop) {
 static int gn_forward_reduce(GnArgs& A, size_t workspace_bytes, const msgm_dropout_t* drop, bool vec, msgm_stream_t stream) {
   const int C = A.C, C0 = A.C0, G = A.G;
   if (!A.x || !A.gamma || !A.beta || !A.acc || A.Bp <= 0 || A.P <= 0 || C <= 0 || G <= 0) return MSGM_E_BADARG;
-  if (C % G || C > 256 || G > 64 || (A.x1 && (C0 % 4 || (C - C0) % 4 || C0 <= 0 || C0 >= C))) return MSGM_E_UNSUPPORTED;
-  if (workspace_bytes < msgm_groupnorm_workspace(A.Bp, G)) return MSGM_E_WORKSPACE;
+  if (C % G || C > gn_max_c(C) || G > 64 || (A.x1 && (C0 % 4 || (C - C0) % 4 || C0 <= 0 || C0 >= C))) return MSGM_E_UNSUPPORTED;
+  if (workspace_bytes < msgm_groupnorm_workspace_c(A.Bp, G, C)) return MSGM_E_WORKSPACE;
   if (drop) {
     const int rc = gn_set_dropout(A, drop);
     if (rc != MSGM_OK) return rc;
@@ -1321,9 +1329,9 @@ __global__ void __launch_bounds__(256) k_gn_affine_cs(const float* __restrict__ 
                                                       int S1, int C1, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, int P, int G, float eps,
                                                       float* __restrict__ scale, float* __restrict__ shift) {
-  __shared__ double red[2][256];
-  const int b = blockIdx.x, c = threadIdx.x, C = C0 + C1, cpg = C / G;
-  if (c < C) {
+  __shared__ double red[2][GN_MAX_C];
+  const int b = blockIdx.x, C = C0 + C1, cpg = C / G;
+  for (int c = threadIdx.x; c < C; c += 256) {
     const bool second = c >= C0;
     const int Cs = second ? C1 : C0, S = second ? S1 : S0, cc = second ? c - C0 : c;
     const float* p = (second ? cs1 : cs0) + (size_t)b * S * 2 * Cs + cc;
@@ -1332,7 +1340,7 @@ __global__ void __launch_bounds__(256) k_gn_affine_cs(const float* __restrict__ 
     red[0][c] = s; red[1][c] = ss;
   }
   __syncthreads();
-  if (c < C) {
+  for (int c = threadIdx.x; c < C; c += 256) {
     const int g0 = (c / cpg) * cpg;
     double a8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int k = 0; k < cpg; ++k) { a8[0] += red[0][g0 + k]; a8[1] += red[1][g0 + k]; }
@@ -1350,7 +1358,7 @@ int msgm_groupnorm_affine_chanstats(const float* cs0, int32_t S0, int32_t C0, co
   if (!cs0 || !gamma || !beta || !scale || !shift || Bp <= 0 || P <= 0 || C0 <= 0 || S0 <= 0 || G <= 0) return MSGM_E_BADARG;
   if (cs1 ? (C1 <= 0 || S1 <= 0) : (C1 != 0)) return MSGM_E_BADARG;
   const int C = C0 + C1;
-  if (C % G || C > 256 || G > 64) return MSGM_E_UNSUPPORTED;
+  if (C % G || C > gn_max_c(C) || G > 64) return MSGM_E_UNSUPPORTED;
   hipLaunchKernelGGL(k_gn_affine_cs, dim3(Bp), dim3(256), 0, S(stream), cs0, S0, C0, cs1, S1, C1, gamma, beta, P, G, eps, scale,
                      shift);
   return msgm_check_launch();
@@ -1367,9 +1375,9 @@ static int gn_backward_impl(const float* x, int32_t C0, const float* x1, int32_t
                             const msgm_dropout_t* drop = nullptr) {
   if (!x || !gamma || !beta || !stats || !gout || !gx || !dgamma || !dbeta || !workspace || Bp <= 0 || P <= 0 || C <= 0 || G <= 0)
     return MSGM_E_BADARG;
-  if (C % G || C > 256 || G > 64) return MSGM_E_UNSUPPORTED;
+  if (C % G || C > gn_max_c(C) || G > 64) return MSGM_E_UNSUPPORTED;
   if (x1 && (!gx1 || residual || residual2 || C0 % 4 || (C - C0) % 4 || C0 <= 0 || C0 >= C)) return MSGM_E_UNSUPPORTED;
-  if (workspace_bytes < msgm_groupnorm_workspace(Bp, G)) return MSGM_E_WORKSPACE;
+  if (workspace_bytes < msgm_groupnorm_workspace_c(Bp, G, C)) return MSGM_E_WORKSPACE;
   GnArgs A{x, gamma, beta, nullptr, reinterpret_cast<double*>(workspace), const_cast<float*>(stats), P, C, G, Bp, 1, silu, 0,
            eps, gout, gx, dgamma, dbeta, x1, C0, gx1};
   if (drop) {

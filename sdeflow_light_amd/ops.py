@@ -760,7 +760,7 @@ def groupnorm_affine(x0, C0, gamma, beta, Bp, P, G, x1=None, C1=0, eps=1e-5):
         raise MsgmError("groupnorm_affine: size mismatch")
     scale = torch.empty(Bp * C, dtype=torch.float32, device=x0.device)
     shift = torch.empty_like(scale)
-    ws = _gn_ws(Bp, G, x0.device)
+    ws = _gn_ws(Bp, G, C, x0.device)
     check(lib().msgm_groupnorm_affine(ptr(f32(x0)), C0, ptr(x1), C1, ptr(f32(gamma)), ptr(f32(beta)), ptr(scale), ptr(shift),
                                       Bp, P, G, float(eps), ptr(ws), ws.numel() * 8, stream()), "msgm_groupnorm_affine")
     return scale, shift
@@ -1072,9 +1072,10 @@ def add_row(x: torch.Tensor, E: torch.Tensor, N: int, P: int, C: int, pos: int, 
 _GN_WS = {}
 
 
-def _gn_ws(Bp: int, G: int, device) -> torch.Tensor:
-    """Per-device scratch for the GroupNorm moment accumulators (consumed in stream order)."""
-    n = int(lib().msgm_groupnorm_workspace(Bp, G)) // 8
+def _gn_ws(Bp: int, G: int, C: int, device) -> torch.Tensor:
+    """Per-device scratch for the GroupNorm moment accumulators (consumed in stream order), sized for C channels: every
+    C <= 256 needs (and shares) the same buffer, a wider tensor a larger one, allocated when the first one asks."""
+    n = int(lib().msgm_groupnorm_workspace_c(Bp, G, C)) // 8
     key = (torch.device(device), n)
     if key not in _GN_WS:
         _GN_WS[key] = torch.empty(n, dtype=torch.float64, device=device)     # per-chunk moment slots: no zero contract
@@ -1114,7 +1115,7 @@ def groupnorm_dual_forward(x, gamma, beta, Bp, P, C, G, dual, silu, stats=None, 
     if stats is not None and stats.numel() != Bp * G * 4:
         raise MsgmError("groupnorm: stats must be [Bp][G][4]")
     out = torch.empty_like(x) if out is None else out
-    ws = _gn_ws(Bp, G, x.device)
+    ws = _gn_ws(Bp, G, C, x.device)
     if dropout is not None:
         check(lib().msgm_groupnorm_dual_forward_dropout(ptr(f32(x)), ptr(f32(gamma)), ptr(f32(beta)), ptr(out), ptr(stats), Bp, P, C,
                                                         G, int(bool(dual)), int(bool(silu)), float(eps), ptr(ws), ws.numel() * 8,
@@ -1133,7 +1134,7 @@ def _gn_backward_in_pass(x0, C0, x1, C1, gamma, beta, stats, gout, gx0, gx1, dga
     C = C0 + C1
     need = int(lib().msgm_groupnorm_param_slots_bytes(Bp, P, C))
     ps, nbytes = d.take(need)
-    ws = _gn_ws(Bp, G, x0.device)
+    ws = _gn_ws(Bp, G, C, x0.device)
     jobs, nj = (L.ReduceJobT * 2)(), C_.c_int32(0)
     params = (ptr(f32(gamma)), ptr(f32(beta)), ptr(f32(stats)), ptr(f32(gout)))
     rest = (int(bool(silu)), float(eps), ptr(residual), ptr(residual2), ptr(ws), ws.numel() * 8, ps, nbytes, jobs, C_.byref(nj))
@@ -1169,7 +1170,7 @@ def groupnorm_dual_backward(x, gamma, beta, stats, gout, dgamma, dbeta, Bp, P, C
             _gn_backward_in_pass(x, C, None, 0, gamma, beta, stats, gout, gx, None, dgamma, dbeta, Bp, P, G, silu, eps, residual, dp,
                                  residual2=residual2, dropout=dropout)
         return gx
-    ws = _gn_ws(Bp, G, x.device)
+    ws = _gn_ws(Bp, G, C, x.device)
     check(lib().msgm_groupnorm_dual_backward(ptr(f32(x)), ptr(f32(gamma)), ptr(f32(beta)), ptr(f32(stats)), ptr(f32(gout)),
                                              ptr(gx), ptr(dgamma), ptr(dbeta), Bp, P, C, G, int(bool(silu)), float(eps),
                                              ptr(residual), ptr(ws), ws.numel() * 8, stream()), "msgm_groupnorm_dual_backward")
@@ -1184,7 +1185,7 @@ def groupnorm_dual_forward2(x0, C0, x1, C1, gamma, beta, Bp, P, G, dual, silu, s
     if x0.numel() != n * C0 or x1.numel() != n * C1:
         raise MsgmError("groupnorm2: size mismatch")
     out = torch.empty(n * (C0 + C1), dtype=torch.float32, device=x0.device)
-    ws = _gn_ws(Bp, G, x0.device)
+    ws = _gn_ws(Bp, G, C0 + C1, x0.device)
     check(lib().msgm_groupnorm_dual_forward2(ptr(f32(x0)), C0, ptr(f32(x1)), C1, ptr(f32(gamma)), ptr(f32(beta)), ptr(out), ptr(stats),
                                              Bp, P, G, int(bool(dual)), int(bool(silu)), float(eps), ptr(ws), ws.numel() * 8, stream()),
           "msgm_groupnorm_dual_forward2")
@@ -1200,7 +1201,7 @@ def groupnorm_dual_backward2(x0, C0, x1, C1, gamma, beta, stats, gout, dgamma, d
     if d is not None and d.device == x0.device:
         _gn_backward_in_pass(x0, C0, x1, C1, gamma, beta, stats, gout, gx0, gx1, dgamma, dbeta, Bp, P, G, silu, eps, None, d)
         return gx0, gx1
-    ws = _gn_ws(Bp, G, x0.device)
+    ws = _gn_ws(Bp, G, C0 + C1, x0.device)
     check(lib().msgm_groupnorm_dual_backward2(ptr(f32(x0)), C0, ptr(f32(x1)), C1, ptr(f32(gamma)), ptr(f32(beta)), ptr(f32(stats)),
                                               ptr(f32(gout)), ptr(gx0), ptr(gx1), ptr(dgamma), ptr(dbeta), Bp, P, G, int(bool(silu)),
                                               float(eps), ptr(ws), ws.numel() * 8, stream()), "msgm_groupnorm_dual_backward2")

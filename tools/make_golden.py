@@ -861,6 +861,43 @@ def g22_unet1d_deep():
     save("g22_unet1d_deep", **out)
 
 
+G23_FULL = ("a.core.output_blocks.0.0.in_layers.0.weight", "a.core.output_blocks.0.0.in_layers.0.bias")
+G23_NETS = (("W64", 64, (1, 2, 4)), ("D4", 32, (1, 2, 4, 8)))
+
+
+def g23_unet2d_wide():
+    """The reference's VorticityUNet wider than the driver's: W64 (base_channels 64, (1, 2, 4)) and D4 (32, (1, 2, 4, 8)) at
+    in_space 16, B = 2, on the well-conditioned parameter set (load_init_like_).  Both have a widest GroupNorm of 512
+    channels, the in-norm of output_blocks.0 over cat([h, skip]).  Forward at t = 0.37, the per-sample SSM loss with the
+    three draws forced, digests of all gradients, the gradients of that widest norm's weight and bias in full, and the
+    parameter names and shapes — the weights are the closed form, not stored."""
+    torch.manual_seed(23)
+    out = {}
+    for tag, base, mults in G23_NETS:
+        net = VorticityUNet(base_channels=base, channel_mults=mults, num_res_blocks=2, premodule=None, in_space=16,
+                            attention_resolutions=(2, 4), flatten_order="F")
+        load_init_like_(net)
+        rev = PluginReverseSDE(sgm(), net, Tparam())
+        B, d = 2, 256
+        x, u_t, eps, u_v = torch.randn(B, d) * 3, torch.rand(B, 1), torch.randn(B, d), torch.rand(B, d)
+        res = _ssm_case(rev, x, u_t, eps, u_v, full_grads=True)
+        grads = {k[len("grad::"):]: v for k, v in res.items() if k.startswith("grad::")}
+        out.update({f"{tag}_x": x, f"{tag}_u_t": u_t, f"{tag}_eps": eps, f"{tag}_u_v": u_v, f"{tag}_per": res["per"],
+                    f"{tag}_loss": res["loss"]})
+        for k in G23_FULL:
+            assert grads[k].numel() == 512 and float(grads[k].norm()) > 0, k
+            out[f"{tag}_grad::{k}"] = grads[k]
+        out.update({f"{tag}_gd_{k}": v for k, v in _grad_digest(grads).items()})
+        sd = {k: v for k, v in net.state_dict().items()}
+        out[f"{tag}_param_names"] = np.array(sorted(sd))
+        out[f"{tag}_param_shapes"] = np.array([",".join(str(int(s)) for s in sd[k].shape) for k in sorted(sd)])
+        with torch.no_grad():
+            t = torch.full((B,), 0.37)
+            out[f"{tag}_fwd_t"], out[f"{tag}_fwd"] = t, net(x, t)
+        print(tag, "parameters", sum(v.numel() for v in sd.values()), "loss", float(res["loss"]), "per", res["per"].tolist())
+    save("g23_unet2d_wide", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)

@@ -133,6 +133,21 @@ class Gn:
         torch.cuda.synchronize()
         return [self.scale.clone(), self.shift.clone(), self.ws.clone()]
 
+    def affine_cs(self, h, S=3):
+        """The same map from channel sums (k_gn_affine_cs): cs [Bp][S][2][C] per source, fp32 sums over the pixels p = s mod S."""
+        self._fill(self.scale, self.shift)
+        p, n = L.ptr, self.Bp * self.P
+
+        def sums(x, C):
+            x = x[: n * C].view(self.Bp, self.P, C)
+            return torch.stack([torch.stack([x[:, s::S].sum(1), (x[:, s::S] ** 2).sum(1)], 1) for s in range(S)], 1).contiguous()
+        cs0 = sums(self.x0, self.C0)
+        cs1 = sums(self.x1, self.C1) if self.C1 else None
+        check(h.msgm_groupnorm_affine_chanstats(p(cs0), S, self.C0, p(cs1), S if self.C1 else 0, self.C1, p(self.gamma), p(self.beta),
+                                                p(self.scale), p(self.shift), self.Bp, self.P, self.G, 1e-5, L.stream()))
+        torch.cuda.synchronize()
+        return [self.scale.clone(), self.shift.clone()]
+
     def mask(self, h):
         self._fill(self.out)
         check(h.msgm_dropout_mask(ctypes.byref(self.drop), self.Bp, self.P, self.C, L.ptr(self.out), L.stream()))
@@ -153,6 +168,7 @@ def gn_cases(Bp=3):
                 yield f"k_gn_bwd_reduce/apply{e} + k_gn_param_reduce {tag} silu={silu} residual", lambda h, gn=gn, s=silu: gn.backward(h, s, "own")
                 yield f"k_gn_bwd_reduce/apply{e} slots {tag} silu={silu} residual+residual2", lambda h, gn=gn, s=silu: gn.backward(h, s, "slots")
             yield f"k_gn_fwd_reduce{gn_expect(C, C, False, Bp, P, True)} + k_gn_affine {tag}", gn.affine
+            yield f"k_gn_affine_cs 3 slots {tag}", gn.affine_cs
             if C % 4 == 0:
                 ed = gn_expect(C, C, True, Bp, P)
                 yield f"k_gn_fwd_reduce<VEC> k_gn_fwd_apply{ed} {tag} dual=1 silu=1 p=0.1", lambda h, gn=gn: gn.forward(h, 1, 1, True)
@@ -166,6 +182,7 @@ def gn_cases(Bp=3):
             yield f"k_gn_bwd_reduce/apply{e} + k_gn_param_reduce two-source {tag} silu={silu}", lambda h, gn=gn, s=silu: gn.backward(h, s, "own")
             yield f"k_gn_bwd_reduce/apply{e} slots two-source {tag} silu={silu}", lambda h, gn=gn, s=silu: gn.backward(h, s, "slots")
         yield f"k_gn_fwd_reduce{gn_expect(96, 32, False, Bp, P, True)} + k_gn_affine two-source {tag}", gn.affine
+        yield f"k_gn_affine_cs 3 | 3 slots two-source {tag}", gn.affine_cs
 
 
 # ------------------------------------------------------------------------------------------------ attention
