@@ -205,6 +205,31 @@ int msgm_sde_stage(float* out, const float* base, float c_out,
                    const float* t_dev, const int64_t* step_dev,
                    msgm_stream_t stream);
 
+/* The same stage for the DENSE tensor with the n^3 contraction on the matrix cores (k_stage_dense_mm,
+ * csrc/sde_dense_mm_kernels.hip).  Replaces, per stage, f = beta L_G x (SDEs.py:415), G(x) = sqrt(beta) G x (SDEs.py:432) and
+ * the (B,n,n) x (B,n) product of EMstep (sde_scheme.py:36) for both w = dW and w = a: a workgroup forms
+ * T[r,(i,k)] = sum_j x_rj G[i,j,k] of a 32-row tile with v_mfma_f32_16x16x4_f32 and contracts it with the rows' w and a in
+ * registers, where msgm_sde_stage gives each output element to one lane running an n^2 scalar loop.  Arguments, draws,
+ * optional outputs and semantics are msgm_sde_stage's; an fp32 MFMA is a j-ordered fma chain and the k-slices meet in a fixed
+ * order, so the result is deterministic, but not msgm_sde_stage's bits: parity of this entry is to float64.
+ *   packed   G and L_G in fragment order, msgm_dense_g_stage_floats(n) floats (0 for n outside 1..64):
+ *            [n + 1][IB][SG][lane 64][r 4] with IB = SG = ceil(n/16); block k < n holds G[:, :, k], block n holds L_G; element
+ *            [ib][sg][lane][r] is entry (i, j) = (16 ib + (lane & 15), 4 (4 sg + r) + (lane >> 4)), +0 where i or j >= n
+ *            (ops.pack_dense_g_stage; for 17 <= n <= 32 this is msgm_mlp_dense_sde_loop's g_packed).  sde->G and sde->L_G are
+ *            not read.
+ * 1 <= n <= 64.  MSGM_E_UNSUPPORTED: n > 64 or a family other than MSGM_SDE_MSGM_DENSE.  MSGM_E_BADARG: what msgm_sde_stage
+ * rejects (out == x, no noise source, the reverse process without `a`) and a NULL `packed`.  Never allocates or synchronises. */
+size_t msgm_dense_g_stage_floats(int64_t n);                                                                /* host only */
+int msgm_sde_stage_dense_mm(float* out, const float* base, float c_out,
+                            const float* x, const float* a, const float* dW, const float* z,
+                            float sqrt_delta, const uint64_t* rng, uint64_t rng_step,
+                            float* dW_out, float* inc_out,
+                            int64_t B, int64_t n, const msgm_sde_t* sde, int32_t proc, int32_t strato,
+                            float t, float delta, float lmbd, const float* norm0,
+                            const float* delta_rows, float t_frac,
+                            const float* t_dev, const int64_t* step_dev,
+                            const float* packed, msgm_stream_t stream);
+
 /* Device-side clock for a hipGraph-replayed sampler step: t_dev[0] = ts[*step],
  * s_out[b] = T - t (score-net time argument).  With t_dev / step_dev passed to
  * msgm_sde_stage (overriding `t` / `rng_step`) one captured step can be

@@ -276,6 +276,7 @@ class MSGMsde(SDE):
         self.estim_cst_norm_dens_r_T = bool(estim_cst_norm_dens_r_T or plot_validate)       # SDEs.py:256-257
         self._cst_log_dens = None
         self._G_packed = None        # G and L_G in the dense sampler loop's fragment order: built on first use (packed_G)
+        self._G_packed_stage = None  # the same for msgm_sde_stage_dense_mm above n = 32 (packed_G_stage)
 
     def to(self, device):
         new = super().to(device)
@@ -289,6 +290,7 @@ class MSGMsde(SDE):
             new.G = self.G.to(device).contiguous()
         new.L_G = self.L_G.to(device).contiguous()
         new._G_packed = None         # rebuilt from the moved tensors when next needed
+        new._G_packed_stage = None
         return new
 
     def packed_G(self):
@@ -299,6 +301,18 @@ class MSGMsde(SDE):
         if self._G_packed is None or self._G_packed.device != self.G.device:
             self._G_packed = ops.pack_dense_g(self.G, self.L_G)
         return self._G_packed
+
+    def packed_G_stage(self):
+        """ops.pack_dense_g_stage(G, L_G) for msgm_sde_stage_dense_mm, built once per tensor on G's device.  For
+        17 <= n <= 32 the image is packed_G()'s and that one copy serves both kernels.  A plain attribute like packed_G: not in
+        state_dict() or checkpoints, and dropped by to()."""
+        if self.sparseTensor:
+            raise MsgmError("packed_G_stage: the sparse tensor has no dense image")
+        if 17 <= self.G.shape[0] <= 32:
+            return self.packed_G()
+        if self._G_packed_stage is None or self._G_packed_stage.device != self.G.device:
+            self._G_packed_stage = ops.pack_dense_g_stage(self.G, self.L_G)
+        return self._G_packed_stage
 
     @staticmethod
     def new_G(n):

@@ -230,6 +230,13 @@ def sde_stage(out: torch.Tensor, base: Optional[torch.Tensor], c_out: float, x: 
               t_frac: float = 0.0, t_dev: Optional[torch.Tensor] = None,
               step_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One integrator stage (K2/K3/K4): out = base + c_out*(drift*delta + sigma.dW)."""
+    return _sde_stage("msgm_sde_stage", (), out, base, c_out, x, a, sde, proc, strato, t, delta, lmbd, dW, z, rng, rng_step, dW_out,
+                      norm0, inc_out, delta_rows, t_frac, t_dev, step_dev)
+
+
+def _sde_stage(entry, extra, out, base, c_out, x, a, sde, proc, strato, t, delta, lmbd, dW, z, rng, rng_step, dW_out, norm0, inc_out,
+               delta_rows, t_frac, t_dev, step_dev):
+    """The checks and the call that the two stage entries share; `extra`: the entry's own arguments ahead of the stream."""
     if x.dim() != 2:
         raise MsgmError("state must be 2-D (B,n)")
     B, n = x.shape
@@ -237,12 +244,60 @@ def sde_stage(out: torch.Tensor, base: Optional[torch.Tensor], c_out: float, x: 
         _same_shape(tt, (B, n), nm)
     _same_shape(norm0, (B,), "norm0")
     _same_shape(delta_rows, (B,), "delta_rows")
-    check(lib().msgm_sde_stage(ptr(f32(out)), ptr(base), float(c_out), ptr(f32(x)), ptr(a), ptr(dW), ptr(z),
-                               float(delta ** 0.5), _rng_ptr(rng), int(rng_step), ptr(dW_out), ptr(inc_out), B, n, sde,
-                               int(proc), int(bool(strato)), float(t), float(delta), float(lmbd), ptr(norm0),
-                               ptr(delta_rows), float(t_frac), ptr(t_dev), ptr(step_dev), stream()),
-          "msgm_sde_stage")
+    check(getattr(lib(), entry)(ptr(f32(out)), ptr(base), float(c_out), ptr(f32(x)), ptr(a), ptr(dW), ptr(z),
+                                float(delta ** 0.5), _rng_ptr(rng), int(rng_step), ptr(dW_out), ptr(inc_out), B, n, sde,
+                                int(proc), int(bool(strato)), float(t), float(delta), float(lmbd), ptr(norm0),
+                                ptr(delta_rows), float(t_frac), ptr(t_dev), ptr(step_dev), *extra, stream()), entry)
     return out
+
+
+def stage_dense_mm_preferred(kind: int, n: int, proc: int) -> bool:
+    """Whether ``_Clock.stage`` sends a stage to msgm_sde_stage_dense_mm: by shape alone — the dense tensor, the reverse
+    process, 31 <= n <= 64.  Below 31 the composed dense route keeps msgm_sde_stage's bits (the yardstick of
+    the one-launch dense loop); the forward process keeps them because msgm_forward_perturb_composed runs through the same
+    ``_Clock.stage`` and equals msgm_forward_perturb bit for bit."""
+    return kind == L.SDE_MSGM_DENSE and proc == L.PROC_REVERSE and 31 <= n <= 64
+
+
+def pack_dense_g_stage(G: torch.Tensor, L_G: torch.Tensor) -> torch.Tensor:
+    """G (n,n,n) and L_G (n,n), n <= 64, in the fragment order msgm_sde_stage_dense_mm streams: (n + 1, IB, SG, 64, 4) fp32 on
+    G's device with IB = SG = ceil(n/16).  Block k < n is G[:, :, k], block n is L_G; element [ib, sg, lane, r] of a block is
+    its entry (i, j) = (16 ib + (lane & 15), 4 (4 sg + r) + (lane >> 4)): the lane's B operand of MFMA step 4 sg + r for the 16
+    outputs i of block ib.  Entries with i >= n or j >= n are +0.  For 17 <= n <= 32 this is pack_dense_g's image.  Plain
+    indexing: works on CPU tensors too."""
+    n = G.shape[0] if G.dim() == 3 else 0
+    if G.dim() != 3 or tuple(G.shape) != (n, n, n) or tuple(L_G.shape) != (n, n) or not 1 <= n <= 64:
+        raise MsgmError("pack_dense_g_stage: G (n,n,n) and L_G (n,n) with n <= 64")
+    dev, nb = G.device, (n + 15) // 16
+    lane = torch.arange(64, device=dev).view(1, 1, 64, 1)
+    ib, sg, r = (torch.arange(m, device=dev) for m in (nb, nb, 4))
+    i = (16 * ib.view(nb, 1, 1, 1) + (lane & 15)).expand(nb, nb, 64, 4)
+    j = (4 * (4 * sg.view(1, nb, 1, 1) + r.view(1, 1, 1, 4)) + (lane >> 4)).expand(nb, nb, 64, 4)
+    live = (i < n) & (j < n)
+    blocks = torch.cat([G.permute(2, 0, 1), L_G.to(dev).unsqueeze(0)], 0).to(torch.float32)          # [k][i][j]
+    out = blocks[:, i.clamp(max=n - 1), j.clamp(max=n - 1)]
+    return torch.where(live.unsqueeze(0), out, torch.zeros((), dtype=torch.float32, device=dev)).contiguous()
+
+
+def sde_stage_dense_mm(out: torch.Tensor, base: Optional[torch.Tensor], c_out: float, x: torch.Tensor,
+                       a: Optional[torch.Tensor], sde: L.SdeT, proc: int, strato: bool, t: float, delta: float, lmbd: float = 0.0,
+                       dW: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None, rng: Optional[PhiloxState] = None,
+                       rng_step: int = 0, dW_out: Optional[torch.Tensor] = None, norm0: Optional[torch.Tensor] = None,
+                       inc_out: Optional[torch.Tensor] = None, delta_rows: Optional[torch.Tensor] = None,
+                       t_frac: float = 0.0, t_dev: Optional[torch.Tensor] = None,
+                       step_dev: Optional[torch.Tensor] = None, packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sde_stage for the dense tensor with the contraction on the matrix cores (1 <= n <= 64): the same keywords plus
+    packed = pack_dense_g_stage(G, L_G) of the tensor in `sde`, on x's device (MSGMsde.packed_G_stage keeps one).
+    Deterministic, but not sde_stage's bits: its parity is to float64."""
+    if packed is not None and x.dim() == 2:
+        n = x.shape[1]
+        want = int(lib().msgm_dense_g_stage_floats(int(n)))
+        if packed.device != x.device:
+            raise MsgmError("dense stage: the packed tensor must be on the state's device")
+        if want and (packed.dtype != torch.float32 or not packed.is_contiguous() or packed.numel() != want):
+            raise MsgmError(f"dense stage: packed must be pack_dense_g_stage's contiguous fp32 image for n = {n}")
+    return _sde_stage("msgm_sde_stage_dense_mm", (ptr(packed),), out, base, c_out, x, a, sde, proc, strato, t, delta, lmbd, dW, z,
+                      rng, rng_step, dW_out, norm0, inc_out, delta_rows, t_frac, t_dev, step_dev)
 
 
 def ssm_loss_diag(out: torch.Tensor, v: torch.Tensor, t: torch.Tensor, sde: L.SdeT, inv_batch: float, *,

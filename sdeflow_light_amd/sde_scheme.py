@@ -53,11 +53,23 @@ class _Clock(NamedTuple):
     at: list            # at[k]: the keywords that place a stage at the step's k-th distinct stage time
     draw: dict          # the keywords of the stage that draws the step's Wiener increment
     score: Callable     # (x, k) -> a(x, T - t_k) for the reverse process, None for the forward one
+    packed: object = None   # the dense tensor's fragment image where ``ops.stage_dense_mm_preferred`` routes the stage (``_stage_image``)
 
     def stage(self, k, out, base, c_out, x, strato, **kw):
-        """out = base + c_out * (the increment at x and stage time k); the score is evaluated first."""
-        return ops.sde_stage(out, base, c_out, x, self.score(x, k), self.struct, self.proc, strato, delta=self.delta,
+        """out = base + c_out * (the increment at x and stage time k); the score is evaluated first.  The one place that
+        picks the stage kernel: with ``packed`` the dense contraction runs on the matrix cores (``msgm_sde_stage_dense_mm``)."""
+        a = self.score(x, k)
+        if self.packed is not None:
+            return ops.sde_stage_dense_mm(out, base, c_out, x, a, self.struct, self.proc, strato, delta=self.delta,
+                                          lmbd=self.lmbd, packed=self.packed, **self.at[k], **kw)
+        return ops.sde_stage(out, base, c_out, x, a, self.struct, self.proc, strato, delta=self.delta,
                              lmbd=self.lmbd, **self.at[k], **kw)
+
+
+def _stage_image(base, struct, n, proc):
+    """The ``packed`` field of a clock: the base SDE's cached fragment image (built here on first use, so before any capture)
+    where ``ops.stage_dense_mm_preferred`` takes the shape — the dense tensor, the reverse process, 31 <= n <= 64 — else None."""
+    return base.packed_G_stage() if ops.stage_dense_mm_preferred(struct.kind, n, proc) else None
 
 
 def _em_step(c, x, other, norm0):
@@ -124,6 +136,7 @@ class _Run:
             raise MsgmError("sde must be a PluginReverseSDE or a forward_SDE")
         self.proc = L.PROC_REVERSE if self.reverse else L.PROC_FORWARD
         self.struct = self.base.struct()
+        self.packed = _stage_image(self.base, self.struct, self.n, self.proc)
         if x_0.is_cuda and x_0.dtype == torch.float32 and x_0.is_contiguous() and x_0.device == self.device:
             # device-to-device copy as a KERNEL (captured steps hold kernel nodes only: see msgm_zero_async in csrc/common.h)
             self.x = ops.lincomb(torch.empty_like(x_0), x_0.detach(), 1.0)
@@ -167,7 +180,7 @@ class _Run:
         t = self.t(i)
         times = [t] + [float(torch.tensor(t, dtype=torch.float32) + self.delta * f) for f in fracs]
         return _Clock(self.struct, self.proc, self.lmbd, self.delta, [dict(t=s) for s in times],
-                      dict(z=self.z(i), rng=self.rng, rng_step=i), lambda x, k: self.score(x, times[k]))
+                      dict(z=self.z(i), rng=self.rng, rng_step=i), lambda x, k: self.score(x, times[k]), self.packed)
 
     def after_step(self, i):
         if self.keep_all:
@@ -184,7 +197,8 @@ class _Run:
         with 17 <= n <= 30, in_dim <= 32 and B > 64, where measured faster; its contraction runs on the matrix cores, so it
         agrees with the composed steps to float64 parity, not to the bit).  Same time grid, stage times and Philox draws as
         the composed steps; trajectory rows and kept rows are written by the kernel.  Returns whether it ran; everything
-        else — dense n >= 31, dense B <= 64, ``noise=`` — keeps the composed route."""
+        else — dense n >= 31, dense B <= 64, ``noise=`` — keeps the composed route, whose dense stage at 31 <= n <= 64 is
+        ``msgm_sde_stage_dense_mm`` (``_Clock.stage``)."""
         from .NN import MLP
         net = self.sde.a if self.reverse else None
         if not isinstance(net, MLP) or self.noise is not None or net.input_dim != self.n:
@@ -449,7 +463,8 @@ class GraphedStepSampler:
         # the fp32 value upstream adds to the fp32 t; 0.0 (no add) for the step's own time
         t_add = [0.0] + [float(torch.tensor(delta * f, dtype=torch.float32)) for f in fracs]
         clock = _Clock(st, L.PROC_REVERSE, lmbd, delta, [dict(t=0.0, t_dev=td) for td in self.t_dev],
-                       dict(rng=self.rng, step_dev=self.step), lambda xx, k: sde.a(xx, self.s[k]).contiguous())
+                       dict(rng=self.rng, step_dev=self.step), lambda xx, k: sde.a(xx, self.s[k]).contiguous(),
+                       _stage_image(base, st, n, L.PROC_REVERSE))
 
         def body():
             for td, s, add in zip(self.t_dev, self.s, t_add):
