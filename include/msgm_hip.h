@@ -135,6 +135,22 @@ int msgm_forward_perturb(const float* x0, const float* t, float* y, int32_t* k_o
                          float t_half, float t_full, const float* z_main, const float* z_short, const uint64_t* rng,
                          msgm_stream_t stream);
 
+/* Every grid state of one forward path per row, in ONE launch — replaces SDE.sample_scheme_allt(y0, include_t0=False,
+ * keep_all_samples=True)[first_keep:] as PluginReverseSDE.ssm calls it with ssm_intT=True (SDEs.py:648-706 with
+ * SDEs.py:124-132; 6 nsf launches and a .to('cpu') upstream).  msgm_forward_perturb's kernels in their all-times mode:
+ * every row takes all nsf grid steps (no row time, no short step, no k_out) and the state after step i >= first_keep is
+ * stored to y_all[(i - first_keep) * B + b, :]; each element of y_all (nsf - first_keep, B, n) gets one store.  Same
+ * stage arithmetic, time grid, stage times and draws as above, so the result equals the composed trajectory
+ * (rk4_stratonovich_sampler on forward_SDE, keep_all_samples) bit for bit.
+ *   first_keep  0 <= first_keep < nsf (MSGM_E_BADARG otherwise)
+ *   z_main      optional (nsf, B, n) standard normals; NULL: Philox RNG_STREAM_DW, extra offset i, global element index
+ *   rng         needed when z_main is NULL; read only (the caller advances the stream by nsf)
+ * y_all must not overlap x0.  Support and alignment rules are msgm_forward_perturb's: msgm_forward_perturb_supported
+ * decides, and above n = 4096 x0, y_all and z_main must be 16-byte aligned.  Never allocates or synchronises. */
+int msgm_forward_paths(const float* x0, float* y_all, int64_t B, int64_t n, const msgm_sde_t* sde, int32_t nsf,
+                       int32_t first_keep, const float* ts, float delta, float sqrt_delta, float t_half, float t_full,
+                       const float* z_main, const uint64_t* rng, msgm_stream_t stream);
+
 /* Rademacher probe v = 2[u>=1/2]-1 (SDEs.py:514-515); u NULL => rng stream 2. */
 int msgm_rademacher(float* v, int64_t n, const float* u, const uint64_t* rng, msgm_stream_t stream);
 

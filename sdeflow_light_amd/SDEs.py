@@ -13,8 +13,9 @@ What runs where
   multiplicative SDE's latent density is a 1-D Gaussian kernel density of the
   radii (a host-side sklearn ``KernelDensity`` upstream, SDEs.py:240): here one
   log-space kernel on the device (``ops.kde_logpdf``);
-* out of scope: plotting / validation branches, ``ssm_intT``,
-  non-Gaussian KDE kernels.
+* out of scope: plotting / validation branches, non-Gaussian KDE kernels.
+* ``ssm_intT=True`` (the time-integrated SSM loss, SDEs.py:648-706) is built: upstream's only defect there is the
+  global name ``device`` in ``sample_t_linspace``, which exists in the driver module and not in ``SDEs.py``.
 
 RNG: the reference draws from torch's global generator (CPU mt19937 for t,
 device generator for the rest, SDEs.py:688,141,515).  Here every draw comes
@@ -481,6 +482,16 @@ def sample_v(shape, device, vtype='rademacher', rng: Optional[PhiloxState] = Non
     raise MsgmError(f'vtype {vtype} not supported')
 
 
+def intT_kept_grid(nsf: int, T: float, t_epsilon: float):
+    """The time grid of the integrated loss on the host: (kept times (nsf',) fp32, k0).  linspace(T/nsf, T, nsf) with the
+    entries <= t_epsilon dropped (SDEs.py:695-706); they are a prefix of length k0 because the grid increases.  nsf' = 0 raises."""
+    t_ = torch.linspace(T / nsf, T, nsf)
+    k0 = int((t_ <= t_epsilon).sum())
+    if k0 == nsf:
+        raise MsgmError(f"ssm_intT: every grid time of the {nsf}-step grid is <= t_epsilon = {t_epsilon}; no row is left")
+    return t_[k0:], k0
+
+
 class PluginReverseSDE(nn.Module):
     """Plug-in reverse SDE (SDEs.py:538-729): f <- g a - f, time reversed.
 
@@ -496,13 +507,16 @@ class PluginReverseSDE(nn.Module):
 
     def __init__(self, base_sde, drift_a, T, vtype='rademacher', debias=False, ssm_intT=False, deviceReverseSDE='cpu'):
         super().__init__()
-        if ssm_intT:
-            raise MsgmError("ssm_intT=True is dead code upstream (undefined global at SDEs.py:700); not built")
+        if ssm_intT and torch.device(deviceReverseSDE).type != "cuda":
+            # the integrated loss exists on the HIP path only (one-launch path kernel, fused passes): refused where the
+            # object is built, like every other option without a kernel, not at the first ssm() call
+            raise MsgmError("ssm_intT=True needs the reverse SDE on a cuda device (deviceReverseSDE=...); there is no CPU fallback")
         self.base_sde = base_sde.to(deviceReverseSDE)
         self.a = drift_a
         self.T = T.to(deviceReverseSDE)
         self.vtype = vtype
-        self.ssm_intT = ssm_intT
+        self.ssm_intT = bool(ssm_intT)
+        self._intT = {}
         self.debias = debias
         self.deviceReverseSDE = deviceReverseSDE
         self._ws = None
@@ -563,6 +577,20 @@ class PluginReverseSDE(nn.Module):
         mask_le_t_eps = (t_ <= self.base_sde.t_epsilon)
         return t_[~mask_le_t_eps], mask_le_t_eps
 
+    def intT_grid(self, dev):
+        """``ssm_intT``: (the kept grid times on ``dev`` (nsf',), k0 = the number of dropped leading entries).  The grid and
+        the ``<=`` mask are ``sample_t_linspace``'s, formed on the host (no device read) and cached per
+        (nsf, T, t_epsilon, device); the dropped entries are a prefix because the grid increases.  nsf' = 0 raises."""
+        base, dev = self.base_sde, torch.device(dev)
+        nsf, T = base.num_steps_forward, base.T_float()
+        key = (nsf, T, float(base.t_epsilon), dev)
+        if key not in self._intT:
+            t_, k0 = intT_kept_grid(nsf, T, base.t_epsilon)
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise MsgmError("the ssm_intT time grid is needed for the first time inside a graph capture; run one eager step first")
+            self._intT[key] = (t_.to(dev), k0)
+        return self._intT[key]
+
     # ---- SSM loss -------------------------------------------------------------
     def sample_t(self, x, u=None):
         """t ~ U(0,T) clamped at t_epsilon (SDEs.py:684-693) — returned by
@@ -571,7 +599,18 @@ class PluginReverseSDE(nn.Module):
 
     @torch.no_grad()
     def sample_txy(self, x, u=None, eps=None):
+        """(t, x, y).  With ``ssm_intT`` (SDEs.py:653-676): one RK4 path of the forward process per row of x, every grid
+        state with t > t_epsilon a training row, time-major — row j B + b holds (t_grid[k0 + j], x[b], y[k0 + j, b]);
+        ``eps`` is the (nsf, B, n) path noise, and ``u`` has no meaning (there is no time draw)."""
         base = self.base_sde
+        if self.ssm_intT:
+            if u is not None:
+                raise MsgmError("ssm_intT: u= injects the time draw, and the integrated loss draws no time")
+            from .sde_scheme import msgm_forward_paths
+            B, n = x.shape
+            tk, k0 = self.intT_grid(x.device)
+            y = msgm_forward_paths(base, x, first_keep=k0, noise=eps)
+            return (tk.repeat_interleave(B).reshape(-1, 1), x.repeat(tk.numel(), 1), y.reshape(tk.numel() * B, n))
         if base.kind != L.SDE_SGM:
             rng = base.philox(x.device)
             if u is None:
@@ -607,6 +646,11 @@ class PluginReverseSDE(nn.Module):
         x = x.contiguous().float()
         B, d = x.shape
         dev = x.device
+        intT = self.ssm_intT and y is None           # ssm_loss(t_, x, y) ignores the flag, as upstream does
+        if intT:
+            if u is not None:
+                raise MsgmError("ssm_intT: u= injects the time draw, and the integrated loss draws no time")
+            B *= self.intT_grid(dev)[0].numel()      # nsf' B training rows; nsf' = 0 raises here, before any launch
         ops._row_weight(row_weight, B)               # CPU / wrong length / wrong dtype: refused before any launch or draw
         rng = base.philox(dev)
         if y is None:
@@ -622,8 +666,8 @@ class PluginReverseSDE(nn.Module):
             v = ops.rademacher((B, d), dev, u=u_v, rng=None if u_v is not None else rng)
         else:
             v = sample_v((B, d), dev, self.vtype, rng=rng).contiguous()
-        if drew_v or (t_given is None and (u is None or eps is None)):
-            rng.advance(1)
+        if drew_v or (t_given is None and not intT and (u is None or eps is None)):
+            rng.advance(1)                           # (ssm_intT: the path draws advanced the stream by nsf themselves)
         st = base.struct()
         uu = cst = None
         if base.kind != L.SDE_SGM or not isinstance(net, MLP) or not pm1:
@@ -690,6 +734,8 @@ class PluginReverseSDE(nn.Module):
         qt = 1.0 / base.T_float()
         with torch.no_grad():
             loss_ssm = self.ssm(x, u=u, eps=eps, u_v=u_v, y=y, t_given=t_given).detach() / qt
+            if self.ssm_intT and y is None:          # the latent term runs on the tiled x (SDEs.py:717-719)
+                x = x.repeat(loss_ssm.numel() // x.shape[0], 1)
             if yT is None:
                 t_ = torch.empty(x.shape[0], 1, device=x.device)
                 yT = (base.cond_latent_sample(t_, base.T_float(), x, eps=eps_T) if base.kind == L.SDE_SGM

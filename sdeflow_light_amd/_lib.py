@@ -93,6 +93,7 @@ SIGNATURES = {
     "msgm_forward_step_index": (C.c_int, [_P, _P, _I64, _I32, _F, _P]),
     "msgm_forward_perturb_supported": (C.c_int, [_I32, _I64]),
     "msgm_forward_perturb": (C.c_int, [_P, _P, _P, _P, _I64, _I64, C.POINTER(SdeT), _I32, _P, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "msgm_forward_paths": (C.c_int, [_P, _P, _I64, _I64, C.POINTER(SdeT), _I32, _I32, _P, _F, _F, _F, _F, _P, _P, _P]),
     "msgm_rademacher": (C.c_int, [_P, _I64, _P, _P, _P]),
     "msgm_sde_stage": (C.c_int, [_P, _P, _F, _P, _P, _P, _P, _F, _P, _U64, _P, _P, _I64, _I64, C.POINTER(SdeT), _I32,
                                  _I32, _F, _F, _F, _P, _P, _F, _P, _P, _P]),

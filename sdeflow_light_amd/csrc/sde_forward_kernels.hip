@@ -22,6 +22,15 @@
 //   dense, n <= 64          a lane per element, a group of pow2 >= n lanes per row; the stage input and the increment of
 //                           a row sit in LDS for dense_g, G and L_G too when n <= 16 (17 KB), else they come through L2
 //                           as in k_stage_rows.  The loop runs to the workgroup's largest count.
+//
+// All-times mode (template parameter PATHS, msgm_forward_paths): the same kernels for the time-integrated SSM loss
+// (PluginReverseSDE(ssm_intT=True), SDEs.py:648-706).  Every row takes all nsf grid steps — no row time, no short step, no
+// k_out, a uniform trip count — and the state after each step it >= first_keep is stored to y_all[(it - first_keep) B + b, :],
+// one store per element, in place of the single store at the end.  The store follows the step's last exchange / barrier and
+// sits under `on && it >= first_keep`: uniform in `it`, per lane in `on`, no shuffle or barrier inside it.  Same regimes,
+// support set and alignment rules; the result equals rk4_stratonovich_sampler(forward_SDE, keep_all_samples)[first_keep:]
+// bit for bit.  The 16-element form needs 147 VGPRs in this mode (144 without), still three waves per SIMD: the bound on n
+// stays 12288.  No instantiation uses scratch (profiles/ssm_intT/kernel_regs.txt).
 #include "common.h"
 #include "sde_stage.h"
 
@@ -33,6 +42,7 @@ struct FwdArgs {
   float b0, b1, T; const float* G; const float* L_G;
   int vec;                     // n % 4 == 0 and x0, y, z_main, z_short 16-byte aligned: float4 loads and stores
   int gs;                      // lanes per row of the lane-group regimes (a power of two)
+  int32_t first_keep;          // PATHS only: the first step whose state is stored (y is y_all, t and k_out are unused)
 };
 
 __device__ __forceinline__ f32x4 fw_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
@@ -41,9 +51,12 @@ __device__ __forceinline__ void fw_st4(float* p, f32x4 v) { *reinterpret_cast<f3
 // What row b has to do: its stop index, the number of RK4 steps it takes and whether that is the one short step of
 // length t_b (k = 0).  An index outside [0, nsf] (a negative time) is never captured by the composed route's
 // msgm_keep_rows, whose buffer starts as zeros: no step, and the row is written as zeros.
+// PATHS (msgm_forward_paths): every row takes all nsf grid steps; there is no row time and no short step.
 struct RowPlan { int32_t k; int nsteps; bool brief; };
+template <bool PATHS>
 __device__ __forceinline__ RowPlan row_plan(const FwdArgs& F, int64_t b, bool live) {
   if (!live) return {-1, 0, false};
+  if constexpr (PATHS) return {F.nsf, F.nsf, false};
   const int32_t k = forward_step_k(F.t[b], F.nsf, F.T);
   return {k, k == 0 ? 1 : (k > 0 && k <= F.nsf ? k : 0), k == 0};
 }
@@ -204,7 +217,9 @@ __device__ __forceinline__ void sparse_stage(const StageArgs& A, const StageCoef
 
 // VEC: the launch guarantees n % 4 == 0 and 16-byte aligned operands (the 16-element chunks: with the scalar loads and the
 // per-element Philox calls compiled in as well, that kernel spills).
-template <int E, bool WG, bool VEC, int THREADS>
+// PATHS: the state after every step it >= first_keep is stored to y_all[(it - first_keep) * B + b, :] and nothing else is;
+// the store sits under a condition that is uniform in it and per lane in `on`, after the step's last exchange.
+template <int E, bool WG, bool VEC, int THREADS, bool PATHS = false>
 __global__ void __launch_bounds__(THREADS) k_forward_perturb_sparse(FwdArgs F) {
   const bool vec = VEC || F.vec;
   __shared__ float tables[WG ? 2 * 3 * 1024 : 1];
@@ -225,8 +240,10 @@ __global__ void __launch_bounds__(THREADS) k_forward_perturb_sparse(FwdArgs F) {
   // idle lanes take part in every exchange; their sources stay inside the row's own lanes
   const int srcm = base + (lane_t == 0 ? chunks - 1 : (lane_t < chunks ? lane_t - 1 : 0));
   const int srcp = base + (lane_t + 1 < chunks ? lane_t + 1 : 0);
-  const RowPlan plan = row_plan(F, b, live);
-  if (on && lane_t == 0 && F.k_out) F.k_out[b] = plan.k;
+  const RowPlan plan = row_plan<PATHS>(F, b, live);
+  if constexpr (!PATHS) {
+    if (on && lane_t == 0 && F.k_out) F.k_out[b] = plan.k;
+  }
   int steps = plan.nsteps;                            // WG: the same in every thread
   if constexpr (!WG) {
 #pragma unroll
@@ -259,14 +276,19 @@ __global__ void __launch_bounds__(THREADS) k_forward_perturb_sparse(FwdArgs F) {
     sparse_stage<E, 3>(A, sc.c1, x, xe, xm, xp, w, wm, cnt, s, xe, act, elast);         // K3 at t + delta/2
     edge_exchange<WG, 2>(xe[0], elast, 0.f, self, srcm, srcp, tables, phase, xm, xp, unused);
     sparse_stage<E, 4>(A, sc.c2, x, xe, xm, xp, w, wm, cnt, s, x, act, xlast);          // K4 at t + delta
+    if constexpr (PATHS) {
+      if (on && it >= F.first_keep) chunk_store<E>(F.y + ((int64_t)(it - F.first_keep) * F.B + b) * F.n, i0, cnt, vec, x);
+    }
   }
-  if (on) chunk_store<E>(F.y + b * F.n, i0, cnt, vec, x);
+  if constexpr (!PATHS) {
+    if (on) chunk_store<E>(F.y + b * F.n, i0, cnt, vec, x);
+  }
 }
 
 // ============================================================ dense
 // Lane lane_t of a row's group owns element lane_t.  xs / ws: the stage input and the Wiener increment of the group's
 // row, read by every lane of the group in dense_g.
-template <bool G_LDS>
+template <bool G_LDS, bool PATHS = false>
 __global__ void __launch_bounds__(256) k_forward_perturb_dense(FwdArgs F) {
   __shared__ float Gs[G_LDS ? 16 * 16 * 16 + 16 * 16 : 1];
   __shared__ float xs[256], ws[256];
@@ -283,8 +305,10 @@ __global__ void __launch_bounds__(256) k_forward_perturb_dense(FwdArgs F) {
     for (int i = tid; i < n * n; i += 256) Gs[n * n * n + i] = F.L_G[i];
     G = Gs; LG = Gs + n * n * n;
   }
-  const RowPlan plan = row_plan(F, b, live);
-  if (on && lane_t == 0 && F.k_out) F.k_out[b] = plan.k;
+  const RowPlan plan = row_plan<PATHS>(F, b, live);
+  if constexpr (!PATHS) {
+    if (on && lane_t == 0 && F.k_out) F.k_out[b] = plan.k;
+  }
   __syncthreads();
   atomicMax(&steps_s, plan.nsteps);
   __syncthreads();
@@ -332,15 +356,53 @@ __global__ void __launch_bounds__(256) k_forward_perturb_dense(FwdArgs F) {
     inc = stage(sc.c2);                              // K4 at x + K3, stored by the composed stage as 0 + 1 * increment
     const float xn = rk4_close(x, s, 0.f + 1.0f * inc);
     x = act ? xn : x;
+    if constexpr (PATHS) {
+      if (on && it >= F.first_keep) F.y[(int64_t)(it - F.first_keep) * F.B * F.n + e] = x;
+    }
     __syncthreads();
   }
-  if (on) F.y[e] = x;
+  if constexpr (!PATHS) {
+    if (on) F.y[e] = x;
+  }
 }
 
 // ============================================================ C ABI
 enum { FWD_SPARSE_GROUP_MAX = 256, FWD_SPARSE_E4_MAX = 4096, FWD_SPARSE_MAX = 12288, FWD_DENSE_MAX = 64, FWD_DENSE_LDS_MAX = 16 };
 
 static int pow2_at_least(int64_t v) { int g = 1; while (g < v) g <<= 1; return g; }
+
+// The launch of either entry: the regime by kind and n only.  F.vec and F.gs are set here.
+template <bool PATHS>
+static int forward_launch(FwdArgs F, int32_t kind, uintptr_t ptrs, msgm_stream_t stream) {
+  const int64_t B = F.B, n = F.n;
+  F.vec = (n % 4 == 0 && (ptrs & 15) == 0) ? 1 : 0;
+  F.gs = 1;
+  if (kind == MSGM_SDE_MSGM_DENSE) {
+    F.gs = pow2_at_least(n);
+    const int64_t grid = (B + 256 / F.gs - 1) / (256 / F.gs);
+    if (grid > INT32_MAX) return MSGM_E_UNSUPPORTED;
+    if (n <= FWD_DENSE_LDS_MAX) hipLaunchKernelGGL((k_forward_perturb_dense<true, PATHS>), dim3((unsigned)grid), dim3(256), 0, S(stream), F);
+    else hipLaunchKernelGGL((k_forward_perturb_dense<false, PATHS>), dim3((unsigned)grid), dim3(256), 0, S(stream), F);
+    return msgm_check_launch();
+  }
+  if (n <= FWD_SPARSE_GROUP_MAX) {
+    F.gs = pow2_at_least((n + 3) / 4);
+    const int64_t grid = (B + 256 / F.gs - 1) / (256 / F.gs);
+    if (grid > INT32_MAX) return MSGM_E_UNSUPPORTED;
+    hipLaunchKernelGGL((k_forward_perturb_sparse<4, false, false, 256, PATHS>), dim3((unsigned)grid), dim3(256), 0, S(stream), F);
+    return msgm_check_launch();
+  }
+  if (B > INT32_MAX) return MSGM_E_UNSUPPORTED;
+  if (n <= FWD_SPARSE_E4_MAX) {
+    const int threads = (int)(((n + 3) / 4 + 63) / 64) * 64;
+    hipLaunchKernelGGL((k_forward_perturb_sparse<4, true, false, 1024, PATHS>), dim3((unsigned)B), dim3(threads), 0, S(stream), F);
+  } else {
+    if (!F.vec) return MSGM_E_UNSUPPORTED;                                   // operands that are only 4-byte aligned
+    const int threads = (int)(((n + 15) / 16 + 63) / 64) * 64;
+    hipLaunchKernelGGL((k_forward_perturb_sparse<16, true, true, 768, PATHS>), dim3((unsigned)B), dim3(threads), 0, S(stream), F);
+  }
+  return msgm_check_launch();
+}
 
 extern "C" {
 
@@ -363,33 +425,25 @@ int msgm_forward_perturb(const float* x0, const float* t, float* y, int32_t* k_o
   if (!msgm_forward_perturb_supported(sde->kind, n)) return MSGM_E_UNSUPPORTED;
   const uintptr_t ptrs = reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(z_main) |
                          reinterpret_cast<uintptr_t>(z_short);
-  FwdArgs F{x0, t, y, k_out, B, n, nsf, ts, delta, sqrt_delta, t_half, t_full, z_main, z_short, rng,
-            sde->beta_min, sde->beta_max, sde->T, sde->G, sde->L_G, (n % 4 == 0 && (ptrs & 15) == 0) ? 1 : 0, 1};
-  if (sde->kind == MSGM_SDE_MSGM_DENSE) {
-    F.gs = pow2_at_least(n);
-    const int64_t grid = (B + 256 / F.gs - 1) / (256 / F.gs);
-    if (grid > INT32_MAX) return MSGM_E_UNSUPPORTED;
-    if (n <= FWD_DENSE_LDS_MAX) hipLaunchKernelGGL(k_forward_perturb_dense<true>, dim3((unsigned)grid), dim3(256), 0, S(stream), F);
-    else hipLaunchKernelGGL(k_forward_perturb_dense<false>, dim3((unsigned)grid), dim3(256), 0, S(stream), F);
-    return msgm_check_launch();
-  }
-  if (n <= FWD_SPARSE_GROUP_MAX) {
-    F.gs = pow2_at_least((n + 3) / 4);
-    const int64_t grid = (B + 256 / F.gs - 1) / (256 / F.gs);
-    if (grid > INT32_MAX) return MSGM_E_UNSUPPORTED;
-    hipLaunchKernelGGL((k_forward_perturb_sparse<4, false, false, 256>), dim3((unsigned)grid), dim3(256), 0, S(stream), F);
-    return msgm_check_launch();
-  }
-  if (B > INT32_MAX) return MSGM_E_UNSUPPORTED;
-  if (n <= FWD_SPARSE_E4_MAX) {
-    const int threads = (int)(((n + 3) / 4 + 63) / 64) * 64;
-    hipLaunchKernelGGL((k_forward_perturb_sparse<4, true, false, 1024>), dim3((unsigned)B), dim3(threads), 0, S(stream), F);
-  } else {
-    if (!F.vec) return MSGM_E_UNSUPPORTED;                                   // operands that are only 4-byte aligned
-    const int threads = (int)(((n + 15) / 16 + 63) / 64) * 64;
-    hipLaunchKernelGGL((k_forward_perturb_sparse<16, true, true, 768>), dim3((unsigned)B), dim3(threads), 0, S(stream), F);
-  }
-  return msgm_check_launch();
+  const FwdArgs F{x0, t, y, k_out, B, n, nsf, ts, delta, sqrt_delta, t_half, t_full, z_main, z_short, rng,
+                  sde->beta_min, sde->beta_max, sde->T, sde->G, sde->L_G, 0, 1, 0};
+  return forward_launch<false>(F, sde->kind, ptrs, stream);
+}
+
+int msgm_forward_paths(const float* x0, float* y_all, int64_t B, int64_t n, const msgm_sde_t* sde, int32_t nsf,
+                       int32_t first_keep, const float* ts, float delta, float sqrt_delta, float t_half, float t_full,
+                       const float* z_main, const uint64_t* rng, msgm_stream_t stream) {
+  if (!x0 || !y_all || !sde || !ts || B <= 0 || n <= 0 || nsf <= 0) return MSGM_E_BADARG;
+  if (first_keep < 0 || first_keep >= nsf) return MSGM_E_BADARG;          // at least one state is kept
+  if (!z_main && !rng) return MSGM_E_BADARG;
+  if (sde->kind < 0 || sde->kind > 2) return MSGM_E_BADARG;
+  if (y_all + (int64_t)(nsf - first_keep) * B * n > x0 && x0 + B * n > y_all) return MSGM_E_BADARG;   // rows are stored while others still read x0
+  if (sde->kind == MSGM_SDE_MSGM_DENSE && (!sde->G || !sde->L_G)) return MSGM_E_BADARG;
+  if (!msgm_forward_perturb_supported(sde->kind, n)) return MSGM_E_UNSUPPORTED;
+  const uintptr_t ptrs = reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(y_all) | reinterpret_cast<uintptr_t>(z_main);
+  const FwdArgs F{x0, nullptr, y_all, nullptr, B, n, nsf, ts, delta, sqrt_delta, t_half, t_full, z_main, nullptr, rng,
+                  sde->beta_min, sde->beta_max, sde->T, sde->G, sde->L_G, 0, 1, first_keep};
+  return forward_launch<true>(F, sde->kind, ptrs, stream);
 }
 
 }  // extern "C"

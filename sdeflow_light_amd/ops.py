@@ -127,6 +127,31 @@ def forward_perturb(x0: torch.Tensor, t: torch.Tensor, sde: L.SdeT, nsf: int, ts
     return y
 
 
+def forward_paths(x0: torch.Tensor, sde: L.SdeT, nsf: int, first_keep: int, ts: torch.Tensor, delta: float,
+                  z_main: Optional[torch.Tensor] = None, rng: Optional[PhiloxState] = None) -> torch.Tensor:
+    """Every grid state of one forward path per row in ONE launch: each row takes all nsf RK4-Stratonovich steps of the
+    forward process on the grid ts (device fp32, nsf + 1 values) and the state after step i >= first_keep is row
+    (i - first_keep, b) of the result.  z_main (nsf,B,n): injected standard normals, else the Philox draws of the composed
+    sampler (the stream is NOT advanced here).  Returns y_all (nsf - first_keep, B, n)."""
+    if x0.dim() != 2 or not x0.is_cuda:
+        raise MsgmError("forward paths: the state must be a (B,n) device tensor; there is no CPU fallback")
+    B, n = x0.shape
+    nsf, first_keep = int(nsf), int(first_keep)
+    if not 0 <= first_keep < nsf:
+        raise MsgmError(f"forward paths: first_keep = {first_keep} keeps no state of the {nsf}-step grid")
+    if ts.device != x0.device or ts.dtype != torch.float32 or ts.numel() != nsf + 1:
+        raise MsgmError("forward paths: ts must be a device fp32 grid of nsf + 1 values")
+    _same_shape(z_main, (nsf, B, n), "z_main")
+    if z_main is not None:
+        f32(z_main, "z_main")
+    y_all = torch.empty((nsf - first_keep, B, n), dtype=torch.float32, device=x0.device)
+    # the stage offsets are rounded to fp32 on the way in, as in forward_perturb
+    check(lib().msgm_forward_paths(ptr(f32(x0)), ptr(y_all), B, n, sde, nsf, first_keep, ptr(ts), float(delta),
+                                   float(delta ** 0.5), float(delta * 0.5), float(delta * 1.0), ptr(z_main), _rng_ptr(rng),
+                                   stream()), "msgm_forward_paths")
+    return y_all
+
+
 def rademacher(shape, device, u: Optional[torch.Tensor] = None, rng: Optional[PhiloxState] = None) -> torch.Tensor:
     v = torch.empty(shape, dtype=torch.float32, device=device)
     _same_shape(u, v.shape, "u")

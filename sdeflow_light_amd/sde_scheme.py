@@ -381,6 +381,48 @@ def msgm_forward_perturb_composed(base, t, y0, noise_main=None, noise_short=None
     return kept
 
 
+@torch.no_grad()
+def msgm_forward_paths(base, y0, first_keep=0, noise=None):
+    """The grid states y_{t_{first_keep+1}}, ..., y_{t_nsf} of ONE forward path per row, (nsf - first_keep, B, n) on the
+    device: SDE.sample_scheme_allt(y0, include_t0=False)[first_keep:] as the integrated SSM loss uses it
+    (``PluginReverseSDE(ssm_intT=True)``, SDEs.py:648-706).  ONE launch (``msgm_forward_paths``) where
+    ``ops.forward_perturb_supported`` takes the row length and the operands are 16-byte aligned: a row lives in registers
+    through all nsf RK4 steps and is stored after every kept one.  Every other shape, and the additive SDE, takes
+    ``msgm_forward_paths_composed``; the result is the same bit for bit.  ``noise`` (nsf,B,n) injects the standard normals;
+    without it both routes draw from the base SDE's Philox stream and advance it by nsf, as the composed sampler does."""
+    st = base.struct()
+    nsf = base.num_steps_forward
+    if not 0 <= int(first_keep) < nsf:
+        raise MsgmError(f"first_keep = {first_keep} keeps no state of the {nsf}-step forward grid")
+    if y0.dim() != 2 or not y0.is_cuda or not ops.forward_perturb_supported(st.kind, y0.shape[1]):
+        return msgm_forward_paths_composed(base, y0, first_keep, noise)
+    dev = y0.device
+    x = y0.detach().contiguous().float()
+    zm = None if noise is None else noise.to(dev).contiguous()
+    if any(v is not None and v.data_ptr() % 16 for v in (x, zm)):
+        return msgm_forward_paths_composed(base, y0, first_keep, noise)
+    ts, delta = _forward_grid(base, nsf, dev)
+    rng = None if zm is not None else base.philox(dev)
+    y_all = ops.forward_paths(x, st, nsf, first_keep, ts, delta, z_main=zm, rng=rng)
+    if rng is not None:
+        rng.advance(nsf)
+    return y_all
+
+
+@torch.no_grad()
+def msgm_forward_paths_composed(base, y0, first_keep=0, noise=None):
+    """msgm_forward_paths on the composed route (nsf RK4 steps of four stage launches, a combine and a trajectory copy
+    each), whatever the shape or SDE: the yardstick of the one-launch kernel.  The trajectory stays on the device."""
+    from .SDEs import forward_SDE
+    nsf = base.num_steps_forward
+    if not 0 <= int(first_keep) < nsf:
+        raise MsgmError(f"first_keep = {first_keep} keeps no state of the {nsf}-step forward grid")
+    r = _rk4(forward_SDE(base, base.T), y0, nsf, 0., True, None, False, -1, False, noise)
+    if r.rng is not None:
+        r.rng.advance(nsf)                           # what _Run.result does
+    return r.traj[int(first_keep):]
+
+
 class GraphedEMSampler:
     """The whole fused EM loop (MLP + SGM) captured as ONE hipGraph: N kernel
     nodes with the time grid and Philox step index baked in by value; the state

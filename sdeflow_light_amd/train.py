@@ -23,6 +23,12 @@ step); every other combination is ``sampler.sample_into(tr.x, tr.rng)`` ahead of
 batch that was trained on.  The stream advances per step as before, so checkpoints keep their keys and a resumed run
 draws the batches of the uninterrupted one; indices and draws are keyed by global row / element, so an N-rank run
 (every rank holding the whole table) trains on the rows of the 1-rank run.
+
+Integrated loss (``gen_sde.ssm_intT``, multiplicative SDE, one rank): ``x`` stays (B, d) and a step trains on
+the nsf' B kept grid states of B forward paths — [data stage] -> msgm_forward_paths (one launch) -> probe -> msgm_ssm_terms
+-> the fused pass -> reduce and optimizer stage as above.  ``tr.rows`` = nsf' B sizes y, t (the resident tiled grid), v,
+u, cst and the row-weight buffer, and ``inv_batch`` = 1 / rows.  The stream advances by nsf + 1 per step, at the positions
+eager ``ssm()`` uses.  Refused at construction: the additive SDE, ``world > 1``, a row length the path kernel does not take.
 """
 from __future__ import annotations
 
@@ -216,8 +222,16 @@ def _msgm_draws(tr):
     (sde_scheme.msgm_forward_perturb), the Rademacher probe, then u = G(y)^T v, cst of the general loss form
     (msgm_ssm_terms).  Every launch is a kernel on the current stream, no host synchronisation: capturable.
     The base SDE draws from the TRAINER's Philox stream (shard placement included)."""
-    from .sde_scheme import msgm_forward_perturb
+    from .sde_scheme import msgm_forward_paths, msgm_forward_perturb
     base, rng = tr.base, tr.rng
+    if tr.intT:
+        # the integrated loss (gen_sde.ssm_intT): one path per row of x in one launch, every kept grid state a training
+        # row (time-major), tr.t the resident tiled grid; the stream positions are those of eager ssm()
+        y = msgm_forward_paths(base, tr.x, first_keep=tr.k0).view(tr.rows, tr.d)      # advances the stream by nsf
+        v = ops.rademacher((tr.rows, tr.d), tr.dev, rng=rng)
+        rng.advance(1)
+        uu, cst = ops.ssm_terms(y, v, tr.t, tr.st)
+        return y, tr.t, v, uu, cst
     ops.fill_uniform(tr.u, rng, L.RNG_STREAM_T)
     torch.mul(tr.u, tr.T_host, out=tr.t)
     tr.t.clamp_(min=base.t_epsilon)                  # == m*t_eps + (1-m)*t of SDEs.py:690-692, bit for bit
@@ -234,7 +248,7 @@ def _init_row_weights(tr, row_weights: bool):
     re-capture.  Weights are per local row; ``inv_batch`` stays 1/(B_local * world), the reported loss is
     inv_batch * sum_b w_b L_b.  A ragged last batch: pad it, weight the valid rows B/n_valid and the padding 0 (the
     padding rows still flow through the arithmetic: keep them finite)."""
-    tr.w = torch.ones(tr.B, dtype=torch.float32, device=tr.dev) if row_weights else None
+    tr.w = torch.ones(tr.rows, dtype=torch.float32, device=tr.dev) if row_weights else None
 
 
 def _set_data(tr, x, weight):
@@ -243,7 +257,7 @@ def _set_data(tr, x, weight):
     if weight is not None:
         if tr.w is None:
             raise MsgmError("set_data(weight=...) needs a trainer built with row_weights=True")
-        ops._row_weight(weight, tr.B)
+        ops._row_weight(weight, tr.rows)
     tr.x.copy_(x)
     if weight is not None:
         tr.w.copy_(weight)
@@ -280,13 +294,35 @@ def _ssm_prep(tr):
                                       tr.rng.ptr(), tr.step_dev.data_ptr(), ops.stream()), "msgm_ssm_prep")
 
 
+def _training_rows(tr):
+    """``tr.rows``: the rows of one step's loss.  B, or with ``gen_sde.ssm_intT`` the nsf' B kept grid states of B forward
+    paths (``tr.k0`` leading grid times dropped, ``tr.t_grid`` the kept ones).  The integrated loss is refused here,
+    before any launch, where the captured step could not hold it."""
+    tr.intT = bool(getattr(tr.gen_sde, "ssm_intT", False))
+    tr.rows, tr.k0 = tr.B, 0
+    if not tr.intT:
+        return
+    if tr.base.kind == L.SDE_SGM:
+        raise MsgmError("ssm_intT trainers are built for the multiplicative SDE; the additive SDE has a closed-form perturbation")
+    if tr.world > 1:
+        raise MsgmError("ssm_intT with world > 1: time-major rows break the shard base of the probe draw; not built")
+    if not ops.forward_perturb_supported(tr.base.kind, tr.d):
+        raise MsgmError(f"ssm_intT trainers need a row length msgm_forward_paths takes in one launch (n = {tr.d} is not): "
+                        "the composed trajectory holds copy nodes, and the captured step kernel nodes only")
+    tr.t_grid, tr.k0 = tr.gen_sde.intT_grid(tr.dev)
+    tr.rows = tr.t_grid.numel() * tr.B
+
+
 def _adopt_stream(tr):
     """The multiplicative SDE's forward perturbation draws through ``base.philox()``: hand it the trainer's stream."""
     tr.msgm = tr.base.kind != L.SDE_SGM
     if tr.msgm:
         tr.base.rng = tr.rng
         tr.T_host = tr.base.T_float()
-        tr.u = torch.empty(tr.B, dtype=torch.float32, device=tr.dev)
+        if tr.intT:
+            tr.t = tr.t_grid.repeat_interleave(tr.B).contiguous()        # a resident constant: the tiled grid
+        else:
+            tr.u = torch.empty(tr.B, dtype=torch.float32, device=tr.dev)
 
 
 class MLPScoreTrainer(_TrainerState):
@@ -305,6 +341,7 @@ class MLPScoreTrainer(_TrainerState):
         self.gen_sde, self.net, self.base = gen_sde, net, base
         self.dev = next(net.parameters()).device
         self.B, self.d, self.world = batch_local, net.input_dim, world
+        _training_rows(self)
         self.flat, self.gflat = net.flat_parameters()
         self.n = self.flat.numel()
         self.m = torch.zeros_like(self.flat)
@@ -323,7 +360,7 @@ class MLPScoreTrainer(_TrainerState):
         self._init_optim(lr, max_grad_norm, ema_rate, lr_schedule, device_lr)
         self.P = net.kernel_params()
         self.st = base.struct()
-        self.inv_batch = 1.0 / (batch_local * world)        # mean over the GLOBAL batch
+        self.inv_batch = 1.0 / (self.rows * world)          # mean over the GLOBAL batch
         self.graph = None
         self.use_graph = use_graph and not parallel.multi(world)
         _init_row_weights(self, row_weights)
@@ -347,7 +384,7 @@ class MLPScoreTrainer(_TrainerState):
             _ssm_prep(self)
             y, t, vp, pu, pc, adv = self.y, self.t, self.vp, None, None, self.rng.ptr()
         nsl = C.c_int32(0)
-        ops.check(lib.msgm_mlp_ssm_partial_w(self.P, y.data_ptr(), t.data_ptr(), vp.data_ptr(), pu, pc, self.B,
+        ops.check(lib.msgm_mlp_ssm_partial_w(self.P, y.data_ptr(), t.data_ptr(), vp.data_ptr(), pu, pc, self.rows,
                                              self.st, self.inv_batch, ops.ptr(self.w), None, self.ws.data_ptr(),
                                              self.ws.numel() * 4, C.byref(nsl), s), "msgm_mlp_ssm_partial_w")
         pre = int(self.net.pre is not None)
@@ -423,6 +460,7 @@ class UNetScoreTrainer(_TrainerState):
         self.gen_sde, self.net, self.base = gen_sde, net, base
         self.dev = next(net.parameters()).device
         self.B, self.d, self.world = batch_local, dim, world
+        _training_rows(self)
         self.flat, self.gflat = net.flat_parameters()
         self.n = self.flat.numel()
         self._init_optim(lr, max_grad_norm, ema_rate, lr_schedule, device_lr)
@@ -435,7 +473,7 @@ class UNetScoreTrainer(_TrainerState):
         self.y, self.vp = torch.empty_like(self.x), torch.empty_like(self.x)
         self.t = torch.empty(batch_local, dtype=torch.float32, device=self.dev)
         self.st = base.struct()
-        self.inv_batch = 1.0 / (batch_local * world)
+        self.inv_batch = 1.0 / (self.rows * world)
         # default: graph everywhere.  With N ranks the graph ends before the collective (capture_error_mode
         # "thread_local": the process group's watchdog thread may touch the runtime during the capture), the
         # all-reduce and Adam follow eagerly on the same stream
@@ -454,6 +492,7 @@ class UNetScoreTrainer(_TrainerState):
         if self.msgm:
             y, t, vp, u, cst = _msgm_draws(self)
             ops.counter_inc(self.step_dev)
+            self._live = (y, vp, u, cst)
         else:
             _ssm_prep(self)
             y, t, vp = self.y, self.t, self.vp

@@ -898,6 +898,87 @@ def g23_unet2d_wide():
     save("g23_unet2d_wide", **out)
 
 
+def _tap(obj, name, log):
+    """Record what obj.name(...) returns (an instance attribute over the method; the reference is not edited)."""
+    fn = getattr(obj, name)
+
+    def f(*a, **k):
+        out = fn(*a, **k)
+        log.append(out)
+        return out
+    setattr(obj, name, f)
+
+
+def g24_ssm_intT():
+    """The time-integrated SSM loss, PluginReverseSDE(ssm_intT=True) (SDEs.py:648-706): one RK4 path of the forward process
+    per row, every grid state with t > t_epsilon a training row, time-major.  B = 3, nsf = 4, T = 1 (grid 0.25 .. 1).
+    MLP cases sp (sparse tensor, d = 6, NormalizeLogRadius) and dn (dense, d = 4), each with t_epsilon = 0.3 (`drop`: the
+    first grid time goes) and 1e-3 (`all`): x, the path noise eps (nsf, B, d), the probe uniforms u_v, then (t, y) of
+    sample_txy, the per-row losses and the parameter gradients of their mean.  One elbo_random_t_slice / evaluate case per
+    SDE family (sg additive d = 2, sp, dn; t_epsilon = 1e-3): upstream draws a second path there only to tile x, then the
+    latent sample; stored are the first path's noise, u_v, yT, the latent term, the ELBO rows and evaluate's two numbers."""
+    import SDEs as ref_sdes
+    import NN as ref_nn
+    # upstream's sample_t_linspace (SDEs.py:700) names a global `device` that exists in the driver module and not in SDEs.py:
+    # the one defect of ssm_intT.  Supplied from outside, the reference itself stays as it is.
+    ref_sdes.device = torch.device("cpu")
+    torch.manual_seed(24)
+    out = {}
+    B, nsf = 3, 4
+
+    def family(tag, d, dense, pre):
+        y0 = torch.randn(64, d) * 1.5
+        base = sgm(nsf) if tag == "sg" else msgm(y0, dense=dense, nsf=nsf)
+        net = MLP(d, premodule=pre)
+        load_det_(net)                               # the closed-form weights: not stored
+        rev = PluginReverseSDE(base, net, Tparam(), ssm_intT=True)
+        if tag != "sg":
+            out[f"{tag}_y0"] = y0
+        if dense:
+            out["dn_G"] = base.G
+        return base, rev
+
+    for tag, d, dense, pre in (("sg", 2, False, None), ("sp", 6, False, "NormalizeLogRadius"), ("dn", 4, True, None)):
+        base, rev = family(tag, d, dense, pre)
+        txy = []
+        _tap(rev, "sample_txy", txy)
+        for sub, t_eps, kept in (("drop", 0.3, 3), ("all", 1e-3, 4)) if tag != "sg" else ():
+            base.t_epsilon = t_eps
+            x = torch.randn(B, d) * 1.5
+            del txy[:]
+            with Recorder() as r:
+                rev.zero_grad()
+                per = rev.ssm(x)
+                per.mean().backward()
+            assert [k for k, _ in r.draws] == ["randn_like"] * nsf + ["rand"] and per.shape == (kept * B,)
+            t_, xt, y = txy[0]
+            assert torch.equal(xt, x.repeat(kept, 1))
+            key = f"{tag}_{sub}"
+            out.update({f"{key}_x": x, f"{key}_eps": torch.stack([v for _, v in r.draws[:nsf]]), f"{key}_u_v": r.draws[nsf][1],
+                        f"{key}_t": t_, f"{key}_y": y.detach(), f"{key}_per": per.detach(), f"{key}_t_epsilon": np.float64(t_eps)})
+            out.update({f"{key}_grad::" + k: p.grad.detach().clone() for k, p in rev.named_parameters() if p.grad is not None})
+            print(key, "rows", per.numel(), "loss", float(per.mean()))
+        base.t_epsilon = 1e-3
+        x = torch.randn(B, d) * 1.5
+        latent, lps = [], []
+        _tap(rev, "cond_latent_sample", latent)
+        _tap(base, "log_latent_pdf", lps)
+        del txy[:]
+        st = torch.get_rng_state()
+        with Recorder() as r:
+            elbo = rev.elbo_random_t_slice(x)
+        assert [k for k, _ in r.draws[:nsf + 1]] == ["randn_like"] * nsf + ["rand"] and elbo.shape == (nsf * B,)
+        torch.set_rng_state(st)
+        mean, sem = ref_nn.evaluate(rev, x)                 # the same draws again
+        assert rev.training and float(mean.detach()) == float(elbo.detach().mean())
+        key = f"{tag}_ev"
+        out.update({f"{key}_x": x, f"{key}_eps": torch.stack([v for _, v in r.draws[:nsf]]), f"{key}_u_v": r.draws[nsf][1],
+                    f"{key}_t": txy[0][0], f"{key}_y": txy[0][2].detach(), f"{key}_yT": latent[0], f"{key}_lp": lps[0].view(nsf * B, -1).sum(1),
+                    f"{key}_elbo": elbo.detach(), f"{key}_mean": mean.detach(), f"{key}_sem": sem.detach()})
+        print(key, "mean", float(mean), "sem", float(sem))
+    save("g24_ssm_intT", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
