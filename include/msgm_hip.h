@@ -353,6 +353,46 @@ int msgm_adam_step_ex(float* p, const float* g, float* m, float* v, float* ema, 
                       const double* partials, int32_t n_partials, float* grad_norm_out,
                       msgm_stream_t stream);
 
+/* msgm_adam_step_ex plus weight decay, a non-finite step guard and an EMA
+ * warm-up, all in the same pass (replaces torch.optim.Adam(weight_decay),
+ * torch.optim.AdamW and the skipped step of a GradScaler-style loop).  The
+ * device values are the six of msgm_opt_t plus weight_decay.  As above, the
+ * arguments fix which work is done, the device values how large the effect is:
+ *  - decay_mode MSGM_DECAY_NONE: the arithmetic of msgm_adam_step_ex, p never
+ *    enters the gradient.  MSGM_DECAY_L2: after scaling and clipping
+ *    g' = ((g * gscale) * coef) + (float)weight_decay * p.
+ *    MSGM_DECAY_DECOUPLED: p <- p * (float)(1 - lr * weight_decay), the factor
+ *    formed in double, then the Adam update on that p.
+ *  - flags & MSGM_OPTIM_CLIP: clip by max_grad_norm (needs partials).  Here the
+ *    partials alone do not switch clipping on: the guard reads them too.
+ *  - skipped_dev != NULL (two int64 on the device, needs partials): when the
+ *    float64 sum of the partials is not finite -- some (g * gscale) rounded to
+ *    float32 is Inf or NaN -- every workgroup leaves before it loads p, g, m, v
+ *    or ema, none of their bytes change, *grad_norm_out receives the non-finite
+ *    norm and the skipped count rises by one.  A step whose attempt count
+ *    *step_dev is st reads the count from skipped_dev[st & 1] and writes
+ *    skipped_dev[(st + 1) & 1] = skipped_dev[st & 1] + verdict: no atomics, no
+ *    race, and every launch of one step (several buffers) writes the same
+ *    value.  So after a step with attempt count st the count is in
+ *    skipped_dev[(st + 1) & 1]; start both slots at the same value.  *step_dev
+ *    counts attempts; the bias corrections and the warm-up use
+ *    k_eff = st - skipped_dev[st & 1].
+ *  - flags & MSGM_OPTIM_EMA_WARMUP (needs ema):
+ *    rate_k = min(ema_rate, (1 + k_eff) / (10 + k_eff)) in double, then the EMA
+ *    form above with (float)rate_k and (float)(1 - rate_k).
+ * decay_mode 0, flags MSGM_OPTIM_CLIP iff partials, skipped_dev NULL: bitwise
+ * msgm_adam_step_ex. */
+typedef struct { double lr, beta1, beta2, eps, max_grad_norm, ema_rate, weight_decay; } msgm_optim_t;
+#define MSGM_DECAY_NONE 0
+#define MSGM_DECAY_L2 1
+#define MSGM_DECAY_DECOUPLED 2
+#define MSGM_OPTIM_CLIP 1
+#define MSGM_OPTIM_EMA_WARMUP 2
+int msgm_optim_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                    const msgm_optim_t* opt_dev, float gscale, const int64_t* step_dev,
+                    const double* partials, int32_t n_partials, float* grad_norm_out,
+                    int32_t decay_mode, int32_t flags, int64_t* skipped_dev, msgm_stream_t stream);
+
 /* a <-> b in place (n floats each, not overlapping): the parameters and their
  * average change places for sampling from the EMA (the copy_ of
  * model/nn_utils.py:117-127's users, without a third buffer). */

@@ -222,6 +222,8 @@ SIGNATURES = {
     "msgm_grad_sqnorm_partials": (_I32, [_I64]),
     "msgm_grad_sqnorm": (C.c_int, [_P, _I64, _F, _P, C.POINTER(C.c_int32), _P]),
     "msgm_adam_step_ex": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _F, _P, _P, _I32, _P, _P]),
+    # msgm_optim_t: the six plus weight_decay; then decay_mode, flags, the two-slot skipped counter
+    "msgm_optim_step": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _F, _P, _P, _I32, _P, _I32, _I32, _P, _P]),
     "msgm_swap": (C.c_int, [_P, _P, _I64, _P]),
     # data stage: a fresh minibatch per step, drawn on the device
     "msgm_data_gather": (C.c_int, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _P]),

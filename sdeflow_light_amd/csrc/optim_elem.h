@@ -1,4 +1,4 @@
-// optim_elem.h — the pieces sde_kernels.hip (K13, msgm_adam_step) and optim_kernels.hip (msgm_adam_step_ex) share:
+// optim_elem.h — the pieces sde_kernels.hip (K13, msgm_adam_step) and optim_kernels.hip (msgm_adam_step_ex, msgm_optim_step) share:
 // 16-byte access to flat buffers and THE Adam element update.  One copy: the build keeps -ffp-contract=off, so two
 // kernels that call adam_elem give the same bits.
 #pragma once
@@ -28,4 +28,13 @@ __device__ __forceinline__ AdamPmv adam_elem(const AdamCoef& c, float p, float g
   v = v * c.b2f + c.w2 * (gg * gg);
   const float denom = sqrtf(v) / c.bc2_sqrt + c.epsf;
   return {p - c.step_size * (m / denom), m, v};
+}
+// Weight decay around THE element update, compiled in by WD: 0 none (adam_elem as it is, p and g untouched),
+// 1 L2 (torch.optim.Adam(weight_decay): g + wd * p, one product and one add, wd = (float)weight_decay),
+// 2 decoupled (torch.optim.AdamW: p * wd first, wd = (float)(1 - lr * weight_decay) formed in double).
+template <int WD>
+__device__ __forceinline__ AdamPmv adam_elem_decay(const AdamCoef& c, float wd, float p, float g, float m, float v) {
+  if constexpr (WD == 1) g = g + wd * p;
+  if constexpr (WD == 2) p = p * wd;
+  return adam_elem(c, p, g, m, v);
 }

@@ -463,6 +463,71 @@ def adam_step_ex(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Ten
                                   stream()), "msgm_adam_step_ex")
 
 
+OPT_WEIGHT_DECAY = 6                                  # the seventh field of msgm_optim_t
+DECAY_NONE, DECAY_L2, DECAY_DECOUPLED = range(3)      # decay_mode of msgm_optim_step
+_OPTIM_CLIP, _OPTIM_EMA_WARMUP = 1, 2                 # its flags
+
+
+def optim_hyper(device, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None,
+                ema_rate: Optional[float] = None, weight_decay: float = 0.0) -> torch.Tensor:
+    """The seven float64 values behind ``msgm_optim_t`` on ``device``: the six of ``opt_hyper`` plus weight_decay, read
+    by ``optim_step`` at every launch."""
+    return torch.cat([opt_hyper("cpu", lr, betas, eps, max_grad_norm, ema_rate),
+                      torch.tensor([float(weight_decay)], dtype=torch.float64)]).to(device)
+
+
+def skipped_counter(device, count: int = 0) -> torch.Tensor:
+    """The two int64 slots ``optim_step(skipped=...)`` counts skipped steps in, both holding ``count``."""
+    return torch.full((2,), int(count), dtype=torch.int64, device=device)
+
+
+def skipped_count(skipped: torch.Tensor, step_dev: torch.Tensor) -> int:
+    """Skipped steps so far (syncs): a step whose attempt count is st leaves the count in slot (st + 1) & 1."""
+    return int(skipped[(int(step_dev) + 1) & 1])
+
+
+def optim_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, hyper: torch.Tensor,
+               step_dev: torch.Tensor, ema: Optional[torch.Tensor] = None, gscale: float = 1.0,
+               partials: Optional[torch.Tensor] = None, grad_norm_out: Optional[torch.Tensor] = None,
+               clip: Optional[bool] = None, decay_mode: int = DECAY_NONE, skipped: Optional[torch.Tensor] = None,
+               ema_warmup: bool = False):
+    """``adam_step_ex`` with ``hyper`` = ``optim_hyper`` (seven values) plus: ``decay_mode`` DECAY_L2
+    (``torch.optim.Adam(weight_decay)``: g + wd p after scaling and clipping) or DECAY_DECOUPLED (``torch.optim.AdamW``:
+    p (1 - lr wd) first); ``skipped`` (``skipped_counter``: a non-finite norm of ``partials`` leaves p, g, m, v, ema
+    untouched and counts the step, and the bias corrections run on step_dev - skipped); ``ema_warmup``
+    (rate_k = min(rate, (1 + k) / (10 + k))).  ``clip`` defaults to ``partials is not None``; pass False for a guard
+    without clipping.  All off: the bits of ``adam_step_ex``."""
+    n = _flat_dev(p, "p").numel()
+    if n < 1:
+        raise MsgmError("optim_step: empty parameter buffer")
+    for nm, tt in (("g", g), ("m", m), ("v", v), ("ema", ema)):
+        if tt is not None:
+            _flat_dev(tt, nm, numel=n)
+    _flat_dev(hyper, "hyper", torch.float64, 7)
+    _flat_dev(step_dev, "step_dev", torch.int64, 1)
+    if partials is not None and _flat_dev(partials, "partials", torch.float64).numel() < 1:
+        raise MsgmError("optim_step: empty partials")
+    if grad_norm_out is not None:
+        _flat_dev(grad_norm_out, "grad_norm_out", numel=1)
+    if skipped is not None:
+        _flat_dev(skipped, "skipped", torch.int64, 2)
+    clip = partials is not None if clip is None else bool(clip)
+    if (clip or skipped is not None) and partials is None:
+        raise MsgmError("optim_step: clipping and the non-finite guard need the partials of grad_sqnorm")
+    if ema_warmup and ema is None:
+        raise MsgmError("optim_step: ema_warmup without an ema buffer")
+    if decay_mode not in (DECAY_NONE, DECAY_L2, DECAY_DECOUPLED):
+        raise MsgmError(f"optim_step: decay_mode {decay_mode!r} is none of DECAY_NONE, DECAY_L2, DECAY_DECOUPLED")
+    for nm, tt in (("g", g), ("m", m), ("v", v), ("ema", ema), ("hyper", hyper), ("step_dev", step_dev),
+                   ("partials", partials), ("grad_norm_out", grad_norm_out), ("skipped", skipped)):
+        if tt is not None and tt.device != p.device:
+            raise MsgmError(f"optim_step: {nm} lives on another device than p")
+    flags = (_OPTIM_CLIP if clip else 0) | (_OPTIM_EMA_WARMUP if ema_warmup else 0)
+    check(lib().msgm_optim_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), n, ptr(hyper), float(gscale), ptr(step_dev),
+                                ptr(partials), 0 if partials is None else partials.numel(), ptr(grad_norm_out),
+                                int(decay_mode), flags, ptr(skipped), stream()), "msgm_optim_step")
+
+
 def swap_(a: torch.Tensor, b: torch.Tensor):
     """Exchanges the contents of two float32 device buffers of equal size in place (one launch, no third buffer)."""
     n = _flat_dev(a, "a").numel()

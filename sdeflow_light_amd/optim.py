@@ -16,6 +16,13 @@ with this optimizer as they do with ``torch.optim.Adam``.
 partial sums into its slice of one buffer, every run's update reads the whole buffer), ``opt.grad_norm`` is a device
 scalar holding the pre-clip norm of the last step, ``opt.ema_state_dict()`` maps a parameter's index to its average.
 Both need every run's gradients in one contiguous buffer (what ``FlatParamMixin`` nets have): MsgmError otherwise.
+
+``weight_decay`` is a param-group default read from the group on every step like ``lr`` (a no-decay group for biases
+works); ``decoupled_weight_decay`` (default True) chooses ``torch.optim.AdamW``'s form over
+``torch.optim.Adam(weight_decay)``'s.  ``skip_nonfinite`` leaves every run untouched when the global gradient norm is
+not finite, decided on the device (``opt.skipped_steps`` syncs; per-parameter ``state["step"]`` then is a device scalar
+holding the effective count).  ``ema_warmup`` ramps the rate as min(rate, (1 + k) / (10 + k)).  Any of the three runs the
+update through ``msgm_optim_step`` and needs contiguous gradients too.
 """
 from __future__ import annotations
 
@@ -47,10 +54,19 @@ def _flat_view(first: torch.Tensor, numel: int) -> torch.Tensor:
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale: float = 1.0, max_grad_norm=None,
-                 ema_rate=None):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+                 ema_rate=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = True,
+                 skip_nonfinite: bool = False, ema_warmup: bool = False):
+        if not float(weight_decay) >= 0.0:
+            raise MsgmError(f"weight_decay must be >= 0 (got {weight_decay})")
+        if ema_warmup and ema_rate is None:
+            raise MsgmError("ema_warmup=True needs ema_rate=...: there is no average to warm up")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = grad_scale          # 1/world_size after a sum all-reduce
         self.max_grad_norm, self.ema_rate = max_grad_norm, ema_rate
+        self.decoupled_weight_decay, self.skip_nonfinite = bool(decoupled_weight_decay), bool(skip_nonfinite)
+        self.ema_warmup = bool(ema_warmup)
+        self._ex = None                       # the update goes through msgm_optim_step (fixed at the first step)
+        self._skipped = None                  # skip_nonfinite: the two-slot device count of skipped steps
         self.grad_norm = None                 # device scalar: pre-clip global norm of the last step (max_grad_norm set)
         self._partials = None
         self._runs = None
@@ -80,7 +96,10 @@ class FusedAdam(torch.optim.Optimizer):
         if self._options():
             if any(r.params[0].device != dev for r in runs):
                 raise MsgmError("FusedAdam(max_grad_norm / ema_rate): all parameters must live on one device")
-            if self.max_grad_norm is not None:
+            self._ex = self._wants_ex()
+            if self.skip_nonfinite:
+                self._skipped = ops.skipped_counter(dev)
+            if self.max_grad_norm is not None or self.skip_nonfinite:       # the guard reads the norm too
                 off = 0
                 for r in runs:
                     r.poff, r.pnum = off, ops.grad_sqnorm_partials(r.numel)
@@ -99,8 +118,16 @@ class FusedAdam(torch.optim.Optimizer):
                                  "exp_avg_sq": r.v[off:off + k].view(p.shape)}
                 off += k
 
+    def _wants_ex(self) -> bool:
+        return self.skip_nonfinite or self.ema_warmup or any(g.get("weight_decay", 0) != 0 for g in self.param_groups)
+
     def _options(self) -> bool:
-        return self.max_grad_norm is not None or self.ema_rate is not None
+        return self.max_grad_norm is not None or self.ema_rate is not None or self._wants_ex()
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps the non-finite guard skipped so far (an int; reading it synchronises).  0 without ``skip_nonfinite``."""
+        return 0 if self._skipped is None else ops.skipped_count(self._skipped, self._step_dev)
 
     @staticmethod
     def _contiguous_grads(r) -> bool:
@@ -122,8 +149,15 @@ class FusedAdam(torch.optim.Optimizer):
                                 "(a FlatParamMixin net); this run's .grad tensors are scattered or missing")
             g = r.group
             vals = (g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.max_grad_norm, self.ema_rate)
+            if self._ex:
+                if not g.get("weight_decay", 0) >= 0:
+                    raise MsgmError(f"weight_decay must be >= 0 (got {g['weight_decay']})")
+                vals += (g.get("weight_decay", 0),)
+            elif g.get("weight_decay", 0) != 0:
+                raise MsgmError("a param group gained a weight_decay after the first step of a FusedAdam built without "
+                                "one; pass weight_decay= at construction")
             if vals != r.hyper_host:           # read from the group on every step; written when it changed (a scheduler)
-                h = ops.opt_hyper("cpu", vals[0], vals[1:3], vals[3], vals[4], vals[5])
+                h = (ops.optim_hyper if self._ex else ops.opt_hyper)("cpu", vals[0], vals[1:3], vals[3], *vals[4:])
                 if r.hyper is None:
                     r.hyper = h.to(r.m.device)
                 else:
@@ -138,8 +172,17 @@ class FusedAdam(torch.optim.Optimizer):
                                 self._partials[r.poff:r.poff + r.pnum])
         for r in self._runs:
             p0 = r.params[0]
-            ops.adam_step_ex(_flat_view(p0.data, r.numel), _flat_view(p0.grad, r.numel), r.m, r.v, r.hyper, self._step_dev,
-                             ema=r.ema, gscale=self.grad_scale, partials=self._partials, grad_norm_out=self.grad_norm)
+            if not self._ex:
+                ops.adam_step_ex(_flat_view(p0.data, r.numel), _flat_view(p0.grad, r.numel), r.m, r.v, r.hyper,
+                                 self._step_dev, ema=r.ema, gscale=self.grad_scale, partials=self._partials,
+                                 grad_norm_out=self.grad_norm)
+                continue
+            mode = (ops.DECAY_NONE if r.group.get("weight_decay", 0) == 0 else
+                    ops.DECAY_DECOUPLED if self.decoupled_weight_decay else ops.DECAY_L2)
+            ops.optim_step(_flat_view(p0.data, r.numel), _flat_view(p0.grad, r.numel), r.m, r.v, r.hyper, self._step_dev,
+                           ema=r.ema, gscale=self.grad_scale, partials=self._partials, grad_norm_out=self.grad_norm,
+                           clip=self.max_grad_norm is not None, decay_mode=mode, skipped=self._skipped,
+                           ema_warmup=self.ema_warmup)
 
     def ema_state_dict(self) -> dict:
         """{index of the parameter in state_dict()'s numbering: its averaged tensor} (ema_rate set, after the first step
@@ -167,9 +210,13 @@ class FusedAdam(torch.optim.Optimizer):
         self._step_host += 1
         if self._options():
             self._step_options()
+            if self._skipped is None:
+                eff = None
+            else:                              # the effective count, formed on the device: no sync in step()
+                eff = (self._step_dev[0] - self._skipped[(self._step_host + 1) & 1]).float()
             for r in self._runs:
                 for p in r.params:
-                    self.state[p]["step"] = torch.tensor(float(self._step_host))
+                    self.state[p]["step"] = torch.tensor(float(self._step_host)) if eff is None else eff
             return None
         for r in self._runs:
             g = r.group
@@ -191,6 +238,12 @@ class FusedAdam(torch.optim.Optimizer):
                 self.state[p]["step"] = torch.tensor(float(self._step_host))
         return None
 
+    def state_dict(self):
+        sd = super().state_dict()
+        if self.skip_nonfinite:                # torch's loader ignores the key
+            sd["skipped"] = self.skipped_steps if self._runs is not None else 0
+        return sd
+
     def load_state_dict(self, state_dict):
         if self._runs is None:
             self._build_runs()
@@ -206,6 +259,10 @@ class FusedAdam(torch.optim.Optimizer):
                 m.copy_(st["exp_avg"]); v.copy_(st["exp_avg_sq"])
                 step = int(float(st["step"]))
             st["exp_avg"], st["exp_avg_sq"] = m, v
+        if self._skipped is not None:          # "step" is the effective count; the device counter counts attempts
+            skipped = int(state_dict.get("skipped", 0))
+            step += skipped
+            self._skipped.fill_(skipped)
         self._step_host = step
         self._step_dev.fill_(step)
         if self.ema_rate is not None and "ema" in state_dict:      # a trainer's checkpoint carries its average under "ema"

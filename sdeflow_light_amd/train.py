@@ -14,7 +14,10 @@ Optimizer stage (keyword-only, all off by default; csrc/optim_kernels.hip, DESIG
 clipping on a deterministic device norm, ``tr.grad_norm``), ``ema_rate`` (``tr.ema``, ``ema_state_dict()``,
 ``with tr.ema_weights():``, an ``"ema"`` entry in the checkpoint), ``lr_schedule`` (k -> lr, e.g. ``warmup_cosine``) and
 ``device_lr`` (``set_lr`` between replays); any of the first three implies the last.  A trainer built without them runs
-the launches it always ran, with the learning rate baked into the captured step.
+the launches it always ran, with the learning rate baked into the captured step.  ``weight_decay`` (with
+``decoupled_weight_decay``: AdamW, the default, or Adam's L2 form), ``skip_nonfinite`` (a step whose gradient norm is
+not finite changes nothing, decided on the device; ``tr.skipped_steps``, a ``"skipped"`` entry in the checkpoint) and
+``ema_warmup`` also imply ``device_lr`` and run the update through ``msgm_optim_step``.
 
 Data stage (keyword-only ``data=sampler``, off by default; csrc/data_kernels.hip): every step begins by
 drawing ``x`` on the device from the trainer's own Philox stream — a fresh minibatch per replay, no host work.  An
@@ -66,7 +69,9 @@ class _TrainerState:
         return allp, mine
 
     def state_dict(self) -> dict:
-        step = float(self.step_dev.item())
+        # "step" is the EFFECTIVE count (attempts - skipped steps): what torch.optim.Adam / AdamW would hold
+        skipped = self.skipped_steps
+        step = float(self.step_dev.item() - skipped)
         allp, mine = self._param_index()
         st = {}
         if step > 0:                              # a never-stepped torch.optim.Adam has an empty state too
@@ -74,10 +79,12 @@ class _TrainerState:
                 k = p.numel()
                 st[i] = {"step": torch.tensor(step), "exp_avg": self.m[off:off + k].view(p.shape).clone(),
                          "exp_avg_sq": self.v[off:off + k].view(p.shape).clone()}
-        group = {"lr": self.lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0, "amsgrad": False,
+        group = {"lr": self.lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": self.weight_decay or 0, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "decoupled_weight_decay": False, "params": list(range(len(allp)))}
+                 "decoupled_weight_decay": self.decay_mode == ops.DECAY_DECOUPLED, "params": list(range(len(allp)))}
         sd = {"state": st, "param_groups": [group], "philox": self.rng.state_dict()}
+        if self.skipped is not None:              # torch's loader ignores the key, as it ignores "ema"
+            sd["skipped"] = skipped
         if self.ema is not None:                  # laid out like "state"; torch.optim.Adam's loader ignores the key
             sd["ema"] = {i: self.ema[off:off + p.numel()].view(p.shape).clone() for i, off, p in mine}
         return sd
@@ -100,8 +107,13 @@ class _TrainerState:
             else:
                 self.m[off:off + k].copy_(e["exp_avg"].reshape(-1)); self.v[off:off + k].copy_(e["exp_avg_sq"].reshape(-1))
                 step = int(float(e["step"]))
-        self.step_dev.fill_(step)
-        self._k = step                          # lr_schedule(k) continues at the update after the loaded one
+        skipped = int(sd.get("skipped", 0))     # absent in older checkpoints and in torch's own
+        self._k = step + skipped                # lr_schedule(k) continues at the call after the loaded one
+        if self.skipped is None:
+            self.step_dev.fill_(step)           # no guard: the device counter is the effective count
+        else:
+            self.step_dev.fill_(step + skipped)         # attempts
+            self.skipped.fill_(skipped)
         if sd.get("param_groups"):
             self.set_lr(float(sd["param_groups"][0]["lr"]))
         if self.ema is not None:
@@ -114,19 +126,39 @@ class _TrainerState:
             self.rng.load_state_dict(sd["philox"])      # stream position only; the shard base stays this rank's
 
     # ------------------------------------------------------------------ optimizer stage (csrc/optim_kernels.hip)
-    def _init_optim(self, lr, max_grad_norm, ema_rate, lr_schedule, device_lr):
+    def _init_optim(self, lr, max_grad_norm, ema_rate, lr_schedule, device_lr, weight_decay=0.0,
+                    decoupled_weight_decay=True, skip_nonfinite=False, ema_warmup=False):
         """``device_lr``: lr, betas, eps, max_grad_norm and ema_rate live in six float64 values on the device
         (``ops.opt_hyper``) that ``msgm_adam_step_ex`` reads at every launch, so a captured step takes a new learning
-        rate without a re-capture.  Clipping, EMA or a schedule imply it.  All off: today's launches, lr baked in."""
+        rate without a re-capture.  Clipping, EMA or a schedule imply it.  All off: today's launches, lr baked in.
+
+        ``weight_decay`` (> 0; ``decoupled_weight_decay`` True = ``torch.optim.AdamW``, False =
+        ``torch.optim.Adam(weight_decay)``; over the whole flat bucket, as one torch param group), ``skip_nonfinite``
+        and ``ema_warmup`` imply it too and move the update to ``msgm_optim_step`` (seven device values,
+        ``ops.optim_hyper``); without them the update stays ``msgm_adam_step_ex``."""
         self.max_grad_norm, self.ema_rate, self.lr_schedule = max_grad_norm, ema_rate, lr_schedule
-        self.device_lr = bool(device_lr) or any(o is not None for o in (max_grad_norm, ema_rate, lr_schedule))
+        self.weight_decay, self.ema_warmup = float(weight_decay), bool(ema_warmup)
+        if not self.weight_decay >= 0.0:
+            raise MsgmError(f"weight_decay must be >= 0 (got {weight_decay})")
+        if self.ema_warmup and ema_rate is None:
+            raise MsgmError("ema_warmup=True needs ema_rate=...: there is no average to warm up")
+        self.decay_mode = (ops.DECAY_NONE if self.weight_decay == 0.0 else
+                           ops.DECAY_DECOUPLED if decoupled_weight_decay else ops.DECAY_L2)
+        self._optim_ex = self.decay_mode != ops.DECAY_NONE or bool(skip_nonfinite) or self.ema_warmup
+        self.device_lr = (bool(device_lr) or self._optim_ex
+                          or any(o is not None for o in (max_grad_norm, ema_rate, lr_schedule)))
         self.lr = float(lr)
-        self.hyper = self.partials = self.grad_norm = self.ema = None
-        self._k, self._in_ema = 0, False          # host count of the updates made; inside ema_weights()
+        self.hyper = self.partials = self.grad_norm = self.ema = self.skipped = None
+        self._k, self._in_ema = 0, False          # host count of the step() calls made; inside ema_weights()
         if not self.device_lr:
             return
-        self.hyper = ops.opt_hyper(self.dev, lr, (0.9, 0.999), 1e-8, max_grad_norm, ema_rate)
-        if max_grad_norm is not None:
+        if self._optim_ex:
+            self.hyper = ops.optim_hyper(self.dev, lr, (0.9, 0.999), 1e-8, max_grad_norm, ema_rate, self.weight_decay)
+        else:
+            self.hyper = ops.opt_hyper(self.dev, lr, (0.9, 0.999), 1e-8, max_grad_norm, ema_rate)
+        if skip_nonfinite:
+            self.skipped = ops.skipped_counter(self.dev)
+        if max_grad_norm is not None or skip_nonfinite:       # the guard reads the norm too
             self.partials = torch.zeros(ops.grad_sqnorm_partials(self.n), dtype=torch.float64, device=self.dev)
             self.grad_norm = torch.zeros((), dtype=torch.float32, device=self.dev)      # the pre-clip global norm
         if ema_rate is not None:
@@ -137,8 +169,24 @@ class _TrainerState:
         so every rank forms the same norm and the same coefficient and the replicas stay bitwise identical."""
         if self.partials is not None:
             ops.grad_sqnorm(g, 1.0, self.partials)
-        ops.adam_step_ex(self.flat, g, self.m, self.v, self.hyper, self.step_dev, ema=self.ema, partials=self.partials,
-                         grad_norm_out=self.grad_norm)
+        if not self._optim_ex:
+            ops.adam_step_ex(self.flat, g, self.m, self.v, self.hyper, self.step_dev, ema=self.ema,
+                             partials=self.partials, grad_norm_out=self.grad_norm)
+            return
+        ops.optim_step(self.flat, g, self.m, self.v, self.hyper, self.step_dev, ema=self.ema, partials=self.partials,
+                       grad_norm_out=self.grad_norm, clip=self.max_grad_norm is not None, decay_mode=self.decay_mode,
+                       skipped=self.skipped, ema_warmup=self.ema_warmup)
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps the non-finite guard skipped so far (``skip_nonfinite=True``; 0 without it).  An int: reading it
+        synchronises with the device.  A skipped step leaves the parameters, the Adam moments and the average untouched,
+        and the bias corrections and the EMA warm-up count effective updates only.  It is still a step in every other
+        respect: (1) the ``loss`` it reports is whatever the kernels produced (usually non-finite); (2) its batch
+        (``data=``) and its Philox draws are consumed, the stream is not rewound; (3) ``lr_schedule(k)`` stays indexed
+        by the host's count of ``step()`` calls, skipped ones included.  With N ranks the norm is taken after the
+        all-reduce, so every rank reaches the same verdict."""
+        return 0 if self.skipped is None else ops.skipped_count(self.skipped, self.step_dev)
 
     def set_lr(self, lr: float) -> None:
         """A device-lr trainer: one ordinary fill kernel on the current stream (outside any capture), legal between
@@ -333,7 +381,8 @@ class MLPScoreTrainer(_TrainerState):
     def __init__(self, gen_sde, batch_local: int, lr: float = 1e-3, world: int = 1, use_graph: bool = True,
                  seed: int = 0, row_base: int = 0, row_weights: bool = False, *, max_grad_norm: Optional[float] = None,
                  ema_rate: Optional[float] = None, lr_schedule: Optional[Callable[[int], float]] = None,
-                 device_lr: bool = False, data=None):
+                 device_lr: bool = False, data=None, weight_decay: float = 0.0, decoupled_weight_decay: bool = True,
+                 skip_nonfinite: bool = False, ema_warmup: bool = False):
         from .NN import MLP
         net, base = gen_sde.a, gen_sde.base_sde
         if not isinstance(net, MLP):
@@ -357,7 +406,8 @@ class MLPScoreTrainer(_TrainerState):
         self.y = torch.empty_like(self.x)
         self.t = torch.empty(batch_local, dtype=torch.float32, device=self.dev)
         self.vp = torch.empty_like(self.x)
-        self._init_optim(lr, max_grad_norm, ema_rate, lr_schedule, device_lr)
+        self._init_optim(lr, max_grad_norm, ema_rate, lr_schedule, device_lr, weight_decay, decoupled_weight_decay,
+                         skip_nonfinite, ema_warmup)
         self.P = net.kernel_params()
         self.st = base.struct()
         self.inv_batch = 1.0 / (self.rows * world)          # mean over the GLOBAL batch
@@ -453,7 +503,9 @@ class UNetScoreTrainer(_TrainerState):
     def __init__(self, gen_sde, batch_local: int, dim: int, lr: float = 1e-4, world: int = 1, seed: int = 0,
                  use_graph: Optional[bool] = None, row_base: int = 0, row_weights: bool = False, *,
                  max_grad_norm: Optional[float] = None, ema_rate: Optional[float] = None,
-                 lr_schedule: Optional[Callable[[int], float]] = None, device_lr: bool = False, data=None):
+                 lr_schedule: Optional[Callable[[int], float]] = None, device_lr: bool = False, data=None,
+                 weight_decay: float = 0.0, decoupled_weight_decay: bool = True, skip_nonfinite: bool = False,
+                 ema_warmup: bool = False):
         net, base = gen_sde.a, gen_sde.base_sde
         if not hasattr(net, "ssm_grad"):
             raise MsgmError("UNetScoreTrainer needs a HIP U-Net score net (SGMsde or MSGMsde)")
@@ -463,7 +515,8 @@ class UNetScoreTrainer(_TrainerState):
         _training_rows(self)
         self.flat, self.gflat = net.flat_parameters()
         self.n = self.flat.numel()
-        self._init_optim(lr, max_grad_norm, ema_rate, lr_schedule, device_lr)
+        self._init_optim(lr, max_grad_norm, ema_rate, lr_schedule, device_lr, weight_decay, decoupled_weight_decay,
+                         skip_nonfinite, ema_warmup)
         self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
         self.gbuf = net.grad_bucket()            # ONE bucket [grads | mean loss]: the net's gradient bucket IS the
         self.loss = self.gbuf[self.n:]           # collective buffer (no 16 MB staging copy per step)
