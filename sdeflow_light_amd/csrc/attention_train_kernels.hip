@@ -43,10 +43,17 @@
 // Transposed formulation (as the sampler kernel): S^T[key][query] = K Q^T, O^T[c][query] += V^T P^T, so a lane owns ONE
 // query (lane&15): running max / sums are per-lane scalars, and e^{S-m} in the C/D layout IS the B operand of the
 // second product (MFMA step r of key tile kt contracts key 16kt + 4(lane>>4) + r on both operands).
+// Occupancy bound (the second __launch_bounds__ argument, waves per SIMD): 2 for the C = 128 four-wave builds, single- and
+// multi-head.  Left to itself hipcc takes 202 VGPRs + 66 AGPRs for them, 12 over what two waves per SIMD allow, and a lone
+// wave has nothing to run under its barriers, staging stores and fragment reads; told, it stops at 221 / 223 VGPRs, no AGPRs,
+// no scratch, and two 33.8 KB workgroups share a CU as at C = 64.  Same MFMAs in the same order, same bits.  Measured against
+// the parent at Bp = 256 (profiles/attn_c128/bench.txt): T = 256, C = 128 292.6 -> 220.2 us (-24.7 %, parent vs parent
+// 0.3 %), two heads of 128 624.9 -> 440.8 us (-29.5 %).  The two-wave builds (NW = 2) spill under the same bound (20 / 36
+// bytes) and every other instantiation keeps 1, i.e. no bound: their machine code is unchanged.
 template <int CT, int QT, int KB, int NW = 4, bool MH = false>   // C = 16*CT channels (per head); QT tiles of 16 queries per
-__global__ void __launch_bounds__(64 * NW) k_attn_dual_fwd(const float* __restrict__ qkv, float* __restrict__ att,   // wave; KB keys
-                                                        float* __restrict__ lse, float* __restrict__ rbar, int T, int nqb,  // per LDS
-                                                        int64_t Bp, float scale, int nh) {                                  // block; NW waves
+__global__ void __launch_bounds__(64 * NW, (CT == 8 && NW == 4) ? 2 : 1)                                             // wave; KB keys
+k_attn_dual_fwd(const float* __restrict__ qkv, float* __restrict__ att, float* __restrict__ lse, float* __restrict__ rbar,   // per LDS
+                int T, int nqb, int64_t Bp, float scale, int nh) {                                                  // block; NW waves
   constexpr int C = 16 * CT, KP = C + 4, KT = KB / 16, NT = 64 * NW;
   constexpr int NV = (KB * C / 4) / NT;                   // float4 per thread per matrix and key block
   static_assert(NV >= 1 && (KB * C / 4) % NT == 0, "key block does not divide over the workgroup's threads");
@@ -247,7 +254,8 @@ __global__ void __launch_bounds__(256) k_attn_dual_delta(const float* __restrict
 // k_attn_dq_reduce read back (3.4 ms of the C4 step, HBM-bound).  The launcher may run the kernel kseq times over every
 // kseq-th key block (launch ks takes key blocks kgi kseq + ks): launches ks > 0 (ACC) ADD their partial sums to the slab
 // rows of their group instead of writing rows of their own — one 16-byte load per store, requested before the MFMAs whose
-// result it joins — so the reduction reads nkg = T / (KB kseq) slabs.  Same fixed summation order every run.  (An in-kernel
+// result it joins (C = 128: a whole phase earlier, see EARLY in the kernel) — so the reduction reads nkg = T / (KB kseq)
+// slabs.  Same fixed summation order every run.  (An in-kernel
 // loop over the key blocks of a group was tried first: it needs ~37 more registers than the 246 the kernel has, spilled, and
 // ran the whole step 1 ms SLOWER at kseq = 1; it also exposed a hipcc hazard bug — no wait states between an MFMA and a global
 // store of its result when a branch sits in between — which a compile-time ACC cannot hit.)
@@ -371,6 +379,23 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
       pst = which < 2 ? stats[o] : ccde[o];
     }
   };
+  // EARLY (the ACC launch at C = 128, one wave per SIMD by its 154 KB of LDS): the slab addends of ALL of this wave's phase-2
+  // tiles are requested behind phase 1a, so their trip to HBM / the Infinity Cache (the previous launch wrote those rows) lies
+  // under the 192 MFMAs of phase 1c and not in front of the 24 they join, where a lone wave sat it out four times per query
+  // block.  The 32 registers come from the next block's q / qd / g / gd prefetch (64), requested behind [C] here: live across
+  // phase 2 only, whose 96 MFMAs cover it; the staging stores go through one address register.  No MFMA moves, same bits, no
+  // scratch (requested behind [B] instead: 32 bytes).  Measured against the parent at Bp = 256, T = 256 (profiles/attn_c128/
+  // bench.txt): both launches + delta + reduce 857.8 -> 785.4 us (-8.4 %, parent vs parent 0.06 %); the ACC launch alone
+  // ran 78 us longer than the plain one before.  The plain launch and every other channel count keep their text.
+  constexpr bool EARLY = ACC && CT == 8;
+  f32x4 adq[EARLY ? CT / KG : 1], adqd[EARLY ? CT / KG : 1];
+  int fs = 0;                                              // EARLY: the 16 staging stores behind ONE address register (as fa / fb / fc
+  if constexpr (EARLY) {                                   // of PF: the staged tiles start past the ds_write's 16-bit immediate)
+    static_assert(NT % (C / 4) == 0 && QFULL, "a thread's staging slots are not whole rows apart");
+    int fs4 = KB * KP + (tid / (C / 4)) * (KP / 4) + tid % (C / 4);
+    asm volatile("" : "+v"(fs4));
+    fs = 4 * fs4;
+  }
   gload(0);
   const int nqb = T / QB;
   for (int qb = 0; qb < nqb; ++qb) {
@@ -382,6 +407,14 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
     for (int i = 0; i < NQ; ++i) {
       const int idx = tid + NT * i, qr = idx / (C / 4), c4 = idx - qr * (C / 4);
       if (!QFULL && idx >= QB * C / 4) break;
+      if constexpr (EARLY) {                               // thread's slot of row tid / (C/4) + (NT / (C/4)) i, tile m at + m QB KP
+        float* d = atb_lds + fs + (NT / (C / 4)) * i * KP;
+        *reinterpret_cast<f32x4*>(d) = pq[i];
+        *reinterpret_cast<f32x4*>(d + QB * KP) = pqd[i];
+        *reinterpret_cast<f32x4*>(d + 2 * QB * KP) = pg[i];
+        *reinterpret_cast<f32x4*>(d + 3 * QB * KP) = pgd[i];
+        continue;
+      }
       *reinterpret_cast<f32x4*>(Qs + qr * KP + 4 * c4) = pq[i];
       *reinterpret_cast<f32x4*>(Qd + qr * KP + 4 * c4) = pqd[i];
       *reinterpret_cast<f32x4*>(Gs + qr * KP + 4 * c4) = pg[i];
@@ -393,7 +426,7 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
     if constexpr (PF) attn_rd_rows<KB * KP>(atb_lds, fb, B[0]);                    // resident tiles: requested in front of [B]
     __syncthreads();                                       // [B] staged block visible
     if constexpr (PF) attn_rd_rows<QB * KP>(atb_lds, fa, A[0]);
-    if (qb + 1 < nqb) gload(qb + 1);
+    if constexpr (!EARLY) { if (qb + 1 < nqb) gload(qb + 1); }
 
     // ---- phase 1a: S, Sd, Pbar, D for (queries 16qs.., keys 16kg..); D layout: lane (key il, queries 4q+r)
     f32x4 s = {0, 0, 0, 0}, sd = {0, 0, 0, 0}, pb = {0, 0, 0, 0}, dd = {0, 0, 0, 0};
@@ -420,6 +453,14 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
         pb = mfma16(aGd[r], bVd[r], pb);
       }
       __builtin_amdgcn_sched_barrier(0);                   // keep one (PF: two) channel groups of fragments in flight, not all
+    }
+    if constexpr (EARLY) {
+#pragma unroll
+      for (int j = 0; j < CT / KG; ++j) {                  // the rows phase 2 adds to, tile ct = kg + KG j
+        const size_t o = ((size_t)qb * QB + 16 * qs + il) * C + 16 * (kg + KG * j) + 4 * q;
+        adq[j] = *reinterpret_cast<const f32x4*>(slab + ((size_t)pr * nkg + kgi) * T * C + o);
+        adqd[j] = *reinterpret_cast<const f32x4*>(slab + ((size_t)(NP + pr) * nkg + kgi) * T * C + o);
+      }
     }
     // ---- phase 1b: elementwise adjoints (row scalars of queries 16qs + 4q + r)
     const f32x4 L4 = *reinterpret_cast<const f32x4*>(St + 16 * qs + 4 * q);
@@ -465,14 +506,18 @@ __global__ void __launch_bounds__(128 * KG) k_attn_dual_bwd(const float* __restr
       __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();                                       // [C] Sbar / Sdbar of the whole 32 x KB block are parked
+    // Q / Qd / G / Gd are free from here on.  No branch around the request: behind one, hipcc's wait for the addends (the older
+    // loads) would also wait for most of these; the last block asks for its own rows again and drops them
+    if constexpr (EARLY) gload(qb + 1 < nqb ? qb + 1 : qb);
     // ---- phase 2: qbar^T[c][query] += K^T Sbar^T + Kd^T Sdbar^T ; qdbar^T += K^T Sdbar^T   (wave (qs, kg): tiles ct = kg, kg+KG, ..)
 #pragma unroll
-    for (int ct = kg; ct < CT; ct += KG) {
+    for (int ct = kg, j = 0; ct < CT; ct += KG, ++j) {
       const size_t row = (size_t)qb * QB + 16 * qs + il;
       float* sp = slab + (((size_t)pr * nkg + kgi) * T + row) * C + 16 * ct + 4 * q;
       float* sdp = slab + (((size_t)(NP + pr) * nkg + kgi) * T + row) * C + 16 * ct + 4 * q;
       f32x4 dq = {0, 0, 0, 0}, dqd = {0, 0, 0, 0}, pdq = {0, 0, 0, 0}, pdqd = {0, 0, 0, 0};
-      if (ACC) {          // compile-time: what the earlier launches left for this key group — requested BEFORE the MFMAs it joins
+      if constexpr (EARLY) { pdq = adq[j]; pdqd = adqd[j]; }
+      else if (ACC) {     // compile-time: what the earlier launches left for this key group — requested BEFORE the MFMAs it joins
         pdq = *reinterpret_cast<const f32x4*>(sp);
         pdqd = *reinterpret_cast<const f32x4*>(sdp);
       }
@@ -583,6 +628,9 @@ static int launch_bwd(const float* qkv, const float* att, const float* datt, con
   // Measured at B = 256 (rocprofv3, 7 steps): one launch 147.2 + 29.1 ms in the two backward kernels + 24.0 ms of reduce;
   // two launches 154.1 + 32.4 + 10.5; four 157.5 + 34.4 + 5.3 — the ACC launches run 7 % (C = 64) to 20 % (C = 128) longer
   // than the plain ones (their slab reads are not free under the MFMAs), so two and four both end 0.5 ms per step ahead.
+  // C = 128 since the ACC build asks for its addends a phase early (EARLY in the kernel): Bp = 256, T = 256, both launches +
+  // delta + reduce 785.4 us at kseq = 2 against 855.9 us at kseq = 1 (8 slabs into the reduction), parent 857.8 us (profiles/
+  // attn_c128/bench.txt); kseq = 1 would also sum the slabs in another order, i.e. other bits.  One rule for every channel count.
   int kseq = 1;
   for (int k = 2; k > 1; k >>= 1)
     if (nkb % k == 0 && NP * (int64_t)(nkb / k) >= 1024) { kseq = k; break; }
@@ -621,6 +669,10 @@ static size_t attn_dual_ws(int64_t Bp, int32_t T, int32_t heads, int32_t D, bool
 
 // D -> <CT, QT, KB, NW>, once.  D = 128: 64-query workgroups (4 waves) while they fill the chip twice over, else 32-query
 // workgroups (2 waves): at the 32-row shard the T = 256 blocks are only 128 workgroups of 64 queries
+// The 64-query build runs at two waves per SIMD (its occupancy bound, see the kernel).  The other way to feed the matrix pipe,
+// 128-query workgroups <8,2,16,4> (twice the MFMAs per fragment read, one wave per SIMD, 256 + 224 registers) for T % 128 == 0
+// and Bp nh T / 128 >= 512, lost to the PARENT: Bp = 256, T = 256 +14.7 %, two heads of 128 +6.8 % (profiles/attn_c128/
+// rejected_forms.txt); it is not instantiated.
 template <bool MH>
 static int attn_dual_fwd_go(const float* qkv, float* att, float* stats, int64_t Bp, int T, int D, int nh, float scale, hipStream_t st) {
   if (D == 128) {

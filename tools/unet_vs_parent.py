@@ -256,7 +256,10 @@ DUAL = [(3, 64, 1, 32, 0), (3, 64, 1, 64, 0), (9, 96, 1, 128, 0), (1, 32, 1, 128
         (1024, 64, 1, 128, 0), (3, 64, 2, 16, 1), (3, 64, 2, 32, 1), (2, 64, 2, 64, 1), (5, 96, 2, 128, 1), (256, 64, 2, 128, 1),
         (256, 128, 4, 32, 1), (3, 64, 1, 64, 1), (3, 64, 1, 16, 1),      # these two: one head through the multi-head entries
         # tests/test_attn_dual_paths_gpu.py: one key block, an odd count, the decode's tail, C = 64 with kseq = 2, D = 64 at two heads
-        (1, 64, 1, 64, 0), (3, 192, 1, 64, 0), (9, 128, 1, 64, 0), (1024, 128, 1, 64, 0), (5, 128, 2, 64, 1)]
+        (1, 64, 1, 64, 0), (3, 192, 1, 64, 0), (9, 128, 1, 64, 0), (1024, 128, 1, 64, 0), (5, 128, 2, 64, 1),
+        # tests/test_attn_dual_c128_gpu.py ((1, 32, 1, 128) is above): T no multiple of 64, the decode's tail, the NW = 4 forward with
+        # the two-launch backward at two slab groups, the multi-head builds at NW = 2 and NW = 4; then the benchmark's own shape
+        (3, 96, 1, 128, 0), (9, 64, 1, 128, 0), (512, 128, 1, 128, 0), (5, 64, 2, 128, 1), (256, 64, 2, 128, 1), (256, 256, 1, 128, 0)]
 
 
 def attn_cases():
@@ -288,7 +291,8 @@ def bitwise():
 # ------------------------------------------------------------------------------------------------ timing
 def timing(path, variants):
     """GroupNorm at the benchmark's C4 64x64x32 layer (dual batch 512) and at the 32-row shard, every attention family at the C4
-    network's two attention shapes (32x32 at 64 channels, 16x16 at 128; two heads for the multi-head builds), the kseq = 2 cases."""
+    network's two attention shapes (32x32 at 64 channels, 16x16 at 128; two heads for the multi-head builds, of 32, 64 and 128
+    channels), the kseq = 2 cases."""
     ROUNDS, REPS, WARM = 5, 20, 3
     rows = []
 
@@ -308,8 +312,8 @@ def timing(path, variants):
             go(f"GroupNorm {name} Bp={Bp} P=4096 C=32", call)
         del gn
         torch.cuda.empty_cache()
-    for (N, T, H, D, mh) in ((256, 1024, 1, 64, 0), (256, 256, 1, 128, 0), (256, 1024, 2, 32, 1), (256, 256, 2, 64, 1), (1024, 128, 1, 32, 0),
-                             (1024, 64, 1, 128, 0)):
+    for (N, T, H, D, mh) in ((256, 1024, 1, 64, 0), (256, 256, 1, 128, 0), (256, 1024, 2, 32, 1), (256, 256, 2, 64, 1), (256, 256, 2, 128, 1),
+                             (1024, 128, 1, 32, 0), (1024, 64, 1, 128, 0)):
         a = Attn(N, T, H, D, mh, seed=N + T)
         if N == 256:
             go(f"{attn_expect('sampler', N, T, H, D, mh)} {a.tag}", lambda h: check((h.msgm_attention_mh_forward if mh else h.msgm_attention_forward)(
