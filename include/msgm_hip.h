@@ -688,7 +688,7 @@ int msgm_unpack_weight(float* dW, const float* dWp, int32_t rows, int32_t ncols,
                        int64_t sr, int64_t sc, int64_t st, int32_t rowsP, int32_t Ktot, int32_t kp_off,
                        int32_t accumulate, msgm_stream_t stream);
 
-/* One launch for every (un)pack job of a network.  `jobs` is a DEVICE array; job j copies
+/* One launch for every (un)pack job of a network.  `jobs_dev` is a DEVICE array; job j copies
  * Wp[t][r][kp_off+c] <- W[r*sr + (col_off+c)*sc + t*st] (unpack != 0: the other way, overwriting W, or adding
  * atomically when the job's `reserved` field is 1).  The
  * table is static as long as the parameter buckets and packed images do not move. */
@@ -697,7 +697,7 @@ typedef struct {
   int64_t sr, sc, st;
   int32_t rows, ncols, col_off, taps, rowsP, Ktot, kp_off, reserved;
 } msgm_pack_job_t;
-int msgm_pack_weights_batched(const msgm_pack_job_t* jobs, int32_t n_jobs, int32_t unpack, msgm_stream_t stream);
+int msgm_pack_weights_batched(const msgm_pack_job_t* jobs_dev, int32_t n_jobs, int32_t unpack, msgm_stream_t stream);
 /* OPT-IN EXPERIMENT (never the default path; MSGM_SAMPLER_BF16X3=1 on the host side): the same 3x3 stride-1 pad-1 forward
  * convolution of the sampler (sde_scheme.py:82 -> model/unet.py:140-158; Ho, Wo multiples of 16; C0, C1, CoutP multiples of
  * 32) with its matrix work in bf16-SPLIT arithmetic: every fp32 operand as three bf16 pieces (24 mantissa bits), six
@@ -713,7 +713,7 @@ int msgm_conv_forward_b6(const msgm_conv_geom_t* geom, const float* src0, int32_
                          const msgm_conv_fuse_t* fuse, msgm_stream_t stream);
 
 /* The Winograd images of msgm_conv_forward_wino: same job table (taps = 9), Wp = [16][rowsP][Ktot]. */
-int msgm_wino_pack_weights_batched(const msgm_pack_job_t* jobs, int32_t n_jobs, msgm_stream_t stream);
+int msgm_wino_pack_weights_batched(const msgm_pack_job_t* jobs_dev, int32_t n_jobs, msgm_stream_t stream);
 
 /* Dual-number activations on a (primal | tangent) stacked tensor of 2*half
  * elements: act 0 = exact-erf GELU (NNUnet1D.py:18), 1 = SiLU (nn_utils.py:44-46).

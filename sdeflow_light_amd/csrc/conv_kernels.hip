@@ -3073,9 +3073,9 @@ static bool conv_has_masks(const ConvArgs& A) {
   return m != 0;
 }
 
-int msgm_wino_pack_weights_batched(const msgm_pack_job_t* jobs, int32_t n_jobs, msgm_stream_t stream) {
-  if (!jobs || n_jobs <= 0) return MSGM_E_BADARG;
-  hipLaunchKernelGGL(k_wino_pack_batched, dim3(8, (unsigned)n_jobs), dim3(256), 0, S(stream), jobs);
+int msgm_wino_pack_weights_batched(const msgm_pack_job_t* jobs_dev, int32_t n_jobs, msgm_stream_t stream) {
+  if (!jobs_dev || n_jobs <= 0) return MSGM_E_BADARG;
+  hipLaunchKernelGGL(k_wino_pack_batched, dim3(8, (unsigned)n_jobs), dim3(256), 0, S(stream), jobs_dev);
   return msgm_check_launch();
 }
 
@@ -3669,9 +3669,9 @@ __global__ void __launch_bounds__(256) k_pack_batched(const msgm_pack_job_t* __r
   }
 }
 
-int msgm_pack_weights_batched(const msgm_pack_job_t* jobs, int32_t n_jobs, int32_t unpack, msgm_stream_t stream) {
-  if (!jobs || n_jobs <= 0) return MSGM_E_BADARG;
-  hipLaunchKernelGGL(k_pack_batched, dim3(32, (unsigned)n_jobs), dim3(256), 0, S(stream), jobs, unpack);
+int msgm_pack_weights_batched(const msgm_pack_job_t* jobs_dev, int32_t n_jobs, int32_t unpack, msgm_stream_t stream) {
+  if (!jobs_dev || n_jobs <= 0) return MSGM_E_BADARG;
+  hipLaunchKernelGGL(k_pack_batched, dim3(32, (unsigned)n_jobs), dim3(256), 0, S(stream), jobs_dev, unpack);
   return msgm_check_launch();
 }
 

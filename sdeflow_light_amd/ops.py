@@ -464,8 +464,9 @@ def adam_step_ex(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Ten
 
 
 OPT_WEIGHT_DECAY = 6                                  # the seventh field of msgm_optim_t
-DECAY_NONE, DECAY_L2, DECAY_DECOUPLED = range(3)      # decay_mode of msgm_optim_step
-_OPTIM_CLIP, _OPTIM_EMA_WARMUP = 1, 2                 # its flags
+# decay_mode of msgm_optim_step and its flags, as include/msgm_hip.h defines them
+DECAY_NONE, DECAY_L2, DECAY_DECOUPLED = (L.CONSTANTS["MSGM_DECAY_" + n] for n in ("NONE", "L2", "DECOUPLED"))
+_OPTIM_CLIP, _OPTIM_EMA_WARMUP = L.CONSTANTS["MSGM_OPTIM_CLIP"], L.CONSTANTS["MSGM_OPTIM_EMA_WARMUP"]
 
 
 def optim_hyper(device, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None,

@@ -11,12 +11,7 @@ from sdeflow_light_amd import _lib  # noqa: E402
 
 
 def load(path):
-    h = ctypes.CDLL(os.path.abspath(path))
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(h, name, None)     # an entry this tree added is missing from the other build
-        if fn is not None:
-            fn.restype, fn.argtypes = res, args
-    return h
+    return _lib.bind(ctypes.CDLL(os.path.abspath(path)), missing_ok=True)     # an entry this tree added is missing from the other build
 
 
 def use(h):

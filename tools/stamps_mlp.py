@@ -20,9 +20,7 @@ from sdeflow_light_amd.build import FLAGS
 for stamps in (False, True):
     so = f"/tmp/libmsgm_stamps_{int(stamps)}.so"
     subprocess.check_call(["hipcc"] + FLAGS + ["-shared"] + (["-DMLP_STAMPS"] if stamps else []) + src + ["-o", so])
-    L = C.CDLL(so)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(L, name); fn.restype, fn.argtypes = res, args
+    L = _lib.bind(C.CDLL(so))
     P = _lib.MlpParamsT(*[w.data_ptr() for w in W], d, 0)
     st = _lib.sde_struct(0, 0.1, 20.0, 1.0, 1e-3)
     ws = torch.empty(int(L.msgm_mlp_ssm_workspace(d, 0)) // 4, device=dev)

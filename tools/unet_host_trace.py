@@ -63,7 +63,7 @@ def _fields(s):
 def _arg(argtype, a):
     """What the trace keeps of one argument: scalars as they are, a pointer as "p" or null, a struct as its fields."""
     if argtype is ctypes.c_void_p:
-        return "p" if a else None
+        return list(a) if isinstance(a, ctypes.Array) else "p" if a else None      # a host array (tap masks): its values
     if isinstance(argtype, type) and issubclass(argtype, ctypes._Pointer):
         if a is None:
             return None
