@@ -168,6 +168,22 @@ int msgm_rademacher(float* v, int64_t n, const float* u, const uint64_t* rng, ms
 int msgm_data_gather(const float* data, int64_t N, float* x, int64_t B, int64_t d, const int32_t* idx_in, int32_t* idx_out,
                      const uint64_t* rng, msgm_stream_t stream);
 
+/* msgm_data_gather WITHOUT replacement: x[b,:] = data[pi_e(p),:] for stream position P = cursor[0] + rng[2] + b, e = P / N,
+ * p = P % N.  The data order is one endless stream of independent permutations pi_0, pi_1, ... of [0, N): every aligned
+ * window of N positions holds every row once, and a batch may straddle an epoch boundary (B > N is legal).  pi_e (N > 1):
+ * bits = max(8, bit_length(N - 1)), a = bits / 2, b = bits - a; keys k[0..11] = words x, y, z, w of the Philox blocks
+ * (counter (q lo, q hi, RNG_STREAM_DATA_PERM = 8, 0), key (seed lo, seed hi)), q = 4 e + j, j = 0, 1, 2 — the seed rng[0] only,
+ * neither the offset nor a shard base;  F(r, k): x = (r + k) 0x9E3779B1, x ^= x >> 15, x *= 0x85EBCA77, x ^= x >> 13,
+ * x *= 0xC2B2AE3D, x ^= x >> 16 (uint32);  one pass: L = v >> b, R = v & (2^b - 1), twelve rounds
+ * (L, R) <- (R, L ^ (F(R, k[i]) & (2^w - 1))) with w = a on even i and b on odd i, v = (L << b) | R;  start at v = p and
+ * repeat the pass until v < N.  rng[2], the shard's first global row, places a rank inside the batch; cursor (device,
+ * int64[1]) is only read: advance it with msgm_counter_add in a launch of its own.  idx_out and the access shape as above. */
+int msgm_data_gather_epoch(const float* data, int64_t N, float* x, int64_t B, int64_t d, int32_t* idx_out, const uint64_t* rng,
+                           const int64_t* cursor, msgm_stream_t stream);
+
+/* *ctr += delta (one thread): moves the cursor of msgm_data_gather_epoch on, as a kernel node of a captured step. */
+int msgm_counter_add(int64_t* ctr, int64_t delta, msgm_stream_t stream);
+
 /* msgm_data_gather followed by msgm_ssm_prep, in ONE launch and with the bits of the two from the same stream state:
  * x receives the gathered batch, y / t_out / v what msgm_ssm_prep writes for it, *step_ctr += 1 (may be NULL). */
 int msgm_ssm_prep_gather(const float* data, int64_t N, float* x, float* y, float* t_out, float* v, int64_t B, int64_t d,

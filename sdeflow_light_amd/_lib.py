@@ -38,7 +38,8 @@ DATA_SWISS, DATA_GAUSSIAN, DATA_CAUCHY, DATA_GAUSSIAN_CAUCHY = _constants(      
 # the Philox stream ids live in csrc/common.h, which is not the interface file
 RNG_STREAM_T, RNG_STREAM_EPS, RNG_STREAM_V, RNG_STREAM_DW, RNG_STREAM_ROWS, RNG_STREAM_USER = 0, 1, 2, 3, 4, 16
 RNG_STREAM_DATA, RNG_STREAM_DATA_ELEM, RNG_STREAM_DATA_CALL = 5, 6, 7     # the data stage: by row, by element, one scalar per call
-RNG_STREAM_DROPOUT = 64          # + the ResBlock's index: the U-Net's dropout masks (include/msgm_hip.h, msgm_dropout_t)
+RNG_STREAM_DATA_PERM = 8         # the round keys of an epoch's permutation (msgm_data_gather_epoch): seed and epoch only
+RNG_STREAM_DROPOUT = 64         # + the ResBlock's index: the U-Net's dropout masks (include/msgm_hip.h, msgm_dropout_t)
 
 # one Structure class per typedef struct of the header, msgm_foo_bar_t -> FooBarT
 SdeT, OptT, OptimT, MlpParamsT, ConvGeomT, ConvFuseT, ReduceJobT, PackJobT, DropoutT, EmbJobT = (

@@ -71,9 +71,11 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 // U-Net's ResBlock l, indexed by the global (row, pixel, channel) element (include/msgm_hip.h, msgm_dropout_t).
 // The data samplers (data_kernels.hip): RNG_STREAM_DATA is indexed by ROW (the row index of a gather, the
 // swiss roll's angle), RNG_STREAM_DATA_ELEM by element (normals, Cauchy draws); RNG_STREAM_DATA_CALL is read at element 0
-// with NO base — one scalar per call, the same on every rank (data_call_word).
+// with NO base — one scalar per call, the same on every rank (data_call_word).  RNG_STREAM_DATA_PERM: the round keys of an
+// epoch's permutation (data_epoch_index), blocks 4 e + j read with the SEED only — neither the running offset nor a base.
 enum { RNG_STREAM_T = 0, RNG_STREAM_EPS = 1, RNG_STREAM_V = 2, RNG_STREAM_DW = 3, RNG_STREAM_ROWS = 4, RNG_STREAM_DATA = 5,
-       RNG_STREAM_DATA_ELEM = 6, RNG_STREAM_DATA_CALL = 7, RNG_STREAM_USER = 16, RNG_STREAM_DROPOUT = 64 };
+       RNG_STREAM_DATA_ELEM = 6, RNG_STREAM_DATA_CALL = 7, RNG_STREAM_DATA_PERM = 8, RNG_STREAM_USER = 16,
+       RNG_STREAM_DROPOUT = 64 };
 __device__ __forceinline__ uint64_t msgm_rng_base(const uint64_t* rng, uint32_t stream) {
   return (stream == RNG_STREAM_T || stream == RNG_STREAM_ROWS || stream == RNG_STREAM_DATA) ? rng[2] : rng[3];
 }

@@ -2,9 +2,11 @@
 // instead of the reference loop's host-side `x = sampler.sample(batch_size).to(device)` (MSGM_higherDim.py:806).
 //   msgm_data_gather       x[b,:] = data[idx_b,:], idx_b drawn with replacement (data.py:691-697)
 //   msgm_ssm_prep_gather   msgm_data_gather + msgm_ssm_prep in one launch (the additive SDE's prologue)
+//   msgm_data_gather_epoch x[b,:] = data[pi_e(p),:], epochs WITHOUT replacement from a device cursor; msgm_counter_add moves it
 //   msgm_data_synth        SwissRoll / Gaussian / Cauchy / GaussianCauchy (data.py:702-802)
 // gfx950 only.  Streams: RNG_STREAM_DATA by global row, RNG_STREAM_DATA_ELEM by global element, RNG_STREAM_DATA_CALL one
-// scalar per call (common.h).  No atomics; every output element is written by exactly one lane.
+// scalar per call, RNG_STREAM_DATA_PERM the keys of an epoch's permutation (common.h).  No atomics; every output element
+// is written by exactly one lane.
 #include "common.h"
 #include "sde_stage.h"
 #include "optim_elem.h"          // ld4 / st4 / aligned16
@@ -49,6 +51,74 @@ __global__ void __launch_bounds__(256) k_data_gather(const float* __restrict__ d
     if (idx_out && c == 0) idx_out[b] = (int32_t)idx;
   }
 }
+
+// ============================================================ the epoch index rule
+// Sampling WITHOUT replacement: the data order is one endless stream of independent permutations pi_0, pi_1, ... of
+// [0, N); stream position P reads row pi_e(p), e = P / N, p = P % N, so every aligned window of N positions holds every
+// row once.  pi_e is a 12-round unbalanced Feistel network on bits = max(8, bit_length(N - 1)) bits (halves a = bits / 2
+// and b = bits - a, changing sides every round) with cycle walking: a bijection of [0, 2^bits), re-applied until the
+// value is a row.  2^bits < 2 N for N > 128, so the mean number of passes stays below 2.  The twelve round keys are the
+// words of blocks 4 e + j, j = 0, 1, 2, of RNG_STREAM_DATA_PERM at offset 0 and with NO shard base: they depend on the
+// seed and the epoch only, so every step and every rank of an epoch sees the same permutation.  All uint32 arithmetic;
+// tests/data_epoch_ref.py restates it to the bit.
+__device__ __forceinline__ uint32_t perm_round(uint32_t r, uint32_t k) {
+  uint32_t x = (r + k) * 0x9E3779B1u;
+  x ^= x >> 15;
+  x *= 0x85EBCA77u;
+  x ^= x >> 13;
+  x *= 0xC2B2AE3Du;
+  x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ int64_t data_epoch_index(const uint64_t* __restrict__ rng, uint64_t P, int64_t N) {
+  if (N == 1) return 0;
+  const uint64_t e = P / (uint64_t)N;
+  const uint32_t n = (uint32_t)N, p = (uint32_t)(P - e * (uint64_t)N);
+  const uint64_t seed = rng[0];
+  uint32_t k[12];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const uint64_t q = 4 * e + (uint64_t)j;
+    const Philox4 w = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), RNG_STREAM_DATA_PERM, 0u, (uint32_t)seed,
+                                    (uint32_t)(seed >> 32));
+    k[4 * j] = w.x; k[4 * j + 1] = w.y; k[4 * j + 2] = w.z; k[4 * j + 3] = w.w;
+  }
+  const int bits = max(8, 32 - __clz(n - 1)), a = bits >> 1, b = bits - a;        // bits <= 31: N < 2^31
+  const uint32_t ma = (1u << a) - 1u, mb = (1u << b) - 1u;
+  uint32_t v = p;
+  do {
+    uint32_t L = v >> b, R = v & mb;                 // L holds a bits, R holds b
+#pragma unroll
+    for (int i = 0; i < 12; i += 2) {                // two rounds (L, R) <- (R, L ^ F(R)): the widths are back in place
+      const uint32_t t = L ^ (perm_round(R, k[i]) & ma);
+      const uint32_t u = R ^ (perm_round(t, k[i + 1]) & mb);
+      L = t; R = u;
+    }
+    v = (L << b) | R;
+  } while (v >= n);
+  return (int64_t)v;
+}
+
+// k_data_gather with the row of stream position cursor[0] + row_base + b.  The cursor is only READ here: every lane of
+// the launch must see the same value, so the advance is a launch of its own behind this one (msgm_counter_add).
+template <int VEC>
+__global__ void __launch_bounds__(256) k_data_gather_epoch(const float* __restrict__ data, int64_t N, float* __restrict__ x,
+                                                           int64_t B, int64_t d, int32_t* __restrict__ idx_out,
+                                                           const uint64_t* __restrict__ rng,
+                                                           const int64_t* __restrict__ cursor) {
+  const int64_t upr = d / VEC, n = B * upr;
+  const uint64_t P0 = (uint64_t)cursor[0] + rng[2];
+  int64_t b_prev = -1, idx = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / upr, c = (i - b * upr) * VEC;
+    if (b != b_prev) { idx = data_epoch_index(rng, P0 + (uint64_t)b, N); b_prev = b; }
+    if constexpr (VEC == 4) st4(x + b * d + c, ld4(data + idx * d + c));
+    else x[b * d + c] = data[idx * d + c];
+    if (idx_out && c == 0) idx_out[b] = (int32_t)idx;
+  }
+}
+
+__global__ void k_counter_add(int64_t* c, int64_t delta) { c[0] += delta; }
 
 // msgm_data_gather + k_ssm_prep (sde_kernels.hip) in one launch: the quad walk of k_ssm_prep with x0[e] read through the
 // row's index and the gathered value written to x as well.  Same streams, same indices, vp_row / vp_value: the bits of the
@@ -304,6 +374,26 @@ int msgm_data_gather(const float* data, int64_t N, float* x, int64_t B, int64_t 
     hipLaunchKernelGGL(k_data_gather<1>, dim3(grid_for(B * d, 256)), dim3(256), 0, S(stream), data, N, x, B, d, idx_in, idx_out,
                        rng);
   }
+  return msgm_check_launch();
+}
+
+int msgm_data_gather_epoch(const float* data, int64_t N, float* x, int64_t B, int64_t d, int32_t* idx_out, const uint64_t* rng,
+                           const int64_t* cursor, msgm_stream_t stream) {
+  if (!data || !x || !rng || !cursor || B <= 0 || d <= 0 || N <= 0) return MSGM_E_BADARG;
+  if (N >= ((int64_t)1 << 31)) return MSGM_E_UNSUPPORTED;                   // the index is an int32, the network uint32
+  if (d % 4 == 0 && aligned16(data, x)) {
+    hipLaunchKernelGGL(k_data_gather_epoch<4>, dim3(grid_for(B * (d / 4), 256)), dim3(256), 0, S(stream), data, N, x, B, d,
+                       idx_out, rng, cursor);
+  } else {
+    hipLaunchKernelGGL(k_data_gather_epoch<1>, dim3(grid_for(B * d, 256)), dim3(256), 0, S(stream), data, N, x, B, d, idx_out,
+                       rng, cursor);
+  }
+  return msgm_check_launch();
+}
+
+int msgm_counter_add(int64_t* ctr, int64_t delta, msgm_stream_t stream) {
+  if (!ctr) return MSGM_E_BADARG;
+  hipLaunchKernelGGL(k_counter_add, dim3(1), dim3(1), 0, S(stream), ctr, delta);
   return msgm_check_launch();
 }
 

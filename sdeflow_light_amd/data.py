@@ -193,11 +193,30 @@ class GaussianCauchy(_Linear):
             self.name = self.name + '_norm'
 
 
-class ArrayData(_DeviceSampler):
+class _ReplaceKeyword(type):
+    """Takes ``replace=`` at the class call, ``ArrayData(train, ..., replace=False)``, so that ``ArrayData.__init__`` keeps
+    the parameter list of the reference's constructor plus ``device`` and ``seed`` (tests/test_data_stage.py pins it)."""
+
+    def __call__(cls, *args, replace: bool = True, **kw):
+        smp = super().__call__(*args, **kw)
+        smp.replace = bool(replace)
+        return smp
+
+
+class ArrayData(_DeviceSampler, metaclass=_ReplaceKeyword):
     """The real-data protocol of data.py:691-700 over resident tables: ``sample(n)`` gathers n rows of ``train`` drawn with
     replacement (np.random.randint + fancy index upstream), ``sampletest(n)`` of ``test``.  ``train`` / ``test``: (N, dim)
     arrays or tensors, kept as float32 on the device.  ``std``: per-feature standard deviation ``get_std()`` reports
-    (default: ``train.std(axis=0)`` as numpy forms it, the population one)."""
+    (default: ``train.std(axis=0)`` as numpy forms it, the population one).
+
+    ``replace=False``: epochs.  The training order is one endless stream of independent permutations of the N rows
+    (DESIGN.md §4g), walked by a device cursor the sampler owns: ``sample_into`` gathers the rows of positions
+    cursor + row_base + b and then moves the cursor on by ``x.shape[0] * stride`` in a launch of its own, so every aligned
+    window of N positions trains on every row once, whatever the batch size.  ``stride`` is 1 until a trainer binds the
+    sampler (``bind(world)``): the ranks of a data-parallel run, built with the same seed and ``row_base`` = the shard's
+    first global row, then read together the rows of the 1-rank run.  The permutations are keyed by the seed of the
+    stream handed to ``sample_into`` (the trainer's, or the sampler's own in ``sample``) and by the epoch, not by the
+    stream's offset.  ``sampletest`` stays with replacement, as upstream."""
 
     def __init__(self, train, test=None, name: str = "array", std=None, *, device=None, seed: int = 0):
         train = self._table(train, "train")
@@ -216,6 +235,9 @@ class ArrayData(_DeviceSampler):
         self._train, self._test = train, test
         self.max_nsamples = int(train.shape[0])
         self.max_nsamplestest = 0 if test is None else int(test.shape[0])
+        self.replace = True                           # replace=False arrives through the class call (_ReplaceKeyword)
+        self._cursor: Optional[torch.Tensor] = None
+        self.stride, self._world = 1, None
         self._moved()
 
     @staticmethod
@@ -229,6 +251,8 @@ class ArrayData(_DeviceSampler):
 
     def _moved(self) -> None:
         self._resident = False
+        if self._cursor is not None:                  # the position moves with the table
+            self._cursor = self._cursor.to(self.device)
 
     def table(self, test: bool = False) -> torch.Tensor:
         """The resident (N, dim) float32 table the kernels read; copied to the device on first use."""
@@ -244,7 +268,62 @@ class ArrayData(_DeviceSampler):
 
     def sample_into(self, x: torch.Tensor, rng: L.PhiloxState, test: bool = False) -> torch.Tensor:
         self._check_batch(x)
-        return ops.data_gather(self.table(test), x, rng=rng)
+        if self.replace or test:
+            return ops.data_gather(self.table(test), x, rng=rng)
+        # the gather only reads the cursor; the advance is the next launch, so no lane races with the update
+        cur = self.cursor()
+        ops.data_gather_epoch(self.table(), x, rng, cur)
+        ops.counter_add(cur, x.shape[0] * self.stride)
+        return x
+
+    # ------------------------------------------------------------------ epochs (replace=False)
+    def _check_epochs(self, what: str) -> None:
+        if self.replace:
+            raise MsgmError(f"{what}: the {self.name} sampler draws with replacement; build it with replace=False")
+
+    def cursor(self) -> torch.Tensor:
+        """The device cursor (int64[1]): the stream position of the next batch's first global row."""
+        self._check_epochs("cursor()")
+        if self._cursor is None:
+            self._cursor = torch.zeros(1, dtype=torch.int64, device=self._check_device())
+        return self._cursor
+
+    def bind(self, world: int) -> None:
+        """A trainer of ``world`` ranks takes the sampler: every step moves the cursor by B_local * world."""
+        self._check_epochs("bind()")
+        world = int(world)
+        if world < 1:
+            raise MsgmError(f"bind(world) needs world >= 1 (got {world})")
+        if self._world is not None and self._world != world:
+            raise MsgmError(f"the {self.name} sampler is bound to world = {self._world}; it cannot serve world = {world} too")
+        self._world = self.stride = world
+
+    @property
+    def position(self) -> int:
+        """Stream position of the next batch (reads the device cursor: eager use only)."""
+        cur = self.cursor()
+        if torch.cuda.is_current_stream_capturing():
+            raise MsgmError("position / epoch read the device cursor on the host; not inside a graph capture")
+        return int(cur.item())
+
+    @position.setter
+    def position(self, value: int) -> None:
+        value = int(value)
+        if value < 0:
+            raise MsgmError(f"the stream position must be >= 0 (got {value})")
+        cur = self.cursor()
+        if torch.cuda.is_current_stream_capturing():
+            raise MsgmError("the cursor is set between replays, not inside a graph capture")
+        cur.fill_(value)                              # in place: a captured step keeps the cursor's address
+
+    @property
+    def epoch(self) -> int:
+        """Index of the permutation the next batch starts in."""
+        return self.position // self.max_nsamples
+
+    def steps_per_epoch(self, batch_global: int) -> float:
+        """N / batch_global: steps per pass over the table (a batch may straddle two passes)."""
+        return self.max_nsamples / int(batch_global)
 
     def sampletest(self, n: int) -> torch.Tensor:
         return self._draw(n, test=True)

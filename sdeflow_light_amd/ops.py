@@ -199,6 +199,33 @@ def data_gather(data: torch.Tensor, x: torch.Tensor, rng: Optional[PhiloxState] 
     return x
 
 
+def _cursor(cursor: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    if (not torch.is_tensor(cursor) or not cursor.is_cuda or cursor.dtype != torch.int64 or cursor.numel() != 1
+            or cursor.device != x.device):
+        raise MsgmError("the cursor must be a one-element int64 tensor on the batch's device")
+    return cursor
+
+
+def data_gather_epoch(data: torch.Tensor, x: torch.Tensor, rng: PhiloxState, cursor: torch.Tensor,
+                      idx_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x[b, :] = data[pi_e(p), :] in one launch, WITHOUT replacement: stream position P = cursor[0] + row_base + b reads
+    row p = P % N of the permutation of epoch e = P // N (include/msgm_hip.h, msgm_data_gather_epoch).  The permutation
+    is keyed by ``rng``'s seed and e alone; neither the stream nor ``cursor`` (device int64[1]) is advanced: follow with
+    ``counter_add(cursor, rows)``.  ``idx_out`` (B int32) receives the rows used.  Returns x."""
+    B, d = _batch_out(x)
+    N = _data_table(data, d)
+    if data.device != x.device:
+        raise MsgmError("data and x live on different devices")
+    if idx_out is not None and (not idx_out.is_cuda or idx_out.dtype != torch.int32 or idx_out.dim() != 1
+                                or idx_out.numel() != B):
+        raise MsgmError(f"idx_out must be a device int32 tensor of {B} entries")
+    if rng is None:
+        raise MsgmError("data_gather_epoch needs rng: its seed keys the permutations")
+    check(lib().msgm_data_gather_epoch(ptr(data), N, ptr(x), B, d, ptr(idx_out), rng.ptr(), ptr(_cursor(cursor, x)), stream()),
+          "msgm_data_gather_epoch")
+    return x
+
+
 def ssm_prep_gather(data: torch.Tensor, x: torch.Tensor, y: torch.Tensor, t: torch.Tensor, v: torch.Tensor, sde: L.SdeT,
                     rng: PhiloxState, step_dev: Optional[torch.Tensor] = None) -> None:
     """data_gather(data, x, rng) + msgm_ssm_prep(x -> y, t, v) in one launch, the bits of the two (additive SDE only)."""
@@ -551,6 +578,13 @@ def time_tick(ts: torch.Tensor, step: torch.Tensor, T: float, t_dev: torch.Tenso
 
 def counter_inc(ctr: torch.Tensor):
     check(lib().msgm_counter_inc(ptr(ctr), stream()), "msgm_counter_inc")
+
+
+def counter_add(ctr: torch.Tensor, delta: int):
+    """ctr[0] += delta on the device (int64[1]; one-thread kernel, a kernel node inside a capture)."""
+    if not torch.is_tensor(ctr) or ctr.dtype != torch.int64 or ctr.numel() != 1:
+        raise MsgmError("counter_add takes a one-element int64 device tensor")
+    check(lib().msgm_counter_add(ptr(ctr), int(delta), stream()), "msgm_counter_add")
 
 
 # ---------------------------------------------------------------- fused MLP

@@ -25,7 +25,10 @@ drawing ``x`` on the device from the trainer's own Philox stream — a fresh min
 step); every other combination is ``sampler.sample_into(tr.x, tr.rng)`` ahead of the existing path.  ``tr.x`` shows the
 batch that was trained on.  The stream advances per step as before, so checkpoints keep their keys and a resumed run
 draws the batches of the uninterrupted one; indices and draws are keyed by global row / element, so an N-rank run
-(every rank holding the whole table) trains on the rows of the 1-rank run.
+(every rank holding the whole table) trains on the rows of the 1-rank run.  ``ArrayData(..., replace=False)`` draws epochs
+without replacement instead: gather at the sampler's device cursor, then cursor += B_local * world in a launch of its own
+(two kernel nodes more than the fixed-batch step, the fused prologue is not used), and the checkpoint gains
+``"data_cursor"``.  Epochs across ranks need the same seed on every rank and ``row_base`` = the shard's first global row.
 
 Integrated loss (``gen_sde.ssm_intT``, multiplicative SDE, one rank): ``x`` stays (B, d) and a step trains on
 the nsf' B kept grid states of B forward paths — [data stage] -> msgm_forward_paths (one launch) -> probe -> msgm_ssm_terms
@@ -85,6 +88,8 @@ class _TrainerState:
         sd = {"state": st, "param_groups": [group], "philox": self.rng.state_dict()}
         if self.skipped is not None:              # torch's loader ignores the key, as it ignores "ema"
             sd["skipped"] = skipped
+        if _epoch_data(self):                     # the stream position of the next batch's first global row
+            sd["data_cursor"] = self.data.position
         if self.ema is not None:                  # laid out like "state"; torch.optim.Adam's loader ignores the key
             sd["ema"] = {i: self.ema[off:off + p.numel()].view(p.shape).clone() for i, off, p in mine}
         return sd
@@ -124,6 +129,8 @@ class _TrainerState:
                 self.ema.copy_(self.flat)
         if "philox" in sd:                      # absent in checkpoints written by torch.optim.Adam: keep the stream
             self.rng.load_state_dict(sd["philox"])      # stream position only; the shard base stays this rank's
+        if _epoch_data(self):                   # absent: the data order starts over; without an epoch sampler: ignored
+            self.data.position = int(sd.get("data_cursor", 0))
 
     # ------------------------------------------------------------------ optimizer stage (csrc/optim_kernels.hip)
     def _init_optim(self, lr, max_grad_norm, ema_rate, lr_schedule, device_lr, weight_decay=0.0,
@@ -323,8 +330,16 @@ def _init_data(tr, data):
     if data.dim != tr.d:
         raise MsgmError(f"the {getattr(data, 'name', 'data')} sampler has dim {data.dim}, the score net takes {tr.d}")
     data.to(tr.dev)
-    if isinstance(data, ArrayData) and tr.base.kind == L.SDE_SGM:
+    if _epoch_data(tr):
+        data.bind(tr.world)       # gather, cursor += B_local * world, then the existing path: the fused prologue has no cursor
+    elif isinstance(data, ArrayData) and tr.base.kind == L.SDE_SGM:
         tr._table = data.table()
+
+
+def _epoch_data(tr) -> bool:
+    """Does the trainer draw epochs without replacement (``data=ArrayData(..., replace=False)``)?"""
+    from .data import ArrayData
+    return isinstance(tr.data, ArrayData) and not tr.data.replace
 
 
 def _draw_data(tr):
